@@ -6,17 +6,23 @@ Headline workload = BASELINE.json configs[2]: 10^5 perturbed mixed-phase deep-co
 graupel active), fp64, per GPU -- the largest single-GPU configuration (BASELINE.json's metric names no config).
 Weak scaling: every rank owns its own columns, no halo, no data-path collective; RCCL only for the final diagnostics
 reduction: one all-gather of the per-rank exact precipitation accumulators (the domain means of W:248-303; 24 int64 limbs,
-summed locally: the same digits for every rank count), inside the timed region; the optional max-q / negative-value scan of the end state runs after the clock and only
-feeds the printed line.
+summed locally: the same digits for every rank count), inside the timed region; with --full, the optional max-q /
+negative-value scan of the end state runs after the clock and only feeds the printed line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config2|config3|config4|config5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config2|config3|config4|config5] [--full]
+                    [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment makes THIS process a launcher: it starts N fresh
 rank processes (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set, 127.0.0.1 rendezvous) before anything touches the
 GPU, rank r binds GPU r, and rank 0 prints the line.  Under `python -m torch.distributed.run` the ranks already
 exist and the script is simply rank RANK.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+A plain run does only what the headline needs: it sets up the workload, runs W untimed and K timed steps, writes
+what the last step computed when `--dump-outputs DIR` is given (dump_outputs) and prints ONE JSON line (rank 0):
+`value` = column-steps/s over the K timed steps, `ms_per_step` = wall-clock milliseconds of one timed step.
+`--full` adds to that line:
+  sanity_max_qc_qr_nr_qs_qi_qg_ni, negative_values
+                   the max-q / negative-value scan of the end state (after the clock).
   roofline         HBM roofline of the column-step kernel: achieved = 19232 B of algorithmic traffic per
                    column-step x columns per launch / average launch duration (one HIP event pair on
                    the launch stream around the K timed launches, / K), peak 8 TB/s; `valu_frac` = the fp64-VALU
@@ -36,6 +42,7 @@ Prints ONE JSON line (rank 0).  Extra objects:
   other_workloads  the other single-GPU configs of BASELINE.json (config 2 and 5 at N = 1; config 4 =
                    125 000 mixed-phase columns per rank at N > 1), timed in the same process after the headline,
                    each with its own full roofline / cpu_baseline / accuracy objects.
+  host_entry       the PCIe-inclusive rate of the host-array entry (host_entry_leg).
 """
 import argparse
 import json
@@ -63,13 +70,17 @@ DEFAULT_NCOL = {"config2": 10000, "config3": 100000, "config4": 125000, "config5
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="config3", choices=sorted(DEFAULT_NCOL))
     ap.add_argument("--ncol", type=int, default=0, help="columns per GPU (default: the config's own size)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-workloads", action="store_true", help="time the named workload only")
-    ap.add_argument("--no-host-entry", action="store_true", help="skip the PCIe-inclusive leg (kidmp_batch_step_host)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the sanity scan, roofline, accuracy, CPU baseline, host-entry leg and other workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (a fixed sample of the columns)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the accuracy and CPU-baseline legs")
+    ap.add_argument("--no-other-workloads", action="store_true", help="--full without the other workloads")
+    ap.add_argument("--no-host-entry", action="store_true", help="--full without the PCIe-inclusive leg (kidmp_batch_step_host)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL, one GPU per rank); gloo only to rehearse N ranks on fewer GPUs")
     ap.add_argument("--arith", default="p64", choices=["p64", "p32n", "f32"],
@@ -78,7 +89,10 @@ def parse_args(argv=None):
     ap.add_argument("--lib", default=None, help="an explicitly named build of libkidmp.so (A/B and profiling builds)")
     ap.add_argument("--rehearse-launcher", action="store_true",
                     help="CPU-only boxes: exercise launcher + rendezvous + reduction with NO physics (value is 0)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------ launcher (never touches the GPU)
@@ -309,6 +323,32 @@ def cpu_baseline(st, iiwarm, budget_s=12.0):
                     "measured in the survey (1.8e4 column-steps/s/core, warm, another CPU); a reported baseline, not a target"}
 
 
+DUMP_COLUMNS = 4096      # 12 profiles x 120 levels x 8 B x 4096 columns = 47 MB: inside the 64 MB a dump may take
+DUMP_SEED = 20241008
+
+
+def dump_outputs(outdir, shard, precip_domain_sums):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step, as outdir/<name>.npy -- the 12
+    INOUT state profiles [n, nz] and the accumulated surface precipitation `ppt` [n, 4] of a fixed sample of this rank's
+    columns (every column up to DUMP_COLUMNS, else DUMP_COLUMNS drawn with DUMP_SEED, in column order), and the domain
+    sums of the exchange `precip_domain_sums` [4].  Float64, or float32 for the binary32 builds."""
+    import numpy as np
+    import torch
+    ncol = shard.ppt.shape[0]
+    idx = np.arange(ncol)
+    if ncol > DUMP_COLUMNS:
+        idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(ncol, DUMP_COLUMNS, replace=False))
+    sel = torch.from_numpy(idx).to(shard.ppt.device)
+    arrays = {"ppt": shard.ppt}
+    if hasattr(shard, "st"):                                  # the launcher rehearsal has no state
+        from kid_amd import STATE_NAMES
+        arrays.update((k, shard.st[k]) for k in STATE_NAMES)
+    os.makedirs(outdir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), v.index_select(0, sel).cpu().numpy())
+    np.save(os.path.join(outdir, "precip_domain_sums.npy"), np.asarray(precip_domain_sums, dtype=np.float64))
+
+
 class _RehearsalShard:
     """--rehearse-launcher only (CPU box, no HIP device): stands in for ShardedColumns so that the launcher, the
     rendezvous and the reduction plumbing can be exercised by the CPU test-suite.  It runs NO physics; the line it
@@ -413,15 +453,16 @@ def run_rank(args):
         diag = shard.diagnostics(cpu_collective=cpu_coll, want_sanity=False)   # the exchange of the path: W:248-303's precipitation sums
         sync_all()
         elapsed = max_over_ranks(time.perf_counter() - t0)
-        # after the clock: the optional max-q / negative-value scan of the end state, for the printed line only
-        diag = dict(diag, sanity=shard.diagnostics(cpu_collective=cpu_coll)["sanity"])
         kern_ms = ev0.elapsed_time(ev1) / steps if ev0 else 0.0   # average launch duration (launch-to-launch)
         res = {"workload": desc + ", nz=120, dt=10 s, " + {"p64": "fp64", "p32n": "P32n (binary32 state, binary64 rates)",
                                                             "f32": "fp32"}[args.arith], "name": name, "ncol_per_gpu": ncol, "iiwarm": iiwarm,
                "value": 0.0 if rehearse else ncol * world * steps / elapsed, "ms_per_step": 1e3 * elapsed / steps,
-               "kernel_ms": kern_ms, "precip_domain_sums": [float(x) for x in diag["precip"].cpu().tolist()],
-               "sanity_max_qc_qr_nr_qs_qi_qg_ni": [float(x) for x in diag["sanity"][:7].cpu().tolist()],
-               "negative_values": int(diag["sanity"][7:].sum().item())}
+               "kernel_ms": kern_ms, "precip_domain_sums": [float(x) for x in diag["precip"].cpu().tolist()]}
+        if args.full:
+            # after the clock: the optional max-q / negative-value scan of the end state, for the printed line only
+            sanity = shard.diagnostics(cpu_collective=cpu_coll)["sanity"]
+            res["sanity_max_qc_qr_nr_qs_qi_qg_ni"] = [float(x) for x in sanity[:7].cpu().tolist()]
+            res["negative_values"] = int(sanity[7:].sum().item())
         return shard, st, res
 
     def roofline(shard, res):
@@ -480,6 +521,8 @@ def run_rank(args):
 
     ncol = args.ncol or DEFAULT_NCOL[args.workload]
     shard, st, res = time_workload(args.workload, ncol, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, shard, res["precip_domain_sums"])
     out = None
     if rank == 0:
         out = {
@@ -492,16 +535,20 @@ def run_rank(args):
                        "parallelism": "columns sharded over ranks, no halo, no data-path collective; one RCCL "
                                       "all-gather of the per-rank exact (int64 fixed-point) precipitation accumulators -- the domain "
                                       "means of W:248-303 --, summed locally, inside the timed region: identical sums for every "
-                                      "rank count; the optional max-q / negative-value scan runs after the clock"},
+                                      "rank count; the optional max-q / negative-value scan (--full) runs after the clock"},
             "precip_domain_sums": res["precip_domain_sums"],
-            "sanity_max_qc_qr_nr_qs_qi_qg_ni": res["sanity_max_qc_qr_nr_qs_qi_qg_ni"],
-            "negative_values": res["negative_values"],
         }
         if not rehearse:
-            out["roofline"] = roofline(shard, res)
             out["init_seconds"] = shard.model.init_seconds
+        if args.full:
+            out["sanity_max_qc_qr_nr_qs_qi_qg_ni"] = res["sanity_max_qc_qr_nr_qs_qi_qg_ni"]
+            out["negative_values"] = res["negative_values"]
+            if not rehearse:
+                out["roofline"] = roofline(shard, res)
     if args.arith != "p64":
         args.no_cpu_baseline = args.no_other_workloads = True   # the accuracy leg and the companion workloads are the p64 build's
+    if not args.full:
+        args.no_cpu_baseline = args.no_host_entry = args.no_other_workloads = True    # a plain run: the headline only
     if not rehearse and not args.no_cpu_baseline and world == 1:   # N = 1 only: the host cores are shared by the ranks
         out["accuracy"] = accuracy_leg(shard.model, st, res["iiwarm"], ACCURACY_COLUMNS[args.workload])
         out["cpu_baseline"] = cpu_baseline(st, res["iiwarm"])
@@ -512,7 +559,7 @@ def run_rank(args):
         shard.close()
     del shard, st
 
-    # ---- the other configs of BASELINE.json, same process, after the headline (default run only) ----
+    # ---- the other configs of BASELINE.json, same process, after the headline (--full, default workload only) ----
     if not rehearse and not args.no_other_workloads and args.workload == "config3" and not args.ncol:
         # config 4 (10^6 columns over 8 GPUs) is represented by ONE of its 125 000-column shards at N = 1 and by a shard per
         # rank at N > 1 (10^6 at N = 8)

@@ -75,7 +75,7 @@ def test_sanity_scan_counts_negatives(gpu_mixed):
     assert out[1] == float(st["qr"].max())
 
 
-def test_bench_launcher_two_ranks_on_one_gpu():
+def test_bench_launcher_two_ranks_on_one_gpu(tmp_path):
     """`python bench.py --gpus 2` as the driver starts it at N > 1 without torchrun: the parent spawns the ranks
     (before touching the GPU), they rendezvous on 127.0.0.1, step their shards on the card and all-reduce the
     diagnostics.  gloo because one card cannot host two RCCL ranks; on a multi-GPU node the default backend is nccl."""
@@ -90,11 +90,22 @@ def test_bench_launcher_two_ranks_on_one_gpu():
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0
     assert d["config"]["ncol_per_gpu"] == 2000
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--ncol", "2000",
-                          "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
+                          "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, env=env,
+                         timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     d1 = json.loads([ln for ln in one.stdout.splitlines() if ln.startswith("{")][0])
     # identical replicated columns on both ranks: the all-reduced precipitation is twice one rank's
     np.testing.assert_allclose(d["precip_domain_sums"], 2 * np.asarray(d1["precip_domain_sums"]), rtol=1e-12)
+    # --dump-outputs: every column of the batch (2000 <= the sample size) after the last step; the precipitation
+    # accumulators add up to the domain sums of the line
+    assert d1["steps"] == 3
+    for k in OUT:
+        a = np.load(str(tmp_path / (k + ".npy")))
+        assert a.shape == (2000, 120) and a.dtype == np.float64 and np.isfinite(a).all(), k
+    ppt = np.load(str(tmp_path / "ppt.npy"))
+    assert ppt.shape == (2000, 4)
+    np.testing.assert_allclose(ppt.sum(axis=0), d1["precip_domain_sums"], rtol=1e-12)
+    assert np.load(str(tmp_path / "precip_domain_sums.npy")).tolist() == d1["precip_domain_sums"]
 
 
 def test_context_survives_other_current_device_and_rejects_foreign_tensors(gpu_mixed):

@@ -72,14 +72,16 @@ def test_two_rank_run_equals_single_rank(tmp_path, oracle_warm):
         np.testing.assert_allclose(p["sums"], tot, rtol=1e-13)                     # all-reduced diagnostics
 
 
-def test_bench_launcher_spawns_ranks_and_reduces():
+def test_bench_launcher_spawns_ranks_and_reduces(tmp_path):
     """`python bench.py --gpus 2` with no WORLD_SIZE: the parent must start two fresh rank processes with
     RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set, they must rendezvous on 127.0.0.1 and all-reduce, and rank 0 must
-    print ONE line with n_gpus = 2.  CPU box: --rehearse-launcher (no physics, value 0)."""
+    print ONE line with n_gpus = 2 and write its outputs under --dump-outputs.  CPU box: --rehearse-launcher (no
+    physics, value 0)."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo",
-                        "--rehearse-launcher", "--steps", "4", "--warmup", "1", "--ncol", "10"],
+                        "--rehearse-launcher", "--steps", "4", "--warmup", "1", "--ncol", "10",
+                        "--dump-outputs", str(tmp_path / "out")],
                        capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -88,6 +90,11 @@ def test_bench_launcher_spawns_ranks_and_reduces():
     assert d["n_gpus"] == 2 and d["steps"] == 4 and d["value"] == 0.0 and "no physics" in d["data"]
     # rank r adds 1e-3*dt*(r+1) per column and step (5 steps incl. warm-up): the reduced sum proves both ranks ran
     np.testing.assert_allclose(d["precip_domain_sums"][0], 10 * 5 * 1e-3 * 10.0 * (1 + 2), rtol=1e-12)
+    # rank 0's accumulators after its last step, and the domain sums of the line
+    ppt = np.load(str(tmp_path / "out" / "ppt.npy"))
+    assert ppt.shape == (10, 4) and ppt.dtype == np.float64
+    np.testing.assert_allclose(ppt[:, 0], 5 * 1e-3 * 10.0, rtol=1e-12)
+    assert np.load(str(tmp_path / "out" / "precip_domain_sums.npy")).tolist() == d["precip_domain_sums"]
 
 
 def test_bench_under_torch_distributed_run():

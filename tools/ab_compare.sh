@@ -9,7 +9,7 @@ for w in "$@"; do
   for rep in 1 2 3; do
     for which in A B; do
       lib=$A; [ $which = B ] && lib=$B
-      t=$(python bench.py --no-other-workloads --lib $lib --workload $w --no-cpu-baseline --steps 20 --warmup 3 2>/dev/null | python -c "import json,sys; print('%.4f'%json.loads(sys.stdin.read())['roofline']['kernel_ms'])")
+      t=$(python bench.py --full --no-other-workloads --lib $lib --workload $w --no-cpu-baseline --steps 20 --warmup 3 2>/dev/null | python -c "import json,sys; print('%.4f'%json.loads(sys.stdin.read())['roofline']['kernel_ms'])")
       if [ $which = A ]; then la="$la $t"; else lb="$lb $t"; fi
     done
   done

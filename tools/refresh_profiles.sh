@@ -19,14 +19,14 @@ for a in p32n f32; do
 done
 # the bench reads profiles/<tag>_pmc_<workload>[_<arith>].json for the measured HBM traffic / VALU counts (fingerprint-checked)
 mkdir -p profiles && cp $out/${tag}_pmc_*.json profiles/
-python bench.py > $out/${tag}_bench_default.json
+python bench.py --full > $out/${tag}_bench_default.json
 echo "bench default: $(cut -c1-160 $out/${tag}_bench_default.json)"
 # rocprofv3 --kernel-trace --stats of the default bench command itself (program directly after `--`), plus the
 # average over the K timed launches only (rocprofv3's own average includes the W warm-up launches)
 for w in default config3 config5 config2; do
   rm -rf gpurun_out/prof_${tag}_$w
   if [ $w = default ]; then
-    # exactly `python bench.py`: three workloads in one process; the headline's 5 warm-up + 20 timed launches come first
+    # exactly `python bench.py`: the headline's 5 warm-up + 20 timed launches
     rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${tag}_$w -- python3 bench.py > /dev/null 2>&1
     python tools/kernel_stats_timed.py gpurun_out/prof_${tag}_$w 20 "thompson_column_step<2, 120, 4, false, false, false>" 5 > $out/${tag}_${w}_kernel_timed_launches.json
   else
