@@ -251,6 +251,45 @@ int kidmp_effective_radii_device(kidmp_ctx *ctx, int64_t n, const double *t, con
                                  const double *qc, const double *nc, const double *qi, const double *ni,
                                  const double *qs, double *re_qc, double *re_qi, double *re_qs, void *stream);
 
+/* calc_refl10cm (M:4946-5244): 10-cm radar reflectivity (Rayleigh, dBZ) of rain, snow and graupel from the scheme's own
+ * size distributions -- what WRF and MPAS write as REFL_10CM.  Every level of every column receives
+ * dbz = 10*log10((ze_rain + ze_snow + ze_graupel)*1e18) (M:5196); a level without precipitation gets 10*log10(3e-4).
+ * Reproduces the reference as shipped: no bright band (its wet-snow / wet-graupel branch is dead with nrbins = 0, M:204).
+ * The graupel intercept is a top-down running minimum over the column, so whole columns are needed: arrays are
+ * x[col*nz + k] as everywhere in this header, k = 0 the lowest level (kts).  qc1d is never read by the reference and is
+ * not taken.  qs and qg may both be NULL in an iiwarm context (zero).  IN: t, p, qv, qr, nr, qs, qg; OUT: dbz.
+ *   kidmp_reflectivity_device     device pointers, asynchronous on `stream`; no allocation
+ *   kidmp_reflectivity_host       host arrays (the compatibility procedure behind the Fortran calc_refl10cm)
+ * The kidmp32_* forms take binary32 arrays: inputs widened to binary64, the same binary64 arithmetic as the kidmp_*
+ * forms, the result rounded to binary32 once (not the reference's native binary32 arithmetic). */
+int kidmp_reflectivity_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const double *t, const double *p,
+                              const double *qv, const double *qr, const double *nr, const double *qs, const double *qg,
+                              double *dbz, void *stream);
+int kidmp32_reflectivity_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const float *t, const float *p,
+                                const float *qv, const float *qr, const float *nr, const float *qs, const float *qg,
+                                float *dbz, void *stream);
+int kidmp_reflectivity_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const double *t, const double *p,
+                            const double *qv, const double *qr, const double *nr, const double *qs, const double *qg,
+                            double *dbz);
+int kidmp32_reflectivity_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const float *t, const float *p,
+                              const float *qv, const float *qr, const float *nr, const float *qs, const float *qg,
+                              float *dbz);
+/* kidmp_batch_step_host_diag / kidmp32_batch_step_host followed, chunk by chunk on the device, by the reflectivity of the
+ * post-step state: dbz (host, [ncol][nz]) is the only extra array that crosses PCIe.  dbz NULL = the plain entry.
+ * State, ppt, rates and nstep are those of the plain entry bit for bit. */
+int kidmp_batch_step_host_refl(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt,
+                               double *qv, double *qc, double *qi, double *qr,
+                               double *qs, double *qg, double *ni, double *nr,
+                               double *nc, double *nwfa, double *nifa, double *t,
+                               const double *p, const double *w, const double *dz,
+                               double *ppt, double *rates, int32_t *nstep, double *dbz);
+int kidmp32_batch_step_host_refl(kidmp_ctx *ctx, int64_t ncol, int32_t nz, float dt,
+                                 float *qv, float *qc, float *qi, float *qr,
+                                 float *qs, float *qg, float *ni, float *nr,
+                                 float *nc, float *nwfa, float *nifa, float *t,
+                                 const float *p, const float *w, const float *dz,
+                                 float *ppt, double *rates, int32_t *nstep, int32_t arith, float *dbz);
+
 /* Introspection for parity tests: copy a lookup table / constant array to the
  * host.  Names are the reference's (tcg_racg ... t_Efsw; cre, crg, Dr ...).
  * Returns the number of doubles (<0 on error); out may be NULL to query. */

@@ -21,6 +21,7 @@
 #include "thompson_column.h"
 #include "thompson_host_init.h"
 #include "thompson_tables.h"
+#include "thompson_reflectivity.h"
 #include "table_cache.h"
 #include "fastmath.h"
 
@@ -424,11 +425,15 @@ struct PipelineDrain {
     }
 };
 
+// dbz (optional): the reflectivity of calc_refl10cm (M:4946-5244) of every chunk's post-step state, formed on the compute
+// stream right after the step; it is the only extra array that comes back, and the staging set grows by its one profile.
 template <class T, class Launch>
 int host_pipeline(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, T *const *io, const T *const *in, T *ppt,
-                  double *rates, int32_t *nstep, Launch launch, bool exact_sums = false, bool scan_sanity = false)
+                  double *rates, int32_t *nstep, Launch launch, bool exact_sums = false, bool scan_sanity = false,
+                  T *dbz = nullptr)
 {
     if (!ctx || !ctx->ready) return fail(ctx, KIDMP_ESTATE, "kidmp: context not initialised");
+    if (dbz && !refl_consts_supported(ctx->hc)) return fail(ctx, KIDMP_ESTATE, "kidmp: reflectivity exponents differ from the kernel's");
     // Arrays the caller may leave out (NULL), as KiD itself does (W:36 passes nc1d, nwfa1d, nifa1d unset; a warm run
     // never touches the frozen species, W:46-52): they then neither cross PCIe nor come back.
     //   nc, nwfa, nifa (all three)   non-aerosol contexts: the defaults of M:958-964, formed on the device
@@ -469,7 +474,8 @@ int host_pipeline(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, T *const 
     const size_t b_prof = up256(prof * sizeof(T));
     const size_t b_ppt = up256(4 * size_t(CH) * sizeof(T));
     const size_t b_nstep = nstep ? up256(4 * size_t(CH) * sizeof(int32_t)) : 0;
-    const size_t b_set = b_rates + 15 * b_prof + b_ppt + b_nstep;
+    const size_t b_dbz = dbz ? b_prof : 0;
+    const size_t b_set = b_rates + 15 * b_prof + b_ppt + b_nstep + b_dbz;
     const size_t need = b_set * size_t(nbuf);
     if (need > ctx->stage_bytes) {
         if (ctx->d_stage) (void)hipFree(ctx->d_stage);
@@ -495,6 +501,8 @@ int host_pipeline(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, T *const 
         for (int v = 0; v < 3; ++v) { dinw[v] = reinterpret_cast<T *>(q); din[v] = dinw[v]; q += b_prof; }
         T *dppt = reinterpret_cast<T *>(q); q += b_ppt;
         int32_t *dnstep = nstep ? reinterpret_cast<int32_t *>(q) : nullptr;
+        q += b_nstep;
+        T *ddbz = dbz ? reinterpret_cast<T *>(q) : nullptr;
         if (!has_w || !in[2]) din[2] = nullptr;
         // upload (the set is free once the download of the chunk that used it last has finished)
         if (i >= nbuf) HIPTRY(ctx, hipStreamWaitEvent(ctx->s_h2d, ctx->ev_down[b], 0));
@@ -513,6 +521,9 @@ int host_pipeline(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, T *const 
             HIPTRY(ctx, hipGetLastError());
         }
         if (int rc = launch(n, dio, din, dppt, drates, dnstep)) return rc;
+        if (dbz)                                              // calc_refl10cm of the chunk's post-step t, p, qv, qr, nr, qs, qg
+            HIPTRY(ctx, launch_reflectivity<T>(refl_consts(ctx->hc), n, nz, dio[11], din[0], dio[0], dio[3], dio[7], dio[4],
+                                               dio[5], ddbz, ctx->stream));
         if (exact_sums) HIPTRY(ctx, launch_ppt_exact<T>(n, dppt, ctx->d_acc, ctx->stream));   // the chunk's share of the domain sums
         if constexpr (std::is_same<T, double>::value)
             if (scan_sanity) {                                // the scan of M:1025-1094 over the chunk's end state (exact integer atomics)
@@ -530,10 +541,101 @@ int host_pipeline(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, T *const 
         HIPTRY(ctx, hipMemcpyAsync(ppt + 4 * c0, dppt, 4 * size_t(n) * sizeof(T), hipMemcpyDeviceToHost, ctx->s_d2h));
         if (rates) HIPTRY(ctx, hipMemcpyAsync(rates + size_t(KIDMP_NRATES) * off, drates, size_t(KIDMP_NRATES) * cnt * sizeof(double), hipMemcpyDeviceToHost, ctx->s_d2h));
         if (nstep) HIPTRY(ctx, hipMemcpyAsync(nstep + 4 * c0, dnstep, 4 * size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->s_d2h));
+        if (dbz) HIPTRY(ctx, hipMemcpyAsync(dbz + off, ddbz, cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->s_d2h));
         HIPTRY(ctx, hipEventRecord(ctx->ev_down[b], ctx->s_d2h));
     }
     HIPTRY(ctx, hipStreamSynchronize(ctx->s_d2h));           // everything else precedes it through the events
     drain.armed = false;
+    return KIDMP_OK;
+}
+
+// ---- calc_refl10cm entries (M:4946-5244) ----
+// arguments common to the four entries; qs/qg: both or neither, neither only in an iiwarm context (a warm run keeps them 0)
+int check_refl_args(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const void *const *req, int nreq, const void *qs, const void *qg)
+{
+    if (!ctx || !ctx->ready) return fail(ctx, KIDMP_ESTATE, "kidmp: context not initialised");
+    if (ncol < 0) return fail(ctx, KIDMP_EINVAL, "kidmp_reflectivity: ncol < 0");
+    if (nz < 2 || nz > KIDMP_MAX_NZ) return fail(ctx, KIDMP_EINVAL, "kidmp_reflectivity: nz outside [2, KIDMP_MAX_NZ]");
+    for (int i = 0; i < nreq; ++i)
+        if (!req[i]) return fail(ctx, KIDMP_EINVAL, "kidmp_reflectivity: null array argument");
+    if ((qs == nullptr) != (qg == nullptr)) return fail(ctx, KIDMP_EINVAL, "kidmp_reflectivity: qs and qg must be given or left out together");
+    if (!qs && !ctx->cfg.iiwarm) return fail(ctx, KIDMP_EINVAL, "kidmp_reflectivity: a mixed-phase context needs qs and qg");
+    if (!refl_consts_supported(ctx->hc)) return fail(ctx, KIDMP_ESTATE, "kidmp_reflectivity: exponents differ from the kernel's");
+    return KIDMP_OK;
+}
+
+// Stricter than check_on_device: the reflectivity device entries refuse anything but device memory of the context's GPU
+// (a pageable host array would otherwise reach the kernel and fault it).
+int check_device_array(kidmp_ctx *c, const void *p, const char *what)
+{
+    if (!p) return KIDMP_OK;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, KIDMP_EINVAL, std::string("kidmp_reflectivity: ") + what + " is not device memory");
+    }
+    if (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged)
+        return fail(c, KIDMP_EINVAL, std::string("kidmp_reflectivity: ") + what + " is not device memory");
+    if (at.device != c->cfg.device)
+        return fail(c, KIDMP_EINVAL, std::string("kidmp_reflectivity: ") + what + " lives on device " + std::to_string(at.device)
+                                     + ", the context is bound to device " + std::to_string(c->cfg.device));
+    return KIDMP_OK;
+}
+
+template <class T>
+int refl_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const T *t, const T *p, const T *qv, const T *qr, const T *nr,
+                const T *qs, const T *qg, T *dbz, void *stream)
+{
+    const void *req[] = {t, p, qv, qr, nr, dbz};
+    if (int rc = check_refl_args(ctx, ncol, nz, req, 6, qs, qg)) return rc;
+    if (ncol == 0) return KIDMP_OK;
+    GUARD(ctx);
+    const char *names[] = {"t", "p", "qv", "qr", "nr", "qs", "qg", "dbz"};
+    const void *ptrs[] = {t, p, qv, qr, nr, qs, qg, dbz};
+    for (int i = 0; i < 8; ++i)
+        if (int rc = check_device_array(ctx, ptrs[i], names[i])) return rc;
+    HIPTRY(ctx, launch_reflectivity<T>(refl_consts(ctx->hc), ncol, nz, t, p, qv, qr, nr, qs, qg, dbz, (hipStream_t)stream));
+    return KIDMP_OK;
+}
+
+// host arrays: chunks of columns through the context's staging memory on its compute stream, one after the other
+template <class T>
+int refl_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const T *t, const T *p, const T *qv, const T *qr, const T *nr,
+              const T *qs, const T *qg, T *dbz)
+{
+    const void *req[] = {t, p, qv, qr, nr, dbz};
+    if (int rc = check_refl_args(ctx, ncol, nz, req, 6, qs, qg)) return rc;
+    if (ncol == 0) return KIDMP_OK;
+    GUARD(ctx);
+    const int64_t CH = pick_host_chunk(ctx, ncol);
+    const size_t b_prof = (size_t(CH) * size_t(nz) * sizeof(T) + 255) / 256 * 256;
+    const size_t need = 8 * b_prof;
+    if (need > ctx->stage_bytes) {
+        if (ctx->d_stage) (void)hipFree(ctx->d_stage);
+        ctx->d_stage = nullptr;
+        ctx->stage_bytes = 0;
+        HIPTRY(ctx, hipMalloc((void **)&ctx->d_stage, need));
+        ctx->stage_bytes = need;
+    }
+    char *const base = reinterpret_cast<char *>(ctx->d_stage);
+    T *d[8];
+    for (int v = 0; v < 8; ++v) d[v] = reinterpret_cast<T *>(base + size_t(v) * b_prof);
+    const T *h[7] = {t, p, qv, qr, nr, qs, qg};
+    const ReflConsts c = refl_consts(ctx->hc);
+    hipError_t e = hipSuccess;
+    for (int64_t c0 = 0; c0 < ncol && e == hipSuccess; c0 += CH) {
+        const int64_t n = c0 + CH <= ncol ? CH : ncol - c0;
+        const size_t off = size_t(c0) * size_t(nz), cnt = size_t(n) * size_t(nz);
+        for (int v = 0; v < 7 && e == hipSuccess; ++v)
+            if (h[v]) e = hipMemcpyAsync(d[v], h[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess)
+            e = launch_reflectivity<T>(c, n, nz, d[0], d[1], d[2], d[3], d[4], qs ? d[5] : nullptr, qg ? d[6] : nullptr,
+                                       d[7], ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dbz + off, d[7], cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(ctx->stream);        // no copy may still be in flight towards the caller's arrays
+    HIPTRY(ctx, e);
+    HIPTRY(ctx, es);
     return KIDMP_OK;
 }
 
@@ -876,6 +978,65 @@ int kidmp_effective_radii_device(kidmp_ctx *ctx, int64_t n, const double *t, con
                        t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs);
     HIPTRY(ctx, hipGetLastError());
     return KIDMP_OK;
+}
+
+int kidmp_reflectivity_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const double *t, const double *p,
+                              const double *qv, const double *qr, const double *nr, const double *qs, const double *qg,
+                              double *dbz, void *stream)
+{
+    return refl_device<double>(ctx, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz, stream);
+}
+
+int kidmp32_reflectivity_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const float *t, const float *p,
+                                const float *qv, const float *qr, const float *nr, const float *qs, const float *qg,
+                                float *dbz, void *stream)
+{
+    return refl_device<float>(ctx, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz, stream);
+}
+
+int kidmp_reflectivity_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const double *t, const double *p,
+                            const double *qv, const double *qr, const double *nr, const double *qs, const double *qg,
+                            double *dbz)
+{
+    return refl_host<double>(ctx, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz);
+}
+
+int kidmp32_reflectivity_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const float *t, const float *p,
+                              const float *qv, const float *qr, const float *nr, const float *qs, const float *qg,
+                              float *dbz)
+{
+    return refl_host<float>(ctx, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz);
+}
+
+int kidmp_batch_step_host_refl(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt,
+                               double *qv, double *qc, double *qi, double *qr, double *qs, double *qg,
+                               double *ni, double *nr, double *nc, double *nwfa, double *nifa, double *t,
+                               const double *p, const double *w, const double *dz, double *ppt, double *rates,
+                               int32_t *nstep, double *dbz)
+{
+    double *io[12] = {qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t};
+    const double *in[3] = {p, dz, w};
+    return host_pipeline<double>(ctx, ncol, nz, dt, io, in, ppt, rates, nstep,
+        [&](int64_t n, double *const *d, const double *const *f, double *dppt, double *drates, int32_t *dnstep) {
+            return kidmp_batch_step_device(ctx, n, nz, dt, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10], d[11],
+                                           f[0], f[2], f[1], dppt, drates, dnstep, ctx->stream);
+        }, false, false, dbz);
+}
+
+int kidmp32_batch_step_host_refl(kidmp_ctx *ctx, int64_t ncol, int32_t nz, float dt,
+                                 float *qv, float *qc, float *qi, float *qr, float *qs, float *qg,
+                                 float *ni, float *nr, float *nc, float *nwfa, float *nifa, float *t,
+                                 const float *p, const float *w, const float *dz, float *ppt, double *rates,
+                                 int32_t *nstep, int32_t arith, float *dbz)
+{
+    float *io[12] = {qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t};
+    const float *in[3] = {p, dz, w};
+    if (arith != KIDMP_ARITH_P32N && arith != KIDMP_ARITH_F32) return fail(ctx, KIDMP_EINVAL, "kidmp32: arith must be KIDMP_ARITH_P32N or KIDMP_ARITH_F32");
+    return host_pipeline<float>(ctx, ncol, nz, double(dt), io, in, ppt, rates, nstep,
+        [&](int64_t n, float *const *d, const float *const *f, float *dppt, double *drates, int32_t *dnstep) {
+            return kidmp32_batch_step_device(ctx, n, nz, dt, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10], d[11],
+                                             f[0], f[2], f[1], dppt, drates, dnstep, arith, ctx->stream);
+        }, false, false, dbz);
 }
 
 const char *kidmp_kernel_fingerprint(kidmp_ctx *ctx)

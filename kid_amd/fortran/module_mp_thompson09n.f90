@@ -51,6 +51,7 @@ module module_mp_thompson09n
 
   public :: thompson_init, mp_thompson, mp_thompson_batch, mp_thompson_staging, thompson_finalize
   public :: kidmp_precip_sums_valid
+  public :: calc_refl10cm, calc_refl10cm_batch
   logical, public :: is_aerosol_aware = .false.          ! M:28 (read at thompson_init)
   logical, public :: l_rate_diagnostics = .true.         ! replay the save_dg calls of M:2962-3124
   integer, public :: kidmp_device = 0                    ! HIP device ordinal of this process (one GPU)
@@ -82,9 +83,9 @@ module module_mp_thompson09n
   type(c_ptr), save :: mctx = c_null_ptr                 ! kidmp_multi handle, when kidmp_ndevices > 1
   ! Staging arrays of mp_thompson_batch: page-locked (kidmp_host_alloc) and kept between calls, so that the library's
   ! upload / step / download pipeline can move them by DMA.  1 = state (12 profiles), 2 = p, w, dz, 3 = ppt,
-  ! 4 = the 36 rate profiles, 5 = the substep counts.
-  type(c_ptr), save :: hbuf(5) = c_null_ptr
-  integer(c_size_t), save :: hbytes(5) = 0_c_size_t
+  ! 4 = the 36 rate profiles, 5 = the substep counts, 6 = the reflectivity (only when asked for).
+  type(c_ptr), save :: hbuf(6) = c_null_ptr
+  integer(c_size_t), save :: hbytes(6) = 0_c_size_t
 
   interface
      integer(c_int) function kidmp_init(cfg, ctx_out) bind(C, name='kidmp_init')
@@ -169,6 +170,43 @@ module module_mp_thompson09n
        type(c_ptr), value :: qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t, p, w, dz, ppt   ! real(c_float)
        type(c_ptr), value :: rates, nstep            ! NULL, or [ncol][36][nz] doubles / [ncol][4] int32
      end function kidmp32_batch_step_host
+     ! calc_refl10cm, M:4946-5244 (include/kidmp.h): t, p, qv, qr, nr, qs, qg in, dbz out; qs/qg NULL in a warm run
+     integer(c_int) function kidmp_reflectivity_host(ctx, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz) &
+          bind(C, name='kidmp_reflectivity_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qr, nr, qs, qg, dbz         ! real(c_double) [ncol][nz]
+     end function kidmp_reflectivity_host
+     integer(c_int) function kidmp32_reflectivity_host(ctx, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz) &
+          bind(C, name='kidmp32_reflectivity_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qr, nr, qs, qg, dbz         ! real(c_float) [ncol][nz]
+     end function kidmp32_reflectivity_host
+     integer(c_int) function kidmp_batch_step_host_refl(ctx, ncol, nz, dt, qv, qc, qi, qr, qs, qg, ni, nr, &
+          nc, nwfa, nifa, t, p, w, dz, ppt, rates, nstep, dbz) bind(C, name='kidmp_batch_step_host_refl')
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       real(c_double), value :: dt
+       type(c_ptr), value :: qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t, p, w, dz, ppt
+       type(c_ptr), value :: rates, nstep, dbz
+     end function kidmp_batch_step_host_refl
+     integer(c_int) function kidmp32_batch_step_host_refl(ctx, ncol, nz, dt, qv, qc, qi, qr, qs, qg, ni, nr, &
+          nc, nwfa, nifa, t, p, w, dz, ppt, rates, nstep, arith, dbz) bind(C, name='kidmp32_batch_step_host_refl')
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz, arith
+       real(c_float), value :: dt
+       type(c_ptr), value :: qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t, p, w, dz, ppt
+       type(c_ptr), value :: rates, nstep, dbz
+     end function kidmp32_batch_step_host_refl
   end interface
 
 contains
@@ -298,7 +336,7 @@ contains
 
   subroutine thompson_finalize
     integer :: i
-    do i = 1, 5
+    do i = 1, 6
        if (c_associated(hbuf(i))) call kidmp_host_free(hbuf(i))
        hbuf(i) = c_null_ptr;  hbytes(i) = 0_c_size_t
     end do
@@ -331,6 +369,40 @@ contains
     if (.false.) print *, ii, jj          ! ii, jj are debug-only in the reference (M:1269-1274)
   end subroutine mp_thompson
 
+  ! calc_refl10cm, M:4946-5244, with the reference's dummy list: 10-cm radar reflectivity (dBZ) of one column.  qc1d is
+  ! never read by the reference's live code and ii, jj only name the column: all three are accepted and ignored.  As
+  ! shipped (nrbins = 0, M:204) there is no bright band.  Default REAL 8 goes to kidmp_reflectivity_host, REAL 4 to
+  ! kidmp32_reflectivity_host (binary32 in and out, binary64 inside).
+  subroutine calc_refl10cm (qv1d, qc1d, qr1d, nr1d, qs1d, qg1d, t1d, p1d, dBZ, kts, kte, ii, jj)
+    integer, intent(in) :: kts, kte, ii, jj
+    real, dimension(kts:kte), intent(in) :: qv1d, qc1d, qr1d, nr1d, qs1d, qg1d, t1d, p1d
+    real, dimension(kts:kte), intent(inout) :: dBZ
+    call calc_refl10cm_batch(1, kte - kts + 1, qv1d, qr1d, nr1d, qs1d, qg1d, t1d, p1d, dBZ)
+    if (.false.) print *, qc1d(kts), ii, jj
+  end subroutine calc_refl10cm
+
+  ! calc_refl10cm over ncol columns of KiD's (nz, ncol) storage in one call.  qs, qg may be left out in an iiwarm run.
+  subroutine calc_refl10cm_batch(ncol, nz, qv, qr, nr, qs, qg, t, p, dbz)
+    integer, intent(in) :: ncol, nz
+    real, dimension(nz,ncol), intent(in), target :: qv, qr, nr, t, p
+    real, dimension(nz,ncol), intent(in), optional, target :: qs, qg
+    real, dimension(nz,ncol), intent(out), target :: dbz
+    type(c_ptr) :: pqs, pqg
+    integer(c_int) :: rc
+    if (.not. c_associated(ctx)) call thompson_init
+    pqs = c_null_ptr;  pqg = c_null_ptr
+    if (present(qs)) pqs = c_loc(qs)
+    if (present(qg)) pqg = c_loc(qg)
+    if (kind(qv) == c_double) then
+       rc = kidmp_reflectivity_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), &
+            c_loc(qr), c_loc(nr), pqs, pqg, c_loc(dbz))
+    else
+       rc = kidmp32_reflectivity_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), &
+            c_loc(qr), c_loc(nr), pqs, pqg, c_loc(dbz))
+    end if
+    call stop_on_error(rc, 'calc_refl10cm')
+  end subroutine calc_refl10cm_batch
+
   ! The page-locked staging arrays themselves, for a caller whose default REAL is the storage type of kidmp_arith
   ! (8-byte REAL with 'p64', 4-byte REAL with 'p32n' / 'f32'): st(nz,ncol,12) in the argument order of mp_thompson
   ! (qv qc qi qr qs qg ni nr nc nwfa nifa t), fo(nz,ncol,3) = p, w, dz, pp(4,ncol).  Filled in place and passed to
@@ -356,7 +428,7 @@ contains
   ! What KiD never fills may be left out (keyword call): nc, nwfa, nifa and w without is_aerosol_aware (W:36 passes
   ! them unset; the library forms the non-aerosol defaults of M:958-964 on the GPU), qi, qs, qg, ni in an iiwarm run
   ! (they stay zero, W:46-52).  Absent arrays are neither staged nor sent across PCIe.
-  subroutine mp_thompson_batch(ncol, nz, dt, qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t, p, w, dz, ppt)
+  subroutine mp_thompson_batch(ncol, nz, dt, qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t, p, w, dz, ppt, dbz)
     integer, intent(in) :: ncol, nz
     real, intent(in) :: dt
     real, dimension(nz,ncol), intent(inout), target :: qv, qc, qr, nr, t
@@ -364,7 +436,10 @@ contains
     real, dimension(nz,ncol), intent(in), target :: p, dz
     real, dimension(nz,ncol), intent(in), optional, target :: w
     real, dimension(4,ncol), intent(inout), target :: ppt
-    real(c_double), pointer :: s(:,:,:), f(:,:,:), pp(:,:), rates(:,:,:)
+    ! dbz (optional): calc_refl10cm (M:4946-5244) of the post-step state, formed on the GPU in the same host call
+    real, dimension(nz,ncol), intent(out), optional, target :: dbz
+    real(c_double), pointer :: s(:,:,:), f(:,:,:), pp(:,:), rates(:,:,:), zd(:,:)
+    real(c_float), pointer :: z4(:,:)
     real(c_float), pointer :: s4(:,:,:), f4(:,:,:), pp4(:,:)
     integer(c_int32_t), pointer :: nstep(:,:)
     type(c_ptr) :: prates, pnstep, ps(12), pf(3)
@@ -431,9 +506,18 @@ contains
           ps(3) = c_null_ptr;  ps(5) = c_null_ptr;  ps(6) = c_null_ptr;  ps(7) = c_null_ptr
        end if
        if (.not. have_aer) ps(9:11) = c_null_ptr
+       if (present(dbz)) then
+          call staging(6, 4_c_size_t * nprof)
+          call c_f_pointer(hbuf(6), z4, [nz, ncol])
+          rc = kidmp32_batch_step_host_refl(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_float), &
+               ps(1), ps(2), ps(3), ps(4), ps(5), ps(6), ps(7), ps(8), ps(9), ps(10), ps(11), ps(12), &
+               pf(1), pf(2), pf(3), c_loc(pp4), prates, pnstep, arith, hbuf(6))
+          if (rc == 0) dbz = z4
+       else
        rc = kidmp32_batch_step_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_float), &
             ps(1), ps(2), ps(3), ps(4), ps(5), ps(6), ps(7), ps(8), ps(9), ps(10), ps(11), ps(12), &
             pf(1), pf(2), pf(3), c_loc(pp4), prates, pnstep, arith)
+       end if
        call stop_on_error(rc, 'mp_thompson')
        if (.not. inplace) then
        qv = s4(:,:,1);  qc = s4(:,:,2);  qr = s4(:,:,4);  nr = s4(:,:,8);  t = s4(:,:,12)
@@ -478,7 +562,18 @@ contains
        ps(3) = c_null_ptr;  ps(5) = c_null_ptr;  ps(6) = c_null_ptr;  ps(7) = c_null_ptr
     end if
     if (.not. have_aer) ps(9:11) = c_null_ptr
-    if (c_associated(mctx)) then                           ! several GPUs: contiguous column ranges, one pipeline each
+    if (present(dbz)) then                                 ! one GPU, the step followed by calc_refl10cm on the device
+       if (c_associated(mctx)) then
+          write(*,'(a)') ' module_mp_thompson09n: radar reflectivity is not available with kidmp_ndevices > 1'
+          stop 1
+       end if
+       call staging(6, 8_c_size_t * nprof)
+       call c_f_pointer(hbuf(6), zd, [nz, ncol])
+       rc = kidmp_batch_step_host_refl(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_double), &
+            ps(1), ps(2), ps(3), ps(4), ps(5), ps(6), ps(7), ps(8), ps(9), ps(10), ps(11), ps(12), &
+            pf(1), pf(2), pf(3), c_loc(pp), prates, pnstep, hbuf(6))
+       if (rc == 0) dbz = real(zd)
+    else if (c_associated(mctx)) then                      ! several GPUs: contiguous column ranges, one pipeline each
        rc = kidmp_batch_step_host_multi(mctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_double), &
             ps(1), ps(2), ps(3), ps(4), ps(5), ps(6), ps(7), ps(8), ps(9), ps(10), ps(11), ps(12), &
             pf(1), pf(2), pf(3), c_loc(pp), prates, pnstep, kidmp_precip_sums)

@@ -29,6 +29,9 @@ module mphys_thompson09n
 
   ! public module variables of the reference adapter (W:22-24)
   logical :: micro_unset=.True.
+  ! calc_refl10cm (M:4946-5244) of the post-step state, asked for in the same host call and saved as 'dBZ' (z,x) after
+  ! the precipitation diagnostics.  .false.: call sequence and output as without it.
+  logical, public :: l_radar_reflectivity = .false.
   integer:: ih, imom
   character(max_char_len) :: name, units
 
@@ -57,6 +60,7 @@ contains
     real, allocatable, target, save :: st_own(:,:,:), fo_own(:,:,:), ppt_own(:,:)
     real, allocatable, save :: total(:)
     real, allocatable, save :: pptrain_2d_prof(:,:)          ! W:32; saved as 'total_ppt_level' for nx > 1 (W:304-307)
+    real, allocatable, save :: dbz(:,:)                      ! l_radar_reflectivity: (nz, nx)
     real :: rho
     logical :: staged
     integer :: i, k, m, s
@@ -120,7 +124,24 @@ contains
 
     ! ---- all nx columns in one call (replaces the loop around W:143-152) ----
     ppt = 0.0
-    if (is_aerosol_aware) then
+    if (l_radar_reflectivity) then
+       if (allocated(dbz)) then
+          if (size(dbz, 1) /= nz .or. size(dbz, 2) /= nx) deallocate(dbz)
+       end if
+       if (.not. allocated(dbz)) allocate(dbz(nz, nx))
+       if (is_aerosol_aware) then
+          call mp_thompson_batch(nx, nz, dt, st(:,:,S_QV), st(:,:,S_QC), st(:,:,S_QI), st(:,:,S_QR), st(:,:,S_QS), &
+               st(:,:,S_QG), st(:,:,S_NI), st(:,:,S_NR), st(:,:,S_NC), st(:,:,S_NWFA), st(:,:,S_NIFA), st(:,:,S_T), &
+               fo(:,:,1), fo(:,:,2), fo(:,:,3), ppt, dbz)
+       else if (iiwarm) then
+          call mp_thompson_batch(nx, nz, dt, qv=st(:,:,S_QV), qc=st(:,:,S_QC), qr=st(:,:,S_QR), nr=st(:,:,S_NR), &
+               t=st(:,:,S_T), p=fo(:,:,1), dz=fo(:,:,3), ppt=ppt, dbz=dbz)
+       else
+          call mp_thompson_batch(nx, nz, dt, qv=st(:,:,S_QV), qc=st(:,:,S_QC), qi=st(:,:,S_QI), qr=st(:,:,S_QR), &
+               qs=st(:,:,S_QS), qg=st(:,:,S_QG), ni=st(:,:,S_NI), nr=st(:,:,S_NR), t=st(:,:,S_T), p=fo(:,:,1), &
+               dz=fo(:,:,3), ppt=ppt, dbz=dbz)
+       end if
+    else if (is_aerosol_aware) then
        call mp_thompson_batch(nx, nz, dt, st(:,:,S_QV), st(:,:,S_QC), st(:,:,S_QI), st(:,:,S_QR), st(:,:,S_QS), &
             st(:,:,S_QG), st(:,:,S_NI), st(:,:,S_NR), st(:,:,S_NC), st(:,:,S_NWFA), st(:,:,S_NIFA), st(:,:,S_T), &
             fo(:,:,1), fo(:,:,2), fo(:,:,3), ppt)
@@ -187,6 +208,8 @@ contains
        name = 'total_ppt_level'
        call save_dg(pptrain_2d_prof, name, i_dgtime, units, dim='z,x')
     end if
+    ! ---- radar reflectivity (calc_refl10cm of the post-step state; no bright band, as the reference ships it) ----
+    if (l_radar_reflectivity) call save_dg(dbz, 'dBZ', i_dgtime, 'dBZ', dim='z,x')
 
   end Subroutine mphys_thompson09_interfacen
 

@@ -100,6 +100,21 @@ def load_library(path=None):
     L.kidmp_sanity_device.argtypes = [_vp, C.c_int64] + [_vp] * 9 + [_vp]
     L.kidmp_effective_radii_device.restype = C.c_int
     L.kidmp_effective_radii_device.argtypes = [_vp, C.c_int64] + [_vp] * 11 + [_vp]
+    L.kidmp_batch_step_host_diag.restype = C.c_int
+    L.kidmp_batch_step_host_diag.argtypes = [_vp, C.c_int64, C.c_int32, C.c_double] + [_dp] * 17 + [C.POINTER(C.c_int32)]
+    L.kidmp_reflectivity_device.restype = C.c_int
+    L.kidmp_reflectivity_device.argtypes = [_vp, C.c_int64, C.c_int32] + [_vp] * 8 + [_vp]
+    L.kidmp32_reflectivity_device.restype = C.c_int
+    L.kidmp32_reflectivity_device.argtypes = [_vp, C.c_int64, C.c_int32] + [_vp] * 8 + [_vp]
+    L.kidmp_reflectivity_host.restype = C.c_int
+    L.kidmp_reflectivity_host.argtypes = [_vp, C.c_int64, C.c_int32] + [_dp] * 8
+    L.kidmp32_reflectivity_host.restype = C.c_int
+    L.kidmp32_reflectivity_host.argtypes = [_vp, C.c_int64, C.c_int32] + [_fpp] * 8
+    L.kidmp_batch_step_host_refl.restype = C.c_int
+    L.kidmp_batch_step_host_refl.argtypes = [_vp, C.c_int64, C.c_int32, C.c_double] + [_dp] * 17 + [C.POINTER(C.c_int32), _dp]
+    L.kidmp32_batch_step_host_refl.restype = C.c_int
+    L.kidmp32_batch_step_host_refl.argtypes = ([_vp, C.c_int64, C.c_int32, C.c_float] + [_fpp] * 16
+                                               + [_dp, C.POINTER(C.c_int32), C.c_int32, _fpp])
     L.kidmp_kernel_fingerprint.restype = C.c_char_p
     L.kidmp_kernel_fingerprint.argtypes = [_vp]
     L.kidmp32_kernel_fingerprint.restype = C.c_char_p
@@ -241,9 +256,11 @@ class ThompsonMP:
         return tuple(ppt)
 
     # ---- batched host entry: numpy [ncol, nz] ----
-    def batch_step_host(self, st, dt, ppt=None, want_rates=False):
+    def batch_step_host(self, st, dt, ppt=None, want_rates=False, want_dbz=False):
         """numpy float64 [ncol, nz] arrays, in place.  Keys KiD itself never fills may be missing (or None): nc, nwfa,
-        nifa and w for a context without aerosol_aware, qi, qs, qg, ni for an iiwarm context (include/kidmp.h)."""
+        nifa and w for a context without aerosol_aware, qi, qs, qg, ni for an iiwarm context (include/kidmp.h).
+        Returns (ppt, rates); with want_dbz (ppt, rates, dbz): the reflectivity of the post-step state, formed on the
+        device in the same call (kidmp_batch_step_host_refl)."""
         ncol, nz = st["qv"].shape
         ptrs = []
         for k in STATE_NAMES + FORCING_NAMES:
@@ -257,6 +274,12 @@ class ThompsonMP:
         if ppt is None:
             ppt = np.zeros((ncol, 4))
         rates = np.zeros((ncol, NRATES, nz)) if want_rates else None
+        if want_dbz:
+            dbz = np.empty((ncol, nz))
+            self._check(load_library().kidmp_batch_step_host_refl(
+                self._h, ncol, nz, float(dt), *ptrs, _np_ptr(ppt), _np_ptr(rates) if want_rates else None, None,
+                _np_ptr(dbz)))
+            return ppt, rates, dbz
         self._check(load_library().kidmp_batch_step_host(
             self._h, ncol, nz, float(dt), *ptrs, _np_ptr(ppt), _np_ptr(rates) if want_rates else None))
         return ppt, rates
@@ -297,8 +320,9 @@ class ThompsonMP:
     #      and the all-binary32 build ("f32") -- include/kidmp.h, kidmp32_* ----
     ARITH = {"p32n": 0, "f32": 1}
 
-    def batch_step32_host(self, st, dt, arith="p32n", ppt=None, want_rates=False, want_nstep=False):
-        """numpy float32 [ncol, nz] arrays, in place.  Returns (ppt float32 [ncol, 4], rates float64 or None, nstep or None)."""
+    def batch_step32_host(self, st, dt, arith="p32n", ppt=None, want_rates=False, want_nstep=False, want_dbz=False):
+        """numpy float32 [ncol, nz] arrays, in place.  Returns (ppt float32 [ncol, 4], rates float64 or None, nstep or None),
+        with want_dbz a fourth element: the float32 reflectivity of the post-step state (kidmp32_batch_step_host_refl)."""
         ncol, nz = st["qv"].shape
         fpp = C.POINTER(C.c_float)
         for k in STATE_NAMES + FORCING_NAMES:
@@ -309,10 +333,14 @@ class ThompsonMP:
             ppt = np.zeros((ncol, 4), dtype=np.float32)
         rates = np.zeros((ncol, NRATES, nz)) if want_rates else None
         nstep = np.zeros((ncol, 4), dtype=np.int32) if want_nstep else None
-        self._check(load_library().kidmp32_batch_step_host(
-            self._h, ncol, nz, float(dt), *[st[k].ctypes.data_as(fpp) for k in STATE_NAMES + FORCING_NAMES],
-            ppt.ctypes.data_as(fpp), _np_ptr(rates) if want_rates else None,
-            nstep.ctypes.data_as(C.POINTER(C.c_int32)) if want_nstep else None, self.ARITH[arith]))
+        args = ([self._h, ncol, nz, float(dt)] + [st[k].ctypes.data_as(fpp) for k in STATE_NAMES + FORCING_NAMES]
+                + [ppt.ctypes.data_as(fpp), _np_ptr(rates) if want_rates else None,
+                   nstep.ctypes.data_as(C.POINTER(C.c_int32)) if want_nstep else None, self.ARITH[arith]])
+        if want_dbz:
+            dbz = np.empty((ncol, nz), dtype=np.float32)
+            self._check(load_library().kidmp32_batch_step_host_refl(*args, dbz.ctypes.data_as(fpp)))
+            return ppt, rates, nstep, dbz
+        self._check(load_library().kidmp32_batch_step_host(*args))
         return ppt, rates, nstep
 
     def batch_step32(self, st, dt, ppt, arith="p32n", rates=None, nstep=None, stream=None):
@@ -416,6 +444,55 @@ class ThompsonMP:
             self._h, q.numel(), *[st[k].data_ptr() for k in ("t", "p", "qv", "qc", "nc", "qi", "ni", "qs")],
             *[o.data_ptr() for o in out], s))
         return tuple(out)
+
+    REFL_NAMES = ("t", "p", "qv", "qr", "nr", "qs", "qg")      # the inputs of calc_refl10cm that are read (qc1d is not)
+
+    def reflectivity(self, st, out=None, stream=None):
+        """calc_refl10cm (M:4946-5244): 10-cm radar reflectivity in dBZ, [ncol, nz] on the device, of the state in `st`
+        (float64 or float32 CUDA tensors [ncol, nz] with the keys REFL_NAMES; qs and qg may be missing or None in an
+        iiwarm context).  float32 state is widened, computed in binary64 and rounded once.  Asynchronous on `stream`."""
+        import torch
+        q = st["t"]
+        if q.dtype not in (torch.float64, torch.float32) or q.dim() != 2:
+            raise KidmpError("reflectivity: state must be float64 or float32 CUDA tensors [ncol, nz]")
+        ncol, nz = q.shape
+        ptrs = []
+        for k in self.REFL_NAMES:
+            a = st.get(k)
+            if a is None and k in ("qs", "qg"):
+                ptrs.append(None)
+                continue
+            self._want(a, q.dtype, (ncol, nz), "reflectivity: " + k)
+            ptrs.append(a.data_ptr())
+        if out is None:
+            out = torch.empty((ncol, nz), dtype=q.dtype, device=q.device)
+        self._want(out, q.dtype, (ncol, nz), "reflectivity: out")
+        s = stream if stream is not None else torch.cuda.current_stream(q.device).cuda_stream
+        fn = load_library().kidmp_reflectivity_device if q.dtype == torch.float64 else load_library().kidmp32_reflectivity_device
+        self._check(fn(self._h, ncol, nz, *ptrs, out.data_ptr(), s))
+        return out
+
+    def reflectivity_host(self, st):
+        """calc_refl10cm on numpy arrays [ncol, nz] (float64 or float32, keys REFL_NAMES; qs/qg optional in an iiwarm
+        context): returns dbz of the same dtype (kidmp_reflectivity_host / kidmp32_reflectivity_host)."""
+        q = st["t"]
+        if q.dtype not in (np.float64, np.float32) or q.ndim != 2:
+            raise KidmpError("reflectivity_host: state must be float64 or float32 numpy arrays [ncol, nz]")
+        ncol, nz = q.shape
+        pt = C.POINTER(C.c_double) if q.dtype == np.float64 else C.POINTER(C.c_float)
+        ptrs = []
+        for k in self.REFL_NAMES:
+            a = st.get(k)
+            if a is None and k in ("qs", "qg"):
+                ptrs.append(None)
+                continue
+            if not (a.dtype == q.dtype and a.flags.c_contiguous and a.shape == (ncol, nz)):
+                raise KidmpError("reflectivity_host: %s must be contiguous %s [ncol, nz]" % (k, q.dtype))
+            ptrs.append(a.ctypes.data_as(pt))
+        out = np.empty((ncol, nz), dtype=q.dtype)
+        fn = load_library().kidmp_reflectivity_host if q.dtype == np.float64 else load_library().kidmp32_reflectivity_host
+        self._check(fn(self._h, ncol, nz, *ptrs, out.ctypes.data_as(pt)))
+        return out
 
     def kernel_fingerprint(self, arith="p64"):
         """'src:<hash>;vgpr:<n>;lds:<bytes>;scratch:<bytes>' of this context's nz <= 120 column-step kernel, in the
