@@ -1,0 +1,134 @@
+// kidmp_ctx.h -- internal to the units behind include/kidmp.h (not installed): the context, the error and device-guard
+// helpers of every entry point, and what the units kidmp_{capi,diag,host,tables,multi}.hip offer one another.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/kidmp.h"
+#include "thompson_column.h"
+#include "thompson_tables.h"
+
+namespace kidmp {
+constexpr int HOST_NBUF = 3;                         // staging sets of the host pipeline
+constexpr int RED_CHUNKS = 128;                      // column chunks of kidmp_reduce_rates_device
+constexpr int ACC_LIMBS = 6, ACC_N = 4 * ACC_LIMBS;  // k_ppt_exact: six 64-bit limbs per species
+static_assert(ACC_N == KIDMP_PPT_LIMBS, "include/kidmp.h");
+// k_sanity: maxima of qc, qr, nr, qs, qi, qg, ni, then the numbers of negative entries of those and of qv
+constexpr int SANITY_MAX = 7, SANITY_NEG = 8, SANITY_N = SANITY_MAX + SANITY_NEG;
+}
+
+struct kidmp_ctx {
+    kidmp_cfg cfg{};
+    kidmp::Consts hc{};
+    kidmp::Bins hb{};
+    kidmp::Consts *d_consts = nullptr;
+    kidmp::Bins *d_bins = nullptr;
+    kidmp::Tables tables{};
+    bool ready = false;
+    double init_s = 0.;
+    std::string err;
+    // staging for the host-array entries: a ring of HOST_NBUF column chunks in HBM, one stream per direction and
+    // one for the kernel, so that the upload of chunk i+1, the step of chunk i and the download of chunk i-1 overlap
+    double *d_stage = nullptr;
+    size_t stage_bytes = 0;
+    hipStream_t stream = nullptr;                    // the context's compute stream
+    hipStream_t s_h2d = nullptr, s_d2h = nullptr;
+    hipEvent_t ev_up[kidmp::HOST_NBUF] = {}, ev_step[kidmp::HOST_NBUF] = {}, ev_down[kidmp::HOST_NBUF] = {};
+    int64_t host_chunk = 0;                          // columns per chunk; 0 = chosen per call (kidmp_set_host_chunk)
+    int debug_stop = 0;
+    int cslot = -1;
+    // partial sums of kidmp_reduce_rates_device, accumulators of kidmp_sanity_device
+    double *d_red = nullptr;
+    size_t red_elems = 0;
+    unsigned long long *d_sanity = nullptr;
+    // exact (fixed-point) domain sums of the surface precipitation: KIDMP_PPT_LIMBS 64-bit accumulators
+    unsigned long long *d_acc = nullptr;
+    std::string fingerprint;
+};
+
+namespace kidmp {
+// ONE object for all units: kidmp_last_error(NULL) reads the failures that have no context (defined in kidmp_capi.hip)
+extern thread_local std::string g_err;
+
+template <class C> int fail(C *c, int code, const std::string &msg)   // C: kidmp_ctx or kidmp_multi
+{
+    if (c) c->err = msg;
+    g_err = msg;
+    return code;
+}
+inline int fail(std::nullptr_t, int code, const std::string &msg) { return fail((kidmp_ctx *)nullptr, code, msg); }
+inline int hipfail(kidmp_ctx *c, hipError_t e, const char *what) { return fail(c, KIDMP_EHIP, std::string(what) + ": " + hipGetErrorString(e)); }
+#define HIPTRY(c, x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return hipfail((c), e_, #x); } while (0)
+
+// `also`: what else the entry needs before anything is touched (a name, a directory); it fails with the same message
+inline int require_ready(kidmp_ctx *c, const char *msg = "kidmp: context not initialised", bool also = true)
+{ return c && c->ready && also ? KIDMP_OK : fail(c, KIDMP_ESTATE, msg); }
+inline bool valid_arith(int32_t arith) { return arith == KIDMP_ARITH_P32N || arith == KIDMP_ARITH_F32; }
+constexpr char BAD_ARITH[] = "kidmp32: arith must be KIDMP_ARITH_P32N or KIDMP_ARITH_F32";
+
+// Every entry point that touches the device runs with the context's device current and puts the caller's
+// device back on exit: the caller (torch, a Fortran host driving several GPUs) may have another one selected,
+// and hipMalloc / kernel launches / the __constant__ slot all bind to the current device.
+struct DeviceGuard {
+    int prev = -1;
+    bool switched = false;
+    hipError_t err = hipSuccess;
+    explicit DeviceGuard(int dev)
+    {
+        err = hipGetDevice(&prev);
+        if (err == hipSuccess && prev != dev) {
+            err = hipSetDevice(dev);
+            switched = err == hipSuccess;
+        }
+    }
+    ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
+    DeviceGuard(const DeviceGuard &) = delete; DeviceGuard &operator=(const DeviceGuard &) = delete;
+};
+#define GUARD(c) DeviceGuard guard_((c)->cfg.device); if (guard_.err != hipSuccess) return hipfail((c), guard_.err, "hipSetDevice")
+
+// A device pointer handed to a device entry must live on the context's GPU: a buffer of another GPU would be
+// reached through peer access at best and fault at worst.
+inline int check_on_device(kidmp_ctx *c, const void *p, const char *what)
+{
+    if (!p) return KIDMP_OK;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return KIDMP_OK; }   // unregistered: let the launch decide
+    if (at.type == hipMemoryTypeDevice && at.device != c->cfg.device)
+        return fail(c, KIDMP_EINVAL, std::string("kidmp: ") + what + " lives on device " + std::to_string(at.device)
+                                     + ", the context is bound to device " + std::to_string(c->cfg.device));
+    return KIDMP_OK;
+}
+
+inline int check_step_args(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, const void *const *ptrs, int nptr)
+{
+    if (int rc = require_ready(ctx)) return rc;
+    if (ncol < 0) return fail(ctx, KIDMP_EINVAL, "kidmp: ncol < 0");
+    if (nz < 2 || nz > KIDMP_MAX_NZ) return fail(ctx, KIDMP_EINVAL, "kidmp: nz outside [2, KIDMP_MAX_NZ]");
+    if (!(dt > 0.)) return fail(ctx, KIDMP_EINVAL, "kidmp: dt must be > 0");
+    for (int i = 0; i < nptr && ncol > 0; ++i)                 // an empty batch has nothing to point at
+        if (!ptrs[i]) return fail(ctx, KIDMP_EINVAL, "kidmp: null array argument");
+    return KIDMP_OK;
+}
+
+// kidmp_capi.hip: the one body of the step's device entries (R = double: p64; float: `arith` selects p32n or f32), which
+// also steps every chunk of the host pipeline; io = qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t
+template <class R>
+int step_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, R dt, R *const *io, const R *p, const R *w, const R *dz,
+                R *ppt, double *rates, int32_t *nstep, int32_t arith, void *stream);
+int check_refl_args(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const void *const *req, int nreq, const void *qs, const void *qg);
+
+// kidmp_diag.hip.  The two void ones only launch: the caller asks hipGetLastError().  v = qc, qr, nr, qs, qi, qg, ni, qv
+template <class T> void launch_default_aerosols(int64_t n, T Nt_c, const T *qv, const T *t, const T *p, T *nc, T *nwfa, T *nifa, hipStream_t s);
+void launch_sanity(int64_t n, const double *const (&v)[SANITY_NEG], unsigned long long *acc, hipStream_t s);
+template <class T> hipError_t launch_ppt_exact(int64_t ncol, const T *ppt, unsigned long long *acc, hipStream_t s);
+
+// kidmp_host.hip.  What an entry may ask of the pipeline beyond the step: the exact precipitation sums and the sanity
+// scan (left in ctx->d_acc / d_sanity), and the reflectivity of every chunk's post-step state.
+template <class T> struct PipelineExtras { bool exact_sums = false, scan_sanity = false; T *dbz = nullptr; };
+template <class T>
+int host_pipeline(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, T *const *io, const T *const *in, T *ppt,
+                  double *rates, int32_t *nstep, int32_t arith, const PipelineExtras<T> &extra = {});
+}  // namespace kidmp

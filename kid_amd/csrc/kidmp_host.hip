@@ -1,0 +1,297 @@
+// kidmp_host.hip -- the entries of include/kidmp.h that take host arrays.
+#include "kidmp_ctx.h"
+#include "thompson_reflectivity.h"
+
+using namespace kidmp;
+
+namespace {
+// ---- the host-array entries (kidmp_batch_step_host*, kidmp32_batch_step_host): a three-stage pipeline over column chunks ----
+// The batch is cut into chunks of CH columns; chunk i is uploaded on the context's H2D stream, stepped on its compute
+// stream and downloaded on its D2H stream, through a ring of HOST_NBUF staging sets in HBM, so the two DMA directions
+// (PCIe is full duplex) and the kernel work on three different chunks at once.  Host arrays that are page-locked
+// (kidmp_host_alloc, or the caller's own hipHostMalloc / hipHostRegister) are moved by the DMA
+// engines asynchronously; pageable arrays still work, but the runtime stages them through its own bounce buffer and
+// the calling thread waits for each copy.  Per column-step the boundary moves 14 (15 with w) profiles in and 12 out
+// (+36 for the rate diagnostics): about 25 KB in binary64.
+int64_t pick_host_chunk(const kidmp_ctx *ctx, int64_t ncol)
+{
+    if (ctx->host_chunk > 0) return ctx->host_chunk < ncol ? ctx->host_chunk : ncol;
+    if (ncol <= 2048) return ncol;                            // one chunk: nothing to overlap with
+    int64_t ch = (ncol + 3) / 4;                              // at least four chunks ...
+    ch = (ch + 255) / 256 * 256;
+    return ch > 8192 ? 8192 : ch;                             // ... of at most 8 192 columns (7.9 MB per profile slice; measured optimum)
+}
+
+// the context's staging memory only grows
+int ensure_stage(kidmp_ctx *ctx, size_t need)
+{
+    if (need <= ctx->stage_bytes) return KIDMP_OK;
+    if (ctx->d_stage) (void)hipFree(ctx->d_stage);
+    ctx->d_stage = nullptr;
+    ctx->stage_bytes = 0;
+    HIPTRY(ctx, hipMalloc((void **)&ctx->d_stage, need));
+    ctx->stage_bytes = need;
+    return KIDMP_OK;
+}
+
+// Leaving host_pipeline with an error must not leave DMA in flight towards the caller's arrays.
+struct PipelineDrain {
+    kidmp_ctx *c;
+    bool armed = true;
+    ~PipelineDrain()
+    {
+        if (!armed) return;
+        (void)hipStreamSynchronize(c->s_h2d);
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipStreamSynchronize(c->s_d2h);
+    }
+};
+
+// host arrays: chunks of columns through the context's staging memory on its compute stream, one after the other
+template <class T>
+int refl_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const T *t, const T *p, const T *qv, const T *qr, const T *nr,
+              const T *qs, const T *qg, T *dbz)
+{
+    const void *req[] = {t, p, qv, qr, nr, dbz};
+    if (int rc = check_refl_args(ctx, ncol, nz, req, 6, qs, qg)) return rc;
+    if (ncol == 0) return KIDMP_OK;
+    GUARD(ctx);
+    const int64_t CH = pick_host_chunk(ctx, ncol);
+    const size_t b_prof = (size_t(CH) * size_t(nz) * sizeof(T) + 255) / 256 * 256;
+    if (int rc = ensure_stage(ctx, 8 * b_prof)) return rc;
+    char *const base = reinterpret_cast<char *>(ctx->d_stage);
+    T *d[8];
+    for (int v = 0; v < 8; ++v) d[v] = reinterpret_cast<T *>(base + size_t(v) * b_prof);
+    const T *h[7] = {t, p, qv, qr, nr, qs, qg};
+    const ReflConsts c = refl_consts(ctx->hc);
+    hipError_t e = hipSuccess;
+    for (int64_t c0 = 0; c0 < ncol && e == hipSuccess; c0 += CH) {
+        const int64_t n = c0 + CH <= ncol ? CH : ncol - c0;
+        const size_t off = size_t(c0) * size_t(nz), cnt = size_t(n) * size_t(nz);
+        for (int v = 0; v < 7 && e == hipSuccess; ++v)
+            if (h[v]) e = hipMemcpyAsync(d[v], h[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess)
+            e = launch_reflectivity<T>(c, n, nz, d[0], d[1], d[2], d[3], d[4], qs ? d[5] : nullptr, qg ? d[6] : nullptr,
+                                       d[7], ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dbz + off, d[7], cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(ctx->stream);        // no copy may still be in flight towards the caller's arrays
+    HIPTRY(ctx, e);
+    HIPTRY(ctx, es);
+    return KIDMP_OK;
+}
+}  // namespace
+
+// extra.dbz (optional): the reflectivity of calc_refl10cm (M:4946-5244) of every chunk's post-step state, formed on the compute
+// stream right after the step; it is the only extra array that comes back, and the staging set grows by its one profile.
+template <class T>
+int kidmp::host_pipeline(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, T *const *io, const T *const *in, T *ppt,
+                         double *rates, int32_t *nstep, int32_t arith, const PipelineExtras<T> &extra)
+{
+    const auto [exact_sums, scan_sanity, dbz] = extra;
+    if (int rc = require_ready(ctx)) return rc;
+    if (dbz && !refl_consts_supported(ctx->hc)) return fail(ctx, KIDMP_ESTATE, "kidmp: reflectivity exponents differ from the kernel's");
+    // Arrays the caller may leave out (NULL), as KiD itself does (W:36 passes nc1d, nwfa1d, nifa1d unset; a warm run
+    // never touches the frozen species, W:46-52): they then neither cross PCIe nor come back.
+    //   nc, nwfa, nifa (all three)   non-aerosol contexts: the defaults of M:958-964, formed on the device
+    //   qi, qs, qg, ni (all four)    iiwarm contexts: exactly zero (and they stay zero)
+    const bool has_w = ctx->cfg.is_aerosol_aware != 0;
+    const int n_aer = (io[8] != nullptr) + (io[9] != nullptr) + (io[10] != nullptr);
+    const int n_frz = (io[2] != nullptr) + (io[4] != nullptr) + (io[5] != nullptr) + (io[6] != nullptr);
+    const bool skip_aer = n_aer == 0 && ncol > 0, skip_frz = n_frz == 0 && ncol > 0;
+    if (ncol > 0 && n_aer != 0 && n_aer != 3) return fail(ctx, KIDMP_EINVAL, "kidmp: nc, nwfa, nifa must be given or left out together");
+    if (ncol > 0 && n_frz != 0 && n_frz != 4) return fail(ctx, KIDMP_EINVAL, "kidmp: qi, qs, qg, ni must be given or left out together");
+    if (skip_aer && has_w) return fail(ctx, KIDMP_EINVAL, "kidmp: an aerosol-aware context needs nc, nwfa and nifa");
+    if (skip_frz && !ctx->cfg.iiwarm) return fail(ctx, KIDMP_EINVAL, "kidmp: a mixed-phase context needs qi, qs, qg and ni");
+    const void *ptrs[15];
+    int np = 0;
+    for (int v = 0; v < 12; ++v) {
+        const bool optional_out = (skip_aer && v >= 8 && v <= 10) || (skip_frz && (v == 2 || v == 4 || v == 5 || v == 6));
+        if (!optional_out) ptrs[np++] = io[v];
+    }
+    ptrs[np++] = in[0]; ptrs[np++] = in[1]; ptrs[np++] = ppt;
+    if (int rc = check_step_args(ctx, ncol, nz, dt, ptrs, np)) return rc;
+    if (has_w && !in[2] && ncol > 0) return fail(ctx, KIDMP_EINVAL, "kidmp: an aerosol-aware context needs the updraft profile w");
+    if (ncol == 0) {
+        if (exact_sums || scan_sanity) {
+            GUARD(ctx);
+            if (exact_sums) HIPTRY(ctx, hipMemset(ctx->d_acc, 0, ACC_N * sizeof(unsigned long long)));
+            if (scan_sanity) HIPTRY(ctx, hipMemset(ctx->d_sanity, 0, SANITY_N * sizeof(unsigned long long)));
+        }
+        return KIDMP_OK;
+    }
+    GUARD(ctx);
+    const int64_t CH = pick_host_chunk(ctx, ncol);
+    const int64_t nchunk = (ncol + CH - 1) / CH;
+    const int nbuf = nchunk < HOST_NBUF ? int(nchunk) : HOST_NBUF;
+    const size_t prof = size_t(CH) * size_t(nz);
+    // one staging set: [rates (double)] [15 profiles + ppt (T)] [nstep (int32)], each part 256-byte aligned
+    auto up256 = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t b_rates = rates ? up256(size_t(KIDMP_NRATES) * prof * sizeof(double)) : 0;
+    const size_t b_prof = up256(prof * sizeof(T));
+    const size_t b_ppt = up256(4 * size_t(CH) * sizeof(T));
+    const size_t b_nstep = nstep ? up256(4 * size_t(CH) * sizeof(int32_t)) : 0;
+    const size_t b_dbz = dbz ? b_prof : 0;
+    const size_t b_set = b_rates + 15 * b_prof + b_ppt + b_nstep + b_dbz;
+    if (int rc = ensure_stage(ctx, b_set * size_t(nbuf))) return rc;
+    char *const base = reinterpret_cast<char *>(ctx->d_stage);
+    PipelineDrain drain{ctx};
+    if (exact_sums) HIPTRY(ctx, hipMemsetAsync(ctx->d_acc, 0, ACC_N * sizeof(unsigned long long), ctx->stream));
+    if (scan_sanity) HIPTRY(ctx, hipMemsetAsync(ctx->d_sanity, 0, SANITY_N * sizeof(unsigned long long), ctx->stream));
+    for (int64_t i = 0; i < nchunk; ++i) {
+        const int b = int(i % nbuf);
+        const int64_t c0 = i * CH, n = (c0 + CH <= ncol ? CH : ncol - c0);
+        const size_t off = size_t(c0) * size_t(nz), cnt = size_t(n) * size_t(nz);
+        char *set = base + size_t(b) * b_set;
+        double *drates = rates ? reinterpret_cast<double *>(set) : nullptr;
+        T *dio[12]; const T *din[3];
+        char *q = set + b_rates;
+        for (int v = 0; v < 12; ++v) { dio[v] = reinterpret_cast<T *>(q); q += b_prof; }
+        T *dinw[3];
+        for (int v = 0; v < 3; ++v) { dinw[v] = reinterpret_cast<T *>(q); din[v] = dinw[v]; q += b_prof; }
+        T *dppt = reinterpret_cast<T *>(q); q += b_ppt;
+        int32_t *dnstep = nstep ? reinterpret_cast<int32_t *>(q) : nullptr;
+        q += b_nstep;
+        T *ddbz = dbz ? reinterpret_cast<T *>(q) : nullptr;
+        if (!has_w || !in[2]) din[2] = nullptr;
+        // upload (the set is free once the download of the chunk that used it last has finished)
+        if (i >= nbuf) HIPTRY(ctx, hipStreamWaitEvent(ctx->s_h2d, ctx->ev_down[b], 0));
+        for (int v = 0; v < 12; ++v)
+            if (io[v]) HIPTRY(ctx, hipMemcpyAsync(dio[v], io[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->s_h2d));
+        for (int v = 0; v < (din[2] ? 3 : 2); ++v) HIPTRY(ctx, hipMemcpyAsync(dinw[v], in[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->s_h2d));
+        HIPTRY(ctx, hipMemcpyAsync(dppt, ppt + 4 * c0, 4 * size_t(n) * sizeof(T), hipMemcpyHostToDevice, ctx->s_h2d));
+        HIPTRY(ctx, hipEventRecord(ctx->ev_up[b], ctx->s_h2d));
+        // step
+        HIPTRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_up[b], 0));
+        if (skip_frz)
+            for (int v : {2, 4, 5, 6}) HIPTRY(ctx, hipMemsetAsync(dio[v], 0, cnt * sizeof(T), ctx->stream));
+        if (skip_aer) {
+            launch_default_aerosols<T>(int64_t(cnt), T(ctx->hc.Nt_c), dio[0], dio[11], din[0], dio[8], dio[9], dio[10], ctx->stream);
+            HIPTRY(ctx, hipGetLastError());
+        }
+        if (int rc = step_device<T>(ctx, n, nz, T(dt), dio, din[0], din[2], din[1], dppt, drates, dnstep, arith, ctx->stream)) return rc;
+        if (dbz)                                              // calc_refl10cm of the chunk's post-step t, p, qv, qr, nr, qs, qg
+            HIPTRY(ctx, launch_reflectivity<T>(refl_consts(ctx->hc), n, nz, dio[11], din[0], dio[0], dio[3], dio[7], dio[4],
+                                               dio[5], ddbz, ctx->stream));
+        if (exact_sums) HIPTRY(ctx, launch_ppt_exact<T>(n, dppt, ctx->d_acc, ctx->stream));   // the chunk's share of the domain sums
+        if constexpr (std::is_same<T, double>::value)
+            if (scan_sanity) {                                // the scan of M:1025-1094 over the chunk's end state (exact integer atomics)
+                launch_sanity(int64_t(cnt), {dio[1], dio[3], dio[7], dio[4], dio[2], dio[5], dio[6], dio[0]}, ctx->d_sanity, ctx->stream);
+                HIPTRY(ctx, hipGetLastError());
+            }
+        HIPTRY(ctx, hipEventRecord(ctx->ev_step[b], ctx->stream));
+        // download
+        HIPTRY(ctx, hipStreamWaitEvent(ctx->s_d2h, ctx->ev_step[b], 0));
+        for (int v = 0; v < 12; ++v)
+            if (io[v]) HIPTRY(ctx, hipMemcpyAsync(io[v] + off, dio[v], cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->s_d2h));
+        HIPTRY(ctx, hipMemcpyAsync(ppt + 4 * c0, dppt, 4 * size_t(n) * sizeof(T), hipMemcpyDeviceToHost, ctx->s_d2h));
+        if (rates) HIPTRY(ctx, hipMemcpyAsync(rates + size_t(KIDMP_NRATES) * off, drates, size_t(KIDMP_NRATES) * cnt * sizeof(double), hipMemcpyDeviceToHost, ctx->s_d2h));
+        if (nstep) HIPTRY(ctx, hipMemcpyAsync(nstep + 4 * c0, dnstep, 4 * size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->s_d2h));
+        if (dbz) HIPTRY(ctx, hipMemcpyAsync(dbz + off, ddbz, cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->s_d2h));
+        HIPTRY(ctx, hipEventRecord(ctx->ev_down[b], ctx->s_d2h));
+    }
+    HIPTRY(ctx, hipStreamSynchronize(ctx->s_d2h));           // everything else precedes it through the events
+    drain.armed = false;
+    return KIDMP_OK;
+}
+template int kidmp::host_pipeline<double>(kidmp_ctx *, int64_t, int32_t, double, double *const *, const double *const *, double *,
+                                          double *, int32_t *, int32_t, const PipelineExtras<double> &);   // for kidmp_multi.hip
+
+extern "C" {
+void *kidmp_host_alloc(size_t bytes)
+{
+    void *p = nullptr;
+    const hipError_t e = hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocPortable);
+    if (e != hipSuccess) { g_err = std::string("kidmp_host_alloc: ") + hipGetErrorString(e); return nullptr; }
+    return p;
+}
+void kidmp_host_free(void *p) { if (p) (void)hipHostFree(p); }
+int kidmp_set_host_chunk(kidmp_ctx *ctx, int64_t ncol_per_chunk)
+{
+    if (int rc = require_ready(ctx)) return rc;
+    if (ncol_per_chunk < 0) return fail(ctx, KIDMP_EINVAL, "kidmp_set_host_chunk: negative chunk size");
+    ctx->host_chunk = ncol_per_chunk;
+    return KIDMP_OK;
+}
+
+int kidmp_batch_step_host_refl(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt,
+                               double *qv, double *qc, double *qi, double *qr, double *qs, double *qg,
+                               double *ni, double *nr, double *nc, double *nwfa, double *nifa, double *t,
+                               const double *p, const double *w, const double *dz, double *ppt, double *rates,
+                               int32_t *nstep, double *dbz)
+{
+    double *io[12] = {qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t};
+    const double *in[3] = {p, dz, w};
+    PipelineExtras<double> extra;
+    extra.dbz = dbz;                                          // NULL: the plain step (kidmp_batch_step_host, _diag)
+    return host_pipeline<double>(ctx, ncol, nz, dt, io, in, ppt, rates, nstep, 0, extra);
+}
+int kidmp32_batch_step_host_refl(kidmp_ctx *ctx, int64_t ncol, int32_t nz, float dt,
+                                 float *qv, float *qc, float *qi, float *qr, float *qs, float *qg,
+                                 float *ni, float *nr, float *nc, float *nwfa, float *nifa, float *t,
+                                 const float *p, const float *w, const float *dz, float *ppt, double *rates,
+                                 int32_t *nstep, int32_t arith, float *dbz)
+{
+    float *io[12] = {qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t};
+    const float *in[3] = {p, dz, w};
+    if (!valid_arith(arith)) return fail(ctx, KIDMP_EINVAL, BAD_ARITH);
+    PipelineExtras<float> extra;
+    extra.dbz = dbz;
+    return host_pipeline<float>(ctx, ncol, nz, double(dt), io, in, ppt, rates, nstep, arith, extra);
+}
+
+int kidmp_batch_step_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt,
+                          double *qv, double *qc, double *qi, double *qr, double *qs, double *qg,
+                          double *ni, double *nr, double *nc, double *nwfa, double *nifa, double *t,
+                          const double *p, const double *w, const double *dz, double *ppt, double *rates)
+{
+    return kidmp_batch_step_host_diag(ctx, ncol, nz, dt, qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t, p, w, dz,
+                                      ppt, rates, nullptr);
+}
+
+int kidmp_batch_step_host_diag(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt,
+                               double *qv, double *qc, double *qi, double *qr, double *qs, double *qg,
+                               double *ni, double *nr, double *nc, double *nwfa, double *nifa, double *t,
+                               const double *p, const double *w, const double *dz, double *ppt, double *rates,
+                               int32_t *nstep)
+{
+    return kidmp_batch_step_host_refl(ctx, ncol, nz, dt, qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t, p, w, dz, ppt, rates, nstep, nullptr);
+}
+
+int kidmp_column_step(kidmp_ctx *ctx, int32_t nz, double dt,
+                      double *qv1d, double *qc1d, double *qi1d, double *qr1d, double *qs1d, double *qg1d,
+                      double *ni1d, double *nr1d, double *nc1d, double *nwfa1d, double *nifa1d, double *t1d,
+                      const double *p1d, const double *w1d, const double *dzq, double *ppt)
+{
+    return kidmp_batch_step_host(ctx, 1, nz, dt, qv1d, qc1d, qi1d, qr1d, qs1d, qg1d, ni1d, nr1d, nc1d, nwfa1d, nifa1d, t1d, p1d, w1d, dzq, ppt, nullptr);
+}
+
+int kidmp32_batch_step_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, float dt,
+                            float *qv, float *qc, float *qi, float *qr, float *qs, float *qg,
+                            float *ni, float *nr, float *nc, float *nwfa, float *nifa, float *t,
+                            const float *p, const float *w, const float *dz, float *ppt, double *rates,
+                            int32_t *nstep, int32_t arith)
+{
+    return kidmp32_batch_step_host_refl(ctx, ncol, nz, dt, qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t, p, w, dz, ppt, rates, nstep, arith, nullptr);
+}
+int kidmp32_column_step(kidmp_ctx *ctx, int32_t nz, float dt,
+                        float *qv1d, float *qc1d, float *qi1d, float *qr1d, float *qs1d, float *qg1d,
+                        float *ni1d, float *nr1d, float *nc1d, float *nwfa1d, float *nifa1d, float *t1d,
+                        const float *p1d, const float *w1d, const float *dzq, float *ppt, int32_t arith)
+{
+    return kidmp32_batch_step_host(ctx, 1, nz, dt, qv1d, qc1d, qi1d, qr1d, qs1d, qg1d, ni1d, nr1d, nc1d, nwfa1d, nifa1d, t1d, p1d, w1d, dzq, ppt, nullptr, nullptr, arith);
+}
+
+int kidmp_reflectivity_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const double *t, const double *p,
+                            const double *qv, const double *qr, const double *nr, const double *qs, const double *qg,
+                            double *dbz)
+{
+    return refl_host<double>(ctx, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz);
+}
+int kidmp32_reflectivity_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const float *t, const float *p,
+                              const float *qv, const float *qr, const float *nr, const float *qs, const float *qg,
+                              float *dbz)
+{
+    return refl_host<float>(ctx, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz);
+}
+}  // extern "C"
