@@ -244,12 +244,30 @@ int kidmp_sanity_device(kidmp_ctx *ctx, int64_t n, const double *qc, const doubl
                         double *out15, void *stream);
 
 /* calc_effectRad (M:4834-4935): radiation effective radii of cloud water, cloud ice and snow, consistent with the
- * scheme's size distributions.  n = ncol*nz elements, device pointers; re_qc/re_qi/re_qs are INOUT like the reference's
- * (a level without the species keeps the caller's value; the scheme's 3-D driver presets 2.49E-6, 4.99E-6, 9.99E-6 m
- * and clamps afterwards, M:1111-1121). */
+ * scheme's size distributions.  n = ncol*nz elements (every level stands alone); re_qc/re_qi/re_qs are INOUT like the
+ * reference's (a level without the species keeps the caller's value, M:4873 / 4888 / 4897; the scheme's 3-D driver
+ * presets 2.49E-6, 4.99E-6, 9.99E-6 m and clamps afterwards, M:1111-1121).
+ *   kidmp_effective_radii_device    device pointers, asynchronous on `stream`; every array required
+ *   kidmp_effective_radii_host      host arrays (the compatibility procedure behind the Fortran calc_effectRad), moved in
+ *                                   chunks of kidmp_set_host_chunk columns of a nominal 128 levels
+ *   kidmp32_effective_radii_device, kidmp32_effective_radii_host   binary32 arrays: inputs widened to binary64, the same
+ *                                   binary64 arithmetic, the result rounded to binary32 once (not the reference's native
+ *                                   binary32 arithmetic)
+ * The host entry and the kidmp32_* entries accept what a caller may not have: nc NULL in a context that is not
+ * aerosol-aware (nc = Nt_c there, M:4863; an aerosol-aware context needs it), and in an iiwarm context qi + ni NULL, qs
+ * NULL (zero) and re_qi + re_qs NULL (not formed). */
 int kidmp_effective_radii_device(kidmp_ctx *ctx, int64_t n, const double *t, const double *p, const double *qv,
                                  const double *qc, const double *nc, const double *qi, const double *ni,
                                  const double *qs, double *re_qc, double *re_qi, double *re_qs, void *stream);
+int kidmp_effective_radii_host(kidmp_ctx *ctx, int64_t n, const double *t, const double *p, const double *qv,
+                               const double *qc, const double *nc, const double *qi, const double *ni,
+                               const double *qs, double *re_qc, double *re_qi, double *re_qs);
+int kidmp32_effective_radii_device(kidmp_ctx *ctx, int64_t n, const float *t, const float *p, const float *qv,
+                                   const float *qc, const float *nc, const float *qi, const float *ni,
+                                   const float *qs, float *re_qc, float *re_qi, float *re_qs, void *stream);
+int kidmp32_effective_radii_host(kidmp_ctx *ctx, int64_t n, const float *t, const float *p, const float *qv,
+                                 const float *qc, const float *nc, const float *qi, const float *ni,
+                                 const float *qs, float *re_qc, float *re_qi, float *re_qs);
 
 /* calc_refl10cm (M:4946-5244): 10-cm radar reflectivity (Rayleigh, dBZ) of rain, snow and graupel from the scheme's own
  * size distributions -- what WRF and MPAS write as REFL_10CM.  Every level of every column receives
@@ -289,6 +307,48 @@ int kidmp32_batch_step_host_refl(kidmp_ctx *ctx, int64_t ncol, int32_t nz, float
                                  float *nc, float *nwfa, float *nifa, float *t,
                                  const float *p, const float *w, const float *dz,
                                  float *ppt, double *rates, int32_t *nstep, int32_t arith, float *dbz);
+
+/* ---- the column outputs: what a host model takes from the state beside the step ----
+ * The scheme's own driver forms the effective radii from each column right after the step (M:1109-1121: presets, then
+ * calc_effectRad, M:4834-4935), and WRF / MPAS form REFL_10CM (calc_refl10cm, M:4946-5244) beside them.  These entries
+ * return any of the four profiles; when the radii AND dbz are wanted, one kernel forms them from a single read of the
+ * column (one wavefront per column).
+ *   dbz                    may be NULL; as kidmp_reflectivity_*
+ *   re_qc, re_qi, re_qs    requested together or not at all; in an iiwarm context re_qi and re_qs may be NULL beside
+ *                          re_qc.  OUT, in the driver's form: a level without the species receives the preset 2.49E-6 /
+ *                          4.99E-6 / 9.99E-6 m (M:1111-1113); the driver's clamps after the call (M:1118-1120) change nothing
+ *                          after the subroutine's own.  Values are those of kidmp_effective_radii_* started from the presets.
+ * Nothing requested (out NULL or all four NULL) = the plain call.  kidmp32_*: binary32 arrays, binary64 arithmetic, one
+ * rounding, as above. */
+typedef struct kidmp_outputs   { double *dbz, *re_qc, *re_qi, *re_qs; } kidmp_outputs;
+typedef struct kidmp32_outputs { float  *dbz, *re_qc, *re_qi, *re_qs; } kidmp32_outputs;
+/* Device pointers [ncol*nz], asynchronous on `stream`, no allocation: capturable into a hipGraph like the step.
+ * IN: t, p, qv; qc, nc, qi, ni (radii); qr, nr (dbz); qs, qg (both).  nc may be NULL unless the context is aerosol-aware;
+ * qi + ni and qs + qg may be NULL pairwise in an iiwarm context (zero). */
+int kidmp_column_outputs_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const double *t, const double *p,
+                                const double *qv, const double *qc, const double *nc, const double *qi, const double *ni,
+                                const double *qr, const double *nr, const double *qs, const double *qg,
+                                const kidmp_outputs *out, void *stream);
+int kidmp32_column_outputs_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const float *t, const float *p,
+                                  const float *qv, const float *qc, const float *nc, const float *qi, const float *ni,
+                                  const float *qr, const float *nr, const float *qs, const float *qg,
+                                  const kidmp32_outputs *out, void *stream);
+/* kidmp_batch_step_host_diag / kidmp32_batch_step_host followed, chunk by chunk on the device, by ONE launch that forms the
+ * requested outputs (host arrays [ncol][nz]) from the chunk's post-step state; only requested profiles are staged and
+ * cross PCIe.  State, ppt, rates and nstep are those of the plain entry bit for bit; kidmp[32]_batch_step_host_refl are
+ * this call with dbz alone. */
+int kidmp_batch_step_host_out(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt,
+                              double *qv, double *qc, double *qi, double *qr,
+                              double *qs, double *qg, double *ni, double *nr,
+                              double *nc, double *nwfa, double *nifa, double *t,
+                              const double *p, const double *w, const double *dz,
+                              double *ppt, double *rates, int32_t *nstep, const kidmp_outputs *out);
+int kidmp32_batch_step_host_out(kidmp_ctx *ctx, int64_t ncol, int32_t nz, float dt,
+                                float *qv, float *qc, float *qi, float *qr,
+                                float *qs, float *qg, float *ni, float *nr,
+                                float *nc, float *nwfa, float *nifa, float *t,
+                                const float *p, const float *w, const float *dz,
+                                float *ppt, double *rates, int32_t *nstep, int32_t arith, const kidmp32_outputs *out);
 
 /* Introspection for parity tests: copy a lookup table / constant array to the
  * host.  Names are the reference's (tcg_racg ... t_Efsw; cre, crg, Dr ...).

@@ -9,7 +9,6 @@
 
 #include "kidmp_ctx.h"
 #include "thompson_host_init.h"
-#include "thompson_reflectivity.h"
 
 using namespace kidmp;
 thread_local std::string kidmp::g_err;
@@ -31,22 +30,6 @@ void give_slot(int i)
     if (i >= 0 && i < MAX_CONST_SLOTS) g_slot_used[i] = false;
 }
 
-// Stricter than check_on_device: the reflectivity device entries refuse anything but device memory of the context's GPU
-// (a pageable host array would otherwise reach the kernel and fault it).
-int check_device_array(kidmp_ctx *c, const void *p, const char *what)
-{
-    if (!p) return KIDMP_OK;
-    hipPointerAttribute_t at;
-    const bool known = hipPointerGetAttributes(&at, p) == hipSuccess;
-    if (!known) (void)hipGetLastError();
-    if (!known || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged))
-        return fail(c, KIDMP_EINVAL, std::string("kidmp_reflectivity: ") + what + " is not device memory");
-    if (at.device != c->cfg.device)
-        return fail(c, KIDMP_EINVAL, std::string("kidmp_reflectivity: ") + what + " lives on device " + std::to_string(at.device)
-                                     + ", the context is bound to device " + std::to_string(c->cfg.device));
-    return KIDMP_OK;
-}
-
 template <class T>
 int refl_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const T *t, const T *p, const T *qv, const T *qr, const T *nr,
                 const T *qs, const T *qg, T *dbz, void *stream)
@@ -58,7 +41,7 @@ int refl_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const T *t, const T *p
     const char *names[] = {"t", "p", "qv", "qr", "nr", "qs", "qg", "dbz"};
     const void *ptrs[] = {t, p, qv, qr, nr, qs, qg, dbz};
     for (int i = 0; i < 8; ++i)
-        if (int rc = check_device_array(ctx, ptrs[i], names[i])) return rc;
+        if (int rc = check_device_array(ctx, "kidmp_reflectivity", ptrs[i], names[i])) return rc;
     HIPTRY(ctx, launch_reflectivity<T>(refl_consts(ctx->hc), ncol, nz, t, p, qv, qr, nr, qs, qg, dbz, (hipStream_t)stream));
     return KIDMP_OK;
 }

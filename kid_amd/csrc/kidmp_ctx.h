@@ -9,6 +9,7 @@
 
 #include "../../include/kidmp.h"
 #include "thompson_column.h"
+#include "thompson_reflectivity.h"
 #include "thompson_tables.h"
 
 namespace kidmp {
@@ -102,6 +103,22 @@ inline int check_on_device(kidmp_ctx *c, const void *p, const char *what)
     return KIDMP_OK;
 }
 
+// Stricter: the entries of the column diagnostics refuse anything but device memory of the context's GPU (a pageable
+// host array would otherwise reach the kernel and fault it).
+inline int check_device_array(kidmp_ctx *c, const char *who, const void *p, const char *what)
+{
+    if (!p) return KIDMP_OK;
+    hipPointerAttribute_t at;
+    const bool known = hipPointerGetAttributes(&at, p) == hipSuccess;
+    if (!known) (void)hipGetLastError();
+    if (!known || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged))
+        return fail(c, KIDMP_EINVAL, std::string(who) + ": " + what + " is not device memory");
+    if (at.device != c->cfg.device)
+        return fail(c, KIDMP_EINVAL, std::string(who) + ": " + what + " lives on device " + std::to_string(at.device)
+                                     + ", the context is bound to device " + std::to_string(c->cfg.device));
+    return KIDMP_OK;
+}
+
 inline int check_step_args(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, const void *const *ptrs, int nptr)
 {
     if (int rc = require_ready(ctx)) return rc;
@@ -124,10 +141,24 @@ int check_refl_args(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const void *const 
 template <class T> void launch_default_aerosols(int64_t n, T Nt_c, const T *qv, const T *t, const T *p, T *nc, T *nwfa, T *nifa, hipStream_t s);
 void launch_sanity(int64_t n, const double *const (&v)[SANITY_NEG], unsigned long long *acc, hipStream_t s);
 template <class T> hipError_t launch_ppt_exact(int64_t ncol, const T *ppt, unsigned long long *acc, hipStream_t s);
+// the column outputs (dbz, re_qc, re_qi, re_qs; preset form): the checks every entry shares, then ONE launch picked from
+// what `out` asks for -- k_reflectivity, k_effective_radii or k_column_outputs
+template <class T> int check_outputs_request(kidmp_ctx *ctx, const char *who, const ColumnOutputs<T> &out);   // `out` alone
+template <class T>
+int check_outputs_args(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, const ColumnState<T> &in, const ColumnOutputs<T> &out);
+template <class T>
+hipError_t launch_outputs(kidmp_ctx *ctx, int64_t ncol, int nz, const ColumnState<T> &in, const ColumnOutputs<T> &out, hipStream_t s);
+// calc_effectRad in its INOUT (keep) form on n elements, with the optional arrays of the lenient entries
+template <class T>
+int check_radii_args(kidmp_ctx *ctx, const char *who, int64_t n, const T *t, const T *p, const T *qv, const T *qc, const T *nc,
+                     const T *qi, const T *ni, const T *qs, T *re_qc, T *re_qi, T *re_qs);
+template <class T>
+hipError_t launch_radii_keep(kidmp_ctx *ctx, int64_t n, const T *t, const T *p, const T *qv, const T *qc, const T *nc,
+                             const T *qi, const T *ni, const T *qs, T *re_qc, T *re_qi, T *re_qs, hipStream_t s);
 
 // kidmp_host.hip.  What an entry may ask of the pipeline beyond the step: the exact precipitation sums and the sanity
-// scan (left in ctx->d_acc / d_sanity), and the reflectivity of every chunk's post-step state.
-template <class T> struct PipelineExtras { bool exact_sums = false, scan_sanity = false; T *dbz = nullptr; };
+// scan (left in ctx->d_acc / d_sanity), and the column outputs (host arrays) of every chunk's post-step state.
+template <class T> struct PipelineExtras { bool exact_sums = false, scan_sanity = false; ColumnOutputs<T> out{}; };
 template <class T>
 int host_pipeline(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, T *const *io, const T *const *in, T *ppt,
                   double *rates, int32_t *nstep, int32_t arith, const PipelineExtras<T> &extra = {});

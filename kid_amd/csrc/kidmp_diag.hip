@@ -1,8 +1,8 @@
 // kidmp_diag.hip -- the small kernels around the column step (aerosol defaults, domain reductions, the sanity scan,
-// effective radii, the fastmath probe) and the entries of include/kidmp.h that wrap them.
+// effective radii, the column outputs, the fastmath probe) and the entries of include/kidmp.h that wrap them.
 // Built with the plain HIPFLAGS (no -fapprox-func): case 9 of k_math_probe relies on it.
 #include "kidmp_ctx.h"
-#include "fastmath.h"
+#include "thompson_levels.h"
 
 using namespace kidmp;
 
@@ -134,13 +134,20 @@ __global__ void k_sanity_final(const unsigned long long *acc, double *out15)
 }
 
 // calc_effectRad, M:4834-4935: effective radii of cloud water, cloud ice and snow for radiation coupling.  Pointwise in
-// (column, level); re_* are INOUT (a level without the species keeps the caller's value, M:4873/4888/4897).  The
-// reference's column-wide has_qc/has_qi/has_qs flags only skip loops whose bodies test the level again.
-struct RadConsts { double Nt_c, cig2, oig1, oams, cse1, sa[10], sb[10]; int aero; };
-__global__ void k_effective_radii(int64_t n, RadConsts c, const double *__restrict__ t, const double *__restrict__ p,
-                                  const double *__restrict__ qv, const double *__restrict__ qc, const double *__restrict__ nc1,
-                                  const double *__restrict__ qi, const double *__restrict__ ni1, const double *__restrict__ qs,
-                                  double *__restrict__ re_qc, double *__restrict__ re_qi, double *__restrict__ re_qs)
+// (column, level); the arithmetic of a level is thompson_levels.h.  The reference's column-wide has_qc/has_qi/has_qs
+// flags only skip loops whose bodies test the level again.
+//   T     double, or float: widened on load, computed in binary64, rounded once on store (not the reference's native
+//         binary32 arithmetic)
+//   KEEP  the subroutine's INOUT (M:4873 / 4888 / 4897): a level without the species is not written.  Otherwise the form of
+//         the scheme's driver (M:1111-1116): such a level receives the preset 2.49E-6 / 4.99E-6 / 9.99E-6 m.  The driver's
+//         clamps after the call (M:1118-1120) change nothing after the subroutine's own and are not computed.
+// nc1 may be null when the context is not aerosol-aware (nc = Nt_c, M:4863); null qi + ni and null qs read as zero; null
+// re_qi / re_qs are not formed.
+template <class T, bool KEEP>
+__global__ void k_effective_radii(int64_t n, RadConsts c, const T *__restrict__ t, const T *__restrict__ p,
+                                  const T *__restrict__ qv, const T *__restrict__ qc, const T *__restrict__ nc1,
+                                  const T *__restrict__ qi, const T *__restrict__ ni1, const T *__restrict__ qs,
+                                  T *__restrict__ re_qc, T *__restrict__ re_qi, T *__restrict__ re_qs)
 {
     const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
 #if KFM_TABLES
@@ -148,36 +155,32 @@ __global__ void k_effective_radii(int64_t n, RadConsts c, const double *__restri
     __syncthreads();
 #endif
     if (i >= n) return;
-    const double am_r_ = PI * rho_w / 6.0, am_i_ = PI * rho_i / 6.0;
-    const double rho = 0.622 * p[i] / (Rgas * t[i] * (qv[i] + 0.622));
-    const double rc = fmax(R1, qc[i] * rho);
-    double nc = fmax(R2, nc1[i] * rho);
-    if (!c.aero) nc = c.Nt_c;                                           // .NOT. is_aerosol_aware, M:4863
-    const double ri = fmax(R1, qi[i] * rho), ni = fmax(R2, ni1[i] * rho), rs = fmax(R1, qs[i] * rho);
-    if (!(rc <= R1 || nc <= R2)) {                                      // M:4873-4884
-        int inu_c;
-        if (nc < 100.) inu_c = 15;
-        else if (nc > 1.E10) inu_c = 2;
-        else { inu_c = int(lround(1000.E6 / nc)) + 2; inu_c = inu_c < 15 ? inu_c : 15; }
-        const double g_ratio = double((inu_c + 1) * (inu_c + 2) * (inu_c + 3));   // 24, 60, 120 ... 4896 = (n+1)(n+2)(n+3)
-        const double lamc = fm::cbrt_pos(nc * am_r_ * g_ratio / rc);
-        re_qc[i] = fmax(2.51E-6, fmin(0.5 * double(3. + inu_c) / lamc, 50.E-6));
+    const double temp = double(t[i]);
+    const double rho = lvl::air_density(double(p[i]), temp, double(qv[i]));
+    double re;
+    if (lvl::cloud_water_radius(c, rho, double(qc[i]), nc1 ? double(nc1[i]) : 0., re)) re_qc[i] = T(re);
+    else if (!KEEP) re_qc[i] = T(lvl::RE_QC_PRESET);
+    if (re_qi) {
+        if (qi && lvl::cloud_ice_radius(c, rho, double(qi[i]), double(ni1[i]), re)) re_qi[i] = T(re);
+        else if (!KEEP) re_qi[i] = T(lvl::RE_QI_PRESET);
     }
-    if (!(ri <= R1 || ni <= R2)) {                                      // M:4887-4893
-        const double lami = fm::cbrt_pos(am_i_ * c.cig2 * c.oig1 * ni / ri);
-        re_qi[i] = fmax(5.01E-6, fmin(0.5 * double(3. + mu_i) / lami, 125.E-6));
+    if (re_qs) {
+        const double rs = fmax(R1, (qs ? double(qs[i]) : 0.) * rho);
+        if (!(rs <= R1)) re_qs[i] = T(lvl::snow_radius(c.sa, c.sb, c.cse1, lvl::snow_level(temp, rs, c.oams)));   // M:4896-4930
+        else if (!KEEP) re_qs[i] = T(lvl::RE_QS_PRESET);
     }
-    if (!(rs <= R1)) {                                                  // M:4896-4930 (bm_s = 2: smo2 = smob)
-        const double tc0 = fmin(-0.1, t[i] - 273.15), x = c.cse1;
-        const double smob = rs * c.oams;
-        const double *a = c.sa, *b = c.sb;
-        const double loga_ = a[0] + a[1] * tc0 + a[2] * x + a[3] * tc0 * x + a[4] * tc0 * tc0 + a[5] * x * x
-                           + a[6] * tc0 * tc0 * x + a[7] * tc0 * x * x + a[8] * tc0 * tc0 * tc0 + a[9] * x * x * x;
-        const double b_ = b[0] + b[1] * tc0 + b[2] * x + b[3] * tc0 * x + b[4] * tc0 * tc0 + b[5] * x * x
-                        + b[6] * tc0 * tc0 * x + b[7] * tc0 * x * x + b[8] * tc0 * tc0 * tc0 + b[9] * x * x * x;
-        const double smoc = fm::pow10_times_pow(loga_, fm::log2_parts(smob), b_);
-        re_qs[i] = fmax(10.E-6, fmin(0.5 * (smoc / smob), 999.E-6));
-    }
+}
+
+template <class T>
+hipError_t launch_effective_radii(const RadConsts &c, bool keep, int64_t n, const T *t, const T *p, const T *qv, const T *qc,
+                                  const T *nc, const T *qi, const T *ni, const T *qs, T *re_qc, T *re_qi, T *re_qs,
+                                  hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (keep) hipLaunchKernelGGL((k_effective_radii<T, true>), grid, block, 0, s, n, c, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs);
+    else      hipLaunchKernelGGL((k_effective_radii<T, false>), grid, block, 0, s, n, c, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs);
+    return hipGetLastError();
 }
 
 // device evaluation of the kernel's math helpers (fastmath.h) for the accuracy test
@@ -233,6 +236,121 @@ void kidmp::launch_sanity(int64_t n, const double *const (&v)[SANITY_NEG], unsig
     if (g > 2048) g = 2048;
     hipLaunchKernelGGL(k_sanity, dim3((unsigned)g), dim3(256), 0, s, n, p, acc);
 }
+
+// ---- the column outputs: what a host model takes from the state beside the step ----
+// One check for the device entries and the host step.  Pairs: qi + ni, qs + qg, both or neither, neither only in an
+// iiwarm context (they are zero there); the radii: re_qc with re_qi and re_qs, the latter two optional in an iiwarm
+// context; nc only where the context is aerosol-aware (M:4863).
+template <class T>
+int kidmp::check_outputs_request(kidmp_ctx *ctx, const char *who, const ColumnOutputs<T> &out)
+{
+    const std::string w(who);
+    if (int rc = require_ready(ctx)) return rc;
+    const bool radii = out.re_qc || out.re_qi || out.re_qs, warm = ctx->cfg.iiwarm != 0;
+    if (radii && !out.re_qc) return fail(ctx, KIDMP_EINVAL, w + ": re_qc, re_qi, re_qs must be requested together");
+    if ((out.re_qi == nullptr) != (out.re_qs == nullptr) || (radii && !out.re_qi && !warm))
+        return fail(ctx, KIDMP_EINVAL, w + ": re_qi and re_qs may be left out only together and only in an iiwarm context");
+    if (out.dbz && !refl_consts_supported(ctx->hc)) return fail(ctx, KIDMP_ESTATE, w + ": reflectivity exponents differ from the kernel's");
+    return KIDMP_OK;
+}
+template <class T>
+int kidmp::check_outputs_args(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, const ColumnState<T> &in,
+                              const ColumnOutputs<T> &out)
+{
+    const std::string w(who);
+    if (int rc = check_outputs_request<T>(ctx, who, out)) return rc;
+    if (ncol < 0) return fail(ctx, KIDMP_EINVAL, w + ": ncol < 0");
+    if (nz < 2 || nz > KIDMP_MAX_NZ) return fail(ctx, KIDMP_EINVAL, w + ": nz outside [2, KIDMP_MAX_NZ]");
+    const bool radii = out.re_qc != nullptr, warm = ctx->cfg.iiwarm != 0;
+    if (ncol == 0 || (!radii && !out.dbz)) return KIDMP_OK;
+    if (!in.t || !in.p || !in.qv || (radii && !in.qc) || (out.dbz && (!in.qr || !in.nr)))
+        return fail(ctx, KIDMP_EINVAL, w + ": null array argument");
+    if ((in.qi == nullptr) != (in.ni == nullptr)) return fail(ctx, KIDMP_EINVAL, w + ": qi and ni must be given or left out together");
+    if ((in.qs == nullptr) != (in.qg == nullptr)) return fail(ctx, KIDMP_EINVAL, w + ": qs and qg must be given or left out together");
+    if (!warm && ((radii && !in.qi) || !in.qs)) return fail(ctx, KIDMP_EINVAL, w + ": a mixed-phase context needs qi, ni, qs and qg");
+    if (radii && ctx->cfg.is_aerosol_aware && !in.nc) return fail(ctx, KIDMP_EINVAL, w + ": an aerosol-aware context needs nc for the radii");
+    return KIDMP_OK;
+}
+
+// One launch, chosen by what is wanted: the reflectivity alone, the radii alone (pointwise, preset form), or both from a
+// single read of the column.  Arguments as checked above.
+template <class T>
+hipError_t kidmp::launch_outputs(kidmp_ctx *ctx, int64_t ncol, int nz, const ColumnState<T> &in, const ColumnOutputs<T> &out,
+                                 hipStream_t s)
+{
+    const bool aero = ctx->cfg.is_aerosol_aware != 0;
+    const T *nc = aero ? in.nc : nullptr;
+    if (out.dbz && out.re_qc) {
+        ColumnState<T> st = in;
+        st.nc = nc;
+        return launch_column_outputs<T>(refl_consts(ctx->hc), rad_consts(ctx->hc, aero), ncol, nz, st, out, s);
+    }
+    if (out.dbz) return launch_reflectivity<T>(refl_consts(ctx->hc), ncol, nz, in.t, in.p, in.qv, in.qr, in.nr, in.qs, in.qg, out.dbz, s);
+    if (out.re_qc)
+        return launch_effective_radii<T>(rad_consts(ctx->hc, aero), false, ncol * int64_t(nz), in.t, in.p, in.qv, in.qc, nc, in.qi,
+                                         in.ni, in.qs, out.re_qc, out.re_qi, out.re_qs, s);
+    return hipSuccess;
+}
+#define KIDMP_INSTANTIATE_OUTPUTS(T) \
+    template int kidmp::check_outputs_request<T>(kidmp_ctx *, const char *, const ColumnOutputs<T> &); \
+    template int kidmp::check_outputs_args<T>(kidmp_ctx *, const char *, int64_t, int32_t, const ColumnState<T> &, const ColumnOutputs<T> &); \
+    template hipError_t kidmp::launch_outputs<T>(kidmp_ctx *, int64_t, int, const ColumnState<T> &, const ColumnOutputs<T> &, hipStream_t);
+KIDMP_INSTANTIATE_OUTPUTS(double)
+KIDMP_INSTANTIATE_OUTPUTS(float)
+#undef KIDMP_INSTANTIATE_OUTPUTS
+
+// calc_effectRad in the subroutine's own INOUT form on n = ncol*nz elements: the lenient compatibility entries
+// (kidmp_effective_radii_host, kidmp32_effective_radii_*).  Null nc / qi + ni / qs as in check_outputs_args.
+template <class T>
+int kidmp::check_radii_args(kidmp_ctx *ctx, const char *who, int64_t n, const T *t, const T *p, const T *qv, const T *qc,
+                            const T *nc, const T *qi, const T *ni, const T *qs, T *re_qc, T *re_qi, T *re_qs)
+{
+    const std::string w(who);
+    if (int rc = require_ready(ctx)) return rc;
+    if (n < 0) return fail(ctx, KIDMP_EINVAL, w + ": n < 0");
+    if (n == 0) return KIDMP_OK;                                // an empty batch has nothing to point at
+    const bool warm = ctx->cfg.iiwarm != 0;
+    if (!t || !p || !qv || !qc || !re_qc) return fail(ctx, KIDMP_EINVAL, w + ": null array argument");
+    if ((qi == nullptr) != (ni == nullptr)) return fail(ctx, KIDMP_EINVAL, w + ": qi and ni must be given or left out together");
+    if (!warm && (!qi || !qs)) return fail(ctx, KIDMP_EINVAL, w + ": a mixed-phase context needs qi, ni and qs");
+    if ((re_qi == nullptr) != (re_qs == nullptr) || (!re_qi && !warm))
+        return fail(ctx, KIDMP_EINVAL, w + ": re_qi and re_qs may be left out only together and only in an iiwarm context");
+    if (ctx->cfg.is_aerosol_aware && !nc) return fail(ctx, KIDMP_EINVAL, w + ": an aerosol-aware context needs nc");
+    return KIDMP_OK;
+}
+template <class T>
+hipError_t kidmp::launch_radii_keep(kidmp_ctx *ctx, int64_t n, const T *t, const T *p, const T *qv, const T *qc, const T *nc,
+                                    const T *qi, const T *ni, const T *qs, T *re_qc, T *re_qi, T *re_qs, hipStream_t s)
+{
+    const bool aero = ctx->cfg.is_aerosol_aware != 0;
+    return launch_effective_radii<T>(rad_consts(ctx->hc, aero), true, n, t, p, qv, qc, aero ? nc : nullptr, qi, ni, qs, re_qc,
+                                     re_qi, re_qs, s);
+}
+#define KIDMP_INSTANTIATE_RADII(T) \
+    template int kidmp::check_radii_args<T>(kidmp_ctx *, const char *, int64_t, const T *, const T *, const T *, const T *, const T *, \
+                                            const T *, const T *, const T *, T *, T *, T *); \
+    template hipError_t kidmp::launch_radii_keep<T>(kidmp_ctx *, int64_t, const T *, const T *, const T *, const T *, const T *, \
+                                                    const T *, const T *, const T *, T *, T *, T *, hipStream_t);
+KIDMP_INSTANTIATE_RADII(double)
+KIDMP_INSTANTIATE_RADII(float)
+#undef KIDMP_INSTANTIATE_RADII
+
+namespace {
+template <class T, class O>
+int column_outputs_device(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, const ColumnState<T> &in, const O *o, void *stream)
+{
+    const ColumnOutputs<T> out = o ? ColumnOutputs<T>{o->dbz, o->re_qc, o->re_qi, o->re_qs} : ColumnOutputs<T>{};
+    if (int rc = check_outputs_args<T>(ctx, who, ncol, nz, in, out)) return rc;
+    if (ncol == 0 || (!out.dbz && !out.re_qc)) return KIDMP_OK;
+    GUARD(ctx);
+    const char *names[] = {"t", "p", "qv", "qc", "nc", "qi", "ni", "qr", "nr", "qs", "qg", "dbz", "re_qc", "re_qi", "re_qs"};
+    const void *ptrs[] = {in.t, in.p, in.qv, in.qc, in.nc, in.qi, in.ni, in.qr, in.nr, in.qs, in.qg, out.dbz, out.re_qc, out.re_qi, out.re_qs};
+    for (int i = 0; i < 15; ++i)
+        if (int rc = check_device_array(ctx, who, ptrs[i], names[i])) return rc;
+    HIPTRY(ctx, launch_outputs<T>(ctx, ncol, nz, in, out, (hipStream_t)stream));
+    return KIDMP_OK;
+}
+}  // namespace
 
 extern "C" {
 int kidmp_default_aerosols_device(kidmp_ctx *ctx, int64_t n, const double *qv, const double *t, const double *p,
@@ -324,14 +442,36 @@ int kidmp_effective_radii_device(kidmp_ctx *ctx, int64_t n, const double *t, con
     GUARD(ctx);
     if (int rc = check_on_device(ctx, t, "t")) return rc;
     if (int rc = check_on_device(ctx, re_qc, "re_qc")) return rc;
-    RadConsts c{};
-    c.aero = ctx->cfg.is_aerosol_aware != 0;
-    c.Nt_c = ctx->hc.Nt_c; c.cig2 = ctx->hc.cig[1]; c.oig1 = ctx->hc.oig1; c.oams = ctx->hc.oams; c.cse1 = ctx->hc.cse[0];
-    for (int i = 0; i < 10; ++i) { c.sa[i] = ctx->hc.sa[i]; c.sb[i] = ctx->hc.sb[i]; }
-    hipLaunchKernelGGL(k_effective_radii, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, c,
-                       t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs);
-    HIPTRY(ctx, hipGetLastError());
+    HIPTRY(ctx, launch_radii_keep<double>(ctx, n, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs, (hipStream_t)stream));
     return KIDMP_OK;
+}
+
+int kidmp32_effective_radii_device(kidmp_ctx *ctx, int64_t n, const float *t, const float *p, const float *qv,
+                                   const float *qc, const float *nc, const float *qi, const float *ni, const float *qs,
+                                   float *re_qc, float *re_qi, float *re_qs, void *stream)
+{
+    if (int rc = check_radii_args<float>(ctx, "kidmp32_effective_radii_device", n, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs)) return rc;
+    if (n == 0) return KIDMP_OK;
+    GUARD(ctx);
+    const char *names[] = {"t", "p", "qv", "qc", "nc", "qi", "ni", "qs", "re_qc", "re_qi", "re_qs"};
+    const void *ptrs[] = {t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs};
+    for (int i = 0; i < 11; ++i)
+        if (int rc = check_device_array(ctx, "kidmp32_effective_radii_device", ptrs[i], names[i])) return rc;
+    HIPTRY(ctx, launch_radii_keep<float>(ctx, n, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs, (hipStream_t)stream));
+    return KIDMP_OK;
+}
+
+int kidmp_column_outputs_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const double *t, const double *p, const double *qv,
+                                const double *qc, const double *nc, const double *qi, const double *ni, const double *qr,
+                                const double *nr, const double *qs, const double *qg, const kidmp_outputs *out, void *stream)
+{
+    return column_outputs_device<double>(ctx, "kidmp_column_outputs_device", ncol, nz, {t, p, qv, qc, nc, qi, ni, qr, nr, qs, qg}, out, stream);
+}
+int kidmp32_column_outputs_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const float *t, const float *p, const float *qv,
+                                  const float *qc, const float *nc, const float *qi, const float *ni, const float *qr,
+                                  const float *nr, const float *qs, const float *qg, const kidmp32_outputs *out, void *stream)
+{
+    return column_outputs_device<float>(ctx, "kidmp32_column_outputs_device", ncol, nz, {t, p, qv, qc, nc, qi, ni, qr, nr, qs, qg}, out, stream);
 }
 
 // the 24 limbs -> four doubles: carries propagated in 128-bit integers, then the digits summed from the top in long

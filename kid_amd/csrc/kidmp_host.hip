@@ -1,6 +1,5 @@
 // kidmp_host.hip -- the entries of include/kidmp.h that take host arrays.
 #include "kidmp_ctx.h"
-#include "thompson_reflectivity.h"
 
 using namespace kidmp;
 
@@ -80,17 +79,55 @@ int refl_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const T *t, const T *p, 
     HIPTRY(ctx, es);
     return KIDMP_OK;
 }
+
+// calc_effectRad (M:4834-4935) on host arrays of n elements, INOUT: chunks through the staging memory on the compute stream
+// like refl_host; re_* go up as well as down.  The entry has no nz, so a chunk is the context's chunk size in columns of a
+// nominal 128 levels.
+template <class T>
+int radii_host(kidmp_ctx *ctx, const char *who, int64_t n, const T *t, const T *p, const T *qv, const T *qc, const T *nc,
+               const T *qi, const T *ni, const T *qs, T *re_qc, T *re_qi, T *re_qs)
+{
+    if (int rc = check_radii_args<T>(ctx, who, n, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs)) return rc;
+    if (n == 0) return KIDMP_OK;
+    GUARD(ctx);
+    const int64_t want = (ctx->host_chunk > 0 ? ctx->host_chunk : 8192) * 128, CH = want < n ? want : n;
+    const size_t b_prof = (size_t(CH) * sizeof(T) + 255) / 256 * 256;
+    if (int rc = ensure_stage(ctx, 11 * b_prof)) return rc;
+    char *const base = reinterpret_cast<char *>(ctx->d_stage);
+    T *d[11];
+    for (int v = 0; v < 11; ++v) d[v] = reinterpret_cast<T *>(base + size_t(v) * b_prof);
+    const T *h[11] = {t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs};
+    T *const hout[3] = {re_qc, re_qi, re_qs};
+    auto dev = [&](int v) { return h[v] ? d[v] : nullptr; };
+    hipError_t e = hipSuccess;
+    for (int64_t off = 0; off < n && e == hipSuccess; off += CH) {
+        const size_t cnt = size_t(off + CH <= n ? CH : n - off);
+        for (int v = 0; v < 11 && e == hipSuccess; ++v)
+            if (h[v]) e = hipMemcpyAsync(d[v], h[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess)
+            e = launch_radii_keep<T>(ctx, int64_t(cnt), d[0], d[1], d[2], d[3], dev(4), dev(5), dev(6), dev(7), d[8], dev(9),
+                                     dev(10), ctx->stream);
+        for (int v = 0; v < 3 && e == hipSuccess; ++v)
+            if (hout[v]) e = hipMemcpyAsync(hout[v] + off, d[8 + v], cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(ctx->stream);        // no copy may still be in flight towards the caller's arrays
+    HIPTRY(ctx, e);
+    HIPTRY(ctx, es);
+    return KIDMP_OK;
+}
 }  // namespace
 
-// extra.dbz (optional): the reflectivity of calc_refl10cm (M:4946-5244) of every chunk's post-step state, formed on the compute
-// stream right after the step; it is the only extra array that comes back, and the staging set grows by its one profile.
+// extra.out (optional, host arrays): calc_refl10cm (M:4946-5244) and calc_effectRad (M:4834-4935, the driver's preset form
+// of M:1111-1116) of every chunk's post-step state, formed by ONE launch on the compute stream right after the step.  Only
+// the requested profiles are staged and come back.
 template <class T>
 int kidmp::host_pipeline(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, T *const *io, const T *const *in, T *ppt,
                          double *rates, int32_t *nstep, int32_t arith, const PipelineExtras<T> &extra)
 {
-    const auto [exact_sums, scan_sanity, dbz] = extra;
-    if (int rc = require_ready(ctx)) return rc;
-    if (dbz && !refl_consts_supported(ctx->hc)) return fail(ctx, KIDMP_ESTATE, "kidmp: reflectivity exponents differ from the kernel's");
+    const auto [exact_sums, scan_sanity, out] = extra;
+    if (int rc = check_outputs_request<T>(ctx, "kidmp", out)) return rc;
+    T *const hout[4] = {out.dbz, out.re_qc, out.re_qi, out.re_qs};
+    const int n_out = (out.dbz != nullptr) + (out.re_qc != nullptr) + (out.re_qi != nullptr) + (out.re_qs != nullptr);
     // Arrays the caller may leave out (NULL), as KiD itself does (W:36 passes nc1d, nwfa1d, nifa1d unset; a warm run
     // never touches the frozen species, W:46-52): they then neither cross PCIe nor come back.
     //   nc, nwfa, nifa (all three)   non-aerosol contexts: the defaults of M:958-964, formed on the device
@@ -131,8 +168,7 @@ int kidmp::host_pipeline(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, T 
     const size_t b_prof = up256(prof * sizeof(T));
     const size_t b_ppt = up256(4 * size_t(CH) * sizeof(T));
     const size_t b_nstep = nstep ? up256(4 * size_t(CH) * sizeof(int32_t)) : 0;
-    const size_t b_dbz = dbz ? b_prof : 0;
-    const size_t b_set = b_rates + 15 * b_prof + b_ppt + b_nstep + b_dbz;
+    const size_t b_set = b_rates + size_t(15 + n_out) * b_prof + b_ppt + b_nstep;
     if (int rc = ensure_stage(ctx, b_set * size_t(nbuf))) return rc;
     char *const base = reinterpret_cast<char *>(ctx->d_stage);
     PipelineDrain drain{ctx};
@@ -152,7 +188,9 @@ int kidmp::host_pipeline(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, T 
         T *dppt = reinterpret_cast<T *>(q); q += b_ppt;
         int32_t *dnstep = nstep ? reinterpret_cast<int32_t *>(q) : nullptr;
         q += b_nstep;
-        T *ddbz = dbz ? reinterpret_cast<T *>(q) : nullptr;
+        T *dout[4] = {};
+        for (int v = 0; v < 4; ++v)
+            if (hout[v]) { dout[v] = reinterpret_cast<T *>(q); q += b_prof; }
         if (!has_w || !in[2]) din[2] = nullptr;
         // upload (the set is free once the download of the chunk that used it last has finished)
         if (i >= nbuf) HIPTRY(ctx, hipStreamWaitEvent(ctx->s_h2d, ctx->ev_down[b], 0));
@@ -170,9 +208,9 @@ int kidmp::host_pipeline(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, T 
             HIPTRY(ctx, hipGetLastError());
         }
         if (int rc = step_device<T>(ctx, n, nz, T(dt), dio, din[0], din[2], din[1], dppt, drates, dnstep, arith, ctx->stream)) return rc;
-        if (dbz)                                              // calc_refl10cm of the chunk's post-step t, p, qv, qr, nr, qs, qg
-            HIPTRY(ctx, launch_reflectivity<T>(refl_consts(ctx->hc), n, nz, dio[11], din[0], dio[0], dio[3], dio[7], dio[4],
-                                               dio[5], ddbz, ctx->stream));
+        if (n_out)                                            // the outputs of the chunk's post-step state
+            HIPTRY(ctx, launch_outputs<T>(ctx, n, nz, {dio[11], din[0], dio[0], dio[1], dio[8], dio[2], dio[6], dio[3], dio[7],
+                                                       dio[4], dio[5]}, {dout[0], dout[1], dout[2], dout[3]}, ctx->stream));
         if (exact_sums) HIPTRY(ctx, launch_ppt_exact<T>(n, dppt, ctx->d_acc, ctx->stream));   // the chunk's share of the domain sums
         if constexpr (std::is_same<T, double>::value)
             if (scan_sanity) {                                // the scan of M:1025-1094 over the chunk's end state (exact integer atomics)
@@ -187,7 +225,8 @@ int kidmp::host_pipeline(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, T 
         HIPTRY(ctx, hipMemcpyAsync(ppt + 4 * c0, dppt, 4 * size_t(n) * sizeof(T), hipMemcpyDeviceToHost, ctx->s_d2h));
         if (rates) HIPTRY(ctx, hipMemcpyAsync(rates + size_t(KIDMP_NRATES) * off, drates, size_t(KIDMP_NRATES) * cnt * sizeof(double), hipMemcpyDeviceToHost, ctx->s_d2h));
         if (nstep) HIPTRY(ctx, hipMemcpyAsync(nstep + 4 * c0, dnstep, 4 * size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->s_d2h));
-        if (dbz) HIPTRY(ctx, hipMemcpyAsync(dbz + off, ddbz, cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->s_d2h));
+        for (int v = 0; v < 4; ++v)
+            if (hout[v]) HIPTRY(ctx, hipMemcpyAsync(hout[v] + off, dout[v], cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->s_d2h));
         HIPTRY(ctx, hipEventRecord(ctx->ev_down[b], ctx->s_d2h));
     }
     HIPTRY(ctx, hipStreamSynchronize(ctx->s_d2h));           // everything else precedes it through the events
@@ -214,17 +253,40 @@ int kidmp_set_host_chunk(kidmp_ctx *ctx, int64_t ncol_per_chunk)
     return KIDMP_OK;
 }
 
+int kidmp_batch_step_host_out(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt,
+                              double *qv, double *qc, double *qi, double *qr, double *qs, double *qg,
+                              double *ni, double *nr, double *nc, double *nwfa, double *nifa, double *t,
+                              const double *p, const double *w, const double *dz, double *ppt, double *rates,
+                              int32_t *nstep, const kidmp_outputs *out)
+{
+    double *io[12] = {qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t};
+    const double *in[3] = {p, dz, w};
+    PipelineExtras<double> extra;
+    if (out) extra.out = {out->dbz, out->re_qc, out->re_qi, out->re_qs};   // nothing requested: the plain step (_diag)
+    return host_pipeline<double>(ctx, ncol, nz, dt, io, in, ppt, rates, nstep, 0, extra);
+}
+int kidmp32_batch_step_host_out(kidmp_ctx *ctx, int64_t ncol, int32_t nz, float dt,
+                                float *qv, float *qc, float *qi, float *qr, float *qs, float *qg,
+                                float *ni, float *nr, float *nc, float *nwfa, float *nifa, float *t,
+                                const float *p, const float *w, const float *dz, float *ppt, double *rates,
+                                int32_t *nstep, int32_t arith, const kidmp32_outputs *out)
+{
+    float *io[12] = {qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t};
+    const float *in[3] = {p, dz, w};
+    if (!valid_arith(arith)) return fail(ctx, KIDMP_EINVAL, BAD_ARITH);
+    PipelineExtras<float> extra;
+    if (out) extra.out = {out->dbz, out->re_qc, out->re_qi, out->re_qs};
+    return host_pipeline<float>(ctx, ncol, nz, double(dt), io, in, ppt, rates, nstep, arith, extra);
+}
+
 int kidmp_batch_step_host_refl(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt,
                                double *qv, double *qc, double *qi, double *qr, double *qs, double *qg,
                                double *ni, double *nr, double *nc, double *nwfa, double *nifa, double *t,
                                const double *p, const double *w, const double *dz, double *ppt, double *rates,
                                int32_t *nstep, double *dbz)
 {
-    double *io[12] = {qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t};
-    const double *in[3] = {p, dz, w};
-    PipelineExtras<double> extra;
-    extra.dbz = dbz;                                          // NULL: the plain step (kidmp_batch_step_host, _diag)
-    return host_pipeline<double>(ctx, ncol, nz, dt, io, in, ppt, rates, nstep, 0, extra);
+    const kidmp_outputs out = {dbz, nullptr, nullptr, nullptr};
+    return kidmp_batch_step_host_out(ctx, ncol, nz, dt, qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t, p, w, dz, ppt, rates, nstep, &out);
 }
 int kidmp32_batch_step_host_refl(kidmp_ctx *ctx, int64_t ncol, int32_t nz, float dt,
                                  float *qv, float *qc, float *qi, float *qr, float *qs, float *qg,
@@ -232,12 +294,8 @@ int kidmp32_batch_step_host_refl(kidmp_ctx *ctx, int64_t ncol, int32_t nz, float
                                  const float *p, const float *w, const float *dz, float *ppt, double *rates,
                                  int32_t *nstep, int32_t arith, float *dbz)
 {
-    float *io[12] = {qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t};
-    const float *in[3] = {p, dz, w};
-    if (!valid_arith(arith)) return fail(ctx, KIDMP_EINVAL, BAD_ARITH);
-    PipelineExtras<float> extra;
-    extra.dbz = dbz;
-    return host_pipeline<float>(ctx, ncol, nz, double(dt), io, in, ppt, rates, nstep, arith, extra);
+    const kidmp32_outputs out = {dbz, nullptr, nullptr, nullptr};
+    return kidmp32_batch_step_host_out(ctx, ncol, nz, dt, qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t, p, w, dz, ppt, rates, nstep, arith, &out);
 }
 
 int kidmp_batch_step_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt,
@@ -293,5 +351,18 @@ int kidmp32_reflectivity_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const fl
                               float *dbz)
 {
     return refl_host<float>(ctx, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz);
+}
+
+int kidmp_effective_radii_host(kidmp_ctx *ctx, int64_t n, const double *t, const double *p, const double *qv,
+                               const double *qc, const double *nc, const double *qi, const double *ni, const double *qs,
+                               double *re_qc, double *re_qi, double *re_qs)
+{
+    return radii_host<double>(ctx, "kidmp_effective_radii_host", n, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs);
+}
+int kidmp32_effective_radii_host(kidmp_ctx *ctx, int64_t n, const float *t, const float *p, const float *qv,
+                                 const float *qc, const float *nc, const float *qi, const float *ni, const float *qs,
+                                 float *re_qc, float *re_qi, float *re_qs)
+{
+    return radii_host<float>(ctx, "kidmp32_effective_radii_host", n, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs);
 }
 }  // extern "C"

@@ -1,0 +1,141 @@
+// thompson_levels.h -- the per-level arithmetic of the two column diagnostics, calc_effectRad (M:4834-4935) and
+// calc_refl10cm (M:4946-5244), as __device__ functions: the pointwise radii kernel (kidmp_diag.hip) and the
+// wave-per-column kernels (thompson_reflectivity.hip) are built from these, so no statement exists twice.
+//
+// What the two diagnostics share at a level -- rho, the snow content rs = qs*rho, tc0, the snow moment smob = rs*oams and
+// its logarithm -- is held in SnowLevel and formed once when both are wanted.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "thompson_params.h"
+#include "fastmath.h"
+
+namespace kidmp {
+
+// the values of thompson_init (M:442-602) the live part of calc_refl10cm reads, taken from the context's Consts
+struct ReflConsts {
+    double crg3, crg4, org2;           // rain: crg(3), crg(4), org2   (obmr = 1/3: cube root; cre(2) = 1, cre(4) = 7)
+    double cse3, oams, sa[10], sb[10]; // snow: the Field et al. fit at the bm_s*2 moment (cse(3)); bm_s = 2: smo2 = smob
+    double cgg1, cgg2, cgg4, lamg_fac; // graupel: cgg(1), cgg(2), cgg(4), (cgg(3)*ogg2*ogg1)**obmg   (oge1 = 1/4;
+                                       //          cge(2) = 1, cge(4) = 7)
+};
+// what calc_effectRad reads beyond oams, sa, sb: Nt_c (M:4863), cig(2), oig1 (M:4890), cse(1) (M:4920-4929)
+struct RadConsts { double Nt_c, cig2, oig1, oams, cse1, sa[10], sb[10]; int aero; };
+
+namespace lvl {
+
+// the presets of the scheme's 3-D driver, M:1111-1113
+constexpr double RE_QC_PRESET = 2.49E-6, RE_QI_PRESET = 4.99E-6, RE_QS_PRESET = 9.99E-6;
+
+// M:4860 / M:4994
+__device__ inline double air_density(double pres, double temp, double qv) { return 0.622 * pres / (Rgas * temp * (qv + 0.622)); }
+
+// the Field et al. (2005) moment fit (M:4920-4930, M:5066-5080) at order x: a_ * smob**b_ with a_ = 10**loga_
+struct SnowLevel { double tc0, smob; fm::Log2Parts l2; };
+__device__ inline SnowLevel snow_level(double temp, double rs, double oams)
+{
+    SnowLevel s;
+    s.tc0 = fmin(-0.1, temp - 273.15);
+    s.smob = rs * oams;                                                 // bm_s = 2: smo2 = smob
+    s.l2 = fm::log2_parts(s.smob);
+    return s;
+}
+__device__ inline double snow_moment(const double *a, const double *b, double x, const SnowLevel &s)
+{
+    const double tc0 = s.tc0;
+    const double loga_ = a[0] + a[1] * tc0 + a[2] * x + a[3] * tc0 * x + a[4] * tc0 * tc0 + a[5] * x * x
+                       + a[6] * tc0 * tc0 * x + a[7] * tc0 * x * x + a[8] * tc0 * tc0 * tc0 + a[9] * x * x * x;
+    const double b_ = b[0] + b[1] * tc0 + b[2] * x + b[3] * tc0 * x + b[4] * tc0 * tc0 + b[5] * x * x
+                    + b[6] * tc0 * tc0 * x + b[7] * tc0 * x * x + b[8] * tc0 * tc0 * tc0 + b[9] * x * x * x;
+    return fm::pow10_times_pow(loga_, s.l2, b_);
+}
+
+// ---- calc_effectRad at one level.  Each function reports whether the level holds the species (the reference CYCLEs
+// otherwise, M:4874 / 4889 / 4897) and, if so, returns the radius in `re`. ----
+__device__ inline bool cloud_water_radius(const RadConsts &c, double rho, double qc, double nc1, double &re)
+{
+    const double am_r_ = PI * rho_w / 6.0;
+    const double rc = fmax(R1, qc * rho);
+    const double nc = c.aero ? fmax(R2, nc1 * rho) : c.Nt_c;            // .NOT. is_aerosol_aware, M:4863
+    if (rc <= R1 || nc <= R2) return false;                             // M:4873-4884
+    int inu_c;
+    if (nc < 100.) inu_c = 15;
+    else if (nc > 1.E10) inu_c = 2;
+    else { inu_c = int(lround(1000.E6 / nc)) + 2; inu_c = inu_c < 15 ? inu_c : 15; }
+    const double g_ratio = double((inu_c + 1) * (inu_c + 2) * (inu_c + 3));   // 24, 60, 120 ... 4896 = (n+1)(n+2)(n+3)
+    const double lamc = fm::cbrt_pos(nc * am_r_ * g_ratio / rc);
+    re = fmax(2.51E-6, fmin(0.5 * double(3. + inu_c) / lamc, 50.E-6));
+    return true;
+}
+__device__ inline bool cloud_ice_radius(const RadConsts &c, double rho, double qi, double ni1, double &re)
+{
+    const double am_i_ = PI * rho_i / 6.0;
+    const double ri = fmax(R1, qi * rho), ni = fmax(R2, ni1 * rho);
+    if (ri <= R1 || ni <= R2) return false;                             // M:4887-4893
+    const double lami = fm::cbrt_pos(am_i_ * c.cig2 * c.oig1 * ni / ri);
+    re = fmax(5.01E-6, fmin(0.5 * double(3. + mu_i) / lami, 125.E-6));
+    return true;
+}
+// rs = MAX(R1, qs*rho) > R1, s = snow_level(temp, rs, oams); M:4896-4930
+__device__ inline double snow_radius(const double *sa, const double *sb, double cse1, const SnowLevel &s)
+{
+    const double smoc = snow_moment(sa, sb, cse1, s);
+    return fmax(10.E-6, fmin(0.5 * (smoc / s.smob), 999.E-6));
+}
+
+// ---- calc_refl10cm at one level ----
+// (0.176/0.93) * (6.0/PI)*(6.0/PI) * (am/900.0)*(am/900.0), M:5131-5135, evaluated left to right as the reference does
+constexpr double ZE_ICE_FAC = (0.176 / 0.93) * (6.0 / PI) * (6.0 / PI);
+constexpr double ZE_SNOW_FAC = ZE_ICE_FAC * (am_s / 900.0) * (am_s / 900.0);
+constexpr double ZE_GRAUPEL_FAC = ZE_ICE_FAC * (am_g / 900.0) * (am_g / 900.0);
+constexpr double MVD_FAC = 3.0 + mu_r + 0.672;       // M:5004
+
+__device__ inline double pw7(double x) { const double s = x * x; return s * s * s * x; }
+
+// cube root of a positive, finite x.  fm::cbrt_pos covers [1e-37, 1e37] (its seed is taken in binary32); the rain slope's
+// argument am_r*crg(3)*org2*nr/rr is unclamped here, as in the reference (M:5001), and leaves that range when nr/rr is
+// huge (qr just above R1 with a very large nr).  Outside [1e-36, 1e36] the argument is first scaled into range by an
+// exact power of two 2**(-3q) and the root scaled back by 2**q.
+__device__ inline double cbrt_any(double x)
+{
+    if (x >= 1.E-36 && x <= 1.E36) return fm::cbrt_pos(x);
+    const int q = ilogb(x) / 3;
+    return fm::cbrt_pos(ldexp(x, -3 * q)) * ldexp(1., q);
+}
+
+// rain of a level with qr > R1: ze_rain and the median volume diameter; no 37.5 um / 2.5 mm limits here (cf. M:1661-1666)
+__device__ inline double rain_ze(const ReflConsts &c, double rho, double qr, double nr1, double &mvd_r)
+{
+    const double rr = qr * rho;
+    const double nr = fmax(R2, nr1 * rho);
+    const double lamr = cbrt_any(am_r * c.crg3 * c.org2 * nr / rr);       // **obmr
+    const double ilamr = 1. / lamr;
+    const double N0_r = nr * c.org2 * lamr;                               // lamr**cre(2), cre(2) = 1
+    mvd_r = MVD_FAC * ilamr;
+    return N0_r * c.crg4 * pw7(ilamr);                                    // ilamr**cre(4), M:5130
+}
+// snow of a level with qs > R2, M:5033-5038 and M:5131-5132
+__device__ inline double snow_ze(const ReflConsts &c, const SnowLevel &s) { return ZE_SNOW_FAC * snow_moment(c.sa, c.sb, c.cse3, s); }
+
+// graupel intercept of one level before the running minimum, M:5088-5096 (clamped to [gonv_min, gonv_max])
+__device__ inline double graupel_n0_exp(bool slw, double mvd_r, double rg)
+{
+    const double xslw1 = slw ? 4.01 + fm::log10(mvd_r) : 0.01;
+    const double ygra1 = 4.31 + fm::log10(fmax(5.E-5, rg));
+    const double zans1 = 3.1 + (100. / (300. * xslw1 * ygra1 / (10. / xslw1 + 1. + 0.25 * ygra1) + 30. + 10. * ygra1));
+    const double n0 = fm::exp10(zans1);
+    return fmax(gonv_min, fmin(n0, gonv_max));
+}
+// graupel of a level with qg > R2 once the running minimum N0_exp is known, M:5099-5102 and M:5133-5135
+__device__ inline double graupel_ze(const ReflConsts &c, double N0_exp, double rg)
+{
+    const double lam_exp = fm::sqrt_pos(fm::sqrt_pos(N0_exp * am_g * c.cgg1 / rg));    // **oge1
+    const double lamg = lam_exp * c.lamg_fac;
+    const double ilamg = 1. / lamg;
+    const double N0_g = N0_exp / (c.cgg2 * lam_exp) * lamg;                             // lamg**cge(2), cge(2) = 1
+    return ZE_GRAUPEL_FAC * N0_g * c.cgg4 * pw7(ilamg);                                 // ilamg**cge(4)
+}
+__device__ inline double dbz_of(double ze) { return 10. * fm::log10(ze * 1.E18); }     // M:5196
+
+}  // namespace lvl
+}  // namespace kidmp

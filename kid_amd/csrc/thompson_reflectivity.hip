@@ -15,56 +15,31 @@
 // 10**x and x**y, and the same integer powers / roots for the exponents the scheme fixes (cube root for obmr = 1/3, two
 // square roots for oge1 = 1/4, multiplies for cre(4) = cge(4) = 7).  Division is IEEE (this file is compiled without the
 // column kernel's reciprocal-math flags).  Binary32 storage is widened on load and rounded once on store.
+//
+// k_column_outputs is the same column body with calc_effectRad (M:4834-4935) of every level formed beside it, in the
+// form of the scheme's driver (presets first, M:1111-1116): re_qc, re_qi, re_qs and dbz from one read of the state.  The
+// per-level arithmetic of both diagnostics is thompson_levels.h, shared with the pointwise k_effective_radii.
 #include "thompson_reflectivity.h"
 
-#include "fastmath.h"
+#include <type_traits>
+
+#include "thompson_levels.h"
 
 namespace kidmp {
+
+// what the fused instantiation takes beyond the reflectivity's own arguments; NoRadii selects the reflectivity alone
+template <class T>
+struct RadiiArgs {
+    RadConsts c;
+    const T *qc, *nc, *qi, *ni;                      // nc null: not aerosol-aware; qi, ni null: zero
+    T *re_qc, *re_qi, *re_qs;                        // re_qi, re_qs null: not wanted (iiwarm)
+};
+struct NoRadii {};
+
 namespace {
 
 constexpr int REFL_WAVES = 4;                        // columns (wavefronts) per workgroup
 constexpr int REFL_THREADS = 64 * REFL_WAVES;
-
-// (0.176/0.93) * (6.0/PI)*(6.0/PI) * (am/900.0)*(am/900.0), M:5131-5135, evaluated left to right as the reference does
-constexpr double ZE_ICE_FAC = (0.176 / 0.93) * (6.0 / PI) * (6.0 / PI);
-constexpr double ZE_SNOW_FAC = ZE_ICE_FAC * (am_s / 900.0) * (am_s / 900.0);
-constexpr double ZE_GRAUPEL_FAC = ZE_ICE_FAC * (am_g / 900.0) * (am_g / 900.0);
-constexpr double MVD_FAC = 3.0 + mu_r + 0.672;       // M:5004
-
-__device__ inline double pw7(double x) { const double s = x * x; return s * s * s * x; }
-
-// cube root of a positive, finite x.  fm::cbrt_pos covers [1e-37, 1e37] (its seed is taken in binary32); the rain slope's
-// argument am_r*crg(3)*org2*nr/rr is unclamped here, as in the reference (M:5001), and leaves that range when nr/rr is
-// huge (qr just above R1 with a very large nr).  Outside [1e-36, 1e36] the argument is first scaled into range by an
-// exact power of two 2**(-3q) and the root scaled back by 2**q.
-__device__ inline double cbrt_any(double x)
-{
-    if (x >= 1.E-36 && x <= 1.E36) return fm::cbrt_pos(x);
-    const int q = ilogb(x) / 3;
-    return fm::cbrt_pos(ldexp(x, -3 * q)) * ldexp(1., q);
-}
-
-// the Field et al. (2005) fit of M:5066-5080 at x = cse(3): a_ = 10**loga_, moment = a_ * smo2**b_
-__device__ inline double snow_moment_z(const ReflConsts &c, double tc0, double smo2)
-{
-    const double x = c.cse3;
-    const double *a = c.sa, *b = c.sb;
-    const double loga_ = a[0] + a[1] * tc0 + a[2] * x + a[3] * tc0 * x + a[4] * tc0 * tc0 + a[5] * x * x
-                       + a[6] * tc0 * tc0 * x + a[7] * tc0 * x * x + a[8] * tc0 * tc0 * tc0 + a[9] * x * x * x;
-    const double b_ = b[0] + b[1] * tc0 + b[2] * x + b[3] * tc0 * x + b[4] * tc0 * tc0 + b[5] * x * x
-                    + b[6] * tc0 * tc0 * x + b[7] * tc0 * x * x + b[8] * tc0 * tc0 * tc0 + b[9] * x * x * x;
-    return fm::pow10_times_pow(loga_, fm::log2_parts(smo2), b_);
-}
-
-// graupel intercept of one level before the running minimum, M:5088-5096 (clamped to [gonv_min, gonv_max])
-__device__ inline double graupel_n0_exp(bool slw, double mvd_r, double rg)
-{
-    const double xslw1 = slw ? 4.01 + fm::log10(mvd_r) : 0.01;
-    const double ygra1 = 4.31 + fm::log10(fmax(5.E-5, rg));
-    const double zans1 = 3.1 + (100. / (300. * xslw1 * ygra1 / (10. / xslw1 + 1. + 0.25 * ygra1) + 30. + 10. * ygra1));
-    const double n0 = fm::exp10(zans1);
-    return fmax(gonv_min, fmin(n0, gonv_max));
-}
 
 // 64-bit DPP move: lane l receives lane l + D of its row of 16 (row_shl:D); lanes whose source lies past the row end get
 // garbage that the caller masks off
@@ -103,15 +78,42 @@ __device__ inline double wave_suffix_min(double v, int lane, double &tail)
     return v;
 }
 
-}  // namespace
-
-// one wavefront per column; the kernel name rocprofv3 lists is kidmp::k_reflectivity<T, NJ>
-template <class T, int NJ>
-__global__ void __launch_bounds__(REFL_THREADS)
-k_reflectivity(ReflConsts c, int64_t ncol, int nz, const T *__restrict__ t1d, const T *__restrict__ p1d,
-               const T *__restrict__ qv1d, const T *__restrict__ qr1d, const T *__restrict__ nr1d,
-               const T *__restrict__ qs1d, const T *__restrict__ qg1d, T *__restrict__ dbz)
+// calc_effectRad of one level in the driver's form (M:1111-1116): a level without the species receives the preset.  The
+// driver's clamps after the call (M:1118-1120) change nothing after the subroutine's own and are not computed.
+// calc_effectRad does not clamp qv (M:4860) where calc_refl10cm does (M:4992): below 1e-10 the radii get a density of
+// their own, and only a level whose two densities are one shares the snow moment `sl` (valid when L_qs).
+template <class T>
+__device__ inline void radii_of_level(const ReflConsts &c, const RadiiArgs<T> &r, int64_t i, double temp, double pres, double qv_in, double qv,
+                                      double rho_z, double qs, bool L_qs, const lvl::SnowLevel &sl)
 {
+    const bool same = qv_in == qv;
+    const double rho = same ? rho_z : lvl::air_density(pres, temp, qv_in);
+    double re;
+    re = lvl::RE_QC_PRESET;
+    lvl::cloud_water_radius(r.c, rho, double(r.qc[i]), r.nc ? double(r.nc[i]) : 0., re);
+    r.re_qc[i] = T(re);
+    if (r.re_qi) {
+        re = lvl::RE_QI_PRESET;
+        if (r.qi) lvl::cloud_ice_radius(r.c, rho, double(r.qi[i]), double(r.ni[i]), re);
+        r.re_qi[i] = T(re);
+    }
+    if (r.re_qs) {
+        re = lvl::RE_QS_PRESET;
+        const double rs = fmax(R1, qs * rho);
+        if (!(rs <= R1)) re = lvl::snow_radius(c.sa, c.sb, r.c.cse1, L_qs && same ? sl : lvl::snow_level(temp, rs, c.oams));   // sa, sb, oams: one copy
+        r.re_qs[i] = T(re);
+    }
+}
+
+// One wavefront per column: the body of k_reflectivity and, with RAD = RadiiArgs<T>, of k_column_outputs.
+template <class T, int NJ, class RAD>
+__device__ __forceinline__ void column_diagnostics(const ReflConsts &c, const RAD &rad, int64_t ncol, int nz,
+                                                   const T *__restrict__ t1d, const T *__restrict__ p1d,
+                                                   const T *__restrict__ qv1d, const T *__restrict__ qr1d,
+                                                   const T *__restrict__ nr1d, const T *__restrict__ qs1d,
+                                                   const T *__restrict__ qg1d, T *__restrict__ dbz)
+{
+    constexpr bool RADII = !std::is_same<RAD, NoRadii>::value;
 #if KFM_TABLES
     fm::tab::load_tables(int(threadIdx.x), REFL_THREADS);            // log10 / 10**x / x**y read their tables from LDS
     __syncthreads();
@@ -135,33 +137,27 @@ k_reflectivity(ReflConsts c, int64_t ncol, int nz, const T *__restrict__ t1d, co
         const int64_t i = base + k;
         // ---- load, M:4991-5028 ----
         const double temp = double(t1d[i]);
-        const double qv = fmax(1.E-10, double(qv1d[i]));
+        const double qv_in = double(qv1d[i]);
+        const double qv = fmax(1.E-10, qv_in);
         const double pres = double(p1d[i]);
-        const double rho = 0.622 * pres / (Rgas * temp * (qv + 0.622));
+        const double rho = lvl::air_density(pres, temp, qv);
         const double qr = double(qr1d[i]);
         const double qs = qs1d ? double(qs1d[i]) : 0.;
         const double qg = qg1d ? double(qg1d[i]) : 0.;
         const bool L_qr = qr > R1, L_qs = qs > R2;
         lqg[j] = qg > R2;
         double ze_rain = 1.E-22, ze_snow = 1.E-22, mvd_r = 50.E-6;
-        if (L_qr) {                                                  // no 37.5 um / 2.5 mm limits here (cf. M:1661-1666)
-            const double rr = qr * rho;
-            const double nr = fmax(R2, double(nr1d[i]) * rho);
-            const double lamr = cbrt_any(am_r * c.crg3 * c.org2 * nr / rr);       // **obmr
-            const double ilamr = 1. / lamr;
-            const double N0_r = nr * c.org2 * lamr;                               // lamr**cre(2), cre(2) = 1
-            mvd_r = MVD_FAC * ilamr;
-            ze_rain = N0_r * c.crg4 * pw7(ilamr);                                  // ilamr**cre(4), M:5130
-        }
+        if (L_qr) ze_rain = lvl::rain_ze(c, rho, qr, double(nr1d[i]), mvd_r);
+        lvl::SnowLevel sl{};
         if (L_qs) {                                                  // bm_s = 2: smo2 = smob = rs*oams, M:5033-5038
-            const double tc0 = fmin(-0.1, temp - 273.15);
-            const double smo2 = qs * rho * c.oams;
-            ze_snow = ZE_SNOW_FAC * snow_moment_z(c, tc0, smo2);                   // M:5131-5132
+            sl = lvl::snow_level(temp, qs * rho, c.oams);
+            ze_snow = lvl::snow_ze(c, sl);                           // M:5131-5132
         }
+        if constexpr (RADII) radii_of_level<T>(c, rad, i, temp, pres, qv_in, qv, rho, qs, L_qs, sl);
         if (lqg[j]) rg[j] = qg * rho;
         ze_rs[j] = ze_rain + ze_snow;
         // ---- graupel intercept before the running minimum, M:5088-5096 ----
-        n0[j] = graupel_n0_exp(temp < 270.65 && L_qr && mvd_r > 100.E-6, mvd_r, rg[j]);
+        n0[j] = lvl::graupel_n0_exp(temp < 270.65 && L_qr && mvd_r > 100.E-6, mvd_r, rg[j]);
     }
 
     // ---- N0_min = MIN(N0_exp, N0_min) from kte down to kts (M:5097-5098): a suffix minimum over the levels ----
@@ -179,28 +175,62 @@ k_reflectivity(ReflConsts c, int64_t ncol, int nz, const T *__restrict__ t1d, co
         const int k = 64 * j + lane;
         if (k >= nz) continue;
         double ze_graupel = 1.E-22;
-        if (lqg[j]) {                                                // M:5099-5102, M:5133-5135
-            const double N0_exp = n0[j];
-            const double lam_exp = fm::sqrt_pos(fm::sqrt_pos(N0_exp * am_g * c.cgg1 / rg[j]));   // **oge1
-            const double lamg = lam_exp * c.lamg_fac;
-            const double ilamg = 1. / lamg;
-            const double N0_g = N0_exp / (c.cgg2 * lam_exp) * lamg;                            // lamg**cge(2), cge(2) = 1
-            ze_graupel = ZE_GRAUPEL_FAC * N0_g * c.cgg4 * pw7(ilamg);                          // ilamg**cge(4)
-        }
-        dbz[base + k] = T(10. * fm::log10((ze_rs[j] + ze_graupel) * 1.E18));                    // M:5196
+        if (lqg[j]) ze_graupel = lvl::graupel_ze(c, n0[j], rg[j]);    // M:5099-5102, M:5133-5135
+        dbz[base + k] = T(lvl::dbz_of(ze_rs[j] + ze_graupel));        // M:5196
     }
+}
+
+}  // namespace
+
+// the reflectivity alone; the kernel name rocprofv3 lists is kidmp::k_reflectivity<T, NJ>
+template <class T, int NJ>
+__global__ void __launch_bounds__(REFL_THREADS)
+k_reflectivity(ReflConsts c, int64_t ncol, int nz, const T *__restrict__ t1d, const T *__restrict__ p1d,
+               const T *__restrict__ qv1d, const T *__restrict__ qr1d, const T *__restrict__ nr1d,
+               const T *__restrict__ qs1d, const T *__restrict__ qg1d, T *__restrict__ dbz)
+{
+    column_diagnostics<T, NJ, NoRadii>(c, NoRadii{}, ncol, nz, t1d, p1d, qv1d, qr1d, nr1d, qs1d, qg1d, dbz);
+}
+
+// radii and reflectivity of a column from one read of its state (kidmp::k_column_outputs<T, NJ>)
+template <class T, int NJ>
+__global__ void __launch_bounds__(REFL_THREADS)
+k_column_outputs(ReflConsts c, RadiiArgs<T> rad, int64_t ncol, int nz, const T *__restrict__ t1d,
+                 const T *__restrict__ p1d, const T *__restrict__ qv1d, const T *__restrict__ qr1d,
+                 const T *__restrict__ nr1d, const T *__restrict__ qs1d, const T *__restrict__ qg1d, T *__restrict__ dbz)
+{
+    column_diagnostics<T, NJ, RadiiArgs<T>>(c, rad, ncol, nz, t1d, p1d, qv1d, qr1d, nr1d, qs1d, qg1d, dbz);
 }
 
 namespace {
 
+// rad null: k_reflectivity; else k_column_outputs
 template <class T, int NJ>
-hipError_t launch_nj(const ReflConsts &c, int64_t ncol, int nz, const T *t, const T *p, const T *qv, const T *qr,
-                     const T *nr, const T *qs, const T *qg, T *dbz, hipStream_t s)
+hipError_t launch_nj(const ReflConsts &c, const RadiiArgs<T> *rad, int64_t ncol, int nz, const T *t, const T *p,
+                     const T *qv, const T *qr, const T *nr, const T *qs, const T *qg, T *dbz, hipStream_t s)
 {
     const int64_t nblk = (ncol + REFL_WAVES - 1) / REFL_WAVES;
-    hipLaunchKernelGGL((k_reflectivity<T, NJ>), dim3((unsigned)nblk), dim3(REFL_THREADS), 0, s, c, ncol, nz, t, p, qv,
-                       qr, nr, qs, qg, dbz);
+    if (rad)
+        hipLaunchKernelGGL((k_column_outputs<T, NJ>), dim3((unsigned)nblk), dim3(REFL_THREADS), 0, s, c, *rad, ncol, nz, t,
+                           p, qv, qr, nr, qs, qg, dbz);
+    else
+        hipLaunchKernelGGL((k_reflectivity<T, NJ>), dim3((unsigned)nblk), dim3(REFL_THREADS), 0, s, c, ncol, nz, t, p, qv,
+                           qr, nr, qs, qg, dbz);
     return hipGetLastError();
+}
+
+template <class T>
+hipError_t launch_any(const ReflConsts &c, const RadiiArgs<T> *rad, int64_t ncol, int nz, const T *t, const T *p,
+                      const T *qv, const T *qr, const T *nr, const T *qs, const T *qg, T *dbz, hipStream_t s)
+{
+    if (ncol <= 0) return hipSuccess;
+    switch ((nz + 63) / 64) {
+    case 1: return launch_nj<T, 1>(c, rad, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz, s);
+    case 2: return launch_nj<T, 2>(c, rad, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz, s);
+    case 3: return launch_nj<T, 3>(c, rad, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz, s);
+    case 4: return launch_nj<T, 4>(c, rad, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz, s);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 }  // namespace
@@ -222,18 +252,28 @@ ReflConsts refl_consts(const Consts &hc)
     return c;
 }
 
+RadConsts rad_consts(const Consts &hc, bool aerosol_aware)
+{
+    RadConsts c{};
+    c.aero = aerosol_aware;
+    c.Nt_c = hc.Nt_c; c.cig2 = hc.cig[1]; c.oig1 = hc.oig1; c.oams = hc.oams; c.cse1 = hc.cse[0];
+    for (int i = 0; i < 10; ++i) { c.sa[i] = hc.sa[i]; c.sb[i] = hc.sb[i]; }
+    return c;
+}
+
 template <class T>
 hipError_t launch_reflectivity(const ReflConsts &c, int64_t ncol, int nz, const T *t, const T *p, const T *qv,
                                const T *qr, const T *nr, const T *qs, const T *qg, T *dbz, hipStream_t s)
 {
-    if (ncol <= 0) return hipSuccess;
-    switch ((nz + 63) / 64) {
-    case 1: return launch_nj<T, 1>(c, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz, s);
-    case 2: return launch_nj<T, 2>(c, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz, s);
-    case 3: return launch_nj<T, 3>(c, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz, s);
-    case 4: return launch_nj<T, 4>(c, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz, s);
-    default: return hipErrorInvalidValue;
-    }
+    return launch_any<T>(c, nullptr, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz, s);
+}
+
+template <class T>
+hipError_t launch_column_outputs(const ReflConsts &c, const RadConsts &rc, int64_t ncol, int nz, const ColumnState<T> &in,
+                                 const ColumnOutputs<T> &out, hipStream_t s)
+{
+    const RadiiArgs<T> rad{rc, in.qc, in.nc, in.qi, in.ni, out.re_qc, out.re_qi, out.re_qs};
+    return launch_any<T>(c, &rad, ncol, nz, in.t, in.p, in.qv, in.qr, in.nr, in.qs, in.qg, out.dbz, s);
 }
 
 template hipError_t launch_reflectivity<double>(const ReflConsts &, int64_t, int, const double *, const double *,
@@ -242,5 +282,9 @@ template hipError_t launch_reflectivity<double>(const ReflConsts &, int64_t, int
 template hipError_t launch_reflectivity<float>(const ReflConsts &, int64_t, int, const float *, const float *,
                                                const float *, const float *, const float *, const float *,
                                                const float *, float *, hipStream_t);
+template hipError_t launch_column_outputs<double>(const ReflConsts &, const RadConsts &, int64_t, int,
+                                                  const ColumnState<double> &, const ColumnOutputs<double> &, hipStream_t);
+template hipError_t launch_column_outputs<float>(const ReflConsts &, const RadConsts &, int64_t, int,
+                                                 const ColumnState<float> &, const ColumnOutputs<float> &, hipStream_t);
 
 }  // namespace kidmp

@@ -10,6 +10,11 @@
 !
 !     mp_thompson_batch(ncol, nz, dt, qv, ..., ppt)
 !
+! and the two diagnostics of the reference module a host model calls beside the step, with its dummy lists:
+!
+!     calc_refl10cm(qv1d, ..., dBZ, kts, kte, ii, jj)   M:4946-4952
+!     calc_effectRad(t1d, ..., re_qs1d, kts, kte)       M:4834-4843
+!
 ! Bodies are ISO_C_BINDING calls into libkidmp.so (include/kidmp.h), where the
 ! column physics runs as hand-written HIP kernels on an MI355X.  Arithmetic (kidmp_arith):
 !   'p64'   (default) state arrays are copied to REAL(c_double) temporaries and the step runs in binary64 -- the
@@ -52,6 +57,7 @@ module module_mp_thompson09n
   public :: thompson_init, mp_thompson, mp_thompson_batch, mp_thompson_staging, thompson_finalize
   public :: kidmp_precip_sums_valid
   public :: calc_refl10cm, calc_refl10cm_batch
+  public :: calc_effectRad, calc_effectRad_batch
   logical, public :: is_aerosol_aware = .false.          ! M:28 (read at thompson_init)
   logical, public :: l_rate_diagnostics = .true.         ! replay the save_dg calls of M:2962-3124
   integer, public :: kidmp_device = 0                    ! HIP device ordinal of this process (one GPU)
@@ -79,11 +85,15 @@ module module_mp_thompson09n
      integer(c_int32_t) :: is_aerosol_aware
   end type kidmp_cfg
 
+  type, bind(C) :: kidmp_outputs                         ! kidmp_outputs / kidmp32_outputs: NULL = not wanted
+     type(c_ptr) :: dbz, re_qc, re_qi, re_qs
+  end type kidmp_outputs
+
   type(c_ptr), save :: ctx = c_null_ptr                  ! the context (of the first device, when there are several)
   type(c_ptr), save :: mctx = c_null_ptr                 ! kidmp_multi handle, when kidmp_ndevices > 1
   ! Staging arrays of mp_thompson_batch: page-locked (kidmp_host_alloc) and kept between calls, so that the library's
   ! upload / step / download pipeline can move them by DMA.  1 = state (12 profiles), 2 = p, w, dz, 3 = ppt,
-  ! 4 = the 36 rate profiles, 5 = the substep counts, 6 = the reflectivity (only when asked for).
+  ! 4 = the 36 rate profiles, 5 = the substep counts, 6 = the column outputs dbz, re_qc, re_qi, re_qs (only when asked for).
   type(c_ptr), save :: hbuf(6) = c_null_ptr
   integer(c_size_t), save :: hbytes(6) = 0_c_size_t
 
@@ -187,26 +197,44 @@ module module_mp_thompson09n
        integer(c_int32_t), value :: nz
        type(c_ptr), value :: t, p, qv, qr, nr, qs, qg, dbz         ! real(c_float) [ncol][nz]
      end function kidmp32_reflectivity_host
-     integer(c_int) function kidmp_batch_step_host_refl(ctx, ncol, nz, dt, qv, qc, qi, qr, qs, qg, ni, nr, &
-          nc, nwfa, nifa, t, p, w, dz, ppt, rates, nstep, dbz) bind(C, name='kidmp_batch_step_host_refl')
-       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
+     ! calc_effectRad, M:4834-4935 (include/kidmp.h): n = ncol*nz elements; re_* INOUT; nc, qi + ni, qs may be NULL
+     integer(c_int) function kidmp_effective_radii_host(ctx, n, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs) &
+          bind(C, name='kidmp_effective_radii_host')
+       import :: c_int, c_int64_t, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: n
+       type(c_ptr), value :: t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs   ! real(c_double) [n]
+     end function kidmp_effective_radii_host
+     integer(c_int) function kidmp32_effective_radii_host(ctx, n, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs) &
+          bind(C, name='kidmp32_effective_radii_host')
+       import :: c_int, c_int64_t, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: n
+       type(c_ptr), value :: t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs   ! real(c_float) [n]
+     end function kidmp32_effective_radii_host
+     ! the step followed by the outputs of the post-step state; nothing requested in `out` = kidmp_batch_step_host_diag
+     integer(c_int) function kidmp_batch_step_host_out(ctx, ncol, nz, dt, qv, qc, qi, qr, qs, qg, ni, nr, &
+          nc, nwfa, nifa, t, p, w, dz, ppt, rates, nstep, out) bind(C, name='kidmp_batch_step_host_out')
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr, kidmp_outputs
        type(c_ptr), value :: ctx
        integer(c_int64_t), value :: ncol
        integer(c_int32_t), value :: nz
        real(c_double), value :: dt
        type(c_ptr), value :: qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t, p, w, dz, ppt
-       type(c_ptr), value :: rates, nstep, dbz
-     end function kidmp_batch_step_host_refl
-     integer(c_int) function kidmp32_batch_step_host_refl(ctx, ncol, nz, dt, qv, qc, qi, qr, qs, qg, ni, nr, &
-          nc, nwfa, nifa, t, p, w, dz, ppt, rates, nstep, arith, dbz) bind(C, name='kidmp32_batch_step_host_refl')
-       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
+       type(c_ptr), value :: rates, nstep
+       type(kidmp_outputs), intent(in) :: out
+     end function kidmp_batch_step_host_out
+     integer(c_int) function kidmp32_batch_step_host_out(ctx, ncol, nz, dt, qv, qc, qi, qr, qs, qg, ni, nr, &
+          nc, nwfa, nifa, t, p, w, dz, ppt, rates, nstep, arith, out) bind(C, name='kidmp32_batch_step_host_out')
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr, kidmp_outputs
        type(c_ptr), value :: ctx
        integer(c_int64_t), value :: ncol
        integer(c_int32_t), value :: nz, arith
        real(c_float), value :: dt
        type(c_ptr), value :: qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t, p, w, dz, ppt
-       type(c_ptr), value :: rates, nstep, dbz
-     end function kidmp32_batch_step_host_refl
+       type(c_ptr), value :: rates, nstep
+       type(kidmp_outputs), intent(in) :: out
+     end function kidmp32_batch_step_host_out
   end interface
 
 contains
@@ -403,6 +431,44 @@ contains
     call stop_on_error(rc, 'calc_refl10cm')
   end subroutine calc_refl10cm_batch
 
+  ! calc_effectRad, M:4834-4935, with the reference's dummy list and intents: effective radii of cloud water, cloud ice
+  ! and snow of one column; re_* are INOUT (a level without the species keeps the caller's value).  Default REAL 8 goes to
+  ! kidmp_effective_radii_host, REAL 4 to kidmp32_effective_radii_host (binary32 in and out, binary64 inside).
+  subroutine calc_effectRad (t1d, p1d, qv1d, qc1d, nc1d, qi1d, ni1d, qs1d, re_qc1d, re_qi1d, re_qs1d, kts, kte)
+    integer, intent(in) :: kts, kte
+    real, dimension(kts:kte), intent(in) :: t1d, p1d, qv1d, qc1d, nc1d, qi1d, ni1d, qs1d
+    real, dimension(kts:kte), intent(inout) :: re_qc1d, re_qi1d, re_qs1d
+    call calc_effectRad_batch(1, kte - kts + 1, t1d, p1d, qv1d, qc1d, re_qc1d, re_qi1d, re_qs1d, &
+         nc=nc1d, qi=qi1d, ni=ni1d, qs=qs1d)
+  end subroutine calc_effectRad
+
+  ! calc_effectRad over ncol columns of KiD's (nz, ncol) storage in one call.  nc may be left out unless
+  ! is_aerosol_aware (it is not read then, M:4863); qi, ni and qs in an iiwarm run (re_qi, re_qs then stay as they came).
+  subroutine calc_effectRad_batch(ncol, nz, t, p, qv, qc, re_qc, re_qi, re_qs, nc, qi, ni, qs)
+    integer, intent(in) :: ncol, nz
+    real, dimension(nz,ncol), intent(in), target :: t, p, qv, qc
+    real, dimension(nz,ncol), intent(inout), target :: re_qc, re_qi, re_qs
+    real, dimension(nz,ncol), intent(in), optional, target :: nc, qi, ni, qs
+    type(c_ptr) :: pnc, pqi, pni, pqs
+    integer(c_int64_t) :: n
+    integer(c_int) :: rc
+    if (.not. c_associated(ctx)) call thompson_init
+    pnc = c_null_ptr;  pqi = c_null_ptr;  pni = c_null_ptr;  pqs = c_null_ptr
+    if (present(nc)) pnc = c_loc(nc)
+    if (present(qi)) pqi = c_loc(qi)
+    if (present(ni)) pni = c_loc(ni)
+    if (present(qs)) pqs = c_loc(qs)
+    n = int(ncol, c_int64_t) * int(nz, c_int64_t)
+    if (kind(t) == c_double) then
+       rc = kidmp_effective_radii_host(ctx, n, c_loc(t), c_loc(p), c_loc(qv), c_loc(qc), pnc, pqi, pni, pqs, &
+            c_loc(re_qc), c_loc(re_qi), c_loc(re_qs))
+    else
+       rc = kidmp32_effective_radii_host(ctx, n, c_loc(t), c_loc(p), c_loc(qv), c_loc(qc), pnc, pqi, pni, pqs, &
+            c_loc(re_qc), c_loc(re_qi), c_loc(re_qs))
+    end if
+    call stop_on_error(rc, 'calc_effectRad')
+  end subroutine calc_effectRad_batch
+
   ! The page-locked staging arrays themselves, for a caller whose default REAL is the storage type of kidmp_arith
   ! (8-byte REAL with 'p64', 4-byte REAL with 'p32n' / 'f32'): st(nz,ncol,12) in the argument order of mp_thompson
   ! (qv qc qi qr qs qg ni nr nc nwfa nifa t), fo(nz,ncol,3) = p, w, dz, pp(4,ncol).  Filled in place and passed to
@@ -428,7 +494,8 @@ contains
   ! What KiD never fills may be left out (keyword call): nc, nwfa, nifa and w without is_aerosol_aware (W:36 passes
   ! them unset; the library forms the non-aerosol defaults of M:958-964 on the GPU), qi, qs, qg, ni in an iiwarm run
   ! (they stay zero, W:46-52).  Absent arrays are neither staged nor sent across PCIe.
-  subroutine mp_thompson_batch(ncol, nz, dt, qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t, p, w, dz, ppt, dbz)
+  subroutine mp_thompson_batch(ncol, nz, dt, qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t, p, w, dz, ppt, dbz, &
+       re_qc, re_qi, re_qs)
     integer, intent(in) :: ncol, nz
     real, intent(in) :: dt
     real, dimension(nz,ncol), intent(inout), target :: qv, qc, qr, nr, t
@@ -438,8 +505,13 @@ contains
     real, dimension(4,ncol), intent(inout), target :: ppt
     ! dbz (optional): calc_refl10cm (M:4946-5244) of the post-step state, formed on the GPU in the same host call
     real, dimension(nz,ncol), intent(out), optional, target :: dbz
-    real(c_double), pointer :: s(:,:,:), f(:,:,:), pp(:,:), rates(:,:,:), zd(:,:)
-    real(c_float), pointer :: z4(:,:)
+    ! re_qc, re_qi, re_qs (optional, all three): calc_effectRad (M:4834-4935) of the post-step state in the form of the
+    ! scheme's driver -- presets first, M:1111-1116 --, formed by the same launch as dbz (kidmp_batch_step_host_out)
+    real, dimension(nz,ncol), intent(out), optional, target :: re_qc, re_qi, re_qs
+    real(c_double), pointer :: s(:,:,:), f(:,:,:), pp(:,:), rates(:,:,:), zd(:,:,:)
+    real(c_float), pointer :: z4(:,:,:)
+    type(kidmp_outputs) :: out
+    logical :: want_radii
     real(c_float), pointer :: s4(:,:,:), f4(:,:,:), pp4(:,:)
     integer(c_int32_t), pointer :: nstep(:,:)
     type(c_ptr) :: prates, pnstep, ps(12), pf(3)
@@ -455,6 +527,16 @@ contains
        write(*,'(a)') ' module_mp_thompson09n: qi, qs, qg, ni (and nc, nwfa, nifa) must be passed or left out together'
        stop 1
     end if
+    want_radii = present(re_qc)
+    if ((want_radii .neqv. present(re_qi)) .or. (want_radii .neqv. present(re_qs))) then
+       write(*,'(a)') ' module_mp_thompson09n: re_qc, re_qi, re_qs must be passed or left out together'
+       stop 1
+    end if
+    if ((present(dbz) .or. want_radii) .and. c_associated(mctx)) then
+       write(*,'(a)') ' module_mp_thompson09n: radar reflectivity is not available with kidmp_ndevices > 1'
+       stop 1
+    end if
+    out = kidmp_outputs(c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr)
     prates = c_null_ptr;  pnstep = c_null_ptr
     nprof = int(nz, c_size_t) * int(ncol, c_size_t)
     if (l_rate_diagnostics) then
@@ -506,13 +588,20 @@ contains
           ps(3) = c_null_ptr;  ps(5) = c_null_ptr;  ps(6) = c_null_ptr;  ps(7) = c_null_ptr
        end if
        if (.not. have_aer) ps(9:11) = c_null_ptr
-       if (present(dbz)) then
-          call staging(6, 4_c_size_t * nprof)
-          call c_f_pointer(hbuf(6), z4, [nz, ncol])
-          rc = kidmp32_batch_step_host_refl(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_float), &
+       if (present(dbz) .or. want_radii) then
+          call staging(6, 4_c_size_t * 4 * nprof)
+          call c_f_pointer(hbuf(6), z4, [nz, ncol, 4])
+          if (present(dbz)) out%dbz = c_loc(z4(1,1,1))
+          if (want_radii) then
+             out%re_qc = c_loc(z4(1,1,2));  out%re_qi = c_loc(z4(1,1,3));  out%re_qs = c_loc(z4(1,1,4))
+          end if
+          rc = kidmp32_batch_step_host_out(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_float), &
                ps(1), ps(2), ps(3), ps(4), ps(5), ps(6), ps(7), ps(8), ps(9), ps(10), ps(11), ps(12), &
-               pf(1), pf(2), pf(3), c_loc(pp4), prates, pnstep, arith, hbuf(6))
-          if (rc == 0) dbz = z4
+               pf(1), pf(2), pf(3), c_loc(pp4), prates, pnstep, arith, out)
+          if (rc == 0 .and. present(dbz)) dbz = z4(:,:,1)
+          if (rc == 0 .and. want_radii) then
+             re_qc = z4(:,:,2);  re_qi = z4(:,:,3);  re_qs = z4(:,:,4)
+          end if
        else
        rc = kidmp32_batch_step_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_float), &
             ps(1), ps(2), ps(3), ps(4), ps(5), ps(6), ps(7), ps(8), ps(9), ps(10), ps(11), ps(12), &
@@ -562,17 +651,20 @@ contains
        ps(3) = c_null_ptr;  ps(5) = c_null_ptr;  ps(6) = c_null_ptr;  ps(7) = c_null_ptr
     end if
     if (.not. have_aer) ps(9:11) = c_null_ptr
-    if (present(dbz)) then                                 ! one GPU, the step followed by calc_refl10cm on the device
-       if (c_associated(mctx)) then
-          write(*,'(a)') ' module_mp_thompson09n: radar reflectivity is not available with kidmp_ndevices > 1'
-          stop 1
+    if (present(dbz) .or. want_radii) then                 ! one GPU, the step followed by ONE launch for the outputs
+       call staging(6, 8_c_size_t * 4 * nprof)
+       call c_f_pointer(hbuf(6), zd, [nz, ncol, 4])
+       if (present(dbz)) out%dbz = c_loc(zd(1,1,1))
+       if (want_radii) then
+          out%re_qc = c_loc(zd(1,1,2));  out%re_qi = c_loc(zd(1,1,3));  out%re_qs = c_loc(zd(1,1,4))
        end if
-       call staging(6, 8_c_size_t * nprof)
-       call c_f_pointer(hbuf(6), zd, [nz, ncol])
-       rc = kidmp_batch_step_host_refl(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_double), &
+       rc = kidmp_batch_step_host_out(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_double), &
             ps(1), ps(2), ps(3), ps(4), ps(5), ps(6), ps(7), ps(8), ps(9), ps(10), ps(11), ps(12), &
-            pf(1), pf(2), pf(3), c_loc(pp), prates, pnstep, hbuf(6))
-       if (rc == 0) dbz = real(zd)
+            pf(1), pf(2), pf(3), c_loc(pp), prates, pnstep, out)
+       if (rc == 0 .and. present(dbz)) dbz = real(zd(:,:,1))
+       if (rc == 0 .and. want_radii) then
+          re_qc = real(zd(:,:,2));  re_qi = real(zd(:,:,3));  re_qs = real(zd(:,:,4))
+       end if
     else if (c_associated(mctx)) then                      ! several GPUs: contiguous column ranges, one pipeline each
        rc = kidmp_batch_step_host_multi(mctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_double), &
             ps(1), ps(2), ps(3), ps(4), ps(5), ps(6), ps(7), ps(8), ps(9), ps(10), ps(11), ps(12), &

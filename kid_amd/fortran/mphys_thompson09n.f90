@@ -32,6 +32,10 @@ module mphys_thompson09n
   ! calc_refl10cm (M:4946-5244) of the post-step state, asked for in the same host call and saved as 'dBZ' (z,x) after
   ! the precipitation diagnostics.  .false.: call sequence and output as without it.
   logical, public :: l_radar_reflectivity = .false.
+  ! calc_effectRad (M:4834-4935) of the post-step state in the form of the scheme's driver (presets first, M:1111-1116),
+  ! asked for in the same host call and saved as 're_cloud', 're_ice', 're_snow' (the driver's names, M:1118-1120; m,
+  ! z,x) at the end of the sequence, after 'dBZ' if that is on too.  .false.: call sequence and output as without it.
+  logical, public :: l_effective_radii = .false.
   integer:: ih, imom
   character(max_char_len) :: name, units
 
@@ -61,6 +65,7 @@ contains
     real, allocatable, save :: total(:)
     real, allocatable, save :: pptrain_2d_prof(:,:)          ! W:32; saved as 'total_ppt_level' for nx > 1 (W:304-307)
     real, allocatable, save :: dbz(:,:)                      ! l_radar_reflectivity: (nz, nx)
+    real, allocatable, save :: re(:,:,:)                     ! l_effective_radii: (nz, nx, 3) = cloud water, ice, snow
     real :: rho
     logical :: staged
     integer :: i, k, m, s
@@ -124,11 +129,29 @@ contains
 
     ! ---- all nx columns in one call (replaces the loop around W:143-152) ----
     ppt = 0.0
-    if (l_radar_reflectivity) then
-       if (allocated(dbz)) then
-          if (size(dbz, 1) /= nz .or. size(dbz, 2) /= nx) deallocate(dbz)
+    if (allocated(dbz)) then
+       if (size(dbz, 1) /= nz .or. size(dbz, 2) /= nx .or. .not. l_radar_reflectivity) deallocate(dbz)
+    end if
+    if (l_radar_reflectivity .and. .not. allocated(dbz)) allocate(dbz(nz, nx))
+    if (l_effective_radii) then
+       if (allocated(re)) then
+          if (size(re, 1) /= nz .or. size(re, 2) /= nx) deallocate(re)
        end if
-       if (.not. allocated(dbz)) allocate(dbz(nz, nx))
+       if (.not. allocated(re)) allocate(re(nz, nx, 3))
+       ! (dbz is allocated only with l_radar_reflectivity: an unallocated actual argument is an absent optional one)
+       if (is_aerosol_aware) then
+          call mp_thompson_batch(nx, nz, dt, st(:,:,S_QV), st(:,:,S_QC), st(:,:,S_QI), st(:,:,S_QR), st(:,:,S_QS), &
+               st(:,:,S_QG), st(:,:,S_NI), st(:,:,S_NR), st(:,:,S_NC), st(:,:,S_NWFA), st(:,:,S_NIFA), st(:,:,S_T), &
+               fo(:,:,1), fo(:,:,2), fo(:,:,3), ppt, dbz, re(:,:,1), re(:,:,2), re(:,:,3))
+       else if (iiwarm) then
+          call mp_thompson_batch(nx, nz, dt, qv=st(:,:,S_QV), qc=st(:,:,S_QC), qr=st(:,:,S_QR), nr=st(:,:,S_NR), &
+               t=st(:,:,S_T), p=fo(:,:,1), dz=fo(:,:,3), ppt=ppt, dbz=dbz, re_qc=re(:,:,1), re_qi=re(:,:,2), re_qs=re(:,:,3))
+       else
+          call mp_thompson_batch(nx, nz, dt, qv=st(:,:,S_QV), qc=st(:,:,S_QC), qi=st(:,:,S_QI), qr=st(:,:,S_QR), &
+               qs=st(:,:,S_QS), qg=st(:,:,S_QG), ni=st(:,:,S_NI), nr=st(:,:,S_NR), t=st(:,:,S_T), p=fo(:,:,1), &
+               dz=fo(:,:,3), ppt=ppt, dbz=dbz, re_qc=re(:,:,1), re_qi=re(:,:,2), re_qs=re(:,:,3))
+       end if
+    else if (l_radar_reflectivity) then
        if (is_aerosol_aware) then
           call mp_thompson_batch(nx, nz, dt, st(:,:,S_QV), st(:,:,S_QC), st(:,:,S_QI), st(:,:,S_QR), st(:,:,S_QS), &
                st(:,:,S_QG), st(:,:,S_NI), st(:,:,S_NR), st(:,:,S_NC), st(:,:,S_NWFA), st(:,:,S_NIFA), st(:,:,S_T), &
@@ -210,6 +233,12 @@ contains
     end if
     ! ---- radar reflectivity (calc_refl10cm of the post-step state; no bright band, as the reference ships it) ----
     if (l_radar_reflectivity) call save_dg(dbz, 'dBZ', i_dgtime, 'dBZ', dim='z,x')
+    ! ---- effective radii for radiation coupling (calc_effectRad of the post-step state) ----
+    if (l_effective_radii) then
+       call save_dg(re(:,:,1), 're_cloud', i_dgtime, 'm', dim='z,x')
+       call save_dg(re(:,:,2), 're_ice', i_dgtime, 'm', dim='z,x')
+       call save_dg(re(:,:,3), 're_snow', i_dgtime, 'm', dim='z,x')
+    end if
 
   end Subroutine mphys_thompson09_interfacen
 

@@ -41,6 +41,11 @@ class _Cfg(C.Structure):
                 ("device", C.c_int32), ("is_aerosol_aware", C.c_int32)]
 
 
+class _Outputs(C.Structure):
+    """kidmp_outputs / kidmp32_outputs (include/kidmp.h): four pointers, null = not wanted."""
+    _fields_ = [("dbz", C.c_void_p), ("re_qc", C.c_void_p), ("re_qi", C.c_void_p), ("re_qs", C.c_void_p)]
+
+
 def lib_path():
     """The in-tree build.  No environment override: a profiling or A/B build is selected explicitly with
     load_library(path) (bench.py --lib) before the first context is made."""
@@ -100,6 +105,22 @@ def load_library(path=None):
     L.kidmp_sanity_device.argtypes = [_vp, C.c_int64] + [_vp] * 9 + [_vp]
     L.kidmp_effective_radii_device.restype = C.c_int
     L.kidmp_effective_radii_device.argtypes = [_vp, C.c_int64] + [_vp] * 11 + [_vp]
+    L.kidmp_effective_radii_host.restype = C.c_int
+    L.kidmp_effective_radii_host.argtypes = [_vp, C.c_int64] + [_dp] * 11
+    L.kidmp32_effective_radii_device.restype = C.c_int
+    L.kidmp32_effective_radii_device.argtypes = [_vp, C.c_int64] + [_vp] * 11 + [_vp]
+    L.kidmp32_effective_radii_host.restype = C.c_int
+    L.kidmp32_effective_radii_host.argtypes = [_vp, C.c_int64] + [_fpp] * 11
+    L.kidmp_column_outputs_device.restype = C.c_int
+    L.kidmp_column_outputs_device.argtypes = [_vp, C.c_int64, C.c_int32] + [_vp] * 11 + [C.POINTER(_Outputs), _vp]
+    L.kidmp32_column_outputs_device.restype = C.c_int
+    L.kidmp32_column_outputs_device.argtypes = [_vp, C.c_int64, C.c_int32] + [_vp] * 11 + [C.POINTER(_Outputs), _vp]
+    L.kidmp_batch_step_host_out.restype = C.c_int
+    L.kidmp_batch_step_host_out.argtypes = ([_vp, C.c_int64, C.c_int32, C.c_double] + [_dp] * 17
+                                            + [C.POINTER(C.c_int32), C.POINTER(_Outputs)])
+    L.kidmp32_batch_step_host_out.restype = C.c_int
+    L.kidmp32_batch_step_host_out.argtypes = ([_vp, C.c_int64, C.c_int32, C.c_float] + [_fpp] * 16
+                                              + [_dp, C.POINTER(C.c_int32), C.c_int32, C.POINTER(_Outputs)])
     L.kidmp_batch_step_host_diag.restype = C.c_int
     L.kidmp_batch_step_host_diag.argtypes = [_vp, C.c_int64, C.c_int32, C.c_double] + [_dp] * 17 + [C.POINTER(C.c_int32)]
     L.kidmp_reflectivity_device.restype = C.c_int
@@ -256,11 +277,20 @@ class ThompsonMP:
         return tuple(ppt)
 
     # ---- batched host entry: numpy [ncol, nz] ----
-    def batch_step_host(self, st, dt, ppt=None, want_rates=False, want_dbz=False):
+    def _host_outputs(self, ncol, nz, dtype, want_dbz, want_radii):
+        """The output arrays of a host step and the kidmp_outputs that names them."""
+        dbz = np.empty((ncol, nz), dtype=dtype) if want_dbz else None
+        radii = tuple(np.empty((ncol, nz), dtype=dtype) for _ in range(3)) if want_radii else None
+        o = _Outputs(dbz.ctypes.data if want_dbz else None, *([a.ctypes.data for a in radii] if want_radii else [None] * 3))
+        return dbz, radii, o
+
+    def batch_step_host(self, st, dt, ppt=None, want_rates=False, want_dbz=False, want_radii=False):
         """numpy float64 [ncol, nz] arrays, in place.  Keys KiD itself never fills may be missing (or None): nc, nwfa,
         nifa and w for a context without aerosol_aware, qi, qs, qg, ni for an iiwarm context (include/kidmp.h).
         Returns (ppt, rates); with want_dbz (ppt, rates, dbz): the reflectivity of the post-step state, formed on the
-        device in the same call (kidmp_batch_step_host_refl)."""
+        device in the same call (kidmp_batch_step_host_refl).  want_radii appends (re_qc, re_qi, re_qs) of the
+        post-step state in the form of the scheme's driver, presets where the species is absent
+        (kidmp_batch_step_host_out: one launch per chunk for everything wanted)."""
         ncol, nz = st["qv"].shape
         ptrs = []
         for k in STATE_NAMES + FORCING_NAMES:
@@ -274,6 +304,12 @@ class ThompsonMP:
         if ppt is None:
             ppt = np.zeros((ncol, 4))
         rates = np.zeros((ncol, NRATES, nz)) if want_rates else None
+        if want_radii:
+            dbz, radii, o = self._host_outputs(ncol, nz, np.float64, want_dbz, True)
+            self._check(load_library().kidmp_batch_step_host_out(
+                self._h, ncol, nz, float(dt), *ptrs, _np_ptr(ppt), _np_ptr(rates) if want_rates else None, None,
+                C.byref(o)))
+            return (ppt, rates, dbz, radii) if want_dbz else (ppt, rates, radii)
         if want_dbz:
             dbz = np.empty((ncol, nz))
             self._check(load_library().kidmp_batch_step_host_refl(
@@ -320,9 +356,11 @@ class ThompsonMP:
     #      and the all-binary32 build ("f32") -- include/kidmp.h, kidmp32_* ----
     ARITH = {"p32n": 0, "f32": 1}
 
-    def batch_step32_host(self, st, dt, arith="p32n", ppt=None, want_rates=False, want_nstep=False, want_dbz=False):
+    def batch_step32_host(self, st, dt, arith="p32n", ppt=None, want_rates=False, want_nstep=False, want_dbz=False,
+                          want_radii=False):
         """numpy float32 [ncol, nz] arrays, in place.  Returns (ppt float32 [ncol, 4], rates float64 or None, nstep or None),
-        with want_dbz a fourth element: the float32 reflectivity of the post-step state (kidmp32_batch_step_host_refl)."""
+        with want_dbz a fourth element: the float32 reflectivity of the post-step state (kidmp32_batch_step_host_refl);
+        want_radii appends the float32 (re_qc, re_qi, re_qs) of that state (kidmp32_batch_step_host_out)."""
         ncol, nz = st["qv"].shape
         fpp = C.POINTER(C.c_float)
         for k in STATE_NAMES + FORCING_NAMES:
@@ -336,6 +374,10 @@ class ThompsonMP:
         args = ([self._h, ncol, nz, float(dt)] + [st[k].ctypes.data_as(fpp) for k in STATE_NAMES + FORCING_NAMES]
                 + [ppt.ctypes.data_as(fpp), _np_ptr(rates) if want_rates else None,
                    nstep.ctypes.data_as(C.POINTER(C.c_int32)) if want_nstep else None, self.ARITH[arith]])
+        if want_radii:
+            dbz, radii, o = self._host_outputs(ncol, nz, np.float32, want_dbz, True)
+            self._check(load_library().kidmp32_batch_step_host_out(*args, C.byref(o)))
+            return (ppt, rates, nstep, dbz, radii) if want_dbz else (ppt, rates, nstep, radii)
         if want_dbz:
             dbz = np.empty((ncol, nz), dtype=np.float32)
             self._check(load_library().kidmp32_batch_step_host_refl(*args, dbz.ctypes.data_as(fpp)))
@@ -433,7 +475,8 @@ class ThompsonMP:
 
     def effective_radii(self, st, preset=(2.49e-6, 4.99e-6, 9.99e-6), stream=None):
         """calc_effectRad (M:4834-4935): (re_qc, re_qi, re_qs) [ncol, nz] on the device, started from the presets of the
-        scheme's driver (M:1111-1113)."""
+        scheme's driver (M:1111-1113).  A caller that wants the radii every step wants column_outputs: it does not fill
+        three preset tensors first, and returns the reflectivity from the same read of the state."""
         import torch
         q = st["qv"]
         for k in ("t", "p", "qv", "qc", "nc", "qi", "ni", "qs"):
@@ -444,6 +487,68 @@ class ThompsonMP:
             self._h, q.numel(), *[st[k].data_ptr() for k in ("t", "p", "qv", "qc", "nc", "qi", "ni", "qs")],
             *[o.data_ptr() for o in out], s))
         return tuple(out)
+
+    RADII_NAMES = ("t", "p", "qv", "qc", "nc", "qi", "ni", "qs")                    # calc_effectRad's IN dummies, M:4842
+    OUTPUT_NAMES = ("t", "p", "qv", "qc", "nc", "qi", "ni", "qr", "nr", "qs", "qg")   # kidmp_column_outputs_device
+
+    def effective_radii_host(self, st, preset=(2.49e-6, 4.99e-6, 9.99e-6)):
+        """calc_effectRad on numpy arrays [ncol, nz] (float64 or float32, keys RADII_NAMES): (re_qc, re_qi, re_qs) of
+        the same dtype (kidmp_effective_radii_host / kidmp32_effective_radii_host), INOUT like the subroutine.
+        `preset`: three scalars to start from, or three arrays that are updated in place and returned.  nc may be
+        missing (or None) unless the context is aerosol-aware; qi + ni and qs in an iiwarm context, where re_qi and
+        re_qs are then returned as they were preset."""
+        q = st["t"]
+        if q.dtype not in (np.float64, np.float32) or q.ndim != 2:
+            raise KidmpError("effective_radii_host: state must be float64 or float32 numpy arrays [ncol, nz]")
+        pt = C.POINTER(C.c_double) if q.dtype == np.float64 else C.POINTER(C.c_float)
+        ptrs = []
+        for k in self.RADII_NAMES:
+            a = st.get(k)
+            if a is None and k in ("nc", "qi", "ni", "qs"):
+                ptrs.append(None)
+                continue
+            if not (a.dtype == q.dtype and a.flags.c_contiguous and a.shape == q.shape):
+                raise KidmpError("effective_radii_host: %s must be contiguous %s [ncol, nz]" % (k, q.dtype))
+            ptrs.append(a.ctypes.data_as(pt))
+        out = []
+        for v in preset:
+            if isinstance(v, np.ndarray):
+                if not (v.dtype == q.dtype and v.flags.c_contiguous and v.shape == q.shape):
+                    raise KidmpError("effective_radii_host: preset arrays must match the state")
+                out.append(v)
+            else:
+                out.append(np.full(q.shape, v, dtype=q.dtype))
+        fn = load_library().kidmp_effective_radii_host if q.dtype == np.float64 else load_library().kidmp32_effective_radii_host
+        self._check(fn(self._h, q.size, *ptrs, *[o.ctypes.data_as(pt) for o in out]))
+        return tuple(out)
+
+    def column_outputs(self, st, dbz=True, radii=True, stream=None):
+        """What a host model takes from the state beside the step (kidmp_column_outputs_device): the reflectivity of
+        calc_refl10cm and the effective radii of calc_effectRad in the driver's form (preset where the species is
+        absent, M:1111-1116), of float64 or float32 CUDA tensors [ncol, nz] with the keys OUTPUT_NAMES.  nc may be
+        missing unless the context is aerosol-aware, qi + ni and qs + qg in an iiwarm context.  With both wanted, one
+        kernel reads the column once.  Returns (dbz, (re_qc, re_qi, re_qs)), None for what was not asked for.
+        Asynchronous on `stream`."""
+        import torch
+        q = st["t"]
+        if q.dtype not in (torch.float64, torch.float32) or q.dim() != 2:
+            raise KidmpError("column_outputs: state must be float64 or float32 CUDA tensors [ncol, nz]")
+        ncol, nz = q.shape
+        ptrs = []
+        for k in self.OUTPUT_NAMES:
+            a = st.get(k)
+            if a is None:
+                ptrs.append(None)                      # the library decides what may be left out
+                continue
+            self._want(a, q.dtype, (ncol, nz), "column_outputs: " + k)
+            ptrs.append(a.data_ptr())
+        o_dbz = torch.empty_like(q) if dbz else None
+        o_rad = tuple(torch.empty_like(q) for _ in range(3)) if radii else None
+        o = _Outputs(o_dbz.data_ptr() if dbz else None, *([a.data_ptr() for a in o_rad] if radii else [None] * 3))
+        s = stream if stream is not None else torch.cuda.current_stream(q.device).cuda_stream
+        fn = load_library().kidmp_column_outputs_device if q.dtype == torch.float64 else load_library().kidmp32_column_outputs_device
+        self._check(fn(self._h, ncol, nz, *ptrs, C.byref(o), s))
+        return o_dbz, o_rad
 
     REFL_NAMES = ("t", "p", "qv", "qr", "nr", "qs", "qg")      # the inputs of calc_refl10cm that are read (qc1d is not)
 
