@@ -350,6 +350,31 @@ int kidmp32_batch_step_host_out(kidmp_ctx *ctx, int64_t ncol, int32_t nz, float 
                                 const float *p, const float *w, const float *dz,
                                 float *ppt, double *rates, int32_t *nstep, int32_t arith, const kidmp32_outputs *out);
 
+/* ---- a droplet number per column: Nd ensembles in one launch ----
+ * set_Nc (KiD namelists, M:22) enters the scheme only as Nt_c = set_Nc*1.e6 (M:381): no lookup table depends on it and
+ * nu_c is formed per level, so one context and one set of tables serve any mix of values.  kidmp_set_column_nc binds an
+ * array of ncol values to the context; while it is bound, column c of every batch uses Nt_c = set_nc[c]*1.e6 wherever the
+ * context's scalar is read on the device: the column step (M:1410, M:2081, M:2602, M:2799), calc_effectRad (M:4863) and
+ * the default aerosols (nc = Nt_c/rho, M:960).  A uniform array reproduces a context initialised with that value bit for
+ * bit; without a binding every entry returns the bits it returned before.  calc_refl10cm does not read Nt_c.
+ *   IN   set_nc   [ncol] binary64 (also for the kidmp32_* entries), cm**-3, host or device memory.  Copied into a buffer
+ *                 the context owns: the call allocates, is synchronous, and the caller's array may be freed afterwards.
+ *                 The step entries still never allocate and stay capturable into a hipGraph.
+ *                 ncol == 0 or set_nc NULL unbinds.  kidmp_column_nc_count: the bound count, 0 when nothing is bound.
+ *   refused (KIDMP_EINVAL, the previous binding stays): a value that is not finite and > 0 -- what kidmp_init demands of
+ *                 cfg->set_Nc; the message names the first such column -- and an aerosol-aware context (n_c is prognostic).
+ * While a binding is active (KIDMP_EINVAL otherwise, no array touched):
+ *   kidmp[32]_column_step (count 1), kidmp[32]_batch_step_device, kidmp[32]_batch_step_host / _diag / _refl / _out and
+ *   kidmp[32]_column_outputs_device take ncol == the bound count; the host pipeline offsets into the bound buffer by each
+ *   chunk's first column, so nothing extra crosses PCIe per call;
+ *   kidmp[32]_effective_radii_{device,host} and kidmp_default_aerosols_device, which have n and no nz, take n as a
+ *   multiple of the bound count: nz = n / count, element e belongs to column e / nz;
+ *   kidmp_batch_step_host_multi[_diag] refuse a multi handle one of whose member contexts holds a binding: sharding the
+ *   array over devices is not implemented.
+ * kidmp_get_const("Nt_c") keeps returning the context's scalar. */
+int kidmp_set_column_nc(kidmp_ctx *ctx, int64_t ncol, const double *set_nc);
+int64_t kidmp_column_nc_count(const kidmp_ctx *ctx);
+
 /* Introspection for parity tests: copy a lookup table / constant array to the
  * host.  Names are the reference's (tcg_racg ... t_Efsw; cre, crg, Dr ...).
  * Returns the number of doubles (<0 on error); out may be NULL to query. */

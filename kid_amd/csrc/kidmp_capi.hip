@@ -49,13 +49,14 @@ int refl_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const T *t, const T *p
 
 template <class R>
 int kidmp::step_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, R dt, R *const *io, const R *p, const R *w, const R *dz,
-                       R *ppt, double *rates, int32_t *nstep, int32_t arith, void *stream)
+                       R *ppt, double *rates, int32_t *nstep, int32_t arith, void *stream, int64_t nc_first)
 {
     // w1d only feeds activ_ncloud (is_aerosol_aware, M:2797): optional otherwise
     const void *ptrs[] = {io[0], io[1], io[2], io[3], io[4], io[5], io[6], io[7], io[8], io[9], io[10], io[11], p, dz, ppt};
     if (int rc = check_step_args(ctx, ncol, nz, double(dt), ptrs, 15)) return rc;
     if (ctx->cfg.is_aerosol_aware && !w) return fail(ctx, KIDMP_EINVAL, "kidmp: an aerosol-aware context needs the updraft profile w");
     if (std::is_same<R, float>::value && !valid_arith(arith)) return fail(ctx, KIDMP_EINVAL, BAD_ARITH);
+    if (nc_first < 0) if (int rc = check_nc_count(ctx, "kidmp_batch_step", ncol)) return rc;
     GUARD(ctx);
     if (int rc = check_on_device(ctx, io[0], "qv")) return rc;
     if (int rc = check_on_device(ctx, ppt, "ppt")) return rc;
@@ -66,15 +67,16 @@ int kidmp::step_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, R dt, R *const 
     a.ppt = ppt; a.rates = rates; a.nstep = nstep; a.ncol = ncol; a.nz = nz; a.dt = dt;
     a.cslot = ctx->cslot; a.tables = ctx->tables; a.iiwarm = ctx->cfg.iiwarm != 0; a.aero = ctx->cfg.is_aerosol_aware != 0;
     a.debug_stop = ctx->debug_stop;
+    a.set_nc_col = ctx->d_nc_col ? ctx->d_nc_col + (nc_first > 0 ? nc_first : 0) : nullptr;
     if constexpr (std::is_same<R, double>::value) HIPTRY(ctx, p64::launch_column_step(a, (hipStream_t)stream));
     else if (arith == KIDMP_ARITH_P32N)           HIPTRY(ctx, p32n::launch_column_step(a, (hipStream_t)stream));
     else                                          HIPTRY(ctx, f32::launch_column_step(a, (hipStream_t)stream));
     return KIDMP_OK;
 }
 template int kidmp::step_device<double>(kidmp_ctx *, int64_t, int32_t, double, double *const *, const double *, const double *,
-                                        const double *, double *, double *, int32_t *, int32_t, void *);
+                                        const double *, double *, double *, int32_t *, int32_t, void *, int64_t);
 template int kidmp::step_device<float>(kidmp_ctx *, int64_t, int32_t, float, float *const *, const float *, const float *,
-                                       const float *, float *, double *, int32_t *, int32_t, void *);
+                                       const float *, float *, double *, int32_t *, int32_t, void *, int64_t);
 
 // ---- calc_refl10cm entries (M:4946-5244) ----
 // arguments common to the four entries; qs/qg: both or neither, neither only in an iiwarm context (a warm run keeps them 0)
@@ -155,7 +157,7 @@ void kidmp_finalize(kidmp_ctx *c)
     if (!c) return;
     DeviceGuard guard_(c->cfg.device);
     free_tables(c->tables);
-    for (void *p : {(void *)c->d_consts, (void *)c->d_bins, (void *)c->d_stage, (void *)c->d_red, (void *)c->d_sanity, (void *)c->d_acc})
+    for (void *p : {(void *)c->d_consts, (void *)c->d_bins, (void *)c->d_stage, (void *)c->d_red, (void *)c->d_sanity, (void *)c->d_acc, (void *)c->d_nc_col})
         if (p) (void)hipFree(p);
     for (hipStream_t s : {c->stream, c->s_h2d, c->s_d2h})
         if (s) (void)hipStreamDestroy(s);
@@ -202,6 +204,39 @@ int kidmp32_reflectivity_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const 
 {
     return refl_device<float>(ctx, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz, stream);
 }
+
+// ---- a droplet number per column (set_Nc, namelists M:22; Nt_c = set_Nc*1.e6, M:381) ----
+int kidmp_set_column_nc(kidmp_ctx *ctx, int64_t ncol, const double *set_nc)
+{
+    if (int rc = require_ready(ctx)) return rc;
+    if (ncol < 0) return fail(ctx, KIDMP_EINVAL, "kidmp_set_column_nc: ncol < 0");
+    if (ctx->cfg.is_aerosol_aware)
+        return fail(ctx, KIDMP_EINVAL, "kidmp_set_column_nc: the context is aerosol-aware (the droplet number is prognostic there)");
+    if (ncol > int64_t(0x7fffffff)) return fail(ctx, KIDMP_EINVAL, "kidmp_set_column_nc: more columns than one launch takes");
+    GUARD(ctx);
+    if (ncol == 0 || !set_nc) {                              // unbind
+        if (ctx->d_nc_col) HIPTRY(ctx, hipFree(ctx->d_nc_col));   // (waits for the work that reads it)
+        ctx->d_nc_col = nullptr;
+        ctx->nc_count = 0;
+        return KIDMP_OK;
+    }
+    if (int rc = check_on_device(ctx, set_nc, "set_nc")) return rc;
+    std::vector<double> h;
+    try { h.resize(size_t(ncol)); } catch (const std::exception &) { return fail(ctx, KIDMP_ENOMEM, "kidmp_set_column_nc: out of host memory"); }
+    HIPTRY(ctx, hipMemcpy(h.data(), set_nc, size_t(ncol) * sizeof(double), hipMemcpyDefault));
+    for (int64_t i = 0; i < ncol; ++i)                       // what kidmp_init demands of cfg->set_Nc, and finite
+        if (!(h[size_t(i)] > 0.) || !(h[size_t(i)] <= 1.7976931348623157e308))
+            return fail(ctx, KIDMP_EINVAL, "kidmp_set_column_nc: set_nc of column " + std::to_string(i) + " is not a finite number > 0");
+    double *d = nullptr;
+    HIPTRY(ctx, hipMalloc((void **)&d, size_t(ncol) * sizeof(double)));
+    const hipError_t e = hipMemcpy(d, h.data(), size_t(ncol) * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); return hipfail(ctx, e, "hipMemcpy(set_nc)"); }
+    if (ctx->d_nc_col) (void)hipFree(ctx->d_nc_col);
+    ctx->d_nc_col = d;
+    ctx->nc_count = ncol;
+    return KIDMP_OK;
+}
+int64_t kidmp_column_nc_count(const kidmp_ctx *ctx) { return ctx && ctx->ready && ctx->d_nc_col ? ctx->nc_count : 0; }
 
 const char *kidmp_kernel_fingerprint(kidmp_ctx *ctx)
 {

@@ -48,6 +48,9 @@ struct kidmp_ctx {
     // exact (fixed-point) domain sums of the surface precipitation: KIDMP_PPT_LIMBS 64-bit accumulators
     unsigned long long *d_acc = nullptr;
     std::string fingerprint;
+    // kidmp_set_column_nc: the bound per-column set_Nc (cm**-3, binary64) in HBM, owned by the context; null = unbound
+    double *d_nc_col = nullptr;
+    int64_t nc_count = 0;
 };
 
 namespace kidmp {
@@ -130,15 +133,38 @@ inline int check_step_args(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, 
     return KIDMP_OK;
 }
 
+// While a per-column droplet number is bound (kidmp_set_column_nc) a batch must be exactly the bound columns.
+inline int check_nc_count(kidmp_ctx *c, const char *who, int64_t ncol)
+{
+    if (!c || !c->d_nc_col || ncol == c->nc_count) return KIDMP_OK;
+    return fail(c, KIDMP_EINVAL, std::string(who) + ": ncol = " + std::to_string(ncol) + ", but kidmp_set_column_nc bound " +
+                                 std::to_string(c->nc_count) + " columns");
+}
+// the entries that take n elements and no nz: n must be whole columns of the binding; nz_col = 0 without a binding
+inline int nc_levels_of(kidmp_ctx *c, const char *who, int64_t n, int64_t &nz_col)
+{
+    nz_col = 0;
+    if (!c || !c->d_nc_col || n <= 0) return KIDMP_OK;
+    if (n % c->nc_count != 0)
+        return fail(c, KIDMP_EINVAL, std::string(who) + ": n = " + std::to_string(n) + " is not a multiple of the " +
+                                     std::to_string(c->nc_count) + " columns kidmp_set_column_nc bound");
+    nz_col = n / c->nc_count;
+    return KIDMP_OK;
+}
+
 // kidmp_capi.hip: the one body of the step's device entries (R = double: p64; float: `arith` selects p32n or f32), which
 // also steps every chunk of the host pipeline; io = qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t
 template <class R>
 int step_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, R dt, R *const *io, const R *p, const R *w, const R *dz,
-                R *ppt, double *rates, int32_t *nstep, int32_t arith, void *stream);
+                R *ppt, double *rates, int32_t *nstep, int32_t arith, void *stream, int64_t nc_first = -1);
+// nc_first: with a per-column droplet number bound, -1 = the batch is the whole binding (ncol is checked against it);
+// >= 0 = a chunk of the host pipeline (which made that check) whose first column is nc_first
 int check_refl_args(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const void *const *req, int nreq, const void *qs, const void *qg);
 
 // kidmp_diag.hip.  The two void ones only launch: the caller asks hipGetLastError().  v = qc, qr, nr, qs, qi, qg, ni, qv
-template <class T> void launch_default_aerosols(int64_t n, T Nt_c, const T *qv, const T *t, const T *p, T *nc, T *nwfa, T *nifa, hipStream_t s);
+// set_nc_col (null: Nt_c everywhere): per-column set_Nc in cm**-3, element i belonging to column (e0 + i) / nz_col
+template <class T> void launch_default_aerosols(int64_t n, T Nt_c, const T *qv, const T *t, const T *p, T *nc, T *nwfa, T *nifa, hipStream_t s,
+                                                const double *set_nc_col = nullptr, int64_t nz_col = 1, int64_t e0 = 0);
 void launch_sanity(int64_t n, const double *const (&v)[SANITY_NEG], unsigned long long *acc, hipStream_t s);
 template <class T> hipError_t launch_ppt_exact(int64_t ncol, const T *ppt, unsigned long long *acc, hipStream_t s);
 // the column outputs (dbz, re_qc, re_qi, re_qs; preset form): the checks every entry shares, then ONE launch picked from
@@ -147,14 +173,16 @@ template <class T> int check_outputs_request(kidmp_ctx *ctx, const char *who, co
 template <class T>
 int check_outputs_args(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, const ColumnState<T> &in, const ColumnOutputs<T> &out);
 template <class T>
-hipError_t launch_outputs(kidmp_ctx *ctx, int64_t ncol, int nz, const ColumnState<T> &in, const ColumnOutputs<T> &out, hipStream_t s);
+hipError_t launch_outputs(kidmp_ctx *ctx, int64_t ncol, int nz, const ColumnState<T> &in, const ColumnOutputs<T> &out, hipStream_t s,
+                          int64_t nc_first = 0);   // first column of the batch within a bound per-column droplet number
 // calc_effectRad in its INOUT (keep) form on n elements, with the optional arrays of the lenient entries
 template <class T>
 int check_radii_args(kidmp_ctx *ctx, const char *who, int64_t n, const T *t, const T *p, const T *qv, const T *qc, const T *nc,
                      const T *qi, const T *ni, const T *qs, T *re_qc, T *re_qi, T *re_qs);
 template <class T>
 hipError_t launch_radii_keep(kidmp_ctx *ctx, int64_t n, const T *t, const T *p, const T *qv, const T *qc, const T *nc,
-                             const T *qi, const T *ni, const T *qs, T *re_qc, T *re_qi, T *re_qs, hipStream_t s);
+                             const T *qi, const T *ni, const T *qs, T *re_qc, T *re_qi, T *re_qs, hipStream_t s,
+                             int64_t nz_col = 0, int64_t e0 = 0);   // nc_levels_of; e0: the first element's index in the binding
 
 // kidmp_host.hip.  What an entry may ask of the pipeline beyond the step: the exact precipitation sums and the sanity
 // scan (left in ctx->d_acc / d_sanity), and the column outputs (host arrays) of every chunk's post-step state.

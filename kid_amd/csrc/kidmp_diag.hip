@@ -10,10 +10,12 @@ namespace {
 // the non-aerosol defaults of M:958-964 in the state's own arithmetic (REAL expressions of the reference)
 template <class T>
 __global__ void k_default_aerosols(int64_t n, T Nt_c, const T *__restrict__ qv, const T *__restrict__ t,
-                                   const T *__restrict__ p, T *__restrict__ nc, T *__restrict__ nwfa, T *__restrict__ nifa)
+                                   const T *__restrict__ p, T *__restrict__ nc, T *__restrict__ nwfa, T *__restrict__ nifa,
+                                   const double *__restrict__ set_nc_col, int64_t nz_col, int64_t e0)
 {
     const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (set_nc_col) Nt_c = T(set_nc_col[(e0 + i) / nz_col] * 1.e6);          // the column's own, rounded as T(Consts::Nt_c)
     const T rho = T(0.622) * p[i] / (T(Rgas) * t[i] * (qv[i] + T(0.622)));   // M:959
     nc[i] = Nt_c / rho;                                                      // M:960
     nwfa[i] = T(11.1E6) / rho;                                               // M:961
@@ -142,12 +144,13 @@ __global__ void k_sanity_final(const unsigned long long *acc, double *out15)
 //         the scheme's driver (M:1111-1116): such a level receives the preset 2.49E-6 / 4.99E-6 / 9.99E-6 m.  The driver's
 //         clamps after the call (M:1118-1120) change nothing after the subroutine's own and are not computed.
 // nc1 may be null when the context is not aerosol-aware (nc = Nt_c, M:4863); null qi + ni and null qs read as zero; null
-// re_qi / re_qs are not formed.
+// re_qi / re_qs are not formed.  set_nc_col (null: c.Nt_c): the bound per-column set_Nc, element i in column (e0 + i) / nz_col.
 template <class T, bool KEEP>
 __global__ void k_effective_radii(int64_t n, RadConsts c, const T *__restrict__ t, const T *__restrict__ p,
                                   const T *__restrict__ qv, const T *__restrict__ qc, const T *__restrict__ nc1,
                                   const T *__restrict__ qi, const T *__restrict__ ni1, const T *__restrict__ qs,
-                                  T *__restrict__ re_qc, T *__restrict__ re_qi, T *__restrict__ re_qs)
+                                  T *__restrict__ re_qc, T *__restrict__ re_qi, T *__restrict__ re_qs,
+                                  const double *__restrict__ set_nc_col, int64_t nz_col, int64_t e0)
 {
     const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
 #if KFM_TABLES
@@ -158,7 +161,8 @@ __global__ void k_effective_radii(int64_t n, RadConsts c, const T *__restrict__ 
     const double temp = double(t[i]);
     const double rho = lvl::air_density(double(p[i]), temp, double(qv[i]));
     double re;
-    if (lvl::cloud_water_radius(c, rho, double(qc[i]), nc1 ? double(nc1[i]) : 0., re)) re_qc[i] = T(re);
+    const double Nt_c = set_nc_col ? set_nc_col[(e0 + i) / nz_col] * 1.e6 : c.Nt_c;
+    if (lvl::cloud_water_radius(c, Nt_c, rho, double(qc[i]), nc1 ? double(nc1[i]) : 0., re)) re_qc[i] = T(re);
     else if (!KEEP) re_qc[i] = T(lvl::RE_QC_PRESET);
     if (re_qi) {
         if (qi && lvl::cloud_ice_radius(c, rho, double(qi[i]), double(ni1[i]), re)) re_qi[i] = T(re);
@@ -174,12 +178,12 @@ __global__ void k_effective_radii(int64_t n, RadConsts c, const T *__restrict__ 
 template <class T>
 hipError_t launch_effective_radii(const RadConsts &c, bool keep, int64_t n, const T *t, const T *p, const T *qv, const T *qc,
                                   const T *nc, const T *qi, const T *ni, const T *qs, T *re_qc, T *re_qi, T *re_qs,
-                                  hipStream_t s)
+                                  hipStream_t s, const double *set_nc_col = nullptr, int64_t nz_col = 1, int64_t e0 = 0)
 {
     if (n <= 0) return hipSuccess;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    if (keep) hipLaunchKernelGGL((k_effective_radii<T, true>), grid, block, 0, s, n, c, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs);
-    else      hipLaunchKernelGGL((k_effective_radii<T, false>), grid, block, 0, s, n, c, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs);
+    if (keep) hipLaunchKernelGGL((k_effective_radii<T, true>), grid, block, 0, s, n, c, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs, set_nc_col, nz_col, e0);
+    else      hipLaunchKernelGGL((k_effective_radii<T, false>), grid, block, 0, s, n, c, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs, set_nc_col, nz_col, e0);
     return hipGetLastError();
 }
 
@@ -210,12 +214,16 @@ __global__ void k_math_probe(int fn, int64_t n, const double *x, const double *y
 }
 }  // namespace
 
-template <class T> void kidmp::launch_default_aerosols(int64_t n, T Nt_c, const T *qv, const T *t, const T *p, T *nc, T *nwfa, T *nifa, hipStream_t s)
+template <class T> void kidmp::launch_default_aerosols(int64_t n, T Nt_c, const T *qv, const T *t, const T *p, T *nc, T *nwfa, T *nifa, hipStream_t s,
+                                                       const double *set_nc_col, int64_t nz_col, int64_t e0)
 {
-    hipLaunchKernelGGL(k_default_aerosols<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, Nt_c, qv, t, p, nc, nwfa, nifa);
+    hipLaunchKernelGGL(k_default_aerosols<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, Nt_c, qv, t, p, nc, nwfa, nifa,
+                       set_nc_col, nz_col > 0 ? nz_col : 1, e0);
 }
-template void kidmp::launch_default_aerosols<double>(int64_t, double, const double *, const double *, const double *, double *, double *, double *, hipStream_t);
-template void kidmp::launch_default_aerosols<float>(int64_t, float, const float *, const float *, const float *, float *, float *, float *, hipStream_t);
+template void kidmp::launch_default_aerosols<double>(int64_t, double, const double *, const double *, const double *, double *, double *, double *, hipStream_t,
+                                                     const double *, int64_t, int64_t);
+template void kidmp::launch_default_aerosols<float>(int64_t, float, const float *, const float *, const float *, float *, float *, float *, hipStream_t,
+                                                    const double *, int64_t, int64_t);
 
 template <class T> hipError_t kidmp::launch_ppt_exact(int64_t ncol, const T *ppt, unsigned long long *acc, hipStream_t s)
 {
@@ -260,6 +268,7 @@ int kidmp::check_outputs_args(kidmp_ctx *ctx, const char *who, int64_t ncol, int
     const std::string w(who);
     if (int rc = check_outputs_request<T>(ctx, who, out)) return rc;
     if (ncol < 0) return fail(ctx, KIDMP_EINVAL, w + ": ncol < 0");
+    if (int rc = check_nc_count(ctx, who, ncol)) return rc;
     if (nz < 2 || nz > KIDMP_MAX_NZ) return fail(ctx, KIDMP_EINVAL, w + ": nz outside [2, KIDMP_MAX_NZ]");
     const bool radii = out.re_qc != nullptr, warm = ctx->cfg.iiwarm != 0;
     if (ncol == 0 || (!radii && !out.dbz)) return KIDMP_OK;
@@ -276,25 +285,26 @@ int kidmp::check_outputs_args(kidmp_ctx *ctx, const char *who, int64_t ncol, int
 // single read of the column.  Arguments as checked above.
 template <class T>
 hipError_t kidmp::launch_outputs(kidmp_ctx *ctx, int64_t ncol, int nz, const ColumnState<T> &in, const ColumnOutputs<T> &out,
-                                 hipStream_t s)
+                                 hipStream_t s, int64_t nc_first)
 {
     const bool aero = ctx->cfg.is_aerosol_aware != 0;
     const T *nc = aero ? in.nc : nullptr;
+    const double *set_nc = ctx->d_nc_col ? ctx->d_nc_col + nc_first : nullptr;   // the batch's share of a bound droplet number
     if (out.dbz && out.re_qc) {
         ColumnState<T> st = in;
         st.nc = nc;
-        return launch_column_outputs<T>(refl_consts(ctx->hc), rad_consts(ctx->hc, aero), ncol, nz, st, out, s);
+        return launch_column_outputs<T>(refl_consts(ctx->hc), rad_consts(ctx->hc, aero), ncol, nz, st, out, s, set_nc);
     }
     if (out.dbz) return launch_reflectivity<T>(refl_consts(ctx->hc), ncol, nz, in.t, in.p, in.qv, in.qr, in.nr, in.qs, in.qg, out.dbz, s);
     if (out.re_qc)
         return launch_effective_radii<T>(rad_consts(ctx->hc, aero), false, ncol * int64_t(nz), in.t, in.p, in.qv, in.qc, nc, in.qi,
-                                         in.ni, in.qs, out.re_qc, out.re_qi, out.re_qs, s);
+                                         in.ni, in.qs, out.re_qc, out.re_qi, out.re_qs, s, set_nc, nz, 0);
     return hipSuccess;
 }
 #define KIDMP_INSTANTIATE_OUTPUTS(T) \
     template int kidmp::check_outputs_request<T>(kidmp_ctx *, const char *, const ColumnOutputs<T> &); \
     template int kidmp::check_outputs_args<T>(kidmp_ctx *, const char *, int64_t, int32_t, const ColumnState<T> &, const ColumnOutputs<T> &); \
-    template hipError_t kidmp::launch_outputs<T>(kidmp_ctx *, int64_t, int, const ColumnState<T> &, const ColumnOutputs<T> &, hipStream_t);
+    template hipError_t kidmp::launch_outputs<T>(kidmp_ctx *, int64_t, int, const ColumnState<T> &, const ColumnOutputs<T> &, hipStream_t, int64_t);
 KIDMP_INSTANTIATE_OUTPUTS(double)
 KIDMP_INSTANTIATE_OUTPUTS(float)
 #undef KIDMP_INSTANTIATE_OUTPUTS
@@ -320,17 +330,18 @@ int kidmp::check_radii_args(kidmp_ctx *ctx, const char *who, int64_t n, const T 
 }
 template <class T>
 hipError_t kidmp::launch_radii_keep(kidmp_ctx *ctx, int64_t n, const T *t, const T *p, const T *qv, const T *qc, const T *nc,
-                                    const T *qi, const T *ni, const T *qs, T *re_qc, T *re_qi, T *re_qs, hipStream_t s)
+                                    const T *qi, const T *ni, const T *qs, T *re_qc, T *re_qi, T *re_qs, hipStream_t s,
+                                    int64_t nz_col, int64_t e0)
 {
     const bool aero = ctx->cfg.is_aerosol_aware != 0;
     return launch_effective_radii<T>(rad_consts(ctx->hc, aero), true, n, t, p, qv, qc, aero ? nc : nullptr, qi, ni, qs, re_qc,
-                                     re_qi, re_qs, s);
+                                     re_qi, re_qs, s, nz_col > 0 ? ctx->d_nc_col : nullptr, nz_col > 0 ? nz_col : 1, e0);
 }
 #define KIDMP_INSTANTIATE_RADII(T) \
     template int kidmp::check_radii_args<T>(kidmp_ctx *, const char *, int64_t, const T *, const T *, const T *, const T *, const T *, \
                                             const T *, const T *, const T *, T *, T *, T *); \
     template hipError_t kidmp::launch_radii_keep<T>(kidmp_ctx *, int64_t, const T *, const T *, const T *, const T *, const T *, \
-                                                    const T *, const T *, const T *, T *, T *, T *, hipStream_t);
+                                                    const T *, const T *, const T *, T *, T *, T *, hipStream_t, int64_t, int64_t);
 KIDMP_INSTANTIATE_RADII(double)
 KIDMP_INSTANTIATE_RADII(float)
 #undef KIDMP_INSTANTIATE_RADII
@@ -359,10 +370,12 @@ int kidmp_default_aerosols_device(kidmp_ctx *ctx, int64_t n, const double *qv, c
     if (int rc = require_ready(ctx)) return rc;
     if (n < 0 || !qv || !t || !p || !nc || !nwfa || !nifa) return fail(ctx, KIDMP_EINVAL, "kidmp_default_aerosols_device: bad argument");
     if (n == 0) return KIDMP_OK;
+    int64_t nz_col = 0;
+    if (int rc = nc_levels_of(ctx, "kidmp_default_aerosols_device", n, nz_col)) return rc;
     GUARD(ctx);
     if (int rc = check_on_device(ctx, qv, "qv")) return rc;
     if (int rc = check_on_device(ctx, nc, "nc")) return rc;
-    launch_default_aerosols<double>(n, ctx->hc.Nt_c, qv, t, p, nc, nwfa, nifa, (hipStream_t)stream);
+    launch_default_aerosols<double>(n, ctx->hc.Nt_c, qv, t, p, nc, nwfa, nifa, (hipStream_t)stream, nz_col ? ctx->d_nc_col : nullptr, nz_col);
     HIPTRY(ctx, hipGetLastError());
     return KIDMP_OK;
 }
@@ -439,10 +452,12 @@ int kidmp_effective_radii_device(kidmp_ctx *ctx, int64_t n, const double *t, con
     if (n < 0 || !t || !p || !qv || !qc || !nc || !qi || !ni || !qs || !re_qc || !re_qi || !re_qs)
         return fail(ctx, KIDMP_EINVAL, "kidmp_effective_radii_device: bad argument");
     if (n == 0) return KIDMP_OK;
+    int64_t nz_col = 0;
+    if (int rc = nc_levels_of(ctx, "kidmp_effective_radii_device", n, nz_col)) return rc;
     GUARD(ctx);
     if (int rc = check_on_device(ctx, t, "t")) return rc;
     if (int rc = check_on_device(ctx, re_qc, "re_qc")) return rc;
-    HIPTRY(ctx, launch_radii_keep<double>(ctx, n, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs, (hipStream_t)stream));
+    HIPTRY(ctx, launch_radii_keep<double>(ctx, n, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs, (hipStream_t)stream, nz_col));
     return KIDMP_OK;
 }
 
@@ -452,12 +467,14 @@ int kidmp32_effective_radii_device(kidmp_ctx *ctx, int64_t n, const float *t, co
 {
     if (int rc = check_radii_args<float>(ctx, "kidmp32_effective_radii_device", n, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs)) return rc;
     if (n == 0) return KIDMP_OK;
+    int64_t nz_col = 0;
+    if (int rc = nc_levels_of(ctx, "kidmp32_effective_radii_device", n, nz_col)) return rc;
     GUARD(ctx);
     const char *names[] = {"t", "p", "qv", "qc", "nc", "qi", "ni", "qs", "re_qc", "re_qi", "re_qs"};
     const void *ptrs[] = {t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs};
     for (int i = 0; i < 11; ++i)
         if (int rc = check_device_array(ctx, "kidmp32_effective_radii_device", ptrs[i], names[i])) return rc;
-    HIPTRY(ctx, launch_radii_keep<float>(ctx, n, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs, (hipStream_t)stream));
+    HIPTRY(ctx, launch_radii_keep<float>(ctx, n, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs, (hipStream_t)stream, nz_col));
     return KIDMP_OK;
 }
 

@@ -89,6 +89,8 @@ int radii_host(kidmp_ctx *ctx, const char *who, int64_t n, const T *t, const T *
 {
     if (int rc = check_radii_args<T>(ctx, who, n, t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs)) return rc;
     if (n == 0) return KIDMP_OK;
+    int64_t nz_col = 0;
+    if (int rc = nc_levels_of(ctx, who, n, nz_col)) return rc;
     GUARD(ctx);
     const int64_t want = (ctx->host_chunk > 0 ? ctx->host_chunk : 8192) * 128, CH = want < n ? want : n;
     const size_t b_prof = (size_t(CH) * sizeof(T) + 255) / 256 * 256;
@@ -106,7 +108,7 @@ int radii_host(kidmp_ctx *ctx, const char *who, int64_t n, const T *t, const T *
             if (h[v]) e = hipMemcpyAsync(d[v], h[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess)
             e = launch_radii_keep<T>(ctx, int64_t(cnt), d[0], d[1], d[2], d[3], dev(4), dev(5), dev(6), dev(7), d[8], dev(9),
-                                     dev(10), ctx->stream);
+                                     dev(10), ctx->stream, nz_col, off);
         for (int v = 0; v < 3 && e == hipSuccess; ++v)
             if (hout[v]) e = hipMemcpyAsync(hout[v] + off, d[8 + v], cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
     }
@@ -148,6 +150,7 @@ int kidmp::host_pipeline(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, T 
     }
     ptrs[np++] = in[0]; ptrs[np++] = in[1]; ptrs[np++] = ppt;
     if (int rc = check_step_args(ctx, ncol, nz, dt, ptrs, np)) return rc;
+    if (int rc = check_nc_count(ctx, "kidmp_batch_step_host", ncol)) return rc;
     if (has_w && !in[2] && ncol > 0) return fail(ctx, KIDMP_EINVAL, "kidmp: an aerosol-aware context needs the updraft profile w");
     if (ncol == 0) {
         if (exact_sums || scan_sanity) {
@@ -204,13 +207,14 @@ int kidmp::host_pipeline(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, T 
         if (skip_frz)
             for (int v : {2, 4, 5, 6}) HIPTRY(ctx, hipMemsetAsync(dio[v], 0, cnt * sizeof(T), ctx->stream));
         if (skip_aer) {
-            launch_default_aerosols<T>(int64_t(cnt), T(ctx->hc.Nt_c), dio[0], dio[11], din[0], dio[8], dio[9], dio[10], ctx->stream);
+            launch_default_aerosols<T>(int64_t(cnt), T(ctx->hc.Nt_c), dio[0], dio[11], din[0], dio[8], dio[9], dio[10], ctx->stream,
+                                       ctx->d_nc_col ? ctx->d_nc_col + c0 : nullptr, nz);   // (the bound buffer: nothing extra crosses PCIe)
             HIPTRY(ctx, hipGetLastError());
         }
-        if (int rc = step_device<T>(ctx, n, nz, T(dt), dio, din[0], din[2], din[1], dppt, drates, dnstep, arith, ctx->stream)) return rc;
+        if (int rc = step_device<T>(ctx, n, nz, T(dt), dio, din[0], din[2], din[1], dppt, drates, dnstep, arith, ctx->stream, c0)) return rc;
         if (n_out)                                            // the outputs of the chunk's post-step state
             HIPTRY(ctx, launch_outputs<T>(ctx, n, nz, {dio[11], din[0], dio[0], dio[1], dio[8], dio[2], dio[6], dio[3], dio[7],
-                                                       dio[4], dio[5]}, {dout[0], dout[1], dout[2], dout[3]}, ctx->stream));
+                                                       dio[4], dio[5]}, {dout[0], dout[1], dout[2], dout[3]}, ctx->stream, c0));
         if (exact_sums) HIPTRY(ctx, launch_ppt_exact<T>(n, dppt, ctx->d_acc, ctx->stream));   // the chunk's share of the domain sums
         if constexpr (std::is_same<T, double>::value)
             if (scan_sanity) {                                // the scan of M:1025-1094 over the chunk's end state (exact integer atomics)

@@ -125,6 +125,8 @@ int kidmp_batch_step_host_multi_diag(kidmp_multi *m, int64_t ncol, int32_t nz, d
     if (!m || m->ctx.empty()) return fail(m, KIDMP_ESTATE, "kidmp_batch_step_host_multi: not initialised");
     if (ncol < 0 || nz < 2 || nz > KIDMP_MAX_NZ) return fail(m, KIDMP_EINVAL, "kidmp_batch_step_host_multi: bad ncol / nz");
     const int nctx = int(m->ctx.size());
+    for (kidmp_ctx *c : m->ctx)                                // sharding a per-column droplet number is not implemented
+        if (c && c->d_nc_col) return fail(m, KIDMP_EINVAL, "kidmp_batch_step_host_multi: a member context holds a kidmp_set_column_nc binding");
     // Nothing below may throw through the C boundary: allocation failures (std::bad_alloc from the vectors, std::system_error
     // from std::thread) are mapped to a status code, and threads that did start are joined before the function returns.
     std::vector<int> rc;

@@ -30,6 +30,10 @@ struct StepArgsT {
     int32_t nz;
     R dt;
     int32_t debug_stop;   // 0 = run everything; n = leave after pass n-1 (libkidmp_prof.so, env KIDMP_DEBUG_STOP)
+    // nullptr or [ncol] set_Nc in cm**-3 (kidmp_set_column_nc; binary64 in every variant): the column's own Nt_c =
+    // real(set_nc_col[col] * 1.e6) (M:381) in place of Consts::Nt_c.  Selects the NCCOL instantiations; non-aerosol
+    // contexts only.  Last, so that no other kernarg offset moves.
+    const double *set_nc_col;
 };
 typedef StepArgsT<double> StepArgs;
 

@@ -52,11 +52,12 @@ __device__ inline double snow_moment(const double *a, const double *b, double x,
 
 // ---- calc_effectRad at one level.  Each function reports whether the level holds the species (the reference CYCLEs
 // otherwise, M:4874 / 4889 / 4897) and, if so, returns the radius in `re`. ----
-__device__ inline bool cloud_water_radius(const RadConsts &c, double rho, double qc, double nc1, double &re)
+// Nt_c: c.Nt_c, or the column's own where a per-column droplet number is bound (kidmp_set_column_nc)
+__device__ inline bool cloud_water_radius(const RadConsts &c, double Nt_c, double rho, double qc, double nc1, double &re)
 {
     const double am_r_ = PI * rho_w / 6.0;
     const double rc = fmax(R1, qc * rho);
-    const double nc = c.aero ? fmax(R2, nc1 * rho) : c.Nt_c;            // .NOT. is_aerosol_aware, M:4863
+    const double nc = c.aero ? fmax(R2, nc1 * rho) : Nt_c;              // .NOT. is_aerosol_aware, M:4863
     if (rc <= R1 || nc <= R2) return false;                             // M:4873-4884
     int inu_c;
     if (nc < 100.) inu_c = 15;

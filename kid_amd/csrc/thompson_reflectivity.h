@@ -30,6 +30,7 @@ template <class T> struct ColumnOutputs { T *dbz, *re_qc, *re_qi, *re_qs; };
 // out.re_qc; out.re_qi and out.re_qs may be null.
 template <class T>
 hipError_t launch_column_outputs(const ReflConsts &c, const RadConsts &rc, int64_t ncol, int nz, const ColumnState<T> &in,
-                                 const ColumnOutputs<T> &out, hipStream_t stream);
+                                 const ColumnOutputs<T> &out, hipStream_t stream, const double *set_nc_col = nullptr);
+// set_nc_col: null, or [ncol] set_Nc in cm**-3 (kidmp_set_column_nc): the column's own Nt_c = set_nc_col[col]*1.e6 for re_qc
 
 }  // namespace kidmp

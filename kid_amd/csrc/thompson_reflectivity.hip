@@ -33,6 +33,7 @@ struct RadiiArgs {
     RadConsts c;
     const T *qc, *nc, *qi, *ni;                      // nc null: not aerosol-aware; qi, ni null: zero
     T *re_qc, *re_qi, *re_qs;                        // re_qi, re_qs null: not wanted (iiwarm)
+    const double *set_nc_col;                        // null, or the per-column set_Nc of the batch (kidmp_set_column_nc)
 };
 struct NoRadii {};
 
@@ -83,14 +84,14 @@ __device__ inline double wave_suffix_min(double v, int lane, double &tail)
 // calc_effectRad does not clamp qv (M:4860) where calc_refl10cm does (M:4992): below 1e-10 the radii get a density of
 // their own, and only a level whose two densities are one shares the snow moment `sl` (valid when L_qs).
 template <class T>
-__device__ inline void radii_of_level(const ReflConsts &c, const RadiiArgs<T> &r, int64_t i, double temp, double pres, double qv_in, double qv,
+__device__ inline void radii_of_level(const ReflConsts &c, const RadiiArgs<T> &r, double Nt_c, int64_t i, double temp, double pres, double qv_in, double qv,
                                       double rho_z, double qs, bool L_qs, const lvl::SnowLevel &sl)
 {
     const bool same = qv_in == qv;
     const double rho = same ? rho_z : lvl::air_density(pres, temp, qv_in);
     double re;
     re = lvl::RE_QC_PRESET;
-    lvl::cloud_water_radius(r.c, rho, double(r.qc[i]), r.nc ? double(r.nc[i]) : 0., re);
+    lvl::cloud_water_radius(r.c, Nt_c, rho, double(r.qc[i]), r.nc ? double(r.nc[i]) : 0., re);
     r.re_qc[i] = T(re);
     if (r.re_qi) {
         re = lvl::RE_QI_PRESET;
@@ -122,6 +123,8 @@ __device__ __forceinline__ void column_diagnostics(const ReflConsts &c, const RA
     const int64_t col = int64_t(blockIdx.x) * REFL_WAVES + (int(threadIdx.x) >> 6);
     if (col >= ncol) return;                                         // whole wavefronts only: the scan needs every lane
     const int64_t base = col * int64_t(nz);
+    double Nt_c = 0.;                                                // the column's droplet number (radii only)
+    if constexpr (RADII) Nt_c = rad.set_nc_col ? rad.set_nc_col[col] * 1.e6 : rad.c.Nt_c;
 
     double ze_rs[NJ], n0[NJ], rg[NJ];
     bool lqg[NJ];
@@ -153,7 +156,7 @@ __device__ __forceinline__ void column_diagnostics(const ReflConsts &c, const RA
             sl = lvl::snow_level(temp, qs * rho, c.oams);
             ze_snow = lvl::snow_ze(c, sl);                           // M:5131-5132
         }
-        if constexpr (RADII) radii_of_level<T>(c, rad, i, temp, pres, qv_in, qv, rho, qs, L_qs, sl);
+        if constexpr (RADII) radii_of_level<T>(c, rad, Nt_c, i, temp, pres, qv_in, qv, rho, qs, L_qs, sl);
         if (lqg[j]) rg[j] = qg * rho;
         ze_rs[j] = ze_rain + ze_snow;
         // ---- graupel intercept before the running minimum, M:5088-5096 ----
@@ -270,9 +273,9 @@ hipError_t launch_reflectivity(const ReflConsts &c, int64_t ncol, int nz, const 
 
 template <class T>
 hipError_t launch_column_outputs(const ReflConsts &c, const RadConsts &rc, int64_t ncol, int nz, const ColumnState<T> &in,
-                                 const ColumnOutputs<T> &out, hipStream_t s)
+                                 const ColumnOutputs<T> &out, hipStream_t s, const double *set_nc_col)
 {
-    const RadiiArgs<T> rad{rc, in.qc, in.nc, in.qi, in.ni, out.re_qc, out.re_qi, out.re_qs};
+    const RadiiArgs<T> rad{rc, in.qc, in.nc, in.qi, in.ni, out.re_qc, out.re_qi, out.re_qs, set_nc_col};
     return launch_any<T>(c, &rad, ncol, nz, in.t, in.p, in.qv, in.qr, in.nr, in.qs, in.qg, out.dbz, s);
 }
 
@@ -283,8 +286,8 @@ template hipError_t launch_reflectivity<float>(const ReflConsts &, int64_t, int,
                                                const float *, const float *, const float *, const float *,
                                                const float *, float *, hipStream_t);
 template hipError_t launch_column_outputs<double>(const ReflConsts &, const RadConsts &, int64_t, int,
-                                                  const ColumnState<double> &, const ColumnOutputs<double> &, hipStream_t);
+                                                  const ColumnState<double> &, const ColumnOutputs<double> &, hipStream_t, const double *);
 template hipError_t launch_column_outputs<float>(const ReflConsts &, const RadConsts &, int64_t, int,
-                                                 const ColumnState<float> &, const ColumnOutputs<float> &, hipStream_t);
+                                                 const ColumnState<float> &, const ColumnOutputs<float> &, hipStream_t, const double *);
 
 }  // namespace kidmp

@@ -58,6 +58,7 @@ module module_mp_thompson09n
   public :: kidmp_precip_sums_valid
   public :: calc_refl10cm, calc_refl10cm_batch
   public :: calc_effectRad, calc_effectRad_batch
+  public :: mp_thompson_set_column_nc
   logical, public :: is_aerosol_aware = .false.          ! M:28 (read at thompson_init)
   logical, public :: l_rate_diagnostics = .true.         ! replay the save_dg calls of M:2962-3124
   integer, public :: kidmp_device = 0                    ! HIP device ordinal of this process (one GPU)
@@ -162,6 +163,12 @@ module module_mp_thompson09n
        integer(c_int32_t), value :: l_reuse, write_if_built
        integer(c_int32_t), intent(out) :: status
      end function kidmp_table_cache_reuse
+     integer(c_int) function kidmp_set_column_nc(ctx, ncol, set_nc) bind(C, name='kidmp_set_column_nc')
+       import :: c_int, c_int64_t, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol
+       type(c_ptr), value :: set_nc
+     end function kidmp_set_column_nc
      type(c_ptr) function kidmp_host_alloc(bytes) bind(C, name='kidmp_host_alloc')   ! page-locked host memory
        import :: c_ptr, c_size_t
        integer(c_size_t), value :: bytes
@@ -468,6 +475,31 @@ contains
     end if
     call stop_on_error(rc, 'calc_effectRad')
   end subroutine calc_effectRad_batch
+
+  ! A droplet number per column (kidmp_set_column_nc): column i of every following batched call uses Nt_c =
+  ! set_nc_col(i)*1.e6 (M:381) in place of the namelist's set_Nc -- an Nd ensemble, or an aerosol gradient along x, in
+  ! one launch.  cm**-3 like set_Nc; the values are copied.  An absent or zero-size argument unbinds.  While bound, a
+  ! batched call must have exactly size(set_nc_col) columns; not with is_aerosol_aware, not on several devices.
+  subroutine mp_thompson_set_column_nc(set_nc_col)
+    real, intent(in), optional :: set_nc_col(:)
+    real(c_double), allocatable, target :: v(:)
+    integer(c_int) :: rc
+    if (.not. c_associated(ctx)) call thompson_init
+    if (c_associated(mctx)) then
+       write(*,'(a)') ' module_mp_thompson09n: mp_thompson_set_column_nc is not available with kidmp_ndevices > 1'
+       stop 1
+    end if
+    if (.not. present(set_nc_col)) then
+       rc = kidmp_set_column_nc(ctx, 0_c_int64_t, c_null_ptr)
+    else if (size(set_nc_col) == 0) then
+       rc = kidmp_set_column_nc(ctx, 0_c_int64_t, c_null_ptr)
+    else
+       allocate(v(size(set_nc_col)))
+       v = real(set_nc_col, c_double)
+       rc = kidmp_set_column_nc(ctx, int(size(v), c_int64_t), c_loc(v))
+    end if
+    call stop_on_error(rc, 'mp_thompson_set_column_nc')
+  end subroutine mp_thompson_set_column_nc
 
   ! The page-locked staging arrays themselves, for a caller whose default REAL is the storage type of kidmp_arith
   ! (8-byte REAL with 'p64', 4-byte REAL with 'p32n' / 'f32'): st(nz,ncol,12) in the argument order of mp_thompson

@@ -36,6 +36,11 @@ module mphys_thompson09n
   ! asked for in the same host call and saved as 're_cloud', 're_ice', 're_snow' (the driver's names, M:1118-1120; m,
   ! z,x) at the end of the sequence, after 'dBZ' if that is on too.  .false.: call sequence and output as without it.
   logical, public :: l_effective_radii = .false.
+  ! A droplet number per column, cm**-3 like the namelist's set_Nc (M:22): allocated with size nx, column i is stepped with
+  ! Nt_c = set_Nc_column(i)*1.e6 (M:381) -- a stock 2-D case then has x as the axis of an Nd ensemble, all members in
+  ! one launch.  Unallocated: call sequence and results as without it.  Any other size stops the run.
+  real, allocatable, public :: set_Nc_column(:)
+  real, allocatable, private, save :: nc_bound(:)          ! what is bound in the library (unallocated: nothing)
   integer:: ih, imom
   character(max_char_len) :: name, units
 
@@ -125,6 +130,28 @@ contains
              st(k,i,S_NIFA) = 0.5E6*0.01/rho
           end do
        end do
+    end if
+
+    ! ---- the droplet number per column: bound before the batched call, again only when its contents changed ----
+    if (allocated(set_Nc_column)) then
+       if (size(set_Nc_column) /= nx) then
+          write(*,'(a,i0,a,i0)') ' mphys_thompson09n: set_Nc_column has ', size(set_Nc_column), ' elements, nx = ', nx
+          stop 1
+       end if
+       if (allocated(nc_bound)) then
+          if (size(nc_bound) /= nx) deallocate(nc_bound)
+       end if
+       if (.not. allocated(nc_bound)) then
+          allocate(nc_bound(nx))
+          nc_bound = set_Nc_column
+          call mp_thompson_set_column_nc(nc_bound)
+       else if (any(nc_bound /= set_Nc_column)) then
+          nc_bound = set_Nc_column
+          call mp_thompson_set_column_nc(nc_bound)
+       end if
+    else if (allocated(nc_bound)) then                      ! deallocated since the last call: back to the namelist's set_Nc
+       deallocate(nc_bound)
+       call mp_thompson_set_column_nc()
     end if
 
     ! ---- all nx columns in one call (replaces the loop around W:143-152) ----

@@ -184,6 +184,10 @@ def load_library(path=None):
     L.kidmp_host_free.argtypes = [_vp]
     L.kidmp_set_host_chunk.restype = C.c_int
     L.kidmp_set_host_chunk.argtypes = [_vp, C.c_int64]
+    L.kidmp_set_column_nc.restype = C.c_int
+    L.kidmp_set_column_nc.argtypes = [_vp, C.c_int64, _vp]
+    L.kidmp_column_nc_count.restype = C.c_int64
+    L.kidmp_column_nc_count.argtypes = [_vp]
     L.kidmp_init_seconds.restype = C.c_double
     L.kidmp_init_seconds.argtypes = [_vp]
     L.kidmp_kernel_name.restype = C.c_char_p
@@ -226,6 +230,27 @@ def host_pinned_copy(a):
     b = host_empty(a.shape, a.dtype)
     b[...] = a
     return b
+
+
+def column_nc_pointer(values, device=None):
+    """What kidmp_set_column_nc takes, from a numpy array or a torch tensor (host or CUDA): (address, count) of a
+    contiguous one-dimensional float64 array with at least one element.  Anything else raises KidmpError here, before
+    the library is called; the values themselves (finite, > 0) are the library's to judge."""
+    if isinstance(values, np.ndarray):
+        if values.dtype != np.float64 or values.ndim != 1 or values.size == 0 or not values.flags.c_contiguous:
+            raise KidmpError("set_column_nc: a numpy array must be contiguous float64 [ncol], ncol >= 1 (got %s %s)"
+                             % (values.dtype, list(values.shape)))
+        return values.ctypes.data, int(values.size)
+    if type(values).__module__.split(".")[0] == "torch" and hasattr(values, "data_ptr"):
+        import torch
+        if values.dtype != torch.float64 or values.dim() != 1 or values.numel() == 0 or not values.is_contiguous():
+            raise KidmpError("set_column_nc: a tensor must be contiguous float64 [ncol], ncol >= 1 (got %s %s)"
+                             % (str(values.dtype).replace("torch.", ""), list(values.shape)))
+        if values.is_cuda and device is not None and values.device.index != device:
+            raise KidmpError("set_column_nc: the tensor lives on cuda:%d but this context is bound to cuda:%d"
+                             % (values.device.index, device))
+        return values.data_ptr(), int(values.numel())
+    raise KidmpError("set_column_nc: expected a numpy array, a torch tensor or None, got %s" % type(values).__name__)
 
 
 class ThompsonMP:
@@ -416,6 +441,22 @@ class ThompsonMP:
             self._h, qv.numel(), qv.data_ptr(), t.data_ptr(), p.data_ptr(), nc.data_ptr(), nwfa.data_ptr(),
             nifa.data_ptr(), s))
         return nc, nwfa, nifa
+
+    def set_column_nc(self, values):
+        """Bind a droplet number per column (kidmp_set_column_nc): `values` is set_Nc in cm**-3, float64 [ncol], a
+        numpy array or a torch tensor on the host or on this context's GPU; None unbinds.  While bound, column c of
+        every batch steps with Nt_c = values[c]*1e6 (an Nd ensemble in one launch), batches must have exactly ncol
+        columns, and the radii and default aerosols follow.  The values are copied: the array may go away."""
+        if values is None:
+            self._check(load_library().kidmp_set_column_nc(self._h, 0, None))
+            return
+        ptr, n = column_nc_pointer(values, self.device)
+        self._check(load_library().kidmp_set_column_nc(self._h, n, ptr))
+
+    @property
+    def column_nc_count(self):
+        """How many columns set_column_nc has bound; 0 when nothing is bound."""
+        return int(load_library().kidmp_column_nc_count(self._h))
 
     def set_host_chunk(self, ncol_per_chunk):
         """Columns per pipeline chunk of the host-array entries (0 = default)."""
