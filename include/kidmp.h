@@ -375,6 +375,76 @@ int kidmp32_batch_step_host_out(kidmp_ctx *ctx, int64_t ncol, int32_t nz, float 
 int kidmp_set_column_nc(kidmp_ctx *ctx, int64_t ncol, const double *set_nc);
 int64_t kidmp_column_nc_count(const kidmp_ctx *ctx);
 
+/* ---- mphys_thompson09_interfacen (W:28-310): the KiD adapter, theta-form state in, tendencies out ----
+ * One call takes KiD's own fields and returns the microphysics tendencies and the surface precipitation:
+ *   gather (W:46-97, one launch)   t = (theta + (dtheta_adv + dtheta_div)*dt)*exner, X1 = X + (dX_adv + dX_div)*dt for
+ *                                  q_v and the hydrometeor moments, p = p0*exner**(1./r_on_cp) (formed on the device),
+ *                                  dz broadcast from KiD's one profile, w = 0, the frozen species exact zeros in an iiwarm
+ *                                  context (W:46-52), nc / nwfa / nifa the non-aerosol defaults of M:958-964 (the bits of
+ *                                  kidmp_default_aerosols_device on the gathered t, qv, p), ppt zeroed (W:55-58)
+ *   mp_thompson                    the column step of kidmp_batch_step_device on the gathered state
+ *   the column outputs             `out` as in kidmp_column_outputs_device, of the post-step state
+ *   back-out (W:198-245, one launch)   dtheta_mphys = (t/exner - theta)/dt - (dtheta_adv + dtheta_div),
+ *                                  dX_mphys = (X1 - X)/dt - (dX_adv + dX_div); /dt is a division
+ * Every operation is rounded in the arrays' format.  Fields are [ncol][nz] (KiD's theta(k,i) storage, W:60-93), dz is
+ * ONE profile of nz values, ppt is [ncol][4] = {rain, snow, graupel, ice}.
+ *   state   IN, never written.  theta, qv, qc, qr, nr always; qi, ni, qs, qg in a mixed-phase context.
+ *   adv, div   the advective and divergence tendencies.  Each may be NULL as a whole and any member may be NULL: NULL
+ *           means zero (never read; the results are bit for bit those of an array of +0.0).
+ *   mphys   OUT: the tendencies, same members as `state` (theta = dtheta_mphys, qv = dqv_mphys, the seven moments =
+ *           dhydrometeors_mphys).  A mixed-phase context requires the frozen members of `state` and `mphys`.
+ *   In an iiwarm context the frozen members (qi, ni, qs, qg) of state, adv, div and mphys are neither read nor written
+ *   and may be NULL.
+ *   ppt     OUT, not INOUT (W:55-58).  rates, nstep, out: optional, as for the step and the column outputs.
+ *   Output arrays must not overlap any input array (stated, not checked).
+ *   work    the device entries' workspace of kidmp_kid_workspace_bytes(ncol, nz) bytes, 16-byte aligned: 15 profiles of
+ *           ncol*nz values, each stride rounded up to 256 bytes; profile v starts at kidmp_kid_workspace_offset(ncol, nz, v):
+ *           0..11 = qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t (the order of mp_thompson's dummies, M:1156), 12 = p,
+ *           13 = w, 14 = dz.  After the call it holds the post-step T/q state: `out` is formed from it.
+ * The device entries never allocate, enqueue only on `stream` (gather, step, outputs, back-out: one linear chain) and
+ * can be captured into a hipGraph.  A bound per-column droplet number (kidmp_set_column_nc) is honoured; ncol must equal
+ * the bound count, as for the step.  The host entries run chunk by chunk inside the three-stream pipeline of
+ * kidmp_batch_step_host (upload of the present members of state, adv, div and exner; dz once; download of mphys, ppt and
+ * what else was requested); results are those of the device entry bit for bit for any chunking (kidmp_set_host_chunk).
+ * Refused with KIDMP_EINVAL, nothing written: a workspace that is too small, a missing required pointer, nz outside
+ * [2, KIDMP_MAX_NZ], dt <= 0, a pointer of another device.  A NULL context returns KIDMP_ESTATE; ncol == 0 KIDMP_OK.
+ * kidmp_kid_workspace_bytes / _offset need no context and no GPU and return 0 for bad arguments (ncol < 0, nz outside
+ * [1, KIDMP_MAX_NZ], v outside [0, 14]).  The kidmp32_* forms take binary32 arrays and `arith` like the step; p is then
+ * pow(double(exner), double(1.f/r_on_cp)) rounded once to binary32 (a correctly rounded powf), times p0 in binary32. */
+typedef struct kidmp_kid_fields   { double *theta, *qv, *qc, *qr, *nr, *qi, *ni, *qs, *qg; } kidmp_kid_fields;    /* each [ncol][nz] */
+typedef struct kidmp32_kid_fields { float  *theta, *qv, *qc, *qr, *nr, *qi, *ni, *qs, *qg; } kidmp32_kid_fields;
+size_t kidmp_kid_workspace_bytes(int64_t ncol, int32_t nz);
+size_t kidmp_kid_workspace_offset(int64_t ncol, int32_t nz, int32_t v);
+size_t kidmp32_kid_workspace_bytes(int64_t ncol, int32_t nz);
+size_t kidmp32_kid_workspace_offset(int64_t ncol, int32_t nz, int32_t v);
+int kidmp_kid_interface_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, double p0, double r_on_cp,
+                               const kidmp_kid_fields *state, const kidmp_kid_fields *adv, const kidmp_kid_fields *div,
+                               const double *exner, const double *dz, const kidmp_kid_fields *mphys, double *ppt,
+                               double *rates, int32_t *nstep, const kidmp_outputs *out,
+                               void *work, size_t work_bytes, void *stream);
+int kidmp_kid_interface_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, double p0, double r_on_cp,
+                             const kidmp_kid_fields *state, const kidmp_kid_fields *adv, const kidmp_kid_fields *div,
+                             const double *exner, const double *dz, const kidmp_kid_fields *mphys, double *ppt,
+                             double *rates, int32_t *nstep, const kidmp_outputs *out);
+int kidmp32_kid_interface_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, float dt, float p0, float r_on_cp,
+                                 const kidmp32_kid_fields *state, const kidmp32_kid_fields *adv, const kidmp32_kid_fields *div,
+                                 const float *exner, const float *dz, const kidmp32_kid_fields *mphys, float *ppt,
+                                 double *rates, int32_t *nstep, const kidmp32_outputs *out, int32_t arith,
+                                 void *work, size_t work_bytes, void *stream);
+int kidmp32_kid_interface_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, float dt, float p0, float r_on_cp,
+                               const kidmp32_kid_fields *state, const kidmp32_kid_fields *adv, const kidmp32_kid_fields *div,
+                               const float *exner, const float *dz, const kidmp32_kid_fields *mphys, float *ppt,
+                               double *rates, int32_t *nstep, const kidmp32_outputs *out, int32_t arith);
+/* The gather alone: fills the workspace with the step's inputs (the pre-step state, p, w, dz, the default aerosols) and
+ * zeroes ppt, for a host that runs kidmp[32]_batch_step_device on the workspace itself, and for the tests.  Arguments,
+ * checks and refusals as above. */
+int kidmp_kid_gather_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, double p0, double r_on_cp,
+                            const kidmp_kid_fields *state, const kidmp_kid_fields *adv, const kidmp_kid_fields *div,
+                            const double *exner, const double *dz, double *ppt, void *work, size_t work_bytes, void *stream);
+int kidmp32_kid_gather_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, float dt, float p0, float r_on_cp,
+                              const kidmp32_kid_fields *state, const kidmp32_kid_fields *adv, const kidmp32_kid_fields *div,
+                              const float *exner, const float *dz, float *ppt, void *work, size_t work_bytes, void *stream);
+
 /* Introspection for parity tests: copy a lookup table / constant array to the
  * host.  Names are the reference's (tcg_racg ... t_Efsw; cre, crg, Dr ...).
  * Returns the number of doubles (<0 on error); out may be NULL to query. */

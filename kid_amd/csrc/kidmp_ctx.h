@@ -1,5 +1,5 @@
 // kidmp_ctx.h -- internal to the units behind include/kidmp.h (not installed): the context, the error and device-guard
-// helpers of every entry point, and what the units kidmp_{capi,diag,host,tables,multi}.hip offer one another.
+// helpers of every entry point, and what the units kidmp_{capi,diag,host,tables,multi,adapter}.hip offer one another.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -190,4 +190,27 @@ template <class T> struct PipelineExtras { bool exact_sums = false, scan_sanity 
 template <class T>
 int host_pipeline(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, T *const *io, const T *const *in, T *ppt,
                   double *rates, int32_t *nstep, int32_t arith, const PipelineExtras<T> &extra = {});
+
+// kidmp_adapter.hip: the KiD adapter (W:28-310).  Members in the order of kidmp_kid_fields; WORK_OF[m] is the profile of
+// the workspace (0..11 the order of mp_thompson's dummies, 12 p, 13 w, 14 dz) that member m is gathered into.
+constexpr int KID_NF = 9, KID_NWARM = 5, KID_NWORK = 15;                 // theta, qv, qc, qr, nr | qi, ni, qs, qg
+constexpr int KID_WORK_OF[KID_NF] = {11, 0, 1, 3, 7, 2, 6, 4, 5};
+template <class T> struct KidFields { T *f[KID_NF]; };
+template <class T> struct KidCall {
+    int64_t ncol; int32_t nz; T dt, p0, r_on_cp;
+    KidFields<T> state, adv, div, mphys;             // a null member of adv / div is a zero operand
+    const T *exner, *dz;
+    T *ppt; double *rates; int32_t *nstep; ColumnOutputs<T> out;
+    int32_t arith;
+};
+inline size_t kid_stride(int64_t ncol, int32_t nz, size_t elem)      // bytes from one workspace profile to the next; 0: bad arguments
+{ return ncol < 0 || nz < 1 || nz > KIDMP_MAX_NZ ? 0 : (size_t(ncol) * size_t(nz) * elem + 255) / 256 * 256; }
+// what the device and the host entries check alike, before anything is written; F = kidmp_kid_fields / kidmp32_kid_fields
+template <class T, class F>
+int kid_check(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, double dt, const F *state, const F *adv, const F *div,
+              const T *exner, const T *dz, const F *mphys, T *ppt, const ColumnOutputs<T> &out, int32_t arith, KidCall<T> &call);
+// gather (gather_only: that alone), step, outputs, back-out on `s`, nothing else: `c` holds device pointers; nc_first as for step_device
+template <class T> int kid_enqueue(kidmp_ctx *ctx, const KidCall<T> &c, void *work, hipStream_t s, int64_t nc_first, bool gather_only = false);
+// kidmp_host.hip
+template <class T> int kid_host(kidmp_ctx *ctx, const KidCall<T> &host);
 }  // namespace kidmp

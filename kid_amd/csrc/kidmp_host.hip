@@ -240,7 +240,125 @@ int kidmp::host_pipeline(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, T 
 template int kidmp::host_pipeline<double>(kidmp_ctx *, int64_t, int32_t, double, double *const *, const double *const *, double *,
                                           double *, int32_t *, int32_t, const PipelineExtras<double> &);   // for kidmp_multi.hip
 
+
+// mphys_thompson09_interfacen (W:28-310) on host arrays, inside the same ring: per chunk the present members of state,
+// adv and div and exner go up (dz once, ahead of the first chunk), gather / step / outputs / back-out run on the compute
+// stream (kid_enqueue, the body of the device entry), and mphys, ppt and what else was asked for come down.  One
+// staging set: [rates] [workspace: 15 profiles] [state, adv, div: 9 each] [exner] [mphys: 9] [outputs] [ppt] [nstep].
+template <class T>
+int kidmp::kid_host(kidmp_ctx *ctx, const KidCall<T> &h)
+{
+    const int64_t ncol = h.ncol;
+    const int32_t nz = h.nz;
+    GUARD(ctx);
+    const int64_t CH = pick_host_chunk(ctx, ncol);
+    const int64_t nchunk = (ncol + CH - 1) / CH;
+    const int nbuf = nchunk < HOST_NBUF ? int(nchunk) : HOST_NBUF;
+    const size_t prof = size_t(CH) * size_t(nz);
+    auto up256 = [](size_t b) { return (b + 255) / 256 * 256; };
+    T *const hout[4] = {h.out.dbz, h.out.re_qc, h.out.re_qi, h.out.re_qs};
+    int n_in = 1, n_out = 0;                                     // exner
+    for (int m = 0; m < KID_NF; ++m) {
+        n_in += (h.state.f[m] != nullptr) + (h.adv.f[m] != nullptr) + (h.div.f[m] != nullptr);
+        n_out += h.mphys.f[m] != nullptr;
+    }
+    for (int v = 0; v < 4; ++v) n_out += hout[v] != nullptr;
+    const size_t b_rates = h.rates ? up256(size_t(KIDMP_NRATES) * prof * sizeof(double)) : 0;
+    const size_t b_prof = up256(prof * sizeof(T));
+    const size_t b_ppt = up256(4 * size_t(CH) * sizeof(T));
+    const size_t b_nstep = h.nstep ? up256(4 * size_t(CH) * sizeof(int32_t)) : 0;
+    const size_t b_set = b_rates + size_t(KID_NWORK + n_in + n_out) * b_prof + b_ppt + b_nstep;
+    const size_t b_dz = up256(size_t(nz) * sizeof(T));
+    if (int rc = ensure_stage(ctx, b_dz + b_set * size_t(nbuf))) return rc;
+    T *const ddz = reinterpret_cast<T *>(ctx->d_stage);
+    char *const base = reinterpret_cast<char *>(ctx->d_stage) + b_dz;
+    PipelineDrain drain{ctx};
+    HIPTRY(ctx, hipMemcpyAsync(ddz, h.dz, size_t(nz) * sizeof(T), hipMemcpyHostToDevice, ctx->s_h2d));
+    for (int64_t i = 0; i < nchunk; ++i) {
+        const int b = int(i % nbuf);
+        const int64_t c0 = i * CH, n = (c0 + CH <= ncol ? CH : ncol - c0);
+        const size_t off = size_t(c0) * size_t(nz), cnt = size_t(n) * size_t(nz);
+        char *q = base + size_t(b) * b_set;
+        double *drates = h.rates ? reinterpret_cast<double *>(q) : nullptr;
+        q += b_rates;
+        // the chunk's workspace: profile strides of the CHUNK's own column count, so that kid_enqueue finds them
+        char *const dwork = q;
+        q += size_t(KID_NWORK) * b_prof;
+        auto take = [&](const void *host) { T *d = nullptr; if (host) { d = reinterpret_cast<T *>(q); q += b_prof; } return d; };
+        KidCall<T> d = h;
+        d.ncol = n;
+        for (int m = 0; m < KID_NF; ++m) { d.state.f[m] = take(h.state.f[m]); d.adv.f[m] = take(h.adv.f[m]); d.div.f[m] = take(h.div.f[m]); }
+        T *const dex = take(h.exner);
+        for (int m = 0; m < KID_NF; ++m) d.mphys.f[m] = take(h.mphys.f[m]);
+        T *dout[4];
+        for (int v = 0; v < 4; ++v) dout[v] = take(hout[v]);
+        d.out = {dout[0], dout[1], dout[2], dout[3]};
+        T *const dppt = reinterpret_cast<T *>(q); q += b_ppt;
+        int32_t *const dnstep = h.nstep ? reinterpret_cast<int32_t *>(q) : nullptr;
+        d.exner = dex; d.dz = ddz; d.ppt = dppt; d.rates = drates; d.nstep = dnstep;
+        // upload (the set is free once the download of the chunk that used it last has finished)
+        if (i >= nbuf) HIPTRY(ctx, hipStreamWaitEvent(ctx->s_h2d, ctx->ev_down[b], 0));
+        for (int m = 0; m < KID_NF; ++m) {
+            const T *const src[3] = {h.state.f[m], h.adv.f[m], h.div.f[m]};
+            T *const dst[3] = {d.state.f[m], d.adv.f[m], d.div.f[m]};
+            for (int a = 0; a < 3; ++a)
+                if (src[a]) HIPTRY(ctx, hipMemcpyAsync(dst[a], src[a] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->s_h2d));
+        }
+        HIPTRY(ctx, hipMemcpyAsync(dex, h.exner + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->s_h2d));
+        HIPTRY(ctx, hipEventRecord(ctx->ev_up[b], ctx->s_h2d));
+        // gather, step, outputs, back-out
+        HIPTRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_up[b], 0));
+        if (int rc = kid_enqueue<T>(ctx, d, dwork, ctx->stream, c0)) return rc;
+        HIPTRY(ctx, hipEventRecord(ctx->ev_step[b], ctx->stream));
+        // download
+        HIPTRY(ctx, hipStreamWaitEvent(ctx->s_d2h, ctx->ev_step[b], 0));
+        for (int m = 0; m < KID_NF; ++m)
+            if (h.mphys.f[m]) HIPTRY(ctx, hipMemcpyAsync(h.mphys.f[m] + off, d.mphys.f[m], cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->s_d2h));
+        HIPTRY(ctx, hipMemcpyAsync(h.ppt + 4 * c0, dppt, 4 * size_t(n) * sizeof(T), hipMemcpyDeviceToHost, ctx->s_d2h));
+        if (h.rates) HIPTRY(ctx, hipMemcpyAsync(h.rates + size_t(KIDMP_NRATES) * off, drates, size_t(KIDMP_NRATES) * cnt * sizeof(double), hipMemcpyDeviceToHost, ctx->s_d2h));
+        if (h.nstep) HIPTRY(ctx, hipMemcpyAsync(h.nstep + 4 * c0, dnstep, 4 * size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->s_d2h));
+        for (int v = 0; v < 4; ++v)
+            if (hout[v]) HIPTRY(ctx, hipMemcpyAsync(hout[v] + off, dout[v], cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->s_d2h));
+        HIPTRY(ctx, hipEventRecord(ctx->ev_down[b], ctx->s_d2h));
+    }
+    HIPTRY(ctx, hipStreamSynchronize(ctx->s_d2h));           // everything else precedes it through the events
+    drain.armed = false;
+    return KIDMP_OK;
+}
+
+namespace {
+template <class T, class F, class O>
+int kid_host_entry(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, T dt, T p0, T r_on_cp, const F *state, const F *adv,
+                   const F *div, const T *exner, const T *dz, const F *mphys, T *ppt, double *rates, int32_t *nstep, const O *out,
+                   int32_t arith)
+{
+    KidCall<T> c{};
+    ColumnOutputs<T> o{};
+    if (out) o = {out->dbz, out->re_qc, out->re_qi, out->re_qs};
+    if (int rc = kid_check<T, F>(ctx, who, ncol, nz, double(dt), state, adv, div, exner, dz, mphys, ppt, o, arith, c)) return rc;
+    if (ncol == 0) return KIDMP_OK;
+    c.dt = dt; c.p0 = p0; c.r_on_cp = r_on_cp; c.rates = rates; c.nstep = nstep;
+    return kid_host<T>(ctx, c);
+}
+}  // namespace
+
 extern "C" {
+int kidmp_kid_interface_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, double p0, double r_on_cp,
+                             const kidmp_kid_fields *state, const kidmp_kid_fields *adv, const kidmp_kid_fields *div,
+                             const double *exner, const double *dz, const kidmp_kid_fields *mphys, double *ppt,
+                             double *rates, int32_t *nstep, const kidmp_outputs *out)
+{
+    return kid_host_entry<double>(ctx, "kidmp_kid_interface_host", ncol, nz, dt, p0, r_on_cp, state, adv, div, exner, dz, mphys, ppt,
+                                  rates, nstep, out, 0);
+}
+int kidmp32_kid_interface_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, float dt, float p0, float r_on_cp,
+                               const kidmp32_kid_fields *state, const kidmp32_kid_fields *adv, const kidmp32_kid_fields *div,
+                               const float *exner, const float *dz, const kidmp32_kid_fields *mphys, float *ppt,
+                               double *rates, int32_t *nstep, const kidmp32_outputs *out, int32_t arith)
+{
+    return kid_host_entry<float>(ctx, "kidmp32_kid_interface_host", ncol, nz, dt, p0, r_on_cp, state, adv, div, exner, dz, mphys, ppt,
+                                 rates, nstep, out, arith);
+}
 void *kidmp_host_alloc(size_t bytes)
 {
     void *p = nullptr;

@@ -59,6 +59,7 @@ module module_mp_thompson09n
   public :: calc_refl10cm, calc_refl10cm_batch
   public :: calc_effectRad, calc_effectRad_batch
   public :: mp_thompson_set_column_nc
+  public :: mp_thompson_kid_interface, mp_thompson_kid_staging
   logical, public :: is_aerosol_aware = .false.          ! M:28 (read at thompson_init)
   logical, public :: l_rate_diagnostics = .true.         ! replay the save_dg calls of M:2962-3124
   integer, public :: kidmp_device = 0                    ! HIP device ordinal of this process (one GPU)
@@ -90,13 +91,18 @@ module module_mp_thompson09n
      type(c_ptr) :: dbz, re_qc, re_qi, re_qs
   end type kidmp_outputs
 
+  type, bind(C) :: kidmp_kid_fields                      ! kidmp_kid_fields / kidmp32_kid_fields: KiD's fields, [ncol][nz] each
+     type(c_ptr) :: theta, qv, qc, qr, nr, qi, ni, qs, qg
+  end type kidmp_kid_fields
+
   type(c_ptr), save :: ctx = c_null_ptr                  ! the context (of the first device, when there are several)
   type(c_ptr), save :: mctx = c_null_ptr                 ! kidmp_multi handle, when kidmp_ndevices > 1
   ! Staging arrays of mp_thompson_batch: page-locked (kidmp_host_alloc) and kept between calls, so that the library's
   ! upload / step / download pipeline can move them by DMA.  1 = state (12 profiles), 2 = p, w, dz, 3 = ppt,
   ! 4 = the 36 rate profiles, 5 = the substep counts, 6 = the column outputs dbz, re_qc, re_qi, re_qs (only when asked for).
-  type(c_ptr), save :: hbuf(6) = c_null_ptr
-  integer(c_size_t), save :: hbytes(6) = 0_c_size_t
+  ! 7 = the hydrometeor moments of mp_thompson_kid_interface (mp_thompson_kid_staging).
+  type(c_ptr), save :: hbuf(7) = c_null_ptr
+  integer(c_size_t), save :: hbytes(7) = 0_c_size_t
 
   interface
      integer(c_int) function kidmp_init(cfg, ctx_out) bind(C, name='kidmp_init')
@@ -242,6 +248,29 @@ module module_mp_thompson09n
        type(c_ptr), value :: rates, nstep
        type(kidmp_outputs), intent(in) :: out
      end function kidmp32_batch_step_host_out
+     ! mphys_thompson09_interfacen (W:28-310) on host arrays: gather, step, outputs and back-out on the GPU
+     integer(c_int) function kidmp_kid_interface_host(ctx, ncol, nz, dt, p0, r_on_cp, state, adv, div, exner, dz, mphys, &
+          ppt, rates, nstep, out) bind(C, name='kidmp_kid_interface_host')
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr, kidmp_outputs, kidmp_kid_fields
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       real(c_double), value :: dt, p0, r_on_cp
+       type(kidmp_kid_fields), intent(in) :: state, adv, div, mphys
+       type(c_ptr), value :: exner, dz, ppt, rates, nstep
+       type(kidmp_outputs), intent(in) :: out
+     end function kidmp_kid_interface_host
+     integer(c_int) function kidmp32_kid_interface_host(ctx, ncol, nz, dt, p0, r_on_cp, state, adv, div, exner, dz, mphys, &
+          ppt, rates, nstep, out, arith) bind(C, name='kidmp32_kid_interface_host')
+       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr, kidmp_outputs, kidmp_kid_fields
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz, arith
+       real(c_float), value :: dt, p0, r_on_cp
+       type(kidmp_kid_fields), intent(in) :: state, adv, div, mphys
+       type(c_ptr), value :: exner, dz, ppt, rates, nstep
+       type(kidmp_outputs), intent(in) :: out
+     end function kidmp32_kid_interface_host
   end interface
 
 contains
@@ -371,7 +400,7 @@ contains
 
   subroutine thompson_finalize
     integer :: i
-    do i = 1, 6
+    do i = 1, size(hbuf)
        if (c_associated(hbuf(i))) call kidmp_host_free(hbuf(i))
        hbuf(i) = c_null_ptr;  hbytes(i) = 0_c_size_t
     end do
@@ -551,7 +580,7 @@ contains
     integer(c_int) :: rc
     integer(c_int32_t) :: arith
     logical :: have_frz, have_aer, inplace
-    integer :: i, k, r, r0
+    integer :: i
     if (.not. c_associated(ctx)) call thompson_init
     have_frz = present(qi);  have_aer = present(nc)
     if ((have_frz .neqv. present(qs)) .or. (have_frz .neqv. present(qg)) .or. (have_frz .neqv. present(ni)) .or. &
@@ -718,25 +747,119 @@ contains
     ppt = pp
     end if
     end if
-    ! ---- the KiD block of M:2962-3124: per column, per level, 30 mixed-phase rates (.not. iiwarm) then 6 warm
-    !      ones; save_dg(k, value, ...) when nx == 1, save_dg(k, ii, value, ...) otherwise; a column that left
-    !      through the no_micro return (M:1540: all four substep counts 0) never reached the block ----
-    if (l_rate_diagnostics) then
-       r0 = 1
-       if (iiwarm) r0 = NRATES_MIXED + 1
-       do i = 1, ncol
-          if (all(nstep(:,i) == 0)) cycle
-          do k = 1, nz
-             do r = r0, NRATES
-                if (nx == 1) then
-                   call save_dg(k, rates(k,r,i), rate_names(r), i_dgtime, units='/kg/s', dim='z')
-                else
-                   call save_dg(k, i, rates(k,r,i), rate_names(r), i_dgtime, units='/kg/s', dim='z')
-                end if
-             end do
+    if (l_rate_diagnostics) call replay_rate_diagnostics(ncol, nz, rates, nstep)
+  end subroutine mp_thompson_batch
+
+  ! The KiD block of M:2962-3124: per column, per level, 30 mixed-phase rates (.not. iiwarm) then 6 warm ones;
+  ! save_dg(k, value, ...) when nx == 1, save_dg(k, ii, value, ...) otherwise; a column that left through the no_micro
+  ! return (M:1540: all four substep counts 0) never reached the block.
+  subroutine replay_rate_diagnostics(ncol, nz, rates, nstep)
+    integer, intent(in) :: ncol, nz
+    real(c_double), intent(in) :: rates(nz, NRATES, ncol)
+    integer(c_int32_t), intent(in) :: nstep(4, ncol)
+    integer :: i, k, r, r0
+    r0 = 1
+    if (iiwarm) r0 = NRATES_MIXED + 1
+    do i = 1, ncol
+       if (all(nstep(:,i) == 0)) cycle
+       do k = 1, nz
+          do r = r0, NRATES
+             if (nx == 1) then
+                call save_dg(k, rates(k,r,i), rate_names(r), i_dgtime, units='/kg/s', dim='z')
+             else
+                call save_dg(k, i, rates(k,r,i), rate_names(r), i_dgtime, units='/kg/s', dim='z')
+             end if
           end do
        end do
+    end do
+  end subroutine replay_rate_diagnostics
+
+  ! Page-locked work arrays for a caller of mp_thompson_kid_interface whose hydrometeor moments are not plain arrays
+  ! (KiD keeps them in a derived type): hyd(nz,ncol,7,4) = the moments qc, qr, nr, qi, ni, qs, qg of the state, of the
+  ! advective and of the divergence tendencies (IN) and of the microphysics tendencies (OUT); pp(4,ncol).
+  subroutine mp_thompson_kid_staging(ncol, nz, hyd, pp)
+    integer, intent(in) :: ncol, nz
+    real, pointer, intent(out) :: hyd(:,:,:,:), pp(:,:)
+    integer(c_size_t) :: esize
+    esize = int(storage_size(1.0) / 8, c_size_t)
+    call staging(7, esize * 28 * int(nz, c_size_t) * int(ncol, c_size_t));  call staging(3, esize * 4 * ncol)
+    call c_f_pointer(hbuf(7), hyd, [nz, ncol, 7, 4]);  call c_f_pointer(hbuf(3), pp, [4, ncol])
+  end subroutine mp_thompson_kid_staging
+
+  ! mphys_thompson09_interfacen (W:28-310) in ONE library call: KiD's theta-form fields and their advective and divergence
+  ! tendencies in, the microphysics tendencies and the surface precipitation out; the gather (W:59-97) and the back-out
+  ! (W:198-245) run on the GPU beside the step (kidmp_kid_interface_host, kidmp32_* for 4-byte default REAL).  Arrays are
+  ! (nz, ncol); hyd* carry the moments qc, qr, nr, qi, ni, qs, qg (the last four are not looked at in an iiwarm run);
+  ! dz is KiD's one profile; ppt is (4, ncol) = rain, snow, graupel, ice, OUT.  dbz, re_*: as mp_thompson_batch.
+  ! The arrays go to the library as they are: no copy, no conversion -- so the build's REAL must be what kidmp_arith
+  ! stores (8-byte with 'p64', 4-byte with 'p32n' / 'f32').
+  subroutine mp_thompson_kid_interface(ncol, nz, dt, p0, r_on_cp, theta, qv, hyd, dtheta_adv, dqv_adv, hyd_adv, &
+       dtheta_div, dqv_div, hyd_div, exner, dz, dtheta_mphys, dqv_mphys, hyd_mphys, ppt, dbz, re_qc, re_qi, re_qs)
+    integer, intent(in) :: ncol, nz
+    real, intent(in) :: dt, p0, r_on_cp
+    real, dimension(nz,ncol), intent(in), target :: theta, qv, dtheta_adv, dqv_adv, dtheta_div, dqv_div, exner
+    real, dimension(nz,ncol,7), intent(in), target :: hyd, hyd_adv, hyd_div
+    real, dimension(nz), intent(in), target :: dz
+    real, dimension(nz,ncol), intent(out), target :: dtheta_mphys, dqv_mphys
+    real, dimension(nz,ncol,7), intent(inout), target :: hyd_mphys
+    real, dimension(4,ncol), intent(out), target :: ppt
+    real, dimension(nz,ncol), intent(out), optional, target :: dbz, re_qc, re_qi, re_qs
+    type(kidmp_kid_fields) :: state, adv, div, mphys
+    type(kidmp_outputs) :: out
+    real(c_double), pointer :: rates(:,:,:)
+    integer(c_int32_t), pointer :: nstep(:,:)
+    type(c_ptr) :: prates, pnstep
+    integer(c_size_t) :: nprof
+    integer(c_int) :: rc
+    integer(c_int32_t) :: arith
+    if (.not. c_associated(ctx)) call thompson_init
+    if (c_associated(mctx)) then
+       write(*,'(a)') ' module_mp_thompson09n: mp_thompson_kid_interface is not available with kidmp_ndevices > 1'
+       stop 1
     end if
-  end subroutine mp_thompson_batch
+    if ((kind(theta) == c_double) .neqv. (trim(kidmp_arith) == 'p64')) then
+       write(*,'(3a)') ' module_mp_thompson09n: mp_thompson_kid_interface with kidmp_arith=', trim(kidmp_arith), &
+            ' needs the matching default REAL (8-byte for p64, 4-byte for p32n / f32)'
+       stop 1
+    end if
+    if ((present(re_qc) .neqv. present(re_qi)) .or. (present(re_qc) .neqv. present(re_qs))) then
+       write(*,'(a)') ' module_mp_thompson09n: re_qc, re_qi, re_qs must be passed or left out together'
+       stop 1
+    end if
+    state = kidmp_kid_fields(c_loc(theta), c_loc(qv), c_loc(hyd(1,1,1)), c_loc(hyd(1,1,2)), c_loc(hyd(1,1,3)), &
+         c_loc(hyd(1,1,4)), c_loc(hyd(1,1,5)), c_loc(hyd(1,1,6)), c_loc(hyd(1,1,7)))
+    adv = kidmp_kid_fields(c_loc(dtheta_adv), c_loc(dqv_adv), c_loc(hyd_adv(1,1,1)), c_loc(hyd_adv(1,1,2)), &
+         c_loc(hyd_adv(1,1,3)), c_loc(hyd_adv(1,1,4)), c_loc(hyd_adv(1,1,5)), c_loc(hyd_adv(1,1,6)), c_loc(hyd_adv(1,1,7)))
+    div = kidmp_kid_fields(c_loc(dtheta_div), c_loc(dqv_div), c_loc(hyd_div(1,1,1)), c_loc(hyd_div(1,1,2)), &
+         c_loc(hyd_div(1,1,3)), c_loc(hyd_div(1,1,4)), c_loc(hyd_div(1,1,5)), c_loc(hyd_div(1,1,6)), c_loc(hyd_div(1,1,7)))
+    mphys = kidmp_kid_fields(c_loc(dtheta_mphys), c_loc(dqv_mphys), c_loc(hyd_mphys(1,1,1)), c_loc(hyd_mphys(1,1,2)), &
+         c_loc(hyd_mphys(1,1,3)), c_loc(hyd_mphys(1,1,4)), c_loc(hyd_mphys(1,1,5)), c_loc(hyd_mphys(1,1,6)), &
+         c_loc(hyd_mphys(1,1,7)))
+    out = kidmp_outputs(c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr)
+    if (present(dbz)) out%dbz = c_loc(dbz)
+    if (present(re_qc)) then
+       out%re_qc = c_loc(re_qc);  out%re_qi = c_loc(re_qi);  out%re_qs = c_loc(re_qs)
+    end if
+    prates = c_null_ptr;  pnstep = c_null_ptr
+    nprof = int(nz, c_size_t) * int(ncol, c_size_t)
+    if (l_rate_diagnostics) then
+       call staging(4, 8_c_size_t * NRATES * nprof)
+       call staging(5, 16_c_size_t * ncol)
+       call c_f_pointer(hbuf(4), rates, [nz, NRATES, ncol])
+       call c_f_pointer(hbuf(5), nstep, [4, ncol])
+       prates = hbuf(4);  pnstep = hbuf(5)
+    end if
+    if (kind(theta) == c_double) then
+       rc = kidmp_kid_interface_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_double), real(p0, c_double), &
+            real(r_on_cp, c_double), state, adv, div, c_loc(exner), c_loc(dz), mphys, c_loc(ppt), prates, pnstep, out)
+    else
+       arith = 0_c_int32_t
+       if (trim(kidmp_arith) == 'f32') arith = 1_c_int32_t
+       rc = kidmp32_kid_interface_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_float), real(p0, c_float), &
+            real(r_on_cp, c_float), state, adv, div, c_loc(exner), c_loc(dz), mphys, c_loc(ppt), prates, pnstep, out, arith)
+    end if
+    call stop_on_error(rc, 'mp_thompson_kid_interface')
+    if (l_rate_diagnostics) call replay_rate_diagnostics(ncol, nz, rates, nstep)
+  end subroutine mp_thompson_kid_interface
 
 end module module_mp_thompson09n

@@ -40,6 +40,12 @@ module mphys_thompson09n
   ! Nt_c = set_Nc_column(i)*1.e6 (M:381) -- a stock 2-D case then has x as the axis of an Nd ensemble, all members in
   ! one launch.  Unallocated: call sequence and results as without it.  Any other size stops the run.
   real, allocatable, public :: set_Nc_column(:)
+  ! .true.: the gather (W:59-97) and the back-out (W:198-245) run on the GPU inside the one library call
+  ! (mp_thompson_kid_interface): theta, exner, qv and their forcing arrays go to the library as they are, only the
+  ! derived-type hydrometeor moments are copied into work arrays and scattered back, and the two arithmetic loops below
+  ! are not run.  Needs one device, and a default REAL that is what kidmp_arith stores.  .false.: call sequence and
+  ! results as without it.
+  logical, public :: l_device_adapter = .false.
   real, allocatable, private, save :: nc_bound(:)          ! what is bound in the library (unallocated: nothing)
   integer:: ih, imom
   character(max_char_len) :: name, units
@@ -66,6 +72,7 @@ contains
     ! stores (mp_thompson_staging; no copy between here and PCIe), else heap arrays kept between calls (as automatic
     ! arrays they overflow the stack from nx ~ 500 on).  pres, wvel, dzc are fo(:,:,1:3).
     real, pointer :: st(:,:,:), fo(:,:,:), ppt(:,:)
+    real, pointer :: hy(:,:,:,:)                             ! l_device_adapter: (nz, nx, 7, 4) = state, adv, div, mphys
     real, allocatable, target, save :: st_own(:,:,:), fo_own(:,:,:), ppt_own(:,:)
     real, allocatable, save :: total(:)
     real, allocatable, save :: pptrain_2d_prof(:,:)          ! W:32; saved as 'total_ppt_level' for nx > 1 (W:304-307)
@@ -79,7 +86,16 @@ contains
        call thompson_init
        micro_unset = .False.
     end if
-    call mp_thompson_staging(nx, nz, st, fo, ppt, staged)
+    if (l_device_adapter) then
+       if (kidmp_ndevices > 1) then
+          write(*,'(a)') ' mphys_thompson09n: l_device_adapter is not available with kidmp_ndevices > 1'
+          stop 1
+       end if
+       call mp_thompson_kid_staging(nx, nz, hy, ppt)
+       staged = .true.
+    else
+       call mp_thompson_staging(nx, nz, st, fo, ppt, staged)
+    end if
     if (.not. staged) then
        if (allocated(st_own)) then
           if (size(st_own,1) /= nz .or. size(st_own,2) /= nx) deallocate(st_own, fo_own, ppt_own)
@@ -92,6 +108,7 @@ contains
     end if
     if (.not. allocated(total)) allocate(total(nx))
 
+    if (.not. l_device_adapter) then
     ! ---- gather: state + (advective + divergence forcing)*dt, W:59-97 ----
     ! Columns are independent: the loop over i is shared among OpenMP threads when the model is built with OpenMP
     ! (the directives are comments otherwise).  At nx = 10^4 this host-side packing, not the GPU, bounds a KiD step.
@@ -131,6 +148,7 @@ contains
           end do
        end do
     end if
+    end if
 
     ! ---- the droplet number per column: bound before the batched call, again only when its contents changed ----
     if (allocated(set_Nc_column)) then
@@ -155,7 +173,7 @@ contains
     end if
 
     ! ---- all nx columns in one call (replaces the loop around W:143-152) ----
-    ppt = 0.0
+    if (.not. l_device_adapter) ppt = 0.0
     if (allocated(dbz)) then
        if (size(dbz, 1) /= nz .or. size(dbz, 2) /= nx .or. .not. l_radar_reflectivity) deallocate(dbz)
     end if
@@ -165,6 +183,42 @@ contains
           if (size(re, 1) /= nz .or. size(re, 2) /= nx) deallocate(re)
        end if
        if (.not. allocated(re)) allocate(re(nz, nx, 3))
+    end if
+    if (l_device_adapter) then
+       ! ---- gather, step and back-out in one library call: only the derived-type moments are copied ----
+       !$omp parallel do default(shared) private(i, k, m) schedule(static) if(nx >= 256)
+       do i = 1, nx
+          do m = 1, NHYD
+             if (iiwarm .and. hyd_spec(m) > 2) cycle
+             do k = 1, nz
+                hy(k,i,m,1) = hydrometeors(k,i,hyd_spec(m))%moments(1,hyd_mom(m))
+                hy(k,i,m,2) = dhydrometeors_adv(k,i,hyd_spec(m))%moments(1,hyd_mom(m))
+                hy(k,i,m,3) = dhydrometeors_div(k,i,hyd_spec(m))%moments(1,hyd_mom(m))
+             end do
+          end do
+       end do
+       !$omp end parallel do
+       ! (dbz is allocated only with l_radar_reflectivity: an unallocated actual argument is an absent optional one)
+       if (l_effective_radii) then
+          call mp_thompson_kid_interface(nx, nz, dt, p0, r_on_cp, theta(:,1:nx), qv(:,1:nx), hy(:,:,:,1), &
+               dtheta_adv(:,1:nx), dqv_adv(:,1:nx), hy(:,:,:,2), dtheta_div(:,1:nx), dqv_div(:,1:nx), hy(:,:,:,3), &
+               exner(:,1:nx), dz, dtheta_mphys(:,1:nx), dqv_mphys(:,1:nx), hy(:,:,:,4), ppt, dbz, re(:,:,1), re(:,:,2), re(:,:,3))
+       else
+          call mp_thompson_kid_interface(nx, nz, dt, p0, r_on_cp, theta(:,1:nx), qv(:,1:nx), hy(:,:,:,1), &
+               dtheta_adv(:,1:nx), dqv_adv(:,1:nx), hy(:,:,:,2), dtheta_div(:,1:nx), dqv_div(:,1:nx), hy(:,:,:,3), &
+               exner(:,1:nx), dz, dtheta_mphys(:,1:nx), dqv_mphys(:,1:nx), hy(:,:,:,4), ppt, dbz)
+       end if
+       !$omp parallel do default(shared) private(i, k, m) schedule(static) if(nx >= 256)
+       do i = 1, nx
+          do m = 1, NHYD
+             if (iiwarm .and. hyd_spec(m) > 2) cycle
+             do k = 1, nz
+                dhydrometeors_mphys(k,i,hyd_spec(m))%moments(1,hyd_mom(m)) = hy(k,i,m,4)
+             end do
+          end do
+       end do
+       !$omp end parallel do
+    else if (l_effective_radii) then
        ! (dbz is allocated only with l_radar_reflectivity: an unallocated actual argument is an absent optional one)
        if (is_aerosol_aware) then
           call mp_thompson_batch(nx, nz, dt, st(:,:,S_QV), st(:,:,S_QC), st(:,:,S_QI), st(:,:,S_QR), st(:,:,S_QS), &
@@ -203,6 +257,7 @@ contains
             qs=st(:,:,S_QS), qg=st(:,:,S_QG), ni=st(:,:,S_NI), nr=st(:,:,S_NR), t=st(:,:,S_T), p=fo(:,:,1), dz=fo(:,:,3), ppt=ppt)
     end if
 
+    if (.not. l_device_adapter) then
     ! ---- back out the microphysics tendencies, W:198-245 ----
     !$omp parallel do default(shared) private(i, k, m, s) schedule(static) if(nx >= 256)
     do i = 1, nx
@@ -220,6 +275,7 @@ contains
        end do
     end do
     !$omp end parallel do
+    end if
 
     ! ---- surface precipitation diagnostics ----
     imom = 1

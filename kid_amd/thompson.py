@@ -46,6 +46,15 @@ class _Outputs(C.Structure):
     _fields_ = [("dbz", C.c_void_p), ("re_qc", C.c_void_p), ("re_qi", C.c_void_p), ("re_qs", C.c_void_p)]
 
 
+KID_FIELDS = ("theta", "qv", "qc", "qr", "nr", "qi", "ni", "qs", "qg")     # members of kidmp_kid_fields; the last four frozen
+KID_WORK_NAMES = STATE_NAMES + FORCING_NAMES                                  # the 15 profiles of the adapter's workspace
+
+
+class _KidFields(C.Structure):
+    """kidmp_kid_fields / kidmp32_kid_fields (include/kidmp.h): nine pointers, null = absent."""
+    _fields_ = [(k, C.c_void_p) for k in KID_FIELDS]
+
+
 def lib_path():
     """The in-tree build.  No environment override: a profiling or A/B build is selected explicitly with
     load_library(path) (bench.py --lib) before the first context is made."""
@@ -188,12 +197,31 @@ def load_library(path=None):
     L.kidmp_set_column_nc.argtypes = [_vp, C.c_int64, _vp]
     L.kidmp_column_nc_count.restype = C.c_int64
     L.kidmp_column_nc_count.argtypes = [_vp]
+    for pre, real in (("kidmp", C.c_double), ("kidmp32", C.c_float)):
+        getattr(L, pre + "_kid_workspace_bytes").restype = C.c_size_t
+        getattr(L, pre + "_kid_workspace_bytes").argtypes = [C.c_int64, C.c_int32]
+        getattr(L, pre + "_kid_workspace_offset").restype = C.c_size_t
+        getattr(L, pre + "_kid_workspace_offset").argtypes = [C.c_int64, C.c_int32, C.c_int32]
+        head = [_vp, C.c_int64, C.c_int32, real, real, real] + [C.POINTER(_KidFields)] * 3 + [_vp, _vp, C.POINTER(_KidFields), _vp,
+                                                                                              _vp, _vp, C.POINTER(_Outputs)]
+        arith = [C.c_int32] if pre == "kidmp32" else []
+        getattr(L, pre + "_kid_interface_device").restype = C.c_int
+        getattr(L, pre + "_kid_interface_device").argtypes = head + arith + [_vp, C.c_size_t, _vp]
+        getattr(L, pre + "_kid_gather_device").restype = C.c_int
+        getattr(L, pre + "_kid_gather_device").argtypes = head[:11] + [_vp, _vp, C.c_size_t, _vp]
+        getattr(L, pre + "_kid_interface_host").restype = C.c_int
+        getattr(L, pre + "_kid_interface_host").argtypes = head + arith
     L.kidmp_init_seconds.restype = C.c_double
     L.kidmp_init_seconds.argtypes = [_vp]
     L.kidmp_kernel_name.restype = C.c_char_p
     L.kidmp_kernel_name.argtypes = []
     _lib = L
     return L
+
+
+def _np_dtype(dtype):
+    """numpy's name for a numpy or torch floating dtype."""
+    return str(dtype).replace("torch.", "") if type(dtype).__module__.split(".")[0] == "torch" else dtype
 
 
 def _np_ptr(a):
@@ -639,6 +667,201 @@ class ThompsonMP:
         fn = load_library().kidmp_reflectivity_host if q.dtype == np.float64 else load_library().kidmp32_reflectivity_host
         self._check(fn(self._h, ncol, nz, *ptrs, out.ctypes.data_as(pt)))
         return out
+
+    # ---- mphys_thompson09_interfacen (W:28-310): KiD's theta-form fields in, tendencies out ----
+    @staticmethod
+    def kid_workspace_bytes(ncol, nz, dtype):
+        """kidmp[32]_kid_workspace_bytes: 15 profiles of ncol*nz values, each stride rounded up to 256 bytes."""
+        L = load_library()
+        fn = L.kidmp_kid_workspace_bytes if np.dtype(_np_dtype(dtype)) == np.float64 else L.kidmp32_kid_workspace_bytes
+        return int(fn(int(ncol), int(nz)))
+
+    def kid_workspace(self, ncol, nz, dtype):
+        """The workspace of kid_interface for [ncol, nz] fields of `dtype` (torch or numpy float64 / float32): a uint8
+        tensor on this context's GPU.  After a call it holds the post-step state: see kid_workspace_views."""
+        import torch
+        n = self.kid_workspace_bytes(ncol, nz, dtype)
+        if n == 0 and ncol > 0:
+            raise KidmpError("kid_workspace: bad ncol / nz (%d, %d)" % (ncol, nz))
+        return torch.empty(max(n, 1), dtype=torch.uint8, device="cuda:%d" % self.device)
+
+    @staticmethod
+    def kid_workspace_views(work, ncol, nz, dtype):
+        """dict name -> [ncol, nz] view of the workspace, names KID_WORK_NAMES (the state in the order of mp_thompson's
+        dummies, then p, w, dz), placed by kidmp[32]_kid_workspace_offset."""
+        import torch
+        L = load_library()
+        is64 = np.dtype(_np_dtype(dtype)) == np.float64
+        off = L.kidmp_kid_workspace_offset if is64 else L.kidmp32_kid_workspace_offset
+        tdt, size = (torch.float64, 8) if is64 else (torch.float32, 4)
+        return {k: work[off(ncol, nz, v): off(ncol, nz, v) + ncol * nz * size].view(tdt).view(ncol, nz)
+                for v, k in enumerate(KID_WORK_NAMES)}
+
+    def _kid_members(self, who, d, name, required, check):
+        """The members of one kidmp_kid_fields argument: `d` is a dict (or None = all absent) with keys KID_FIELDS.
+        In an iiwarm context the frozen members are not looked at.  Returns the list of present (key, array)."""
+        if d is None:
+            if required:
+                raise KidmpError("%s: %s is required" % (who, name))
+            return []
+        if not isinstance(d, dict):
+            raise KidmpError("%s: %s must be a dict with keys from %s" % (who, name, ", ".join(KID_FIELDS)))
+        bad = [k for k in d if k not in KID_FIELDS]
+        if bad:
+            raise KidmpError("%s: %s has unknown members %s" % (who, name, bad))
+        keys = KID_FIELDS[:5] if self.iiwarm else KID_FIELDS
+        got = []
+        for k in keys:
+            a = d.get(k)
+            if a is None:
+                if required:
+                    raise KidmpError("%s: %s[%r] is required%s" % (who, name, k, "" if k in KID_FIELDS[:5] else " in a mixed-phase context"))
+                continue
+            check(a, "%s: %s[%r]" % (who, name, k))
+            got.append((k, a))
+        return got
+
+    def kid_interface(self, state, dt, p0, r_on_cp, exner, dz, adv=None, div=None, work=None, rates=None, nstep=None,
+                      dbz=False, radii=False, arith=None, stream=None, out=None, gather_only=False):
+        """The KiD adapter on the device (kidmp[32]_kid_interface_device).  state / adv / div: dicts of float64 or float32
+        CUDA tensors [ncol, nz] with keys from KID_FIELDS (adv, div and any of their members may be missing: zero;
+        the frozen members only matter in a mixed-phase context); exner [ncol, nz]; dz [nz].  Returns a dict: the
+        tendencies under the keys of KID_FIELDS, "ppt" [ncol, 4] (rain, snow, graupel, ice), with dbz / radii also "dbz" /
+        "radii" of the post-step state, and "work", the workspace (kid_workspace_views).  `out`: a dict returned by
+        an earlier call, whose tensors are then written again (nothing is allocated: what a captured graph needs).
+        float32 fields step in `arith` "p32n" (default) or "f32"; `rates` stays float64.  Asynchronous on `stream`.
+        gather_only (kidmp[32]_kid_gather_device): only the workspace is filled with the step's inputs and ppt zeroed;
+        returns {"ppt", "work"}."""
+        import torch
+        who = "kid_interface"
+        q = state.get("theta") if isinstance(state, dict) else None
+        if q is None or not hasattr(q, "is_cuda") or q.dtype not in (torch.float64, torch.float32) or q.dim() != 2:
+            raise KidmpError("kid_interface: state['theta'] must be a float64 or float32 CUDA tensor [ncol, nz]")
+        ncol, nz = q.shape
+        is64 = q.dtype == torch.float64
+        if is64 and arith is not None:
+            raise KidmpError("kid_interface: arith applies to float32 fields only")
+        if not is64 and (arith or "p32n") not in self.ARITH:
+            raise KidmpError("kid_interface: arith must be 'p32n' or 'f32'")
+
+        def check(a, what):
+            if not hasattr(a, "is_cuda"):
+                raise KidmpError("%s must be a torch tensor" % what)
+            self._want(a, q.dtype, (ncol, nz), what)
+        f_state = self._kid_members(who, state, "state", True, check)
+        f_adv = self._kid_members(who, adv, "adv", False, check)
+        f_div = self._kid_members(who, div, "div", False, check)
+        check(exner, "kid_interface: exner")
+        if not hasattr(dz, "is_cuda"):
+            raise KidmpError("kid_interface: dz must be a torch tensor")
+        self._want(dz, q.dtype, (nz,), "kid_interface: dz")
+        if rates is not None:
+            self._want(rates, torch.float64, (ncol, NRATES, nz), "kid_interface: rates")
+        if nstep is not None:
+            self._want(nstep, torch.int32, (ncol, 4), "kid_interface: nstep")
+        need = 15 * ((ncol * nz * q.element_size() + 255) // 256 * 256)
+        if work is not None:
+            if not (hasattr(work, "is_cuda") and work.is_cuda and work.dtype == torch.uint8 and work.dim() == 1 and work.is_contiguous()
+                    and work.device.index == self.device and work.numel() >= need and work.data_ptr() % 16 == 0):
+                raise KidmpError("kid_interface: work must be a contiguous uint8 CUDA tensor of at least %d bytes on cuda:%d "
+                                 "(kid_workspace)" % (need, self.device))
+        keys = [k for k, _ in f_state]
+        if out is not None:
+            if not isinstance(out, dict) or out.get("ppt") is None or (dbz and out.get("dbz") is None) or (radii and out.get("radii") is None):
+                raise KidmpError("kid_interface: out must be a dict holding ppt (and dbz / radii when they are wanted)")
+            self._kid_members(who, {k: out.get(k) for k in KID_FIELDS}, "out", True, check)
+            self._want(out["ppt"], q.dtype, (ncol, 4), "kid_interface: out['ppt']")
+            res = out
+        else:
+            res = {k: torch.empty_like(q) for k in ([] if gather_only else keys)}
+            res["ppt"] = torch.empty((ncol, 4), dtype=q.dtype, device=q.device)
+            if dbz:
+                res["dbz"] = torch.empty_like(q)
+            if radii:
+                res["radii"] = tuple(torch.empty_like(q) for _ in range(3))
+        if dbz:
+            check(res["dbz"], "kid_interface: out['dbz']")
+        if radii:
+            for a in res["radii"]:
+                check(a, "kid_interface: out['radii']")
+        if work is None:
+            work = self.kid_workspace(ncol, nz, q.dtype)
+        res["work"] = work
+
+        def fields(members):
+            d = dict(members)
+            return _KidFields(*[d[k].data_ptr() if k in d else None for k in KID_FIELDS])
+        c_state, c_adv, c_div = fields(f_state), fields(f_adv), fields(f_div)
+        c_out = fields([(k, res[k]) for k in keys if k in res])
+        o = _Outputs(res["dbz"].data_ptr() if dbz else None, *([a.data_ptr() for a in res["radii"]] if radii else [None] * 3))
+        s = stream if stream is not None else torch.cuda.current_stream(q.device).cuda_stream
+        L = load_library()
+        args = [self._h, ncol, nz, float(dt), float(p0), float(r_on_cp), C.byref(c_state), C.byref(c_adv) if adv is not None else None,
+                C.byref(c_div) if div is not None else None, exner.data_ptr(), dz.data_ptr(), C.byref(c_out), res["ppt"].data_ptr(),
+                rates.data_ptr() if rates is not None else None, nstep.data_ptr() if nstep is not None else None,
+                C.byref(o) if (dbz or radii) else None]
+        if gather_only:
+            fn = L.kidmp_kid_gather_device if is64 else L.kidmp32_kid_gather_device
+            self._check(fn(*args[:11], res["ppt"].data_ptr(), work.data_ptr(), work.numel(), s))
+            return {"ppt": res["ppt"], "work": work}
+        if is64:
+            self._check(L.kidmp_kid_interface_device(*args, work.data_ptr(), work.numel(), s))
+        else:
+            self._check(L.kidmp32_kid_interface_device(*args, self.ARITH[arith or "p32n"], work.data_ptr(), work.numel(), s))
+        return res
+
+    def kid_interface_host(self, state, dt, p0, r_on_cp, exner, dz, adv=None, div=None, want_rates=False, want_nstep=False,
+                           dbz=False, radii=False, arith=None):
+        """The KiD adapter on numpy arrays (kidmp[32]_kid_interface_host): arguments as kid_interface, float64 or float32
+        arrays [ncol, nz] (page-locked ones, host_empty, move by DMA).  Returns the dict of tendencies and "ppt", with
+        "rates" / "nstep" / "dbz" / "radii" when asked for.  Bit for bit the device entry, for any chunking."""
+        who = "kid_interface_host"
+        q = state.get("theta") if isinstance(state, dict) else None
+        if not isinstance(q, np.ndarray) or q.dtype not in (np.float64, np.float32) or q.ndim != 2:
+            raise KidmpError("kid_interface_host: state['theta'] must be a float64 or float32 numpy array [ncol, nz]")
+        ncol, nz = q.shape
+        is64 = q.dtype == np.float64
+        if is64 and arith is not None:
+            raise KidmpError("kid_interface_host: arith applies to float32 fields only")
+        if not is64 and (arith or "p32n") not in self.ARITH:
+            raise KidmpError("kid_interface_host: arith must be 'p32n' or 'f32'")
+
+        def check(a, what, shape=(ncol, nz)):
+            if not (isinstance(a, np.ndarray) and a.dtype == q.dtype and a.flags.c_contiguous and a.shape == shape):
+                raise KidmpError("%s must be a contiguous %s numpy array %s" % (what, q.dtype, list(shape)))
+        f_state = self._kid_members(who, state, "state", True, check)
+        f_adv = self._kid_members(who, adv, "adv", False, check)
+        f_div = self._kid_members(who, div, "div", False, check)
+        check(exner, "kid_interface_host: exner")
+        check(dz, "kid_interface_host: dz", (nz,))
+        keys = [k for k, _ in f_state]
+        res = {k: np.empty_like(q) for k in keys}
+        res["ppt"] = np.empty((ncol, 4), dtype=q.dtype)
+        if want_rates:
+            res["rates"] = np.zeros((ncol, NRATES, nz))
+        if want_nstep:
+            res["nstep"] = np.zeros((ncol, 4), dtype=np.int32)
+        if dbz:
+            res["dbz"] = np.empty_like(q)
+        if radii:
+            res["radii"] = tuple(np.empty_like(q) for _ in range(3))
+
+        def fields(members):
+            d = dict(members)
+            return _KidFields(*[d[k].ctypes.data if k in d else None for k in KID_FIELDS])
+        c_state, c_adv, c_div = fields(f_state), fields(f_adv), fields(f_div)
+        c_out = fields([(k, res[k]) for k in keys])
+        o = _Outputs(res["dbz"].ctypes.data if dbz else None, *([a.ctypes.data for a in res["radii"]] if radii else [None] * 3))
+        L = load_library()
+        args = [self._h, ncol, nz, float(dt), float(p0), float(r_on_cp), C.byref(c_state), C.byref(c_adv) if adv is not None else None,
+                C.byref(c_div) if div is not None else None, exner.ctypes.data, dz.ctypes.data, C.byref(c_out), res["ppt"].ctypes.data,
+                res["rates"].ctypes.data if want_rates else None, res["nstep"].ctypes.data if want_nstep else None,
+                C.byref(o) if (dbz or radii) else None]
+        if is64:
+            self._check(L.kidmp_kid_interface_host(*args))
+        else:
+            self._check(L.kidmp32_kid_interface_host(*args, self.ARITH[arith or "p32n"]))
+        return res
 
     def kernel_fingerprint(self, arith="p64"):
         """'src:<hash>;vgpr:<n>;lds:<bytes>;scratch:<bytes>' of this context's nz <= 120 column-step kernel, in the
