@@ -119,17 +119,6 @@ module module_mp_thompson09n
        type(c_ptr), value :: ctx
        type(c_ptr) :: msg
      end function kidmp_last_error
-     ! arrays by address: the ones KiD never fills (nc, nwfa, nifa, w; the frozen species of a warm run) may be NULL
-     integer(c_int) function kidmp_batch_step_host_diag(ctx, ncol, nz, dt, qv, qc, qi, qr, qs, qg, ni, nr, &
-          nc, nwfa, nifa, t, p, w, dz, ppt, rates, nstep) bind(C, name='kidmp_batch_step_host_diag')
-       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
-       type(c_ptr), value :: ctx
-       integer(c_int64_t), value :: ncol
-       integer(c_int32_t), value :: nz
-       real(c_double), value :: dt
-       type(c_ptr), value :: qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t, p, w, dz, ppt   ! real(c_double) [ncol][nz]; ppt [ncol][4]
-       type(c_ptr), value :: rates, nstep            ! NULL, or [ncol][36][nz] doubles / [ncol][4] int32
-     end function kidmp_batch_step_host_diag
      integer(c_int) function kidmp_init_multi(cfg, ndev, devices, m_out) bind(C, name='kidmp_init_multi')
        import :: c_int, c_int32_t, c_ptr, kidmp_cfg
        type(kidmp_cfg), intent(in) :: cfg
@@ -183,16 +172,6 @@ module module_mp_thompson09n
        import :: c_ptr
        type(c_ptr), value :: p
      end subroutine kidmp_host_free
-     integer(c_int) function kidmp32_batch_step_host(ctx, ncol, nz, dt, qv, qc, qi, qr, qs, qg, ni, nr, &
-          nc, nwfa, nifa, t, p, w, dz, ppt, rates, nstep, arith) bind(C, name='kidmp32_batch_step_host')
-       import :: c_int, c_int32_t, c_int64_t, c_float, c_ptr
-       type(c_ptr), value :: ctx
-       integer(c_int64_t), value :: ncol
-       integer(c_int32_t), value :: nz, arith
-       real(c_float), value :: dt
-       type(c_ptr), value :: qv, qc, qi, qr, qs, qg, ni, nr, nc, nwfa, nifa, t, p, w, dz, ppt   ! real(c_float)
-       type(c_ptr), value :: rates, nstep            ! NULL, or [ncol][36][nz] doubles / [ncol][4] int32
-     end function kidmp32_batch_step_host
      ! calc_refl10cm, M:4946-5244 (include/kidmp.h): t, p, qv, qr, nr, qs, qg in, dbz out; qs/qg NULL in a warm run
      integer(c_int) function kidmp_reflectivity_host(ctx, ncol, nz, t, p, qv, qr, nr, qs, qg, dbz) &
           bind(C, name='kidmp_reflectivity_host')
@@ -225,7 +204,8 @@ module module_mp_thompson09n
        integer(c_int64_t), value :: n
        type(c_ptr), value :: t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs   ! real(c_float) [n]
      end function kidmp32_effective_radii_host
-     ! the step followed by the outputs of the post-step state; nothing requested in `out` = kidmp_batch_step_host_diag
+     ! the step followed by the outputs of the post-step state (nothing requested in `out`: the plain step).  Arrays by
+     ! address: the ones KiD never fills (nc, nwfa, nifa, w; the frozen species of a warm run) may be NULL
      integer(c_int) function kidmp_batch_step_host_out(ctx, ncol, nz, dt, qv, qc, qi, qr, qs, qg, ni, nr, &
           nc, nwfa, nifa, t, p, w, dz, ppt, rates, nstep, out) bind(C, name='kidmp_batch_step_host_out')
        import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr, kidmp_outputs
@@ -317,6 +297,54 @@ contains
        stop 1
     end if
   end subroutine staging
+
+  ! the address `off` bytes into the block at p
+  type(c_ptr) function byte_offset(p, off)
+    type(c_ptr), intent(in) :: p
+    integer(c_size_t), intent(in) :: off
+    integer(c_int8_t), pointer :: b(:)
+    call c_f_pointer(p, b, [off + 1])
+    byte_offset = c_loc(b(off + 1))
+  end function byte_offset
+
+  ! the `arith` argument of the kidmp32_* entries (KIDMP_ARITH_P32N, KIDMP_ARITH_F32)
+  integer(c_int32_t) function arith_code()
+    arith_code = merge(1_c_int32_t, 0_c_int32_t, trim(kidmp_arith) == 'f32')
+  end function arith_code
+
+  subroutine radii_together(have_qc, have_qi, have_qs)
+    logical, intent(in) :: have_qc, have_qi, have_qs
+    if ((have_qc .neqv. have_qi) .or. (have_qc .neqv. have_qs)) then
+       write(*,'(a)') ' module_mp_thompson09n: re_qc, re_qi, re_qs must be passed or left out together'
+       stop 1
+    end if
+  end subroutine radii_together
+
+  ! With l_rate_diagnostics the page-locked arrays the step writes its rates and substep counts to, in the C ABI's layout
+  ! [ncol][36][nz] / [ncol][4], and their addresses; else NULL: nothing is diagnosed.
+  subroutine rate_staging(ncol, nz, rates, nstep, prates, pnstep)
+    integer, intent(in) :: ncol, nz
+    real(c_double), pointer, intent(out) :: rates(:,:,:)
+    integer(c_int32_t), pointer, intent(out) :: nstep(:,:)
+    type(c_ptr), intent(out) :: prates, pnstep
+    nullify(rates, nstep)
+    prates = c_null_ptr;  pnstep = c_null_ptr
+    if (.not. l_rate_diagnostics) return
+    call staging(4, 8_c_size_t * NRATES * int(nz, c_size_t) * int(ncol, c_size_t))
+    call staging(5, 16_c_size_t * ncol)
+    call c_f_pointer(hbuf(4), rates, [nz, NRATES, ncol])
+    call c_f_pointer(hbuf(5), nstep, [4, ncol])
+    prates = hbuf(4);  pnstep = hbuf(5)
+  end subroutine rate_staging
+
+  ! one kidmp_kid_fields: theta-like, qv-like and the seven moments of hyd(nz*ncol, 7)
+  function kid_fields(n, th, qv, hyd) result(f)
+    integer, intent(in) :: n
+    real, intent(in), target :: th(n), qv(n), hyd(n, 7)
+    type(kidmp_kid_fields) :: f
+    f = kidmp_kid_fields(c_loc(th), c_loc(qv), c_loc(hyd(1,1)), c_loc(hyd(1,2)), c_loc(hyd(1,3)), c_loc(hyd(1,4)), &
+         c_loc(hyd(1,5)), c_loc(hyd(1,6)), c_loc(hyd(1,7)))
+  end function kid_fields
 
   ! thompson_init, M:374-797: constants on the host, lookup tables built on the GPU (on every GPU of the device list).
   subroutine thompson_init
@@ -569,18 +597,14 @@ contains
     ! re_qc, re_qi, re_qs (optional, all three): calc_effectRad (M:4834-4935) of the post-step state in the form of the
     ! scheme's driver -- presets first, M:1111-1116 --, formed by the same launch as dbz (kidmp_batch_step_host_out)
     real, dimension(nz,ncol), intent(out), optional, target :: re_qc, re_qi, re_qs
-    real(c_double), pointer :: s(:,:,:), f(:,:,:), pp(:,:), rates(:,:,:), zd(:,:,:)
-    real(c_float), pointer :: z4(:,:,:)
-    type(kidmp_outputs) :: out
-    logical :: want_radii
-    real(c_float), pointer :: s4(:,:,:), f4(:,:,:), pp4(:,:)
+    real(c_double), pointer :: rates(:,:,:)
     integer(c_int32_t), pointer :: nstep(:,:)
-    type(c_ptr) :: prates, pnstep, ps(12), pf(3)
-    integer(c_size_t) :: nprof
+    type(kidmp_outputs) :: out
+    type(c_ptr) :: prates, pnstep, ps(15)
+    integer(c_size_t) :: nprof, esize
     integer(c_int) :: rc
-    integer(c_int32_t) :: arith
-    logical :: have_frz, have_aer, inplace
-    integer :: i
+    logical :: have_frz, have_aer, want_radii, is64, inplace
+    integer :: i, n
     if (.not. c_associated(ctx)) call thompson_init
     have_frz = present(qi);  have_aer = present(nc)
     if ((have_frz .neqv. present(qs)) .or. (have_frz .neqv. present(qg)) .or. (have_frz .neqv. present(ni)) .or. &
@@ -589,165 +613,123 @@ contains
        stop 1
     end if
     want_radii = present(re_qc)
-    if ((want_radii .neqv. present(re_qi)) .or. (want_radii .neqv. present(re_qs))) then
-       write(*,'(a)') ' module_mp_thompson09n: re_qc, re_qi, re_qs must be passed or left out together'
-       stop 1
-    end if
+    call radii_together(want_radii, present(re_qi), present(re_qs))
     if ((present(dbz) .or. want_radii) .and. c_associated(mctx)) then
        write(*,'(a)') ' module_mp_thompson09n: radar reflectivity is not available with kidmp_ndevices > 1'
        stop 1
     end if
-    out = kidmp_outputs(c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr)
-    prates = c_null_ptr;  pnstep = c_null_ptr
+    ! ---- the storage kind of the staging arrays: binary64 for 'p64' (a 4-byte REAL is converted on the way), else
+    !      binary32 state straight to the GPU: the reference's own REAL / DOUBLE PRECISION split, or all binary32 ----
+    is64 = trim(kidmp_arith) == 'p64'
+    if (.not. is64 .and. kind(qv) /= c_float) then
+       write(*,'(3a)') ' module_mp_thompson09n: kidmp_arith=', trim(kidmp_arith), ' needs KiD built with 4-byte default REAL'
+       stop 1
+    end if
+    esize = merge(8_c_size_t, 4_c_size_t, is64)
+    n = nz * ncol
     nprof = int(nz, c_size_t) * int(ncol, c_size_t)
-    if (l_rate_diagnostics) then
-       call staging(4, 8_c_size_t * NRATES * nprof)
-       call staging(5, 16_c_size_t * ncol)
-       call c_f_pointer(hbuf(4), rates, [nz, NRATES, ncol])  ! the C ABI's [ncol][36][nz] / [ncol][4]
-       call c_f_pointer(hbuf(5), nstep, [4, ncol])
-       prates = hbuf(4);  pnstep = hbuf(5)
-    end if
-    ps = c_null_ptr;  pf = c_null_ptr
-    if (trim(kidmp_arith) /= 'p64') then
-       ! ---- binary32 state straight to the GPU: the reference's own REAL / DOUBLE PRECISION split, or all binary32 ----
-       if (kind(qv) /= c_float) then
-          write(*,'(3a)') ' module_mp_thompson09n: kidmp_arith=', trim(kidmp_arith), ' needs KiD built with 4-byte default REAL'
-          stop 1
-       end if
-       arith = 0_c_int32_t
-       if (trim(kidmp_arith) == 'f32') arith = 1_c_int32_t
-       call staging(1, 4_c_size_t * 12 * nprof);  call staging(2, 4_c_size_t * 3 * nprof);  call staging(3, 16_c_size_t * ncol)
-       call c_f_pointer(hbuf(1), s4, [nz, ncol, 12]);  call c_f_pointer(hbuf(2), f4, [nz, ncol, 3]);  call c_f_pointer(hbuf(3), pp4, [4, ncol])
-       ! (an argument that IS its staging slot -- mp_thompson_staging -- needs no copy, in or out)
-       inplace = c_associated(c_loc(qv), c_loc(s4(1,1,1))) .and. c_associated(c_loc(qc), c_loc(s4(1,1,2))) .and. &
-            c_associated(c_loc(qr), c_loc(s4(1,1,4))) .and. c_associated(c_loc(nr), c_loc(s4(1,1,8))) .and. &
-            c_associated(c_loc(t), c_loc(s4(1,1,12))) .and. c_associated(c_loc(p), c_loc(f4(1,1,1))) .and. &
-            c_associated(c_loc(dz), c_loc(f4(1,1,3))) .and. c_associated(c_loc(ppt), c_loc(pp4(1,1)))
-       if (inplace .and. have_frz) inplace = c_associated(c_loc(qi), c_loc(s4(1,1,3))) .and. c_associated(c_loc(qs), c_loc(s4(1,1,5))) &
-            .and. c_associated(c_loc(qg), c_loc(s4(1,1,6))) .and. c_associated(c_loc(ni), c_loc(s4(1,1,7)))
-       if (inplace .and. have_aer) inplace = c_associated(c_loc(nc), c_loc(s4(1,1,9))) .and. c_associated(c_loc(nwfa), c_loc(s4(1,1,10))) &
-            .and. c_associated(c_loc(nifa), c_loc(s4(1,1,11)))
-       if (inplace .and. present(w)) inplace = c_associated(c_loc(w), c_loc(f4(1,1,2)))
-       if (.not. inplace) then
-       s4(:,:,1) = qv;  s4(:,:,2) = qc;  s4(:,:,4) = qr;  s4(:,:,8) = nr;  s4(:,:,12) = t
-       if (have_frz) then
-          s4(:,:,3) = qi;  s4(:,:,5) = qs;  s4(:,:,6) = qg;  s4(:,:,7) = ni
-       end if
-       if (have_aer) then
-          s4(:,:,9) = nc;  s4(:,:,10) = nwfa;  s4(:,:,11) = nifa
-       end if
-       f4(:,:,1) = p;  f4(:,:,3) = dz
-       if (present(w)) f4(:,:,2) = w
-       pp4 = ppt
-       end if
-       do i = 1, 12
-          ps(i) = c_loc(s4(1,1,i))
-       end do
-       pf(1) = c_loc(f4(1,1,1));  pf(3) = c_loc(f4(1,1,3))
-       if (present(w)) pf(2) = c_loc(f4(1,1,2))
-       if (.not. have_frz) then
-          ps(3) = c_null_ptr;  ps(5) = c_null_ptr;  ps(6) = c_null_ptr;  ps(7) = c_null_ptr
-       end if
-       if (.not. have_aer) ps(9:11) = c_null_ptr
-       if (present(dbz) .or. want_radii) then
-          call staging(6, 4_c_size_t * 4 * nprof)
-          call c_f_pointer(hbuf(6), z4, [nz, ncol, 4])
-          if (present(dbz)) out%dbz = c_loc(z4(1,1,1))
-          if (want_radii) then
-             out%re_qc = c_loc(z4(1,1,2));  out%re_qi = c_loc(z4(1,1,3));  out%re_qs = c_loc(z4(1,1,4))
-          end if
-          rc = kidmp32_batch_step_host_out(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_float), &
-               ps(1), ps(2), ps(3), ps(4), ps(5), ps(6), ps(7), ps(8), ps(9), ps(10), ps(11), ps(12), &
-               pf(1), pf(2), pf(3), c_loc(pp4), prates, pnstep, arith, out)
-          if (rc == 0 .and. present(dbz)) dbz = z4(:,:,1)
-          if (rc == 0 .and. want_radii) then
-             re_qc = z4(:,:,2);  re_qi = z4(:,:,3);  re_qs = z4(:,:,4)
-          end if
-       else
-       rc = kidmp32_batch_step_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_float), &
-            ps(1), ps(2), ps(3), ps(4), ps(5), ps(6), ps(7), ps(8), ps(9), ps(10), ps(11), ps(12), &
-            pf(1), pf(2), pf(3), c_loc(pp4), prates, pnstep, arith)
-       end if
-       call stop_on_error(rc, 'mp_thompson')
-       if (.not. inplace) then
-       qv = s4(:,:,1);  qc = s4(:,:,2);  qr = s4(:,:,4);  nr = s4(:,:,8);  t = s4(:,:,12)
-       if (have_frz) then
-          qi = s4(:,:,3);  qs = s4(:,:,5);  qg = s4(:,:,6);  ni = s4(:,:,7)
-       end if
-       if (have_aer) then
-          nc = s4(:,:,9);  nwfa = s4(:,:,10);  nifa = s4(:,:,11)
-       end if
-       ppt = pp4
-       end if
-    else
-    call staging(1, 8_c_size_t * 12 * nprof);  call staging(2, 8_c_size_t * 3 * nprof);  call staging(3, 32_c_size_t * ncol)
-    call c_f_pointer(hbuf(1), s, [nz, ncol, 12]);  call c_f_pointer(hbuf(2), f, [nz, ncol, 3]);  call c_f_pointer(hbuf(3), pp, [4, ncol])
-    inplace = c_associated(c_loc(qv), c_loc(s(1,1,1))) .and. c_associated(c_loc(qc), c_loc(s(1,1,2))) .and. &
-         c_associated(c_loc(qr), c_loc(s(1,1,4))) .and. c_associated(c_loc(nr), c_loc(s(1,1,8))) .and. &
-         c_associated(c_loc(t), c_loc(s(1,1,12))) .and. c_associated(c_loc(p), c_loc(f(1,1,1))) .and. &
-         c_associated(c_loc(dz), c_loc(f(1,1,3))) .and. c_associated(c_loc(ppt), c_loc(pp(1,1)))
-    if (inplace .and. have_frz) inplace = c_associated(c_loc(qi), c_loc(s(1,1,3))) .and. c_associated(c_loc(qs), c_loc(s(1,1,5))) &
-         .and. c_associated(c_loc(qg), c_loc(s(1,1,6))) .and. c_associated(c_loc(ni), c_loc(s(1,1,7)))
-    if (inplace .and. have_aer) inplace = c_associated(c_loc(nc), c_loc(s(1,1,9))) .and. c_associated(c_loc(nwfa), c_loc(s(1,1,10))) &
-         .and. c_associated(c_loc(nifa), c_loc(s(1,1,11)))
-    if (inplace .and. present(w)) inplace = c_associated(c_loc(w), c_loc(f(1,1,2)))
-    if (.not. inplace) then
-    s(:,:,1) = qv;  s(:,:,2) = qc;  s(:,:,4) = qr;  s(:,:,8) = nr;  s(:,:,12) = t
-    if (have_frz) then
-       s(:,:,3) = qi;  s(:,:,5) = qs;  s(:,:,6) = qg;  s(:,:,7) = ni
-    end if
-    if (have_aer) then
-       s(:,:,9) = nc;  s(:,:,10) = nwfa;  s(:,:,11) = nifa
-    end if
-    f(:,:,1) = p;  f(:,:,3) = dz
-    if (present(w)) f(:,:,2) = w
-    pp = ppt
-    end if
-    do i = 1, 12
-       ps(i) = c_loc(s(1,1,i))
+    call rate_staging(ncol, nz, rates, nstep, prates, pnstep)
+    call staging(1, esize * 12 * nprof);  call staging(2, esize * 3 * nprof);  call staging(3, esize * 4 * ncol)
+    do i = 1, 12                                           ! the slots: 1..12 the state, 13..15 p, w, dz
+       ps(i) = byte_offset(hbuf(1), (i - 1) * esize * nprof)
     end do
-    pf(1) = c_loc(f(1,1,1));  pf(3) = c_loc(f(1,1,3))
-    if (present(w)) pf(2) = c_loc(f(1,1,2))
+    do i = 1, 3
+       ps(12 + i) = byte_offset(hbuf(2), (i - 1) * esize * nprof)
+    end do
+    ! (an argument that IS its staging slot -- mp_thompson_staging -- needs no copy, in or out)
+    inplace = c_associated(c_loc(qv), ps(1)) .and. c_associated(c_loc(qc), ps(2)) .and. c_associated(c_loc(qr), ps(4)) .and. &
+         c_associated(c_loc(nr), ps(8)) .and. c_associated(c_loc(t), ps(12)) .and. c_associated(c_loc(p), ps(13)) .and. &
+         c_associated(c_loc(dz), ps(15)) .and. c_associated(c_loc(ppt), hbuf(3))
+    if (inplace .and. have_frz) inplace = c_associated(c_loc(qi), ps(3)) .and. c_associated(c_loc(qs), ps(5)) .and. &
+         c_associated(c_loc(qg), ps(6)) .and. c_associated(c_loc(ni), ps(7))
+    if (inplace .and. have_aer) inplace = c_associated(c_loc(nc), ps(9)) .and. c_associated(c_loc(nwfa), ps(10)) .and. &
+         c_associated(c_loc(nifa), ps(11))
+    if (inplace .and. present(w)) inplace = c_associated(c_loc(w), ps(14))
+    if (.not. inplace) then
+       call put(ps(1), qv, n);  call put(ps(2), qc, n);  call put(ps(4), qr, n);  call put(ps(8), nr, n);  call put(ps(12), t, n)
+       if (have_frz) then
+          call put(ps(3), qi, n);  call put(ps(5), qs, n);  call put(ps(6), qg, n);  call put(ps(7), ni, n)
+       end if
+       if (have_aer) then
+          call put(ps(9), nc, n);  call put(ps(10), nwfa, n);  call put(ps(11), nifa, n)
+       end if
+       call put(ps(13), p, n);  call put(ps(15), dz, n)
+       if (present(w)) call put(ps(14), w, n)
+       call put(hbuf(3), ppt, 4 * ncol)
+    end if
+    ! absent arrays are not sent: the library sees NULL
     if (.not. have_frz) then
-       ps(3) = c_null_ptr;  ps(5) = c_null_ptr;  ps(6) = c_null_ptr;  ps(7) = c_null_ptr
+       ps(3) = c_null_ptr;  ps(5:7) = c_null_ptr
     end if
     if (.not. have_aer) ps(9:11) = c_null_ptr
+    if (.not. present(w)) ps(14) = c_null_ptr
+    out = kidmp_outputs(c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr)
     if (present(dbz) .or. want_radii) then                 ! one GPU, the step followed by ONE launch for the outputs
-       call staging(6, 8_c_size_t * 4 * nprof)
-       call c_f_pointer(hbuf(6), zd, [nz, ncol, 4])
-       if (present(dbz)) out%dbz = c_loc(zd(1,1,1))
+       call staging(6, esize * 4 * nprof)
+       if (present(dbz)) out%dbz = hbuf(6)
        if (want_radii) then
-          out%re_qc = c_loc(zd(1,1,2));  out%re_qi = c_loc(zd(1,1,3));  out%re_qs = c_loc(zd(1,1,4))
+          out%re_qc = byte_offset(hbuf(6), esize * nprof);  out%re_qi = byte_offset(hbuf(6), 2 * esize * nprof)
+          out%re_qs = byte_offset(hbuf(6), 3 * esize * nprof)
        end if
-       rc = kidmp_batch_step_host_out(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_double), &
+    end if
+    if (.not. is64) then
+       rc = kidmp32_batch_step_host_out(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_float), &
             ps(1), ps(2), ps(3), ps(4), ps(5), ps(6), ps(7), ps(8), ps(9), ps(10), ps(11), ps(12), &
-            pf(1), pf(2), pf(3), c_loc(pp), prates, pnstep, out)
-       if (rc == 0 .and. present(dbz)) dbz = real(zd(:,:,1))
-       if (rc == 0 .and. want_radii) then
-          re_qc = real(zd(:,:,2));  re_qi = real(zd(:,:,3));  re_qs = real(zd(:,:,4))
-       end if
+            ps(13), ps(14), ps(15), hbuf(3), prates, pnstep, arith_code(), out)
     else if (c_associated(mctx)) then                      ! several GPUs: contiguous column ranges, one pipeline each
        rc = kidmp_batch_step_host_multi(mctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_double), &
             ps(1), ps(2), ps(3), ps(4), ps(5), ps(6), ps(7), ps(8), ps(9), ps(10), ps(11), ps(12), &
-            pf(1), pf(2), pf(3), c_loc(pp), prates, pnstep, kidmp_precip_sums)
+            ps(13), ps(14), ps(15), hbuf(3), prates, pnstep, kidmp_precip_sums)
     else
-       rc = kidmp_batch_step_host_diag(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_double), &
+       rc = kidmp_batch_step_host_out(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_double), &
             ps(1), ps(2), ps(3), ps(4), ps(5), ps(6), ps(7), ps(8), ps(9), ps(10), ps(11), ps(12), &
-            pf(1), pf(2), pf(3), c_loc(pp), prates, pnstep)
+            ps(13), ps(14), ps(15), hbuf(3), prates, pnstep, out)
     end if
     call stop_on_error(rc, 'mp_thompson')
+    if (present(dbz)) call get(out%dbz, dbz, n)
+    if (want_radii) then
+       call get(out%re_qc, re_qc, n);  call get(out%re_qi, re_qi, n);  call get(out%re_qs, re_qs, n)
+    end if
     if (.not. inplace) then
-    qv = s(:,:,1);  qc = s(:,:,2);  qr = s(:,:,4);  nr = s(:,:,8);  t = s(:,:,12)
-    if (have_frz) then
-       qi = s(:,:,3);  qs = s(:,:,5);  qg = s(:,:,6);  ni = s(:,:,7)
-    end if
-    if (have_aer) then
-       nc = s(:,:,9);  nwfa = s(:,:,10);  nifa = s(:,:,11)
-    end if
-    ppt = pp
-    end if
+       call get(ps(1), qv, n);  call get(ps(2), qc, n);  call get(ps(4), qr, n);  call get(ps(8), nr, n);  call get(ps(12), t, n)
+       if (have_frz) then
+          call get(ps(3), qi, n);  call get(ps(5), qs, n);  call get(ps(6), qg, n);  call get(ps(7), ni, n)
+       end if
+       if (have_aer) then
+          call get(ps(9), nc, n);  call get(ps(10), nwfa, n);  call get(ps(11), nifa, n)
+       end if
+       call get(hbuf(3), ppt, 4 * ncol)
     end if
     if (l_rate_diagnostics) call replay_rate_diagnostics(ncol, nz, rates, nstep)
+
+  contains
+
+    ! m values of the caller's REAL to / from staging memory of the arithmetic's storage kind
+    subroutine put(slot, a, m)
+      type(c_ptr), intent(in) :: slot
+      integer, intent(in) :: m
+      real, intent(in) :: a(m)
+      real(c_double), pointer :: v8(:)
+      real(c_float), pointer :: v4(:)
+      if (is64) then
+         call c_f_pointer(slot, v8, [m]);  v8 = a
+      else
+         call c_f_pointer(slot, v4, [m]);  v4 = a
+      end if
+    end subroutine put
+
+    subroutine get(slot, a, m)
+      type(c_ptr), intent(in) :: slot
+      integer, intent(in) :: m
+      real, intent(out) :: a(m)
+      real(c_double), pointer :: v8(:)
+      real(c_float), pointer :: v4(:)
+      if (is64) then
+         call c_f_pointer(slot, v8, [m]);  a = real(v8)
+      else
+         call c_f_pointer(slot, v4, [m]);  a = v4
+      end if
+    end subroutine get
   end subroutine mp_thompson_batch
 
   ! The KiD block of M:2962-3124: per column, per level, 30 mixed-phase rates (.not. iiwarm) then 6 warm ones;
@@ -809,9 +791,8 @@ contains
     real(c_double), pointer :: rates(:,:,:)
     integer(c_int32_t), pointer :: nstep(:,:)
     type(c_ptr) :: prates, pnstep
-    integer(c_size_t) :: nprof
     integer(c_int) :: rc
-    integer(c_int32_t) :: arith
+    integer :: n
     if (.not. c_associated(ctx)) call thompson_init
     if (c_associated(mctx)) then
        write(*,'(a)') ' module_mp_thompson09n: mp_thompson_kid_interface is not available with kidmp_ndevices > 1'
@@ -822,41 +803,22 @@ contains
             ' needs the matching default REAL (8-byte for p64, 4-byte for p32n / f32)'
        stop 1
     end if
-    if ((present(re_qc) .neqv. present(re_qi)) .or. (present(re_qc) .neqv. present(re_qs))) then
-       write(*,'(a)') ' module_mp_thompson09n: re_qc, re_qi, re_qs must be passed or left out together'
-       stop 1
-    end if
-    state = kidmp_kid_fields(c_loc(theta), c_loc(qv), c_loc(hyd(1,1,1)), c_loc(hyd(1,1,2)), c_loc(hyd(1,1,3)), &
-         c_loc(hyd(1,1,4)), c_loc(hyd(1,1,5)), c_loc(hyd(1,1,6)), c_loc(hyd(1,1,7)))
-    adv = kidmp_kid_fields(c_loc(dtheta_adv), c_loc(dqv_adv), c_loc(hyd_adv(1,1,1)), c_loc(hyd_adv(1,1,2)), &
-         c_loc(hyd_adv(1,1,3)), c_loc(hyd_adv(1,1,4)), c_loc(hyd_adv(1,1,5)), c_loc(hyd_adv(1,1,6)), c_loc(hyd_adv(1,1,7)))
-    div = kidmp_kid_fields(c_loc(dtheta_div), c_loc(dqv_div), c_loc(hyd_div(1,1,1)), c_loc(hyd_div(1,1,2)), &
-         c_loc(hyd_div(1,1,3)), c_loc(hyd_div(1,1,4)), c_loc(hyd_div(1,1,5)), c_loc(hyd_div(1,1,6)), c_loc(hyd_div(1,1,7)))
-    mphys = kidmp_kid_fields(c_loc(dtheta_mphys), c_loc(dqv_mphys), c_loc(hyd_mphys(1,1,1)), c_loc(hyd_mphys(1,1,2)), &
-         c_loc(hyd_mphys(1,1,3)), c_loc(hyd_mphys(1,1,4)), c_loc(hyd_mphys(1,1,5)), c_loc(hyd_mphys(1,1,6)), &
-         c_loc(hyd_mphys(1,1,7)))
+    call radii_together(present(re_qc), present(re_qi), present(re_qs))
+    n = nz * ncol
+    state = kid_fields(n, theta, qv, hyd);  adv = kid_fields(n, dtheta_adv, dqv_adv, hyd_adv)
+    div = kid_fields(n, dtheta_div, dqv_div, hyd_div);  mphys = kid_fields(n, dtheta_mphys, dqv_mphys, hyd_mphys)
     out = kidmp_outputs(c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr)
     if (present(dbz)) out%dbz = c_loc(dbz)
     if (present(re_qc)) then
        out%re_qc = c_loc(re_qc);  out%re_qi = c_loc(re_qi);  out%re_qs = c_loc(re_qs)
     end if
-    prates = c_null_ptr;  pnstep = c_null_ptr
-    nprof = int(nz, c_size_t) * int(ncol, c_size_t)
-    if (l_rate_diagnostics) then
-       call staging(4, 8_c_size_t * NRATES * nprof)
-       call staging(5, 16_c_size_t * ncol)
-       call c_f_pointer(hbuf(4), rates, [nz, NRATES, ncol])
-       call c_f_pointer(hbuf(5), nstep, [4, ncol])
-       prates = hbuf(4);  pnstep = hbuf(5)
-    end if
+    call rate_staging(ncol, nz, rates, nstep, prates, pnstep)
     if (kind(theta) == c_double) then
        rc = kidmp_kid_interface_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_double), real(p0, c_double), &
             real(r_on_cp, c_double), state, adv, div, c_loc(exner), c_loc(dz), mphys, c_loc(ppt), prates, pnstep, out)
     else
-       arith = 0_c_int32_t
-       if (trim(kidmp_arith) == 'f32') arith = 1_c_int32_t
        rc = kidmp32_kid_interface_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), real(dt, c_float), real(p0, c_float), &
-            real(r_on_cp, c_float), state, adv, div, c_loc(exner), c_loc(dz), mphys, c_loc(ppt), prates, pnstep, out, arith)
+            real(r_on_cp, c_float), state, adv, div, c_loc(exner), c_loc(dz), mphys, c_loc(ppt), prates, pnstep, out, arith_code())
     end if
     call stop_on_error(rc, 'mp_thompson_kid_interface')
     if (l_rate_diagnostics) call replay_rate_diagnostics(ncol, nz, rates, nstep)

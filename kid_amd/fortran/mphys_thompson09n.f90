@@ -77,7 +77,11 @@ contains
     real, allocatable, save :: total(:)
     real, allocatable, save :: pptrain_2d_prof(:,:)          ! W:32; saved as 'total_ppt_level' for nx > 1 (W:304-307)
     real, allocatable, save :: dbz(:,:)                      ! l_radar_reflectivity: (nz, nx)
-    real, allocatable, save :: re(:,:,:)                     ! l_effective_radii: (nz, nx, 3) = cloud water, ice, snow
+    real, allocatable, target, save :: re(:,:,:)             ! l_effective_radii: (nz, nx, 3) = cloud water, ice, snow
+    ! the optional arguments of the one batched call: a disassociated pointer is an absent argument, and `contiguous`
+    ! lets an associated one pass without a temporary, so that the library still finds a staging slot to be itself
+    real, pointer, contiguous :: o_qi(:,:), o_qs(:,:), o_qg(:,:), o_ni(:,:), o_nc(:,:), o_nwfa(:,:), o_nifa(:,:), o_w(:,:)
+    real, pointer, contiguous :: o_rc(:,:), o_ri(:,:), o_rs(:,:)
     real :: rho
     logical :: staged
     integer :: i, k, m, s
@@ -184,6 +188,19 @@ contains
        end if
        if (.not. allocated(re)) allocate(re(nz, nx, 3))
     end if
+    ! What goes to the library beside the always-present arrays.  dbz is allocated only with l_radar_reflectivity: an
+    ! unallocated actual argument is an absent optional one, like a disassociated pointer.  The frozen species of a warm
+    ! run stay zero (W:46-52) and stay at home; the aerosols and w are sent only where they are read.
+    nullify(o_qi, o_qs, o_qg, o_ni, o_nc, o_nwfa, o_nifa, o_w, o_rc, o_ri, o_rs)
+    if (l_effective_radii) then
+       o_rc => re(:,:,1);  o_ri => re(:,:,2);  o_rs => re(:,:,3)
+    end if
+    if (.not. l_device_adapter .and. (is_aerosol_aware .or. .not. iiwarm)) then
+       o_qi => st(:,:,S_QI);  o_qs => st(:,:,S_QS);  o_qg => st(:,:,S_QG);  o_ni => st(:,:,S_NI)
+    end if
+    if (.not. l_device_adapter .and. is_aerosol_aware) then
+       o_nc => st(:,:,S_NC);  o_nwfa => st(:,:,S_NWFA);  o_nifa => st(:,:,S_NIFA);  o_w => fo(:,:,2)
+    end if
     if (l_device_adapter) then
        ! ---- gather, step and back-out in one library call: only the derived-type moments are copied ----
        !$omp parallel do default(shared) private(i, k, m) schedule(static) if(nx >= 256)
@@ -198,16 +215,9 @@ contains
           end do
        end do
        !$omp end parallel do
-       ! (dbz is allocated only with l_radar_reflectivity: an unallocated actual argument is an absent optional one)
-       if (l_effective_radii) then
-          call mp_thompson_kid_interface(nx, nz, dt, p0, r_on_cp, theta(:,1:nx), qv(:,1:nx), hy(:,:,:,1), &
-               dtheta_adv(:,1:nx), dqv_adv(:,1:nx), hy(:,:,:,2), dtheta_div(:,1:nx), dqv_div(:,1:nx), hy(:,:,:,3), &
-               exner(:,1:nx), dz, dtheta_mphys(:,1:nx), dqv_mphys(:,1:nx), hy(:,:,:,4), ppt, dbz, re(:,:,1), re(:,:,2), re(:,:,3))
-       else
-          call mp_thompson_kid_interface(nx, nz, dt, p0, r_on_cp, theta(:,1:nx), qv(:,1:nx), hy(:,:,:,1), &
-               dtheta_adv(:,1:nx), dqv_adv(:,1:nx), hy(:,:,:,2), dtheta_div(:,1:nx), dqv_div(:,1:nx), hy(:,:,:,3), &
-               exner(:,1:nx), dz, dtheta_mphys(:,1:nx), dqv_mphys(:,1:nx), hy(:,:,:,4), ppt, dbz)
-       end if
+       call mp_thompson_kid_interface(nx, nz, dt, p0, r_on_cp, theta(:,1:nx), qv(:,1:nx), hy(:,:,:,1), &
+            dtheta_adv(:,1:nx), dqv_adv(:,1:nx), hy(:,:,:,2), dtheta_div(:,1:nx), dqv_div(:,1:nx), hy(:,:,:,3), &
+            exner(:,1:nx), dz, dtheta_mphys(:,1:nx), dqv_mphys(:,1:nx), hy(:,:,:,4), ppt, dbz, o_rc, o_ri, o_rs)
        !$omp parallel do default(shared) private(i, k, m) schedule(static) if(nx >= 256)
        do i = 1, nx
           do m = 1, NHYD
@@ -218,43 +228,9 @@ contains
           end do
        end do
        !$omp end parallel do
-    else if (l_effective_radii) then
-       ! (dbz is allocated only with l_radar_reflectivity: an unallocated actual argument is an absent optional one)
-       if (is_aerosol_aware) then
-          call mp_thompson_batch(nx, nz, dt, st(:,:,S_QV), st(:,:,S_QC), st(:,:,S_QI), st(:,:,S_QR), st(:,:,S_QS), &
-               st(:,:,S_QG), st(:,:,S_NI), st(:,:,S_NR), st(:,:,S_NC), st(:,:,S_NWFA), st(:,:,S_NIFA), st(:,:,S_T), &
-               fo(:,:,1), fo(:,:,2), fo(:,:,3), ppt, dbz, re(:,:,1), re(:,:,2), re(:,:,3))
-       else if (iiwarm) then
-          call mp_thompson_batch(nx, nz, dt, qv=st(:,:,S_QV), qc=st(:,:,S_QC), qr=st(:,:,S_QR), nr=st(:,:,S_NR), &
-               t=st(:,:,S_T), p=fo(:,:,1), dz=fo(:,:,3), ppt=ppt, dbz=dbz, re_qc=re(:,:,1), re_qi=re(:,:,2), re_qs=re(:,:,3))
-       else
-          call mp_thompson_batch(nx, nz, dt, qv=st(:,:,S_QV), qc=st(:,:,S_QC), qi=st(:,:,S_QI), qr=st(:,:,S_QR), &
-               qs=st(:,:,S_QS), qg=st(:,:,S_QG), ni=st(:,:,S_NI), nr=st(:,:,S_NR), t=st(:,:,S_T), p=fo(:,:,1), &
-               dz=fo(:,:,3), ppt=ppt, dbz=dbz, re_qc=re(:,:,1), re_qi=re(:,:,2), re_qs=re(:,:,3))
-       end if
-    else if (l_radar_reflectivity) then
-       if (is_aerosol_aware) then
-          call mp_thompson_batch(nx, nz, dt, st(:,:,S_QV), st(:,:,S_QC), st(:,:,S_QI), st(:,:,S_QR), st(:,:,S_QS), &
-               st(:,:,S_QG), st(:,:,S_NI), st(:,:,S_NR), st(:,:,S_NC), st(:,:,S_NWFA), st(:,:,S_NIFA), st(:,:,S_T), &
-               fo(:,:,1), fo(:,:,2), fo(:,:,3), ppt, dbz)
-       else if (iiwarm) then
-          call mp_thompson_batch(nx, nz, dt, qv=st(:,:,S_QV), qc=st(:,:,S_QC), qr=st(:,:,S_QR), nr=st(:,:,S_NR), &
-               t=st(:,:,S_T), p=fo(:,:,1), dz=fo(:,:,3), ppt=ppt, dbz=dbz)
-       else
-          call mp_thompson_batch(nx, nz, dt, qv=st(:,:,S_QV), qc=st(:,:,S_QC), qi=st(:,:,S_QI), qr=st(:,:,S_QR), &
-               qs=st(:,:,S_QS), qg=st(:,:,S_QG), ni=st(:,:,S_NI), nr=st(:,:,S_NR), t=st(:,:,S_T), p=fo(:,:,1), &
-               dz=fo(:,:,3), ppt=ppt, dbz=dbz)
-       end if
-    else if (is_aerosol_aware) then
-       call mp_thompson_batch(nx, nz, dt, st(:,:,S_QV), st(:,:,S_QC), st(:,:,S_QI), st(:,:,S_QR), st(:,:,S_QS), &
-            st(:,:,S_QG), st(:,:,S_NI), st(:,:,S_NR), st(:,:,S_NC), st(:,:,S_NWFA), st(:,:,S_NIFA), st(:,:,S_T), &
-            fo(:,:,1), fo(:,:,2), fo(:,:,3), ppt)
-    else if (iiwarm) then                        ! a warm run: the frozen species stay zero (W:46-52) and stay at home
-       call mp_thompson_batch(nx, nz, dt, qv=st(:,:,S_QV), qc=st(:,:,S_QC), qr=st(:,:,S_QR), nr=st(:,:,S_NR), &
-            t=st(:,:,S_T), p=fo(:,:,1), dz=fo(:,:,3), ppt=ppt)
     else
-       call mp_thompson_batch(nx, nz, dt, qv=st(:,:,S_QV), qc=st(:,:,S_QC), qi=st(:,:,S_QI), qr=st(:,:,S_QR), &
-            qs=st(:,:,S_QS), qg=st(:,:,S_QG), ni=st(:,:,S_NI), nr=st(:,:,S_NR), t=st(:,:,S_T), p=fo(:,:,1), dz=fo(:,:,3), ppt=ppt)
+       call mp_thompson_batch(nx, nz, dt, st(:,:,S_QV), st(:,:,S_QC), o_qi, st(:,:,S_QR), o_qs, o_qg, o_ni, st(:,:,S_NR), &
+            o_nc, o_nwfa, o_nifa, st(:,:,S_T), fo(:,:,1), o_w, fo(:,:,3), ppt, dbz, o_rc, o_ri, o_rs)
     end if
 
     if (.not. l_device_adapter) then

@@ -48,6 +48,7 @@ class _Outputs(C.Structure):
 
 KID_FIELDS = ("theta", "qv", "qc", "qr", "nr", "qi", "ni", "qs", "qg")     # members of kidmp_kid_fields; the last four frozen
 KID_WORK_NAMES = STATE_NAMES + FORCING_NAMES                                  # the 15 profiles of the adapter's workspace
+_STEP_REQUIRED = STATE_NAMES + ("p", "dz")                                    # what a device step cannot do without (w: optional)
 
 
 class _KidFields(C.Structure):
@@ -63,7 +64,78 @@ def lib_path():
 
 _lib = None
 _dp = C.POINTER(C.c_double)
+_fp = C.POINTER(C.c_float)
+_ip = C.POINTER(C.c_int32)
 _vp = C.c_void_p
+
+
+def _declarations():
+    """name -> (restype, argtypes) of every entry of include/kidmp.h.  An entry that exists as kidmp_* (binary64 arrays)
+    and kidmp32_* (binary32 arrays, plus the `arith` selector where the entry steps) is written once."""
+    i32, i64, size, text, rc = C.c_int32, C.c_int64, C.c_size_t, C.c_char_p, C.c_int
+    cfg, outs, fields = C.POINTER(_Cfg), C.POINTER(_Outputs), C.POINTER(_KidFields)
+    step64 = [_vp, i64, i32, C.c_double] + [_dp] * 16 + [_dp, _ip]       # the host step of either prefix, see below
+    d = {
+        "kidmp_init": (rc, [cfg, C.POINTER(_vp)]),
+        "kidmp_finalize": (None, [_vp]),
+        "kidmp_last_error": (text, [_vp]),
+        "kidmp_init_seconds": (C.c_double, [_vp]),
+        "kidmp_kernel_name": (text, []),
+        "kidmp_reserve": (rc, [_vp, i64, i32]),
+        "kidmp_host_alloc": (_vp, [size]),
+        "kidmp_host_free": (None, [_vp]),
+        "kidmp_set_host_chunk": (rc, [_vp, i64]),
+        "kidmp_set_column_nc": (rc, [_vp, i64, _vp]),
+        "kidmp_column_nc_count": (i64, [_vp]),
+        "kidmp_batch_step_host_diag": (rc, step64),
+        "kidmp_default_aerosols_device": (rc, [_vp, i64] + [_vp] * 6 + [_vp]),
+        "kidmp_reduce_ppt_device": (rc, [_vp, i64, _vp, _vp, _vp]),
+        "kidmp_reduce_ppt_exact_device": (rc, [_vp, i64, _vp, _vp, _vp]),
+        "kidmp_ppt_limbs_to_sums": (rc, [C.POINTER(i64), _dp]),
+        "kidmp_reduce_rates_device": (rc, [_vp, i64, i32, _vp, _vp, _vp]),
+        "kidmp_sanity_device": (rc, [_vp, i64] + [_vp] * 9 + [_vp]),
+        "kidmp_shard_bounds": (rc, [i64, i32, i32, C.POINTER(i64), C.POINTER(i64)]),
+        "kidmp_init_multi": (rc, [cfg, i32, _ip, C.POINTER(_vp)]),
+        "kidmp_finalize_multi": (None, [_vp]),
+        "kidmp_multi_last_error": (text, [_vp]),
+        "kidmp_multi_size": (i32, [_vp]),
+        "kidmp_multi_context": (_vp, [_vp, i32]),
+        "kidmp_batch_step_host_multi": (rc, step64 + [_dp]),
+        "kidmp_batch_step_host_multi_diag": (rc, step64 + [_dp, _dp]),
+        "kidmp_math_probe": (rc, [_vp, i32, i64, _dp, _dp, _dp]),
+        "kidmp_get_table": (i64, [_vp, text, _dp, i64]),
+        "kidmp_get_const": (i64, [_vp, text, _dp, i64]),
+        "kidmp_save_table_cache": (rc, [_vp, text]),
+        "kidmp_load_table_cache": (rc, [_vp, text]),
+        "kidmp_table_cache_reuse": (rc, [_vp, text, i32, i32, _ip]),
+        "kidmp_cache_write_file": (rc, [text, i32, C.POINTER(_dp), i64]),
+        "kidmp_cache_read_file": (rc, [text, i32, C.POINTER(_dp), i64]),
+    }
+    for pre, real, rp in (("kidmp", C.c_double, _dp), ("kidmp32", C.c_float, _fp)):
+        arith = [i32] if pre == "kidmp32" else []
+        head = [_vp, i64, i32, real]                         # ctx, ncol, nz, dt
+        host = head + [rp] * 16 + [_dp, _ip]                 # 12 state + 3 forcing profiles, ppt; rates, nstep
+        kid = [_vp, i64, i32, real, real, real] + [fields] * 3 + [_vp, _vp, fields, _vp, _vp, _vp, outs]
+        d.update({
+            pre + "_column_step": (rc, [_vp, i32, real] + [rp] * 16 + arith),
+            # (kidmp_batch_step_host alone is older than nstep: kidmp_batch_step_host_diag is its full form)
+            pre + "_batch_step_host": (rc, host + arith if arith else host[:-1]),
+            pre + "_batch_step_host_refl": (rc, host + arith + [rp]),
+            pre + "_batch_step_host_out": (rc, host + arith + [outs]),
+            pre + "_batch_step_device": (rc, head + [_vp] * 18 + arith + [_vp]),
+            pre + "_effective_radii_device": (rc, [_vp, i64] + [_vp] * 11 + [_vp]),
+            pre + "_effective_radii_host": (rc, [_vp, i64] + [rp] * 11),
+            pre + "_reflectivity_device": (rc, [_vp, i64, i32] + [_vp] * 8 + [_vp]),
+            pre + "_reflectivity_host": (rc, [_vp, i64, i32] + [rp] * 8),
+            pre + "_column_outputs_device": (rc, [_vp, i64, i32] + [_vp] * 11 + [outs, _vp]),
+            pre + "_kernel_fingerprint": (text, [_vp] + arith),
+            pre + "_kid_workspace_bytes": (size, [i64, i32]),
+            pre + "_kid_workspace_offset": (size, [i64, i32, i32]),
+            pre + "_kid_interface_device": (rc, kid + arith + [_vp, size, _vp]),
+            pre + "_kid_interface_host": (rc, kid + arith),
+            pre + "_kid_gather_device": (rc, kid[:11] + [_vp, _vp, size, _vp]),
+        })
+    return d
 
 
 def load_library(path=None):
@@ -85,136 +157,9 @@ def load_library(path=None):
         raise KidmpError("%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                          "(hipcc --offload-arch=gfx950). There is no CPU fallback." % path)
     L = C.CDLL(path)
-    L.kidmp_init.restype = C.c_int
-    L.kidmp_init.argtypes = [C.POINTER(_Cfg), C.POINTER(_vp)]
-    L.kidmp_finalize.restype = None
-    L.kidmp_finalize.argtypes = [_vp]
-    L.kidmp_last_error.restype = C.c_char_p
-    L.kidmp_last_error.argtypes = [_vp]
-    L.kidmp_column_step.restype = C.c_int
-    L.kidmp_column_step.argtypes = [_vp, C.c_int32, C.c_double] + [_dp] * 16
-    L.kidmp_batch_step_host.restype = C.c_int
-    L.kidmp_batch_step_host.argtypes = [_vp, C.c_int64, C.c_int32, C.c_double] + [_dp] * 17
-    L.kidmp_batch_step_device.restype = C.c_int
-    L.kidmp_batch_step_device.argtypes = [_vp, C.c_int64, C.c_int32, C.c_double] + [_vp] * 18 + [_vp]
-    _fpp = C.POINTER(C.c_float)
-    L.kidmp32_batch_step_host.restype = C.c_int
-    L.kidmp32_batch_step_host.argtypes = [_vp, C.c_int64, C.c_int32, C.c_float] + [_fpp] * 16 + [_dp, C.POINTER(C.c_int32), C.c_int32]
-    L.kidmp32_batch_step_device.restype = C.c_int
-    L.kidmp32_batch_step_device.argtypes = [_vp, C.c_int64, C.c_int32, C.c_float] + [_vp] * 18 + [C.c_int32, _vp]
-    L.kidmp32_column_step.restype = C.c_int
-    L.kidmp32_column_step.argtypes = [_vp, C.c_int32, C.c_float] + [_fpp] * 16 + [C.c_int32]
-    L.kidmp_default_aerosols_device.restype = C.c_int
-    L.kidmp_default_aerosols_device.argtypes = [_vp, C.c_int64] + [_vp] * 6 + [_vp]
-    L.kidmp_reduce_ppt_device.restype = C.c_int
-    L.kidmp_reduce_ppt_device.argtypes = [_vp, C.c_int64, _vp, _vp, _vp]
-    L.kidmp_reduce_rates_device.restype = C.c_int
-    L.kidmp_reduce_rates_device.argtypes = [_vp, C.c_int64, C.c_int32, _vp, _vp, _vp]
-    L.kidmp_sanity_device.restype = C.c_int
-    L.kidmp_sanity_device.argtypes = [_vp, C.c_int64] + [_vp] * 9 + [_vp]
-    L.kidmp_effective_radii_device.restype = C.c_int
-    L.kidmp_effective_radii_device.argtypes = [_vp, C.c_int64] + [_vp] * 11 + [_vp]
-    L.kidmp_effective_radii_host.restype = C.c_int
-    L.kidmp_effective_radii_host.argtypes = [_vp, C.c_int64] + [_dp] * 11
-    L.kidmp32_effective_radii_device.restype = C.c_int
-    L.kidmp32_effective_radii_device.argtypes = [_vp, C.c_int64] + [_vp] * 11 + [_vp]
-    L.kidmp32_effective_radii_host.restype = C.c_int
-    L.kidmp32_effective_radii_host.argtypes = [_vp, C.c_int64] + [_fpp] * 11
-    L.kidmp_column_outputs_device.restype = C.c_int
-    L.kidmp_column_outputs_device.argtypes = [_vp, C.c_int64, C.c_int32] + [_vp] * 11 + [C.POINTER(_Outputs), _vp]
-    L.kidmp32_column_outputs_device.restype = C.c_int
-    L.kidmp32_column_outputs_device.argtypes = [_vp, C.c_int64, C.c_int32] + [_vp] * 11 + [C.POINTER(_Outputs), _vp]
-    L.kidmp_batch_step_host_out.restype = C.c_int
-    L.kidmp_batch_step_host_out.argtypes = ([_vp, C.c_int64, C.c_int32, C.c_double] + [_dp] * 17
-                                            + [C.POINTER(C.c_int32), C.POINTER(_Outputs)])
-    L.kidmp32_batch_step_host_out.restype = C.c_int
-    L.kidmp32_batch_step_host_out.argtypes = ([_vp, C.c_int64, C.c_int32, C.c_float] + [_fpp] * 16
-                                              + [_dp, C.POINTER(C.c_int32), C.c_int32, C.POINTER(_Outputs)])
-    L.kidmp_batch_step_host_diag.restype = C.c_int
-    L.kidmp_batch_step_host_diag.argtypes = [_vp, C.c_int64, C.c_int32, C.c_double] + [_dp] * 17 + [C.POINTER(C.c_int32)]
-    L.kidmp_reflectivity_device.restype = C.c_int
-    L.kidmp_reflectivity_device.argtypes = [_vp, C.c_int64, C.c_int32] + [_vp] * 8 + [_vp]
-    L.kidmp32_reflectivity_device.restype = C.c_int
-    L.kidmp32_reflectivity_device.argtypes = [_vp, C.c_int64, C.c_int32] + [_vp] * 8 + [_vp]
-    L.kidmp_reflectivity_host.restype = C.c_int
-    L.kidmp_reflectivity_host.argtypes = [_vp, C.c_int64, C.c_int32] + [_dp] * 8
-    L.kidmp32_reflectivity_host.restype = C.c_int
-    L.kidmp32_reflectivity_host.argtypes = [_vp, C.c_int64, C.c_int32] + [_fpp] * 8
-    L.kidmp_batch_step_host_refl.restype = C.c_int
-    L.kidmp_batch_step_host_refl.argtypes = [_vp, C.c_int64, C.c_int32, C.c_double] + [_dp] * 17 + [C.POINTER(C.c_int32), _dp]
-    L.kidmp32_batch_step_host_refl.restype = C.c_int
-    L.kidmp32_batch_step_host_refl.argtypes = ([_vp, C.c_int64, C.c_int32, C.c_float] + [_fpp] * 16
-                                               + [_dp, C.POINTER(C.c_int32), C.c_int32, _fpp])
-    L.kidmp_kernel_fingerprint.restype = C.c_char_p
-    L.kidmp_kernel_fingerprint.argtypes = [_vp]
-    L.kidmp32_kernel_fingerprint.restype = C.c_char_p
-    L.kidmp32_kernel_fingerprint.argtypes = [_vp, C.c_int32]
-    L.kidmp_reduce_ppt_exact_device.restype = C.c_int
-    L.kidmp_reduce_ppt_exact_device.argtypes = [_vp, C.c_int64, _vp, _vp, _vp]
-    L.kidmp_ppt_limbs_to_sums.restype = C.c_int
-    L.kidmp_ppt_limbs_to_sums.argtypes = [C.POINTER(C.c_int64), _dp]
-    L.kidmp_shard_bounds.restype = C.c_int
-    L.kidmp_shard_bounds.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    L.kidmp_init_multi.restype = C.c_int
-    L.kidmp_init_multi.argtypes = [C.POINTER(_Cfg), C.c_int32, C.POINTER(C.c_int32), C.POINTER(_vp)]
-    L.kidmp_finalize_multi.restype = None
-    L.kidmp_finalize_multi.argtypes = [_vp]
-    L.kidmp_multi_last_error.restype = C.c_char_p
-    L.kidmp_multi_last_error.argtypes = [_vp]
-    L.kidmp_multi_size.restype = C.c_int32
-    L.kidmp_multi_size.argtypes = [_vp]
-    L.kidmp_multi_context.restype = _vp
-    L.kidmp_multi_context.argtypes = [_vp, C.c_int32]
-    L.kidmp_batch_step_host_multi.restype = C.c_int
-    L.kidmp_batch_step_host_multi.argtypes = [_vp, C.c_int64, C.c_int32, C.c_double] + [_dp] * 17 + [C.POINTER(C.c_int32), _dp]
-    L.kidmp_batch_step_host_multi_diag.restype = C.c_int
-    L.kidmp_batch_step_host_multi_diag.argtypes = [_vp, C.c_int64, C.c_int32, C.c_double] + [_dp] * 17 + [C.POINTER(C.c_int32), _dp, _dp]
-    L.kidmp_reserve.restype = C.c_int
-    L.kidmp_reserve.argtypes = [_vp, C.c_int64, C.c_int32]
-    L.kidmp_math_probe.restype = C.c_int
-    L.kidmp_math_probe.argtypes = [_vp, C.c_int32, C.c_int64, _dp, _dp, _dp]
-    L.kidmp_get_table.restype = C.c_int64
-    L.kidmp_get_table.argtypes = [_vp, C.c_char_p, _dp, C.c_int64]
-    L.kidmp_get_const.restype = C.c_int64
-    L.kidmp_get_const.argtypes = [_vp, C.c_char_p, _dp, C.c_int64]
-    L.kidmp_save_table_cache.restype = C.c_int
-    L.kidmp_save_table_cache.argtypes = [_vp, C.c_char_p]
-    L.kidmp_load_table_cache.restype = C.c_int
-    L.kidmp_load_table_cache.argtypes = [_vp, C.c_char_p]
-    L.kidmp_table_cache_reuse.restype = C.c_int
-    L.kidmp_table_cache_reuse.argtypes = [_vp, C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
-    L.kidmp_cache_write_file.restype = C.c_int
-    L.kidmp_cache_write_file.argtypes = [C.c_char_p, C.c_int32, C.POINTER(_dp), C.c_int64]
-    L.kidmp_cache_read_file.restype = C.c_int
-    L.kidmp_cache_read_file.argtypes = [C.c_char_p, C.c_int32, C.POINTER(_dp), C.c_int64]
-    L.kidmp_host_alloc.restype = _vp
-    L.kidmp_host_alloc.argtypes = [C.c_size_t]
-    L.kidmp_host_free.restype = None
-    L.kidmp_host_free.argtypes = [_vp]
-    L.kidmp_set_host_chunk.restype = C.c_int
-    L.kidmp_set_host_chunk.argtypes = [_vp, C.c_int64]
-    L.kidmp_set_column_nc.restype = C.c_int
-    L.kidmp_set_column_nc.argtypes = [_vp, C.c_int64, _vp]
-    L.kidmp_column_nc_count.restype = C.c_int64
-    L.kidmp_column_nc_count.argtypes = [_vp]
-    for pre, real in (("kidmp", C.c_double), ("kidmp32", C.c_float)):
-        getattr(L, pre + "_kid_workspace_bytes").restype = C.c_size_t
-        getattr(L, pre + "_kid_workspace_bytes").argtypes = [C.c_int64, C.c_int32]
-        getattr(L, pre + "_kid_workspace_offset").restype = C.c_size_t
-        getattr(L, pre + "_kid_workspace_offset").argtypes = [C.c_int64, C.c_int32, C.c_int32]
-        head = [_vp, C.c_int64, C.c_int32, real, real, real] + [C.POINTER(_KidFields)] * 3 + [_vp, _vp, C.POINTER(_KidFields), _vp,
-                                                                                              _vp, _vp, C.POINTER(_Outputs)]
-        arith = [C.c_int32] if pre == "kidmp32" else []
-        getattr(L, pre + "_kid_interface_device").restype = C.c_int
-        getattr(L, pre + "_kid_interface_device").argtypes = head + arith + [_vp, C.c_size_t, _vp]
-        getattr(L, pre + "_kid_gather_device").restype = C.c_int
-        getattr(L, pre + "_kid_gather_device").argtypes = head[:11] + [_vp, _vp, C.c_size_t, _vp]
-        getattr(L, pre + "_kid_interface_host").restype = C.c_int
-        getattr(L, pre + "_kid_interface_host").argtypes = head + arith
-    L.kidmp_init_seconds.restype = C.c_double
-    L.kidmp_init_seconds.argtypes = [_vp]
-    L.kidmp_kernel_name.restype = C.c_char_p
-    L.kidmp_kernel_name.argtypes = []
+    for name, (restype, argtypes) in _declarations().items():
+        entry = getattr(L, name)
+        entry.restype, entry.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -224,8 +169,57 @@ def _np_dtype(dtype):
     return str(dtype).replace("torch.", "") if type(dtype).__module__.split(".")[0] == "torch" else dtype
 
 
-def _np_ptr(a):
-    return a.ctypes.data_as(_dp)
+def _np_ptr(a, pt=_dp):
+    return a.ctypes.data_as(pt)
+
+
+def _stream(stream, like):
+    """The stream an asynchronous entry runs on: the caller's, else torch's current stream on the device of `like`."""
+    if stream is not None:
+        return stream
+    import torch
+    return torch.cuda.current_stream(like.device).cuda_stream
+
+
+def _pointers(st, names, optional, check, addr):
+    """The arrays of the dict `st` under `names` as the addresses an entry takes, each judged by check(a, name).  A name
+    in `optional` that is missing (or None) gives a null pointer: whether it may be left out is the library's to say."""
+    out = []
+    for k in names:
+        a = st.get(k)
+        if a is None and k in optional:
+            out.append(None)
+        else:
+            check(a, k)
+            out.append(addr(a))
+    return out
+
+
+def _host_check(who, dtype, shape):
+    def check(a, k):
+        if not (a.dtype == dtype and a.flags.c_contiguous and a.shape == shape):
+            raise KidmpError("%s: %s must be contiguous %s [ncol, nz]" % (who, k, np.dtype(dtype).name))
+    return check
+
+
+def _outputs(dbz, radii, addr):
+    """The kidmp_outputs that names `dbz` and the three `radii`; None = not wanted."""
+    return _Outputs(addr(dbz) if dbz is not None else None, *([addr(a) for a in radii] if radii is not None else [None] * 3))
+
+
+def _host_step(who, st, dtype, dt, ppt, want_rates, want_nstep):
+    """What the host-array step entries share.  Checks the [ncol, nz] arrays of `st` (any of them may be missing: what
+    KiD itself never fills, include/kidmp.h) and makes ppt, rates and nstep.  Returns (ppt, rates, nstep) and the
+    arguments from ncol to nstep."""
+    ncol, nz = st["qv"].shape
+    pt = _dp if dtype == np.float64 else _fp
+    ptrs = _pointers(st, KID_WORK_NAMES, KID_WORK_NAMES, _host_check(who, dtype, (ncol, nz)), lambda a: _np_ptr(a, pt))
+    if ppt is None:
+        ppt = np.zeros((ncol, 4), dtype=dtype)
+    rates = np.zeros((ncol, NRATES, nz)) if want_rates else None
+    nstep = np.zeros((ncol, 4), dtype=np.int32) if want_nstep else None
+    return (ppt, rates, nstep), [ncol, nz, float(dt)] + ptrs + [_np_ptr(ppt, pt), _np_ptr(rates) if want_rates else None,
+                                                                _np_ptr(nstep, _ip) if want_nstep else None]
 
 
 class _PinnedBlock:
@@ -334,8 +328,7 @@ class ThompsonMP:
         """The output arrays of a host step and the kidmp_outputs that names them."""
         dbz = np.empty((ncol, nz), dtype=dtype) if want_dbz else None
         radii = tuple(np.empty((ncol, nz), dtype=dtype) for _ in range(3)) if want_radii else None
-        o = _Outputs(dbz.ctypes.data if want_dbz else None, *([a.ctypes.data for a in radii] if want_radii else [None] * 3))
-        return dbz, radii, o
+        return dbz, radii, _outputs(dbz, radii, lambda a: a.ctypes.data)
 
     def batch_step_host(self, st, dt, ppt=None, want_rates=False, want_dbz=False, want_radii=False):
         """numpy float64 [ncol, nz] arrays, in place.  Keys KiD itself never fills may be missing (or None): nc, nwfa,
@@ -344,66 +337,64 @@ class ThompsonMP:
         device in the same call (kidmp_batch_step_host_refl).  want_radii appends (re_qc, re_qi, re_qs) of the
         post-step state in the form of the scheme's driver, presets where the species is absent
         (kidmp_batch_step_host_out: one launch per chunk for everything wanted)."""
-        ncol, nz = st["qv"].shape
-        ptrs = []
-        for k in STATE_NAMES + FORCING_NAMES:
-            a = st.get(k)
-            if a is None:
-                ptrs.append(None)
-                continue
-            if not (a.dtype == np.float64 and a.flags.c_contiguous and a.shape == (ncol, nz)):
-                raise KidmpError("batch_step_host: %s must be contiguous float64 [ncol, nz]" % k)
-            ptrs.append(_np_ptr(a))
-        if ppt is None:
-            ppt = np.zeros((ncol, 4))
-        rates = np.zeros((ncol, NRATES, nz)) if want_rates else None
+        (ppt, rates, _), args = _host_step("batch_step_host", st, np.float64, dt, ppt, want_rates, False)
+        ncol, nz = args[:2]
+        L = load_library()
         if want_radii:
             dbz, radii, o = self._host_outputs(ncol, nz, np.float64, want_dbz, True)
-            self._check(load_library().kidmp_batch_step_host_out(
-                self._h, ncol, nz, float(dt), *ptrs, _np_ptr(ppt), _np_ptr(rates) if want_rates else None, None,
-                C.byref(o)))
+            self._check(L.kidmp_batch_step_host_out(self._h, *args, C.byref(o)))
             return (ppt, rates, dbz, radii) if want_dbz else (ppt, rates, radii)
         if want_dbz:
             dbz = np.empty((ncol, nz))
-            self._check(load_library().kidmp_batch_step_host_refl(
-                self._h, ncol, nz, float(dt), *ptrs, _np_ptr(ppt), _np_ptr(rates) if want_rates else None, None,
-                _np_ptr(dbz)))
+            self._check(L.kidmp_batch_step_host_refl(self._h, *args, _np_ptr(dbz)))
             return ppt, rates, dbz
-        self._check(load_library().kidmp_batch_step_host(
-            self._h, ncol, nz, float(dt), *ptrs, _np_ptr(ppt), _np_ptr(rates) if want_rates else None))
+        self._check(L.kidmp_batch_step_host(self._h, *args[:-1]))            # the one entry without nstep
         return ppt, rates
 
-    def _want(self, a, dtype, shape, what):
-        """A device-entry argument: contiguous CUDA tensor of the given dtype/shape on THIS context's GPU."""
+    def _device_check(self, who, dtype, shape):
+        return lambda a, k: self._want(a, dtype, shape, who + ": " + k)
+
+    def _want(self, a, dtype, shape, what, key=""):
+        """A device-entry argument: contiguous CUDA tensor of the given dtype/shape on THIS context's GPU.  A message
+        names it `what` + `key` (two parts, so that a loop over keys does not join strings for tensors that are right)."""
         if not (a.is_cuda and a.dtype == dtype and a.is_contiguous() and tuple(a.shape) == tuple(shape)):
-            raise KidmpError("%s must be a contiguous %s CUDA tensor %s" % (what, str(dtype).replace("torch.", ""), list(shape)))
+            raise KidmpError("%s must be a contiguous %s CUDA tensor %s" % (what + key, str(dtype).replace("torch.", ""), list(shape)))
         if a.device.index != self.device:
-            raise KidmpError("%s lives on cuda:%d but this context is bound to cuda:%d" % (what, a.device.index, self.device))
+            raise KidmpError("%s lives on cuda:%d but this context is bound to cuda:%d" % (what + key, a.device.index, self.device))
 
     # ---- batched device entry: torch CUDA tensors [ncol, nz], in place ----
-    def batch_step(self, st, dt, ppt, rates=None, nstep=None, stream=None):
-        """st: dict of float64 CUDA tensors [ncol, nz] (STATE_NAMES + p, dz; w optional).
-        ppt: float64 [ncol, 4], accumulated in place.  Asynchronous on `stream`
-        (default: torch's current stream)."""
+    def _step_device(self, who, st, dt, ppt, rates, nstep, stream, arith=None):
+        """batch_step (arith None: float64 tensors, kidmp_batch_step_device) and batch_step32 (float32 tensors,
+        kidmp32_batch_step_device).  On the clock of bench.py: nothing here that a call does not need."""
         import torch
+        dtype = torch.float64 if arith is None else torch.float32
         q = st["qv"]
         ncol, nz = q.shape
         w = st.get("w")
-        for k in STATE_NAMES + ("p", "dz"):
-            self._want(st[k], torch.float64, (ncol, nz), "batch_step: " + k)
+        for k in _STEP_REQUIRED:
+            self._want(st[k], dtype, (ncol, nz), who, k)
         if w is not None:
-            self._want(w, torch.float64, (ncol, nz), "batch_step: w")
-        self._want(ppt, torch.float64, (ncol, 4), "batch_step: ppt")
+            self._want(w, dtype, (ncol, nz), who, "w")
+        self._want(ppt, dtype, (ncol, 4), who, "ppt")
         if rates is not None:
-            self._want(rates, torch.float64, (ncol, NRATES, nz), "batch_step: rates")
+            self._want(rates, torch.float64, (ncol, NRATES, nz), who, "rates")
         if nstep is not None:
-            self._want(nstep, torch.int32, (ncol, 4), "batch_step: nstep")
-        s = stream if stream is not None else torch.cuda.current_stream(q.device).cuda_stream
+            self._want(nstep, torch.int32, (ncol, 4), who, "nstep")
+        s = _stream(stream, q)
         args = [st[k].data_ptr() for k in STATE_NAMES] + [st["p"].data_ptr(), w.data_ptr() if w is not None else None,
                                                           st["dz"].data_ptr(), ppt.data_ptr(),
                                                           rates.data_ptr() if rates is not None else None,
                                                           nstep.data_ptr() if nstep is not None else None]
-        self._check(load_library().kidmp_batch_step_device(self._h, ncol, nz, float(dt), *args, s))
+        if arith is None:
+            self._check(load_library().kidmp_batch_step_device(self._h, ncol, nz, float(dt), *args, s))
+        else:
+            self._check(load_library().kidmp32_batch_step_device(self._h, ncol, nz, float(dt), *args, self.ARITH[arith], s))
+
+    def batch_step(self, st, dt, ppt, rates=None, nstep=None, stream=None):
+        """st: dict of float64 CUDA tensors [ncol, nz] (STATE_NAMES + p, dz; w optional).
+        ppt: float64 [ncol, 4], accumulated in place.  Asynchronous on `stream`
+        (default: torch's current stream)."""
+        self._step_device("batch_step: ", st, dt, ppt, rates, nstep, stream)
 
     # ---- binary32 state: the reference's native arithmetic ("p32n": REAL = binary32, DOUBLE PRECISION = binary64)
     #      and the all-binary32 build ("f32") -- include/kidmp.h, kidmp32_* ----
@@ -414,49 +405,24 @@ class ThompsonMP:
         """numpy float32 [ncol, nz] arrays, in place.  Returns (ppt float32 [ncol, 4], rates float64 or None, nstep or None),
         with want_dbz a fourth element: the float32 reflectivity of the post-step state (kidmp32_batch_step_host_refl);
         want_radii appends the float32 (re_qc, re_qi, re_qs) of that state (kidmp32_batch_step_host_out)."""
-        ncol, nz = st["qv"].shape
-        fpp = C.POINTER(C.c_float)
-        for k in STATE_NAMES + FORCING_NAMES:
-            a = st[k]
-            if not (a.dtype == np.float32 and a.flags.c_contiguous and a.shape == (ncol, nz)):
-                raise KidmpError("batch_step32_host: %s must be contiguous float32 [ncol, nz]" % k)
-        if ppt is None:
-            ppt = np.zeros((ncol, 4), dtype=np.float32)
-        rates = np.zeros((ncol, NRATES, nz)) if want_rates else None
-        nstep = np.zeros((ncol, 4), dtype=np.int32) if want_nstep else None
-        args = ([self._h, ncol, nz, float(dt)] + [st[k].ctypes.data_as(fpp) for k in STATE_NAMES + FORCING_NAMES]
-                + [ppt.ctypes.data_as(fpp), _np_ptr(rates) if want_rates else None,
-                   nstep.ctypes.data_as(C.POINTER(C.c_int32)) if want_nstep else None, self.ARITH[arith]])
+        (ppt, rates, nstep), args = _host_step("batch_step32_host", st, np.float32, dt, ppt, want_rates, want_nstep)
+        ncol, nz = args[:2]
+        args.append(self.ARITH[arith])
+        L = load_library()
         if want_radii:
             dbz, radii, o = self._host_outputs(ncol, nz, np.float32, want_dbz, True)
-            self._check(load_library().kidmp32_batch_step_host_out(*args, C.byref(o)))
+            self._check(L.kidmp32_batch_step_host_out(self._h, *args, C.byref(o)))
             return (ppt, rates, nstep, dbz, radii) if want_dbz else (ppt, rates, nstep, radii)
         if want_dbz:
             dbz = np.empty((ncol, nz), dtype=np.float32)
-            self._check(load_library().kidmp32_batch_step_host_refl(*args, dbz.ctypes.data_as(fpp)))
+            self._check(L.kidmp32_batch_step_host_refl(self._h, *args, _np_ptr(dbz, _fp)))
             return ppt, rates, nstep, dbz
-        self._check(load_library().kidmp32_batch_step_host(*args))
+        self._check(L.kidmp32_batch_step_host(self._h, *args))
         return ppt, rates, nstep
 
     def batch_step32(self, st, dt, ppt, arith="p32n", rates=None, nstep=None, stream=None):
         """torch float32 CUDA tensors [ncol, nz], in place, asynchronous (the device entry of the binary32 builds)."""
-        import torch
-        q = st["qv"]
-        ncol, nz = q.shape
-        for k in STATE_NAMES + ("p", "dz"):
-            self._want(st[k], torch.float32, (ncol, nz), "batch_step32: " + k)
-        self._want(ppt, torch.float32, (ncol, 4), "batch_step32: ppt")
-        if rates is not None:
-            self._want(rates, torch.float64, (ncol, NRATES, nz), "batch_step32: rates")
-        if nstep is not None:
-            self._want(nstep, torch.int32, (ncol, 4), "batch_step32: nstep")
-        s = stream if stream is not None else torch.cuda.current_stream(q.device).cuda_stream
-        w = st.get("w")
-        args = [st[k].data_ptr() for k in STATE_NAMES] + [st["p"].data_ptr(), w.data_ptr() if w is not None else None,
-                                                          st["dz"].data_ptr(), ppt.data_ptr(),
-                                                          rates.data_ptr() if rates is not None else None,
-                                                          nstep.data_ptr() if nstep is not None else None]
-        self._check(load_library().kidmp32_batch_step_device(self._h, ncol, nz, float(dt), *args, self.ARITH[arith], s))
+        self._step_device("batch_step32: ", st, dt, ppt, rates, nstep, stream, arith)
 
     def default_aerosols(self, qv, t, p, stream=None):
         """nc, nwfa, nifa for the inputs the KiD wrapper leaves unset (W:36; formulas M:958-964)."""
@@ -464,7 +430,7 @@ class ThompsonMP:
         for name, a in (("qv", qv), ("t", t), ("p", p)):
             self._want(a, torch.float64, tuple(qv.shape), "default_aerosols: " + name)
         nc, nwfa, nifa = torch.empty_like(qv), torch.empty_like(qv), torch.empty_like(qv)
-        s = stream if stream is not None else torch.cuda.current_stream(qv.device).cuda_stream
+        s = _stream(stream, qv)
         self._check(load_library().kidmp_default_aerosols_device(
             self._h, qv.numel(), qv.data_ptr(), t.data_ptr(), p.data_ptr(), nc.data_ptr(), nwfa.data_ptr(),
             nifa.data_ptr(), s))
@@ -495,7 +461,7 @@ class ThompsonMP:
         import torch
         self._want(ppt, torch.float64, (ppt.shape[0], 4), "reduce_ppt: ppt")
         out = torch.empty(4, dtype=torch.float64, device=ppt.device)
-        s = stream if stream is not None else torch.cuda.current_stream(ppt.device).cuda_stream
+        s = _stream(stream, ppt)
         self._check(load_library().kidmp_reduce_ppt_device(self._h, ppt.shape[0], ppt.data_ptr(), out.data_ptr(), s))
         return out
 
@@ -506,7 +472,7 @@ class ThompsonMP:
         import torch
         self._want(ppt, torch.float64, (ppt.shape[0], 4), "reduce_ppt_exact: ppt")
         out = torch.empty(PPT_LIMBS, dtype=torch.int64, device=ppt.device)
-        s = stream if stream is not None else torch.cuda.current_stream(ppt.device).cuda_stream
+        s = _stream(stream, ppt)
         self._check(load_library().kidmp_reduce_ppt_exact_device(self._h, ppt.shape[0], ppt.data_ptr(), out.data_ptr(), s))
         return out
 
@@ -517,7 +483,7 @@ class ThompsonMP:
         ncol, nr, nz = rates.shape
         self._want(rates, torch.float64, (ncol, NRATES, nz), "reduce_rates: rates")
         out = torch.empty(NRATES, nz, dtype=torch.float64, device=rates.device)
-        s = stream if stream is not None else torch.cuda.current_stream(rates.device).cuda_stream
+        s = _stream(stream, rates)
         self._check(load_library().kidmp_reduce_rates_device(self._h, ncol, nz, rates.data_ptr(), out.data_ptr(), s))
         return out
 
@@ -537,7 +503,7 @@ class ThompsonMP:
         for k in self.SANITY_NEG:
             self._want(st[k], torch.float64, tuple(q.shape), "sanity: " + k)
         out = torch.empty(15, dtype=torch.float64, device=q.device)
-        s = stream if stream is not None else torch.cuda.current_stream(q.device).cuda_stream
+        s = _stream(stream, q)
         self._check(load_library().kidmp_sanity_device(self._h, q.numel(), *[st[k].data_ptr() for k in self.SANITY_NEG],
                                                        out.data_ptr(), s))
         return out
@@ -548,13 +514,11 @@ class ThompsonMP:
         three preset tensors first, and returns the reflectivity from the same read of the state."""
         import torch
         q = st["qv"]
-        for k in ("t", "p", "qv", "qc", "nc", "qi", "ni", "qs"):
-            self._want(st[k], torch.float64, tuple(q.shape), "effective_radii: " + k)
+        ptrs = _pointers(st, self.RADII_NAMES, (), self._device_check("effective_radii", torch.float64, tuple(q.shape)),
+                         torch.Tensor.data_ptr)
         out = [torch.full_like(q, v) for v in preset]
-        s = stream if stream is not None else torch.cuda.current_stream(q.device).cuda_stream
-        self._check(load_library().kidmp_effective_radii_device(
-            self._h, q.numel(), *[st[k].data_ptr() for k in ("t", "p", "qv", "qc", "nc", "qi", "ni", "qs")],
-            *[o.data_ptr() for o in out], s))
+        s = _stream(stream, q)
+        self._check(load_library().kidmp_effective_radii_device(self._h, q.numel(), *ptrs, *[o.data_ptr() for o in out], s))
         return tuple(out)
 
     RADII_NAMES = ("t", "p", "qv", "qc", "nc", "qi", "ni", "qs")                    # calc_effectRad's IN dummies, M:4842
@@ -569,16 +533,9 @@ class ThompsonMP:
         q = st["t"]
         if q.dtype not in (np.float64, np.float32) or q.ndim != 2:
             raise KidmpError("effective_radii_host: state must be float64 or float32 numpy arrays [ncol, nz]")
-        pt = C.POINTER(C.c_double) if q.dtype == np.float64 else C.POINTER(C.c_float)
-        ptrs = []
-        for k in self.RADII_NAMES:
-            a = st.get(k)
-            if a is None and k in ("nc", "qi", "ni", "qs"):
-                ptrs.append(None)
-                continue
-            if not (a.dtype == q.dtype and a.flags.c_contiguous and a.shape == q.shape):
-                raise KidmpError("effective_radii_host: %s must be contiguous %s [ncol, nz]" % (k, q.dtype))
-            ptrs.append(a.ctypes.data_as(pt))
+        pt = _dp if q.dtype == np.float64 else _fp
+        ptrs = _pointers(st, self.RADII_NAMES, ("nc", "qi", "ni", "qs"), _host_check("effective_radii_host", q.dtype, q.shape),
+                         lambda a: _np_ptr(a, pt))
         out = []
         for v in preset:
             if isinstance(v, np.ndarray):
@@ -588,7 +545,7 @@ class ThompsonMP:
             else:
                 out.append(np.full(q.shape, v, dtype=q.dtype))
         fn = load_library().kidmp_effective_radii_host if q.dtype == np.float64 else load_library().kidmp32_effective_radii_host
-        self._check(fn(self._h, q.size, *ptrs, *[o.ctypes.data_as(pt) for o in out]))
+        self._check(fn(self._h, q.size, *ptrs, *[_np_ptr(o, pt) for o in out]))
         return tuple(out)
 
     def column_outputs(self, st, dbz=True, radii=True, stream=None):
@@ -603,18 +560,12 @@ class ThompsonMP:
         if q.dtype not in (torch.float64, torch.float32) or q.dim() != 2:
             raise KidmpError("column_outputs: state must be float64 or float32 CUDA tensors [ncol, nz]")
         ncol, nz = q.shape
-        ptrs = []
-        for k in self.OUTPUT_NAMES:
-            a = st.get(k)
-            if a is None:
-                ptrs.append(None)                      # the library decides what may be left out
-                continue
-            self._want(a, q.dtype, (ncol, nz), "column_outputs: " + k)
-            ptrs.append(a.data_ptr())
+        ptrs = _pointers(st, self.OUTPUT_NAMES, self.OUTPUT_NAMES, self._device_check("column_outputs", q.dtype, (ncol, nz)),
+                         torch.Tensor.data_ptr)
         o_dbz = torch.empty_like(q) if dbz else None
         o_rad = tuple(torch.empty_like(q) for _ in range(3)) if radii else None
-        o = _Outputs(o_dbz.data_ptr() if dbz else None, *([a.data_ptr() for a in o_rad] if radii else [None] * 3))
-        s = stream if stream is not None else torch.cuda.current_stream(q.device).cuda_stream
+        o = _outputs(o_dbz, o_rad, torch.Tensor.data_ptr)
+        s = _stream(stream, q)
         fn = load_library().kidmp_column_outputs_device if q.dtype == torch.float64 else load_library().kidmp32_column_outputs_device
         self._check(fn(self._h, ncol, nz, *ptrs, C.byref(o), s))
         return o_dbz, o_rad
@@ -630,18 +581,12 @@ class ThompsonMP:
         if q.dtype not in (torch.float64, torch.float32) or q.dim() != 2:
             raise KidmpError("reflectivity: state must be float64 or float32 CUDA tensors [ncol, nz]")
         ncol, nz = q.shape
-        ptrs = []
-        for k in self.REFL_NAMES:
-            a = st.get(k)
-            if a is None and k in ("qs", "qg"):
-                ptrs.append(None)
-                continue
-            self._want(a, q.dtype, (ncol, nz), "reflectivity: " + k)
-            ptrs.append(a.data_ptr())
+        ptrs = _pointers(st, self.REFL_NAMES, ("qs", "qg"), self._device_check("reflectivity", q.dtype, (ncol, nz)),
+                         torch.Tensor.data_ptr)
         if out is None:
             out = torch.empty((ncol, nz), dtype=q.dtype, device=q.device)
         self._want(out, q.dtype, (ncol, nz), "reflectivity: out")
-        s = stream if stream is not None else torch.cuda.current_stream(q.device).cuda_stream
+        s = _stream(stream, q)
         fn = load_library().kidmp_reflectivity_device if q.dtype == torch.float64 else load_library().kidmp32_reflectivity_device
         self._check(fn(self._h, ncol, nz, *ptrs, out.data_ptr(), s))
         return out
@@ -653,19 +598,12 @@ class ThompsonMP:
         if q.dtype not in (np.float64, np.float32) or q.ndim != 2:
             raise KidmpError("reflectivity_host: state must be float64 or float32 numpy arrays [ncol, nz]")
         ncol, nz = q.shape
-        pt = C.POINTER(C.c_double) if q.dtype == np.float64 else C.POINTER(C.c_float)
-        ptrs = []
-        for k in self.REFL_NAMES:
-            a = st.get(k)
-            if a is None and k in ("qs", "qg"):
-                ptrs.append(None)
-                continue
-            if not (a.dtype == q.dtype and a.flags.c_contiguous and a.shape == (ncol, nz)):
-                raise KidmpError("reflectivity_host: %s must be contiguous %s [ncol, nz]" % (k, q.dtype))
-            ptrs.append(a.ctypes.data_as(pt))
+        pt = _dp if q.dtype == np.float64 else _fp
+        ptrs = _pointers(st, self.REFL_NAMES, ("qs", "qg"), _host_check("reflectivity_host", q.dtype, (ncol, nz)),
+                         lambda a: _np_ptr(a, pt))
         out = np.empty((ncol, nz), dtype=q.dtype)
         fn = load_library().kidmp_reflectivity_host if q.dtype == np.float64 else load_library().kidmp32_reflectivity_host
-        self._check(fn(self._h, ncol, nz, *ptrs, out.ctypes.data_as(pt)))
+        self._check(fn(self._h, ncol, nz, *ptrs, _np_ptr(out, pt)))
         return out
 
     # ---- mphys_thompson09_interfacen (W:28-310): KiD's theta-form fields in, tendencies out ----
@@ -721,6 +659,36 @@ class ThompsonMP:
             got.append((k, a))
         return got
 
+    def _kid_interface(self, who, q, is64, check, addr, outputs, state, dt, p0, r_on_cp, exner, dz, adv, div, dbz, radii, arith):
+        """What kid_interface and kid_interface_host share.  They differ in how an array is judged (check(a, what[, shape])),
+        in how its address is taken (addr) and in outputs(keys), which checks or makes what the call writes: the
+        dict that is returned -- a tendency for each of `keys`, ppt, dbz / radii when wanted -- and rates, nstep or None.
+        Returns that dict, the 16 arguments every entry begins with and, for the kidmp32_* entries, [arith]."""
+        ncol, nz = q.shape
+        if is64 and arith is not None:
+            raise KidmpError("%s: arith applies to float32 fields only" % who)
+        if not is64 and (arith or "p32n") not in self.ARITH:
+            raise KidmpError("%s: arith must be 'p32n' or 'f32'" % who)
+        f_state = self._kid_members(who, state, "state", True, check)
+        f_adv = self._kid_members(who, adv, "adv", False, check)
+        f_div = self._kid_members(who, div, "div", False, check)
+        check(exner, who + ": exner")
+        check(dz, who + ": dz", (nz,))
+        keys = [k for k, _ in f_state]
+        res, rates, nstep = outputs(keys)
+
+        def fields(members):
+            d = dict(members)
+            return _KidFields(*[addr(d[k]) if k in d else None for k in KID_FIELDS])
+        c_state, c_adv, c_div = fields(f_state), fields(f_adv), fields(f_div)
+        c_out = fields([(k, res[k]) for k in keys if k in res])
+        o = _outputs(res["dbz"] if dbz else None, res["radii"] if radii else None, addr)
+        args = [self._h, ncol, nz, float(dt), float(p0), float(r_on_cp), C.byref(c_state), C.byref(c_adv) if adv is not None else None,
+                C.byref(c_div) if div is not None else None, addr(exner), addr(dz), C.byref(c_out), addr(res["ppt"]),
+                addr(rates) if rates is not None else None, addr(nstep) if nstep is not None else None,
+                C.byref(o) if (dbz or radii) else None]
+        return res, args, [] if is64 else [self.ARITH[arith or "p32n"]]
+
     def kid_interface(self, state, dt, p0, r_on_cp, exner, dz, adv=None, div=None, work=None, rates=None, nstep=None,
                       dbz=False, radii=False, arith=None, stream=None, out=None, gather_only=False):
         """The KiD adapter on the device (kidmp[32]_kid_interface_device).  state / adv / div: dicts of float64 or float32
@@ -733,81 +701,59 @@ class ThompsonMP:
         gather_only (kidmp[32]_kid_gather_device): only the workspace is filled with the step's inputs and ppt zeroed;
         returns {"ppt", "work"}."""
         import torch
-        who = "kid_interface"
         q = state.get("theta") if isinstance(state, dict) else None
         if q is None or not hasattr(q, "is_cuda") or q.dtype not in (torch.float64, torch.float32) or q.dim() != 2:
             raise KidmpError("kid_interface: state['theta'] must be a float64 or float32 CUDA tensor [ncol, nz]")
         ncol, nz = q.shape
         is64 = q.dtype == torch.float64
-        if is64 and arith is not None:
-            raise KidmpError("kid_interface: arith applies to float32 fields only")
-        if not is64 and (arith or "p32n") not in self.ARITH:
-            raise KidmpError("kid_interface: arith must be 'p32n' or 'f32'")
 
-        def check(a, what):
+        def check(a, what, shape=(ncol, nz)):
             if not hasattr(a, "is_cuda"):
                 raise KidmpError("%s must be a torch tensor" % what)
-            self._want(a, q.dtype, (ncol, nz), what)
-        f_state = self._kid_members(who, state, "state", True, check)
-        f_adv = self._kid_members(who, adv, "adv", False, check)
-        f_div = self._kid_members(who, div, "div", False, check)
-        check(exner, "kid_interface: exner")
-        if not hasattr(dz, "is_cuda"):
-            raise KidmpError("kid_interface: dz must be a torch tensor")
-        self._want(dz, q.dtype, (nz,), "kid_interface: dz")
-        if rates is not None:
-            self._want(rates, torch.float64, (ncol, NRATES, nz), "kid_interface: rates")
-        if nstep is not None:
-            self._want(nstep, torch.int32, (ncol, 4), "kid_interface: nstep")
-        need = 15 * ((ncol * nz * q.element_size() + 255) // 256 * 256)
-        if work is not None:
-            if not (hasattr(work, "is_cuda") and work.is_cuda and work.dtype == torch.uint8 and work.dim() == 1 and work.is_contiguous()
-                    and work.device.index == self.device and work.numel() >= need and work.data_ptr() % 16 == 0):
-                raise KidmpError("kid_interface: work must be a contiguous uint8 CUDA tensor of at least %d bytes on cuda:%d "
-                                 "(kid_workspace)" % (need, self.device))
-        keys = [k for k, _ in f_state]
-        if out is not None:
-            if not isinstance(out, dict) or out.get("ppt") is None or (dbz and out.get("dbz") is None) or (radii and out.get("radii") is None):
-                raise KidmpError("kid_interface: out must be a dict holding ppt (and dbz / radii when they are wanted)")
-            self._kid_members(who, {k: out.get(k) for k in KID_FIELDS}, "out", True, check)
-            self._want(out["ppt"], q.dtype, (ncol, 4), "kid_interface: out['ppt']")
-            res = out
-        else:
-            res = {k: torch.empty_like(q) for k in ([] if gather_only else keys)}
-            res["ppt"] = torch.empty((ncol, 4), dtype=q.dtype, device=q.device)
-            if dbz:
-                res["dbz"] = torch.empty_like(q)
-            if radii:
-                res["radii"] = tuple(torch.empty_like(q) for _ in range(3))
-        if dbz:
-            check(res["dbz"], "kid_interface: out['dbz']")
-        if radii:
-            for a in res["radii"]:
-                check(a, "kid_interface: out['radii']")
-        if work is None:
-            work = self.kid_workspace(ncol, nz, q.dtype)
-        res["work"] = work
+            self._want(a, q.dtype, shape, what)
 
-        def fields(members):
-            d = dict(members)
-            return _KidFields(*[d[k].data_ptr() if k in d else None for k in KID_FIELDS])
-        c_state, c_adv, c_div = fields(f_state), fields(f_adv), fields(f_div)
-        c_out = fields([(k, res[k]) for k in keys if k in res])
-        o = _Outputs(res["dbz"].data_ptr() if dbz else None, *([a.data_ptr() for a in res["radii"]] if radii else [None] * 3))
-        s = stream if stream is not None else torch.cuda.current_stream(q.device).cuda_stream
+        def outputs(keys):
+            if rates is not None:
+                self._want(rates, torch.float64, (ncol, NRATES, nz), "kid_interface: rates")
+            if nstep is not None:
+                self._want(nstep, torch.int32, (ncol, 4), "kid_interface: nstep")
+            need = 15 * ((ncol * nz * q.element_size() + 255) // 256 * 256)
+            if work is not None:
+                if not (hasattr(work, "is_cuda") and work.is_cuda and work.dtype == torch.uint8 and work.dim() == 1 and work.is_contiguous()
+                        and work.device.index == self.device and work.numel() >= need and work.data_ptr() % 16 == 0):
+                    raise KidmpError("kid_interface: work must be a contiguous uint8 CUDA tensor of at least %d bytes on cuda:%d "
+                                     "(kid_workspace)" % (need, self.device))
+            if out is not None:
+                if not isinstance(out, dict) or out.get("ppt") is None or (dbz and out.get("dbz") is None) or (radii and out.get("radii") is None):
+                    raise KidmpError("kid_interface: out must be a dict holding ppt (and dbz / radii when they are wanted)")
+                self._kid_members("kid_interface", {k: out.get(k) for k in KID_FIELDS}, "out", True, check)
+                self._want(out["ppt"], q.dtype, (ncol, 4), "kid_interface: out['ppt']")
+                res = out
+            else:
+                res = {k: torch.empty_like(q) for k in ([] if gather_only else keys)}
+                res["ppt"] = torch.empty((ncol, 4), dtype=q.dtype, device=q.device)
+                if dbz:
+                    res["dbz"] = torch.empty_like(q)
+                if radii:
+                    res["radii"] = tuple(torch.empty_like(q) for _ in range(3))
+            if dbz:
+                check(res["dbz"], "kid_interface: out['dbz']")
+            if radii:
+                for a in res["radii"]:
+                    check(a, "kid_interface: out['radii']")
+            res["work"] = work if work is not None else self.kid_workspace(ncol, nz, q.dtype)
+            return res, rates, nstep
+        res, args, code = self._kid_interface("kid_interface", q, is64, check, torch.Tensor.data_ptr, outputs, state, dt, p0,
+                                              r_on_cp, exner, dz, adv, div, dbz, radii, arith)
+        work = res["work"]
+        s = _stream(stream, q)
         L = load_library()
-        args = [self._h, ncol, nz, float(dt), float(p0), float(r_on_cp), C.byref(c_state), C.byref(c_adv) if adv is not None else None,
-                C.byref(c_div) if div is not None else None, exner.data_ptr(), dz.data_ptr(), C.byref(c_out), res["ppt"].data_ptr(),
-                rates.data_ptr() if rates is not None else None, nstep.data_ptr() if nstep is not None else None,
-                C.byref(o) if (dbz or radii) else None]
         if gather_only:
             fn = L.kidmp_kid_gather_device if is64 else L.kidmp32_kid_gather_device
             self._check(fn(*args[:11], res["ppt"].data_ptr(), work.data_ptr(), work.numel(), s))
             return {"ppt": res["ppt"], "work": work}
-        if is64:
-            self._check(L.kidmp_kid_interface_device(*args, work.data_ptr(), work.numel(), s))
-        else:
-            self._check(L.kidmp32_kid_interface_device(*args, self.ARITH[arith or "p32n"], work.data_ptr(), work.numel(), s))
+        fn = L.kidmp_kid_interface_device if is64 else L.kidmp32_kid_interface_device
+        self._check(fn(*args, *code, work.data_ptr(), work.numel(), s))
         return res
 
     def kid_interface_host(self, state, dt, p0, r_on_cp, exner, dz, adv=None, div=None, want_rates=False, want_nstep=False,
@@ -815,52 +761,33 @@ class ThompsonMP:
         """The KiD adapter on numpy arrays (kidmp[32]_kid_interface_host): arguments as kid_interface, float64 or float32
         arrays [ncol, nz] (page-locked ones, host_empty, move by DMA).  Returns the dict of tendencies and "ppt", with
         "rates" / "nstep" / "dbz" / "radii" when asked for.  Bit for bit the device entry, for any chunking."""
-        who = "kid_interface_host"
         q = state.get("theta") if isinstance(state, dict) else None
         if not isinstance(q, np.ndarray) or q.dtype not in (np.float64, np.float32) or q.ndim != 2:
             raise KidmpError("kid_interface_host: state['theta'] must be a float64 or float32 numpy array [ncol, nz]")
         ncol, nz = q.shape
         is64 = q.dtype == np.float64
-        if is64 and arith is not None:
-            raise KidmpError("kid_interface_host: arith applies to float32 fields only")
-        if not is64 and (arith or "p32n") not in self.ARITH:
-            raise KidmpError("kid_interface_host: arith must be 'p32n' or 'f32'")
 
         def check(a, what, shape=(ncol, nz)):
             if not (isinstance(a, np.ndarray) and a.dtype == q.dtype and a.flags.c_contiguous and a.shape == shape):
                 raise KidmpError("%s must be a contiguous %s numpy array %s" % (what, q.dtype, list(shape)))
-        f_state = self._kid_members(who, state, "state", True, check)
-        f_adv = self._kid_members(who, adv, "adv", False, check)
-        f_div = self._kid_members(who, div, "div", False, check)
-        check(exner, "kid_interface_host: exner")
-        check(dz, "kid_interface_host: dz", (nz,))
-        keys = [k for k, _ in f_state]
-        res = {k: np.empty_like(q) for k in keys}
-        res["ppt"] = np.empty((ncol, 4), dtype=q.dtype)
-        if want_rates:
-            res["rates"] = np.zeros((ncol, NRATES, nz))
-        if want_nstep:
-            res["nstep"] = np.zeros((ncol, 4), dtype=np.int32)
-        if dbz:
-            res["dbz"] = np.empty_like(q)
-        if radii:
-            res["radii"] = tuple(np.empty_like(q) for _ in range(3))
 
-        def fields(members):
-            d = dict(members)
-            return _KidFields(*[d[k].ctypes.data if k in d else None for k in KID_FIELDS])
-        c_state, c_adv, c_div = fields(f_state), fields(f_adv), fields(f_div)
-        c_out = fields([(k, res[k]) for k in keys])
-        o = _Outputs(res["dbz"].ctypes.data if dbz else None, *([a.ctypes.data for a in res["radii"]] if radii else [None] * 3))
+        def outputs(keys):
+            res = {k: np.empty_like(q) for k in keys}
+            res["ppt"] = np.empty((ncol, 4), dtype=q.dtype)
+            if want_rates:
+                res["rates"] = np.zeros((ncol, NRATES, nz))
+            if want_nstep:
+                res["nstep"] = np.zeros((ncol, 4), dtype=np.int32)
+            if dbz:
+                res["dbz"] = np.empty_like(q)
+            if radii:
+                res["radii"] = tuple(np.empty_like(q) for _ in range(3))
+            return res, res.get("rates"), res.get("nstep")
+        res, args, code = self._kid_interface("kid_interface_host", q, is64, check, lambda a: a.ctypes.data, outputs, state, dt, p0,
+                                              r_on_cp, exner, dz, adv, div, dbz, radii, arith)
         L = load_library()
-        args = [self._h, ncol, nz, float(dt), float(p0), float(r_on_cp), C.byref(c_state), C.byref(c_adv) if adv is not None else None,
-                C.byref(c_div) if div is not None else None, exner.ctypes.data, dz.ctypes.data, C.byref(c_out), res["ppt"].ctypes.data,
-                res["rates"].ctypes.data if want_rates else None, res["nstep"].ctypes.data if want_nstep else None,
-                C.byref(o) if (dbz or radii) else None]
-        if is64:
-            self._check(L.kidmp_kid_interface_host(*args))
-        else:
-            self._check(L.kidmp32_kid_interface_host(*args, self.ARITH[arith or "p32n"]))
+        fn = L.kidmp_kid_interface_host if is64 else L.kidmp32_kid_interface_host
+        self._check(fn(*args, *code))
         return res
 
     def kernel_fingerprint(self, arith="p64"):
@@ -969,30 +896,14 @@ class ThompsonMulti:
         """numpy float64 [ncol, nz] arrays, in place (optional keys as ThompsonMP.batch_step_host).
         Returns (ppt, rates or None, nstep or None, precip_sums[4]) -- with want_sanity a fifth element, the 15-number
         sanity scan of the end state (kidmp_batch_step_host_multi_diag), reduced over the devices like the sums."""
-        ncol, nz = st["qv"].shape
-        ptrs = []
-        for k in STATE_NAMES + FORCING_NAMES:
-            a = st.get(k)
-            if a is None:
-                ptrs.append(None)
-                continue
-            if not (a.dtype == np.float64 and a.flags.c_contiguous and a.shape == (ncol, nz)):
-                raise KidmpError("batch_step_host: %s must be contiguous float64 [ncol, nz]" % k)
-            ptrs.append(_np_ptr(a))
-        if ppt is None:
-            ppt = np.zeros((ncol, 4))
-        rates = np.zeros((ncol, NRATES, nz)) if want_rates else None
-        nstep = np.zeros((ncol, 4), dtype=np.int32) if want_nstep else None
+        (ppt, rates, nstep), args = _host_step("batch_step_host", st, np.float64, dt, ppt, want_rates, want_nstep)
         sums = np.zeros(4)
         L = load_library()
-        a_rates = _np_ptr(rates) if want_rates else None
-        a_nstep = nstep.ctypes.data_as(C.POINTER(C.c_int32)) if want_nstep else None
         if want_sanity:
             sanity = np.zeros(15)
-            rc = L.kidmp_batch_step_host_multi_diag(self._h, ncol, nz, float(dt), *ptrs, _np_ptr(ppt), a_rates, a_nstep,
-                                                    _np_ptr(sums), _np_ptr(sanity))
+            rc = L.kidmp_batch_step_host_multi_diag(self._h, *args, _np_ptr(sums), _np_ptr(sanity))
         else:
-            rc = L.kidmp_batch_step_host_multi(self._h, ncol, nz, float(dt), *ptrs, _np_ptr(ppt), a_rates, a_nstep, _np_ptr(sums))
+            rc = L.kidmp_batch_step_host_multi(self._h, *args, _np_ptr(sums))
         if rc != 0:
             raise KidmpError("kidmp_batch_step_host_multi failed (%d): %s" % (rc, L.kidmp_multi_last_error(self._h).decode()))
         return (ppt, rates, nstep, sums, sanity) if want_sanity else (ppt, rates, nstep, sums)

@@ -115,8 +115,8 @@ def _adapter(build, nx, case, refl, arith, aero, cwd):
     return log, state_text, post
 
 
-# (build, arithmetic, case, is_aerosol_aware): both default REAL kinds (build: kidmp_batch_step_host_refl; build32 with
-# 'p32n': kidmp32_batch_step_host_refl), the warm and the mixed-phase call forms of the adapter, and its aerosol-aware form
+# (build, arithmetic, case, is_aerosol_aware): both default REAL kinds (build: kidmp_batch_step_host_out; build32 with
+# 'p32n': kidmp32_batch_step_host_out), the warm and the mixed-phase call forms of the adapter, and its aerosol-aware form
 ADAPTER_RUNS = [("build", "p64", "warm", 0), ("build", "p64", "mixed", 0), ("build", "p64", "warm", 1),
                 ("build32", "p32n", "warm", 0), ("build32", "p32n", "mixed", 0)]
 
