@@ -6,3 +6,4 @@ as hand-written HIP kernels for gfx950 behind a C ABI (include/kidmp.h).
 from .thompson import (KidmpError, ThompsonMP, ThompsonMulti, mp_thompson, thompson_init, STATE_NAMES,  # noqa: F401
                        FORCING_NAMES, RATE_NAMES, KID_FIELDS, KID_WORK_NAMES, lib_path, load_library, cache_read_file, cache_write_file,
                        limbs_to_sums, shard_bounds)
+from .stats import LevelStats, level_stats, stats_chunks, stats_workspace_bytes  # noqa: F401

@@ -570,6 +570,12 @@ class ThompsonMP:
         self._check(fn(self._h, ncol, nz, *ptrs, C.byref(o), s))
         return o_dbz, o_rad
 
+    def level_stats(self, fields, group=None, ngroup=1, edges=None, floor=None, work=None, stream=None):
+        """Moments and histograms of [ncol, nz] CUDA tensors over the columns, per level and per ensemble group
+        (include/kidmp_stats.h): kid_amd.stats.level_stats on this context."""
+        from .stats import level_stats
+        return level_stats(self, fields, group, ngroup, edges, floor, work, stream)
+
     REFL_NAMES = ("t", "p", "qv", "qr", "nr", "qs", "qg")      # the inputs of calc_refl10cm that are read (qc1d is not)
 
     def reflectivity(self, st, out=None, stream=None):
