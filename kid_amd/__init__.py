@@ -7,3 +7,4 @@ from .thompson import (KidmpError, ThompsonMP, ThompsonMulti, mp_thompson, thomp
                        FORCING_NAMES, RATE_NAMES, KID_FIELDS, KID_WORK_NAMES, lib_path, load_library, cache_read_file, cache_write_file,
                        limbs_to_sums, shard_bounds)
 from .stats import LevelStats, level_stats, stats_chunks, stats_workspace_bytes  # noqa: F401
+from .summary import SUMMARY_INPUTS, SUMMARY_NAMES, column_summary, column_summary_host  # noqa: F401

@@ -1,5 +1,5 @@
 // kidmp_ctx.h -- internal to the units behind include/kidmp.h (not installed): the context, the error and device-guard
-// helpers of every entry point, and what the units kidmp_{capi,diag,host,tables,multi,adapter}.hip offer one another.
+// helpers of every entry point, and what the units kidmp_{capi,diag,host,tables,multi,adapter,stats,summary}.hip offer one another.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -184,6 +184,9 @@ hipError_t launch_radii_keep(kidmp_ctx *ctx, int64_t n, const T *t, const T *p, 
                              const T *qi, const T *ni, const T *qs, T *re_qc, T *re_qi, T *re_qs, hipStream_t s,
                              int64_t nz_col = 0, int64_t e0 = 0);   // nc_levels_of; e0: the first element's index in the binding
 
+// kidmp_host.hip: the columns per chunk of a host-array entry, and the context's staging memory (it only grows)
+int64_t pick_host_chunk(const kidmp_ctx *ctx, int64_t ncol);
+int ensure_stage(kidmp_ctx *ctx, size_t need);
 // kidmp_host.hip.  What an entry may ask of the pipeline beyond the step: the exact precipitation sums and the sanity
 // scan (left in ctx->d_acc / d_sanity), and the column outputs (host arrays) of every chunk's post-step state.
 template <class T> struct PipelineExtras { bool exact_sums = false, scan_sanity = false; ColumnOutputs<T> out{}; };

@@ -3,7 +3,6 @@
 
 using namespace kidmp;
 
-namespace {
 // ---- the host-array entries (kidmp_batch_step_host*, kidmp32_batch_step_host): a three-stage pipeline over column chunks ----
 // The batch is cut into chunks of CH columns; chunk i is uploaded on the context's H2D stream, stepped on its compute
 // stream and downloaded on its D2H stream, through a ring of HOST_NBUF staging sets in HBM, so the two DMA directions
@@ -12,7 +11,7 @@ namespace {
 // engines asynchronously; pageable arrays still work, but the runtime stages them through its own bounce buffer and
 // the calling thread waits for each copy.  Per column-step the boundary moves 14 (15 with w) profiles in and 12 out
 // (+36 for the rate diagnostics): about 25 KB in binary64.
-int64_t pick_host_chunk(const kidmp_ctx *ctx, int64_t ncol)
+int64_t kidmp::pick_host_chunk(const kidmp_ctx *ctx, int64_t ncol)
 {
     if (ctx->host_chunk > 0) return ctx->host_chunk < ncol ? ctx->host_chunk : ncol;
     if (ncol <= 2048) return ncol;                            // one chunk: nothing to overlap with
@@ -22,7 +21,7 @@ int64_t pick_host_chunk(const kidmp_ctx *ctx, int64_t ncol)
 }
 
 // the context's staging memory only grows
-int ensure_stage(kidmp_ctx *ctx, size_t need)
+int kidmp::ensure_stage(kidmp_ctx *ctx, size_t need)
 {
     if (need <= ctx->stage_bytes) return KIDMP_OK;
     if (ctx->d_stage) (void)hipFree(ctx->d_stage);
@@ -33,6 +32,7 @@ int ensure_stage(kidmp_ctx *ctx, size_t need)
     return KIDMP_OK;
 }
 
+namespace {
 // Leaving host_pipeline with an error must not leave DMA in flight towards the caller's arrays.
 struct PipelineDrain {
     kidmp_ctx *c;

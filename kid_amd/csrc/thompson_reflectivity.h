@@ -33,4 +33,18 @@ hipError_t launch_column_outputs(const ReflConsts &c, const RadConsts &rc, int64
                                  const ColumnOutputs<T> &out, hipStream_t stream, const double *set_nc_col = nullptr);
 // set_nc_col: null, or [ncol] set_Nc in cm**-3 (kidmp_set_column_nc): the column's own Nt_c = set_nc_col[col]*1.e6 for re_qc
 
+// The per-column summary (include/kidmp_summary.h): SUMMARY_N doubles per column from one read of its profiles.  Null
+// means: nc -- the context is not aerosol-aware; qi, qs and qg -- zero (iiwarm); set_nc_col -- the context's Nt_c.
+// dz: element (col, k) = dz[col*dz_col_stride + k], dz_col_stride 0 = one profile for all columns.
+constexpr int SUMMARY_N = 16;
+template <class T> struct SummaryArgs {
+    const T *t, *p, *qv, *qc, *nc, *qi, *qr, *nr, *qs, *qg, *dz;
+    int64_t dz_col_stride;
+    double dbz_echo, q_cloud, t_freeze;
+    const double *set_nc_col;
+};
+template <class T>
+hipError_t launch_column_summary(const ReflConsts &c, const RadConsts &rc, int64_t ncol, int nz, const SummaryArgs<T> &a,
+                                 double *summary, hipStream_t stream);
+
 }  // namespace kidmp

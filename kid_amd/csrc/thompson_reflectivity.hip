@@ -106,26 +106,15 @@ __device__ inline void radii_of_level(const ReflConsts &c, const RadiiArgs<T> &r
     }
 }
 
-// One wavefront per column: the body of k_reflectivity and, with RAD = RadiiArgs<T>, of k_column_outputs.
-template <class T, int NJ, class RAD>
-__device__ __forceinline__ void column_diagnostics(const ReflConsts &c, const RAD &rad, int64_t ncol, int nz,
-                                                   const T *__restrict__ t1d, const T *__restrict__ p1d,
-                                                   const T *__restrict__ qv1d, const T *__restrict__ qr1d,
-                                                   const T *__restrict__ nr1d, const T *__restrict__ qs1d,
-                                                   const T *__restrict__ qg1d, T *__restrict__ dbz)
+// calc_refl10cm of the lane's levels k = 64 j + lane of the column at `base`, left in dbz[j] (untouched where k >= nz).
+// at_level(j, i, temp, pres, qv_in, qv, rho, qs, L_qs, sl) is called once for every level of the lane, between its load
+// and the graupel scan: what a kernel forms beside the reflectivity from the same read.  Whole wavefronts only.
+template <class T, int NJ, class F>
+__device__ __forceinline__ void column_dbz(const ReflConsts &c, int nz, int lane, int64_t base, const T *__restrict__ t1d,
+                                           const T *__restrict__ p1d, const T *__restrict__ qv1d, const T *__restrict__ qr1d,
+                                           const T *__restrict__ nr1d, const T *__restrict__ qs1d, const T *__restrict__ qg1d,
+                                           double (&dbz)[NJ], F &&at_level)
 {
-    constexpr bool RADII = !std::is_same<RAD, NoRadii>::value;
-#if KFM_TABLES
-    fm::tab::load_tables(int(threadIdx.x), REFL_THREADS);            // log10 / 10**x / x**y read their tables from LDS
-    __syncthreads();
-#endif
-    const int lane = int(threadIdx.x) & 63;
-    const int64_t col = int64_t(blockIdx.x) * REFL_WAVES + (int(threadIdx.x) >> 6);
-    if (col >= ncol) return;                                         // whole wavefronts only: the scan needs every lane
-    const int64_t base = col * int64_t(nz);
-    double Nt_c = 0.;                                                // the column's droplet number (radii only)
-    if constexpr (RADII) Nt_c = rad.set_nc_col ? rad.set_nc_col[col] * 1.e6 : rad.c.Nt_c;
-
     double ze_rs[NJ], n0[NJ], rg[NJ];
     bool lqg[NJ];
 #pragma unroll
@@ -156,7 +145,7 @@ __device__ __forceinline__ void column_diagnostics(const ReflConsts &c, const RA
             sl = lvl::snow_level(temp, qs * rho, c.oams);
             ze_snow = lvl::snow_ze(c, sl);                           // M:5131-5132
         }
-        if constexpr (RADII) radii_of_level<T>(c, rad, Nt_c, i, temp, pres, qv_in, qv, rho, qs, L_qs, sl);
+        at_level(j, i, temp, pres, qv_in, qv, rho, qs, L_qs, sl);
         if (lqg[j]) rg[j] = qg * rho;
         ze_rs[j] = ze_rain + ze_snow;
         // ---- graupel intercept before the running minimum, M:5088-5096 ----
@@ -175,12 +164,105 @@ __device__ __forceinline__ void column_diagnostics(const ReflConsts &c, const RA
 
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-        const int k = 64 * j + lane;
-        if (k >= nz) continue;
+        if (64 * j + lane >= nz) continue;
         double ze_graupel = 1.E-22;
         if (lqg[j]) ze_graupel = lvl::graupel_ze(c, n0[j], rg[j]);    // M:5099-5102, M:5133-5135
-        dbz[base + k] = T(lvl::dbz_of(ze_rs[j] + ze_graupel));        // M:5196
+        dbz[j] = lvl::dbz_of(ze_rs[j] + ze_graupel);                  // M:5196
     }
+}
+
+// One wavefront per column: the body of k_reflectivity and, with RAD = RadiiArgs<T>, of k_column_outputs.
+template <class T, int NJ, class RAD>
+__device__ __forceinline__ void column_diagnostics(const ReflConsts &c, const RAD &rad, int64_t ncol, int nz,
+                                                   const T *__restrict__ t1d, const T *__restrict__ p1d,
+                                                   const T *__restrict__ qv1d, const T *__restrict__ qr1d,
+                                                   const T *__restrict__ nr1d, const T *__restrict__ qs1d,
+                                                   const T *__restrict__ qg1d, T *__restrict__ dbz)
+{
+    constexpr bool RADII = !std::is_same<RAD, NoRadii>::value;
+#if KFM_TABLES
+    fm::tab::load_tables(int(threadIdx.x), REFL_THREADS);            // log10 / 10**x / x**y read their tables from LDS
+    __syncthreads();
+#endif
+    const int lane = int(threadIdx.x) & 63;
+    const int64_t col = int64_t(blockIdx.x) * REFL_WAVES + (int(threadIdx.x) >> 6);
+    if (col >= ncol) return;                                         // whole wavefronts only: the scan needs every lane
+    const int64_t base = col * int64_t(nz);
+    double Nt_c = 0.;                                                // the column's droplet number (radii only)
+    if constexpr (RADII) Nt_c = rad.set_nc_col ? rad.set_nc_col[col] * 1.e6 : rad.c.Nt_c;
+
+    double d[NJ];
+    column_dbz<T, NJ>(c, nz, lane, base, t1d, p1d, qv1d, qr1d, nr1d, qs1d, qg1d, d,
+                      [&](int, int64_t i, double temp, double pres, double qv_in, double qv, double rho, double qs, bool L_qs,
+                          const lvl::SnowLevel &sl) __attribute__((always_inline)) {
+                          if constexpr (RADII) radii_of_level<T>(c, rad, Nt_c, i, temp, pres, qv_in, qv, rho, qs, L_qs, sl);
+                      });
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        if (k < nz) dbz[base + k] = T(d[j]);
+    }
+}
+
+// ---- the per-column summary (include/kidmp_summary.h) ----
+// butterfly over the wave: every lane ends with the same bits (a + b == b + a), in an order that depends on nothing
+__device__ inline double wave_sum(double v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+__device__ inline double wave_max(double v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v = fmax(v, __shfl_xor(v, m, 64));
+    return v;
+}
+// the lowest / highest level whose predicate holds, -1 if none: one ballot per level group, the level is a bit position
+template <int NJ>
+__device__ inline int lowest_level(const bool (&pred)[NJ])
+{
+    int k = -1;
+#pragma unroll
+    for (int j = NJ - 1; j >= 0; --j) {
+        const unsigned long long b = __ballot(pred[j]);
+        if (b) k = 64 * j + __builtin_ctzll(b);
+    }
+    return k;
+}
+template <int NJ>
+__device__ inline int highest_level(const bool (&pred)[NJ], int &count)
+{
+    int k = -1;
+    count = 0;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const unsigned long long b = __ballot(pred[j]);
+        if (b) k = 64 * j + 63 - __builtin_clzll(b);
+        count += __builtin_popcountll(b);
+    }
+    return k;
+}
+// sum of dz over the column's levels below `ktop` (ktop <= 0: +0.0), in the fixed order of wave_sum
+template <int NJ>
+__device__ inline double height_below(const double (&dz)[NJ], int lane, int ktop)
+{
+    double s = 0.;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) s += 64 * j + lane < ktop ? dz[j] : 0.;
+    return wave_sum(s);
+}
+// v of level k (wave-uniform, 0 <= k < nz)
+template <int NJ>
+__device__ inline double level_of(const double (&v)[NJ], int k)
+{
+    double x = readlane(v[0], k & 63);                               // a lane read per group: the array stays in registers
+#pragma unroll
+    for (int j = 1; j < NJ; ++j) {
+        const double y = readlane(v[j], k & 63);
+        x = (k >> 6) == j ? y : x;
+    }
+    return x;
 }
 
 }  // namespace
@@ -203,6 +285,80 @@ k_column_outputs(ReflConsts c, RadiiArgs<T> rad, int64_t ncol, int nz, const T *
                  const T *__restrict__ nr1d, const T *__restrict__ qs1d, const T *__restrict__ qg1d, T *__restrict__ dbz)
 {
     column_diagnostics<T, NJ, RadiiArgs<T>>(c, rad, ncol, nz, t1d, p1d, qv1d, qr1d, nr1d, qs1d, qg1d, dbz);
+}
+
+// One wavefront per column: the 15 numbers of include/kidmp_summary.h from one read of the column, no profile written.
+// dBZ and re_qc of every level are those of k_reflectivity and k_effective_radii (the same functions on the same
+// operands) and stay in registers.  Every sum is a per-lane sum over the level groups in ascending order followed by
+// wave_sum: an order fixed by nz alone.  Levels are chosen with ballots, heights are masked sums of dz.  Lanes 0-15
+// store the column's 16 doubles as one 128-byte line.
+template <class T, int NJ>
+__global__ void __launch_bounds__(REFL_THREADS)
+k_column_summary(ReflConsts c, RadConsts rc, SummaryArgs<T> a, int64_t ncol, int nz, double *__restrict__ summary)
+{
+#if KFM_TABLES
+    fm::tab::load_tables(int(threadIdx.x), REFL_THREADS);
+    __syncthreads();
+#endif
+    const int lane = int(threadIdx.x) & 63;
+    const int64_t col = int64_t(blockIdx.x) * REFL_WAVES + (int(threadIdx.x) >> 6);
+    if (col >= ncol) return;                                         // whole wavefronts only
+    const int64_t base = col * int64_t(nz);
+    const double Nt_c = a.set_nc_col ? a.set_nc_col[col] * 1.e6 : rc.Nt_c;
+    const T *__restrict__ dzc = a.dz + col * a.dz_col_stride;
+
+    double dbz[NJ], dz[NJ], sum[7] = {0., 0., 0., 0., 0., 0., 0.};   // WVP, CWP, RWP, IWP, SWP, GWP, TAU_C of the lane
+    bool cloudy[NJ], frozen[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) { dbz[j] = -double(__builtin_inf()); dz[j] = 0.; cloudy[j] = frozen[j] = false; }
+    column_dbz<T, NJ>(c, nz, lane, base, a.t, a.p, a.qv, a.qr, a.nr, a.qs, a.qg, dbz,
+                      [&](int j, int64_t i, double temp, double pres, double qv_in, double qv, double rho, double qs, bool,
+                          const lvl::SnowLevel &) __attribute__((always_inline)) {
+                          const double qc = double(a.qc[i]), qi = a.qi ? double(a.qi[i]) : 0.;
+                          const double h = double(dzc[i - base]);
+                          dz[j] = h;
+                          const double cw = rho * qc * h;
+                          sum[0] += rho * qv * h;
+                          sum[1] += cw;
+                          sum[2] += rho * double(a.qr[i]) * h;
+                          sum[3] += rho * qi * h;
+                          sum[4] += rho * qs * h;
+                          sum[5] += rho * (a.qg ? double(a.qg[i]) : 0.) * h;
+                          double re;                                 // calc_effectRad's own density: qv unclamped, M:4860
+                          const double rho_r = qv_in == qv ? rho : lvl::air_density(pres, temp, qv_in);
+                          if (lvl::cloud_water_radius(rc, Nt_c, rho_r, qc, a.nc ? double(a.nc[i]) : 0., re))
+                              sum[6] += 1.5 * cw / (1000.0 * re);
+                          cloudy[j] = qc + qi > a.q_cloud;
+                          frozen[j] = temp < a.t_freeze;
+                      });
+#pragma unroll
+    for (int s = 0; s < 7; ++s) sum[s] = wave_sum(sum[s]);
+
+    const double nan = __builtin_nan("");
+    double lmax = dbz[0];
+#pragma unroll
+    for (int j = 1; j < NJ; ++j) lmax = fmax(lmax, dbz[j]);
+    const double dbz_max = wave_max(lmax);
+    bool at_max[NJ], echo[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) { at_max[j] = dbz[j] == dbz_max; echo[j] = dbz[j] >= a.dbz_echo; }   // false past nz: -inf
+    int n_cloud, n_echo;
+    const int k_max = lowest_level<NJ>(at_max), k_echo = highest_level<NJ>(echo, n_echo);
+    const int k_base = lowest_level<NJ>(cloudy), k_top = highest_level<NJ>(cloudy, n_cloud), k_frz = lowest_level<NJ>(frozen);
+    // k_max < 0 only for NaN input: the slot is then NaN, and no index is formed from it
+    const double z_max = k_max < 0 ? nan : height_below<NJ>(dz, lane, k_max) + 0.5 * level_of<NJ>(dz, k_max);
+    const double z_echo = k_echo < 0 ? nan : height_below<NJ>(dz, lane, k_echo + 1);
+    const double z_base = k_base < 0 ? nan : height_below<NJ>(dz, lane, k_base);
+    const double z_top = k_top < 0 ? nan : height_below<NJ>(dz, lane, k_top + 1);
+    const double z_frz = k_frz < 0 ? nan : height_below<NJ>(dz, lane, k_frz) + 0.5 * level_of<NJ>(dz, k_frz);
+    const double dbz_sfc = readlane(dbz[0], 0);
+
+    const double slot[SUMMARY_N] = {sum[0], sum[1], sum[2], sum[3], sum[4], sum[5], sum[6], dbz_max, z_max, z_echo, dbz_sfc,
+                                    z_base, z_top, double(n_cloud), z_frz, 0.};
+    double out = slot[0];
+#pragma unroll
+    for (int s = 1; s < SUMMARY_N; ++s) out = lane == s ? slot[s] : out;
+    if (lane < SUMMARY_N) summary[col * SUMMARY_N + lane] = out;
 }
 
 namespace {
@@ -237,6 +393,26 @@ hipError_t launch_any(const ReflConsts &c, const RadiiArgs<T> *rad, int64_t ncol
 }
 
 }  // namespace
+
+template <class T>
+hipError_t launch_column_summary(const ReflConsts &c, const RadConsts &rc, int64_t ncol, int nz, const SummaryArgs<T> &a,
+                                 double *summary, hipStream_t s)
+{
+    if (ncol <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((ncol + REFL_WAVES - 1) / REFL_WAVES)), block(REFL_THREADS);
+    switch ((nz + 63) / 64) {
+    case 1: hipLaunchKernelGGL((k_column_summary<T, 1>), grid, block, 0, s, c, rc, a, ncol, nz, summary); break;
+    case 2: hipLaunchKernelGGL((k_column_summary<T, 2>), grid, block, 0, s, c, rc, a, ncol, nz, summary); break;
+    case 3: hipLaunchKernelGGL((k_column_summary<T, 3>), grid, block, 0, s, c, rc, a, ncol, nz, summary); break;
+    case 4: hipLaunchKernelGGL((k_column_summary<T, 4>), grid, block, 0, s, c, rc, a, ncol, nz, summary); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+template hipError_t launch_column_summary<double>(const ReflConsts &, const RadConsts &, int64_t, int, const SummaryArgs<double> &,
+                                                  double *, hipStream_t);
+template hipError_t launch_column_summary<float>(const ReflConsts &, const RadConsts &, int64_t, int, const SummaryArgs<float> &,
+                                                 double *, hipStream_t);
 
 bool refl_consts_supported(const Consts &hc)
 {

@@ -59,6 +59,7 @@ module module_mp_thompson09n
   public :: calc_refl10cm, calc_refl10cm_batch
   public :: calc_effectRad, calc_effectRad_batch
   public :: mp_thompson_set_column_nc
+  public :: column_summary_batch
   public :: mp_thompson_kid_interface, mp_thompson_kid_staging
   logical, public :: is_aerosol_aware = .false.          ! M:28 (read at thompson_init)
   logical, public :: l_rate_diagnostics = .true.         ! replay the save_dg calls of M:2962-3124
@@ -251,6 +252,26 @@ module module_mp_thompson09n
        type(c_ptr), value :: exner, dz, ppt, rates, nstep
        type(kidmp_outputs), intent(in) :: out
      end function kidmp32_kid_interface_host
+     ! the per-column summary (include/kidmp_summary.h): summary [ncol][16] is real(c_double) in both; nc, qi, qs + qg and
+     ! cfg may be NULL; dz_col_stride 0 = one dz profile for all columns
+     integer(c_int) function kidmp_column_summary_host(ctx, ncol, nz, t, p, qv, qc, nc, qi, qr, nr, qs, qg, dz, &
+          dz_col_stride, cfg, summary) bind(C, name='kidmp_column_summary_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol, dz_col_stride
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qc, nc, qi, qr, nr, qs, qg, dz   ! real(c_double) [ncol][nz], dz [nz]
+       type(c_ptr), value :: cfg, summary
+     end function kidmp_column_summary_host
+     integer(c_int) function kidmp32_column_summary_host(ctx, ncol, nz, t, p, qv, qc, nc, qi, qr, nr, qs, qg, dz, &
+          dz_col_stride, cfg, summary) bind(C, name='kidmp32_column_summary_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol, dz_col_stride
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qc, nc, qi, qr, nr, qs, qg, dz   ! real(c_float) [ncol][nz], dz [nz]
+       type(c_ptr), value :: cfg, summary
+     end function kidmp32_column_summary_host
   end interface
 
 contains
@@ -532,6 +553,44 @@ contains
     end if
     call stop_on_error(rc, 'calc_effectRad')
   end subroutine calc_effectRad_batch
+
+  ! The per-column summary of include/kidmp_summary.h over ncol columns of KiD's (nz, ncol) storage in one call: water
+  ! paths, liquid cloud optical depth, composite reflectivity, echo-top, cloud and freezing heights; summary(s+1, i) is slot
+  ! s of column i, always real(c_double).  dz(nz) is KiD's one profile of layer depths.  nc may be left out unless
+  ! is_aerosol_aware, qi, qs and qg in an iiwarm run; a threshold left out keeps the library's default (18 dBZ, 1e-5
+  ! kg/kg, 273.15 K).  Default REAL 8 goes to kidmp_column_summary_host, REAL 4 to kidmp32_column_summary_host.
+  subroutine column_summary_batch(ncol, nz, t, p, qv, qc, qr, nr, dz, summary, nc, qi, qs, qg, dbz_echo, q_cloud, t_freeze)
+    integer, intent(in) :: ncol, nz
+    real, dimension(nz,ncol), intent(in), target :: t, p, qv, qc, qr, nr
+    real, dimension(nz), intent(in), target :: dz
+    real(c_double), dimension(16,ncol), intent(out), target :: summary
+    real, dimension(nz,ncol), intent(in), optional, target :: nc, qi, qs, qg
+    real, intent(in), optional :: dbz_echo, q_cloud, t_freeze
+    real(c_double), target :: cfg(3)                       ! kidmp_summary_cfg: three doubles
+    type(c_ptr) :: pnc, pqi, pqs, pqg, pcfg
+    integer(c_int) :: rc
+    if (.not. c_associated(ctx)) call thompson_init
+    pnc = c_null_ptr;  pqi = c_null_ptr;  pqs = c_null_ptr;  pqg = c_null_ptr;  pcfg = c_null_ptr
+    if (present(nc)) pnc = c_loc(nc)
+    if (present(qi)) pqi = c_loc(qi)
+    if (present(qs)) pqs = c_loc(qs)
+    if (present(qg)) pqg = c_loc(qg)
+    if (present(dbz_echo) .or. present(q_cloud) .or. present(t_freeze)) then
+       cfg = (/ 18.0_c_double, 1.0e-5_c_double, 273.15_c_double /)
+       if (present(dbz_echo)) cfg(1) = real(dbz_echo, c_double)
+       if (present(q_cloud)) cfg(2) = real(q_cloud, c_double)
+       if (present(t_freeze)) cfg(3) = real(t_freeze, c_double)
+       pcfg = c_loc(cfg)
+    end if
+    if (kind(t) == c_double) then
+       rc = kidmp_column_summary_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), &
+            c_loc(qc), pnc, pqi, c_loc(qr), c_loc(nr), pqs, pqg, c_loc(dz), 0_c_int64_t, pcfg, c_loc(summary))
+    else
+       rc = kidmp32_column_summary_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), &
+            c_loc(qc), pnc, pqi, c_loc(qr), c_loc(nr), pqs, pqg, c_loc(dz), 0_c_int64_t, pcfg, c_loc(summary))
+    end if
+    call stop_on_error(rc, 'column_summary_batch')
+  end subroutine column_summary_batch
 
   ! A droplet number per column (kidmp_set_column_nc): column i of every following batched call uses Nt_c =
   ! set_nc_col(i)*1.e6 (M:381) in place of the namelist's set_Nc -- an Nd ensemble, or an aerosol gradient along x, in

@@ -576,6 +576,17 @@ class ThompsonMP:
         from .stats import level_stats
         return level_stats(self, fields, group, ngroup, edges, floor, work, stream)
 
+    def column_summary(self, st, dz, cfg=None, out=None, stream=None):
+        """Water paths, cloud optical depth, echo and cloud heights: [ncol, 16] float64 on the device, one number per
+        column and slot (include/kidmp_summary.h): kid_amd.summary.column_summary on this context."""
+        from .summary import column_summary
+        return column_summary(self, st, dz, cfg, out, stream)
+
+    def column_summary_host(self, st, dz, cfg=None):
+        """column_summary on numpy arrays: kid_amd.summary.column_summary_host on this context."""
+        from .summary import column_summary_host
+        return column_summary_host(self, st, dz, cfg)
+
     REFL_NAMES = ("t", "p", "qv", "qr", "nr", "qs", "qg")      # the inputs of calc_refl10cm that are read (qc1d is not)
 
     def reflectivity(self, st, out=None, stream=None):
