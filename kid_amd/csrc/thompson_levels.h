@@ -1,6 +1,7 @@
-// thompson_levels.h -- the per-level arithmetic of the two column diagnostics, calc_effectRad (M:4834-4935) and
-// calc_refl10cm (M:4946-5244), as __device__ functions: the pointwise radii kernel (kidmp_diag.hip) and the
-// wave-per-column kernels (thompson_reflectivity.hip) are built from these, so no statement exists twice.
+// thompson_levels.h -- the per-level arithmetic of the column diagnostics, calc_effectRad (M:4834-4935), calc_refl10cm
+// (M:4946-5244) and the fall speeds of block O (M:3206-3354), as __device__ functions: the pointwise radii kernel
+// (kidmp_diag.hip) and the wave-per-column kernels (thompson_reflectivity.hip) are built from these, so no statement
+// exists twice.
 //
 // What the two diagnostics share at a level -- rho, the snow content rs = qs*rho, tc0, the snow moment smob = rs*oams and
 // its logarithm -- is held in SnowLevel and formed once when both are wanted.
@@ -21,6 +22,13 @@ struct ReflConsts {
 };
 // what calc_effectRad reads beyond oams, sa, sb: Nt_c (M:4863), cig(2), oig1 (M:4890), cse(1) (M:4920-4929)
 struct RadConsts { double Nt_c, cig2, oig1, oams, cse1, sa[10], sb[10]; int aero; };
+// what block O (M:3206-3354) and the load it follows (M:1420-1467) read; crg6 is crg(6) and so on
+struct FallConsts {
+    double crg2, crg3, crg6, crg7, crg12, org2, org3;           // rain
+    double cie2, cig1, cig2, cig3, cig6, cig7, oig1, oig2;      // cloud ice
+    double cse1, cse4, cse7, cse10, csg1, csg4, csg7, csg10, oams, sa[10], sb[10];   // snow
+    double cgg1, cgg6, ogg3, lamg_fac;                          // graupel: lamg_fac = (cgg(3)*ogg2*ogg1)**obmg
+};
 
 namespace lvl {
 
@@ -137,6 +145,112 @@ __device__ inline double graupel_ze(const ReflConsts &c, double N0_exp, double r
     return ZE_GRAUPEL_FAC * N0_g * c.cgg4 * pw7(ilamg);                                 // ilamg**cge(4)
 }
 __device__ inline double dbz_of(double ze) { return 10. * fm::log10(ze * 1.E18); }     // M:5196
+
+// ---- block O (M:3206-3354) at one level: the fall speeds of a state as mp_thompson loads it (M:1387-1493).  The
+// exponents the scheme fixes are taken as roots and integer powers (fall_consts_supported): obmr = obmi = 1/3,
+// bm_i = bm_r = 3, cre(3) = 4, cre(6) = 5, cre(12) = 2.5, cre(7) = 3.5, bv_i = 1, cse(1) = 3, oge1 = 1/4. ----
+__device__ inline double cube(double x) { return x * x * x; }
+constexpr double XDI_FAC = bm_i + mu_i + 1.;          // M:1431
+
+// rain as loaded, M:1447-1474: rr, the limited nr, the limited median volume diameter and the slope block O forms
+// from them (M:3222).  A level without rain: rr = R1, nr = R2, has = false; mvd and lamr are not read.
+struct RainLoad { double rr, nr, mvd, lamr; bool has; };
+__device__ inline double nr_of_mvd(const FallConsts &c, double rr, double mvd)
+{
+    const double lamr = MVD_FAC / mvd;
+    return c.crg2 * c.org3 * rr * cube(lamr) / am_r;                       // lamr**bm_r
+}
+__device__ inline double rain_slope(const FallConsts &c, double rr, double nr) { return cbrt_any(am_r * c.crg3 * c.org2 * nr / rr); }
+__device__ inline RainLoad rain_load(const FallConsts &c, double rho, double qr, double nr1)
+{
+    RainLoad r{R1, R2, 0., 0., qr > R1};
+    if (!r.has) return r;
+    r.rr = qr * rho;
+    r.nr = fmax(R2, nr1 * rho);
+    if (r.nr <= R2) r.nr = nr_of_mvd(c, r.rr, 1.0E-3);
+    r.lamr = rain_slope(c, r.rr, r.nr);
+    r.mvd = MVD_FAC / r.lamr;
+    if (r.mvd > 2.5E-3) r.mvd = 2.5E-3;
+    else if (r.mvd < D0r * 0.75) r.mvd = D0r * 0.75;
+    else return r;
+    r.nr = nr_of_mvd(c, r.rr, r.mvd);
+    r.lamr = rain_slope(c, r.rr, r.nr);                                    // M:3222 on the limited number
+    return r;
+}
+// M:3223-3233
+__device__ inline void rain_fall_speeds(const FallConsts &c, double rhof, double lamr, double &vtr, double &vtnr)
+{
+    const double s = lamr + fv_r, l2 = lamr * lamr, s2 = s * s;
+    vtr = rhof * av_r * c.crg6 * c.org3 * (l2 * l2) * (1. / (s2 * s2 * s));                                    // **cre(3), **(-cre(6))
+    vtnr = rhof * av_r * c.crg7 / c.crg12 * (l2 * fm::sqrt_pos(lamr)) * (1. / (s2 * s * fm::sqrt_pos(s)));    // **cre(12), **(-cre(7))
+}
+
+// cloud ice as loaded, M:1420-1445, and its slope in block O (M:3257)
+struct IceLoad { double ri, ni, lami; bool has; };
+__device__ inline double ice_slope(const FallConsts &c, double ri, double ni) { return cbrt_any(am_i * c.cig2 * c.oig1 * ni / ri); }
+__device__ inline double ni_of_slope(const FallConsts &c, double ri, double lami) { return c.cig1 * c.oig2 * ri / am_i * cube(lami); }
+__device__ inline IceLoad ice_load(const FallConsts &c, double rho, double qi, double ni1)
+{
+    IceLoad r{R1, R2, 0., qi > R1};
+    if (!r.has) return r;
+    r.ri = qi * rho;
+    r.ni = fmax(R2, ni1 * rho);
+    if (r.ni <= R2) r.ni = fmin(499.E3, ni_of_slope(c, r.ri, c.cie2 / 25.E-6));
+    r.lami = ice_slope(c, r.ri, r.ni);
+    const double xDi = XDI_FAC * (1. / r.lami);
+    if (xDi < 5.E-6) r.ni = fmin(499.E3, ni_of_slope(c, r.ri, c.cie2 / 5.E-6));
+    else if (xDi > 300.E-6) r.ni = ni_of_slope(c, r.ri, c.cie2 / 300.E-6);
+    else return r;
+    r.lami = ice_slope(c, r.ri, r.ni);                                     // M:3257 on the limited number
+    return r;
+}
+// M:3258-3265, ilami**bv_i with bv_i = 1
+__device__ inline void ice_fall_speeds(const FallConsts &c, double rhof, double lami, double &vti, double &vtni)
+{
+    const double ilami = 1. / lami;
+    vti = rhof * av_i * c.cig3 * c.oig2 * ilami;
+    vtni = rhof * av_i * c.cig6 / c.cig7 * ilami;
+}
+
+// snow's mass-weighted speed before the boost, M:3289-3299; s = snow_level(temp, rs, oams) of a level with rs > R1
+__device__ inline double snow_fall_speed(const FallConsts &c, double rhof, const SnowLevel &s)
+{
+    const double smoc = snow_moment(c.sa, c.sb, c.cse1, s);               // M:1590-1600
+    const double xDs = smoc / s.smob;
+    const double Mrat = 1. / xDs;
+    double ils1 = 1. / (Mrat * Lam0 + fv_s);
+    double ils2 = 1. / (Mrat * Lam1 + fv_s);
+    const double mm = fm::pow(Mrat, mu_s);
+    const double t1_vts = Kap0 * c.csg4 * fm::pow(ils1, c.cse4);
+    const double t2_vts = Kap1 * mm * c.csg10 * fm::pow(ils2, c.cse10);
+    ils1 = 1. / (Mrat * Lam0);
+    ils2 = 1. / (Mrat * Lam1);
+    const double t3_vts = Kap0 * c.csg1 * cube(ils1);                     // **cse(1)
+    const double t4_vts = Kap1 * mm * c.csg7 * fm::pow(ils2, c.cse7);
+    return rhof * av_s * (t1_vts + t2_vts) / (t3_vts + t4_vts);
+}
+// M:3300-3305: vtr is the rain speed the level holds after the inheritance
+__device__ inline double snow_boosted(double vts, double boost, double temp, double vtr)
+{
+    if (temp > (T_0 + 0.1)) return fmax(vts * boost, vts * ((vtr - vts * boost) / (temp - T_0)));
+    return vts * boost;
+}
+// graupel of a level with rg > R1 once the running minimum N0_exp is known: M:1650-1652, M:3326-3331
+__device__ inline double graupel_fall_speed(const FallConsts &c, double rhof, double N0_exp, double rg, double temp, double vtr)
+{
+    const double lam_exp = fm::sqrt_pos(fm::sqrt_pos(N0_exp * am_g * c.cgg1 / rg));    // **oge1
+    const double lamg = lam_exp * c.lamg_fac;
+    const double ilamg = 1. / lamg;
+    const double vtg = rhof * av_g * c.cgg6 * c.ogg3 * fm::pow(ilamg, bv_g);
+    return temp > T_0 ? fmax(vtg, vtr) : vtg;
+}
+// INT(DT/delta_tp + 1.) with delta_tp = dzq(k)/v, M:3241-3242, capped (U5); v > 1.E-3
+constexpr int FALL_MAX_SUBSTEPS = 10000;
+__device__ inline int fall_substeps(double dt, double dz, double v)
+{
+    const double x = dt / (dz / v) + 1.;
+    return x < double(FALL_MAX_SUBSTEPS) ? int(x) : FALL_MAX_SUBSTEPS;    // a NaN counts as the cap
+}
 
 }  // namespace lvl
 }  // namespace kidmp

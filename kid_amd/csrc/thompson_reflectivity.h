@@ -47,4 +47,21 @@ template <class T>
 hipError_t launch_column_summary(const ReflConsts &c, const RadConsts &rc, int64_t ncol, int nz, const SummaryArgs<T> &a,
                                  double *summary, hipStream_t stream);
 
+// The fall speeds of block O (M:3206-3354) as a diagnostic of a state (include/kidmp_fall.h).  Null means: qi, ni, qs, qg
+// -- not read (warm); boost -- 1.0 where T < T_0, 1.5 elsewhere; an output -- not wanted; nstep -- not wanted, and then
+// dz and dt are not read.  out: vt_r, vt_nr, vt_i, vt_ni, vt_s, vt_g, flux_r, flux_i, flux_s, flux_g, flux_total.
+constexpr int FALL_NOUT = 11;
+template <class T> struct FallArgs {
+    const T *t, *p, *qv, *qr, *nr, *qi, *ni, *qs, *qg, *boost, *dz;
+    int64_t dz_col_stride;
+    double dt;
+    T *out[FALL_NOUT];
+    int32_t *nstep;                                  // [ncol][4]: rain, ice, snow, graupel
+    int warm;                                        // iiwarm: the frozen speeds and fluxes are +0.0 (M:3346-3352)
+};
+bool fall_consts_supported(const Consts &hc);
+// d_consts: the context's Consts in device memory (kidmp_ctx::d_consts)
+template <class T>
+hipError_t launch_fall_speeds(const Consts *d_consts, int64_t ncol, int nz, const FallArgs<T> &a, hipStream_t stream);
+
 }  // namespace kidmp

@@ -265,7 +265,256 @@ __device__ inline double level_of(const double (&v)[NJ], int k)
     return x;
 }
 
+// ---- the fall speeds (include/kidmp_fall.h) ----
+__device__ inline int wave_max_int(int v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v = max(v, __shfl_xor(v, m, 64));
+    return v;
+}
+template <int D>
+__device__ inline int row_shl_int(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x100 + D, 0xf, 0xf, false); }
+
+// One step of the inheritance scan: a lane whose level lacks the species takes what lane l + D of its row holds.
+template <int D, bool TWO>
+__device__ inline void carry_step(double &a, double &b, int &h, int r)
+{
+    const double oa = row_shl<D>(a), ob = TWO ? row_shl<D>(b) : 0.;
+    const int oh = row_shl_int<D>(h);
+    const bool take = r + D < 16 && !h;
+    a = take ? oa : a;
+    if (TWO) b = take ? ob : b;
+    h = take ? oh : h;
+}
+// vtrk(k) = vtrk(k+1) where the level lacks the species (M:3235, 3267, 3307, 3333) over the 64 levels of a wave: a suffix
+// scan with the associative operator "keep mine if my level has the species, else take the one above".  Only moves: a
+// lane ends with the bits of the nearest lane at or above it whose `has` is set, and the return value tells whether
+// there is one.  (ta, tb, th): lane 0's result, wave-uniform -- what the whole wave hands down to the levels below it.
+// One predicate carries both values (TWO: the mass- and the number-weighted speed).  Whole wavefronts only.
+template <bool TWO>
+__device__ inline bool wave_carry_down(double &a, double &b, bool has, int lane, double &ta, double &tb, bool &th)
+{
+    int h = has;
+    const int r = lane & 15;
+    carry_step<1, TWO>(a, b, h, r);
+    carry_step<2, TWO>(a, b, h, r);
+    carry_step<4, TWO>(a, b, h, r);
+    carry_step<8, TWO>(a, b, h, r);
+    // lane 16 q holds what row q hands down
+    const double a1 = readlane(a, 16), a2 = readlane(a, 32), a3 = readlane(a, 48);
+    const double b1 = TWO ? readlane(b, 16) : 0., b2 = TWO ? readlane(b, 32) : 0., b3 = TWO ? readlane(b, 48) : 0.;
+    const int h1 = __builtin_amdgcn_readlane(h, 16), h2 = __builtin_amdgcn_readlane(h, 32), h3 = __builtin_amdgcn_readlane(h, 48);
+    const double u2a = a3, u1a = h2 ? a2 : a3, u0a = h1 ? a1 : u1a;     // what the rows above row q hand down
+    const double u2b = b3, u1b = h2 ? b2 : b3, u0b = h1 ? b1 : u1b;
+    const int u2h = h3, u1h = h2 | h3, u0h = h1 | u1h;
+    const int q = lane >> 4;
+    const int uh = q == 0 ? u0h : q == 1 ? u1h : q == 2 ? u2h : 0;
+    if (!h && uh) {
+        a = q == 0 ? u0a : q == 1 ? u1a : u2a;
+        if (TWO) b = q == 0 ? u0b : q == 1 ? u1b : u2b;
+        h = 1;
+    }
+    ta = readlane(a, 0);
+    tb = TWO ? readlane(b, 0) : 0.;
+    th = __builtin_amdgcn_readlane(h, 0) != 0;
+    return h != 0;
+}
+// the column: the level groups chained from the top, the value above the top level is 0 (M:3209-3216)
+template <int NJ, bool TWO>
+__device__ inline void carry_down_column(double (&a)[NJ], double (&b)[NJ], const bool (&has)[NJ], int lane)
+{
+    double ca = 0., cb = 0.;
+#pragma unroll
+    for (int j = NJ - 1; j >= 0; --j) {
+        double ta, tb;
+        bool th;
+        const bool h = wave_carry_down<TWO>(a[j], b[j], has[j], lane, ta, tb, th);
+        if (!h) { a[j] = ca; if (TWO) b[j] = cb; }
+        if (th) { ca = ta; cb = tb; }
+    }
+}
+// nstep of one species: MAX over the levels with v > 1.E-3 of INT(DT/delta_tp + 1.) (M:3239-3243); 0 is reported as 1,
+// as NINT(1./onstep) gives it (M:3365)
+template <int NJ>
+__device__ inline int column_substeps(const double (&v)[NJ], const double (&dz)[NJ], double dt, int nz, int lane)
+{
+    int ns = 0;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+        if (64 * j + lane < nz && v[j] > 1.E-3) ns = max(ns, lvl::fall_substeps(dt, dz[j], v[j]));
+    ns = wave_max_int(ns);
+    return ns > 0 ? ns : 1;
+}
+template <class T, int NJ>
+__device__ inline void store_profile(T *__restrict__ out, int64_t base, int nz, int lane, const double (&v)[NJ])
+{
+    if (!out) return;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        if (k < nz) out[base + k] = T(v[j]);
+    }
+}
+
 }  // namespace
+
+// what block O reads, picked from the context's Consts: on the device from its copy in HBM (scalar loads on demand: as
+// kernel arguments the 50 values pressed on the SGPRs), on the host for whoever wants to look
+__host__ __device__ FallConsts fall_consts(const Consts &hc)
+{
+    FallConsts c{};
+    c.crg2 = hc.crg[1]; c.crg3 = hc.crg[2]; c.crg6 = hc.crg[5]; c.crg7 = hc.crg[6]; c.crg12 = hc.crg[11];
+    c.org2 = hc.org2; c.org3 = hc.org3;
+    c.cie2 = hc.cie[1]; c.cig1 = hc.cig[0]; c.cig2 = hc.cig[1]; c.cig3 = hc.cig[2]; c.cig6 = hc.cig[5]; c.cig7 = hc.cig[6];
+    c.oig1 = hc.oig1; c.oig2 = hc.oig2;
+    c.cse1 = hc.cse[0]; c.cse4 = hc.cse[3]; c.cse7 = hc.cse[6]; c.cse10 = hc.cse[9];
+    c.csg1 = hc.csg[0]; c.csg4 = hc.csg[3]; c.csg7 = hc.csg[6]; c.csg10 = hc.csg[9]; c.oams = hc.oams;
+    for (int i = 0; i < 10; ++i) { c.sa[i] = hc.sa[i]; c.sb[i] = hc.sb[i]; }
+    c.cgg1 = hc.cgg[0]; c.cgg6 = hc.cgg[5]; c.ogg3 = hc.ogg3; c.lamg_fac = hc.lamg_fac;
+    return c;
+}
+
+// One wavefront per column: block O (M:3206-3354) of the state as mp_thompson loads it -- the fall speeds of rain, ice,
+// snow and graupel at every level, the sedimentation fluxes v * rho q and, on request, the CFL substep counts
+// (include/kidmp_fall.h).  Species by species: the level's own speed, the inheritance scan, the stores; rain first,
+// because snow and graupel read the inherited rain speed.  Nothing but the fastmath tables is in LDS.
+template <class T, int NJ>
+__global__ void __launch_bounds__(REFL_THREADS)
+k_fall_speeds(const Consts *__restrict__ hc, FallArgs<T> a, int64_t ncol, int nz)
+{
+    const FallConsts c = fall_consts(*hc);
+#if KFM_TABLES
+    fm::tab::load_tables(int(threadIdx.x), REFL_THREADS);
+    __syncthreads();
+#endif
+    const int lane = int(threadIdx.x) & 63;
+    const int64_t col = int64_t(blockIdx.x) * REFL_WAVES + (int(threadIdx.x) >> 6);
+    if (col >= ncol) return;                                         // whole wavefronts only: the scans need every lane
+    const int64_t base = col * int64_t(nz);
+    const bool count = a.nstep != nullptr;
+
+    double temp[NJ], rho[NJ], rhof[NJ], mvd[NJ], dz[NJ], vtr[NJ], ftot[NJ];
+    double va[NJ], vb[NJ], rq[NJ], fx[NJ];                           // the species at hand: its two speeds, its content rho*q, its flux
+    bool has[NJ];
+    int ns_r = 1, ns_i = 1, ns_s = 1, ns_g = 1;
+
+    // ---- load (M:1387-1391, M:1447-1474) and rain (M:3221-3237) ----
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        temp[j] = 0.; rho[j] = 1.; rhof[j] = 0.; mvd[j] = 0.; dz[j] = 1.; va[j] = vb[j] = 0.; rq[j] = R1; has[j] = false;
+        if (k >= nz) continue;
+        const int64_t i = base + k;
+        temp[j] = double(a.t[i]);
+        rho[j] = lvl::air_density(double(a.p[i]), temp[j], fmax(1.E-10, double(a.qv[i])));
+        rhof[j] = fm::sqrt_pos(rho_not / rho[j]);                    // M:3219
+        if (count) dz[j] = double(a.dz[col * a.dz_col_stride + k]);
+        const lvl::RainLoad r = lvl::rain_load(c, rho[j], double(a.qr[i]), double(a.nr[i]));
+        has[j] = r.rr > R1;                                          // block O asks the content, M:3221
+        rq[j] = r.rr;
+        if (r.has) mvd[j] = r.mvd;                                   // 0: no rain (block E asks L_qr, M:1639)
+        if (has[j]) lvl::rain_fall_speeds(c, rhof[j], r.lamr, va[j], vb[j]);
+    }
+    carry_down_column<NJ, true>(va, vb, has, lane);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) { vtr[j] = va[j]; fx[j] = va[j] * rq[j]; ftot[j] = fx[j]; }      // sed_r, M:3368
+    store_profile<T, NJ>(a.out[0], base, nz, lane, va);
+    store_profile<T, NJ>(a.out[1], base, nz, lane, vb);
+    store_profile<T, NJ>(a.out[6], base, nz, lane, fx);
+    if (count) {
+        double vm[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) vm[j] = fmax(va[j], vb[j]);     // M:3239
+        ns_r = column_substeps<NJ>(vm, dz, a.dt, nz, lane);
+    }
+
+    if (a.warm) {                                                    // M:3346-3352: exact zeros
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) va[j] = 0.;
+#pragma unroll
+        for (int o = 2; o < 10; ++o)
+            if (o != 6) store_profile<T, NJ>(a.out[o], base, nz, lane, va);
+    } else {
+        // ---- cloud ice, M:1420-1445 and M:3253-3269 ----
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int k = 64 * j + lane;
+            va[j] = vb[j] = 0.; rq[j] = R1; has[j] = false;
+            if (k >= nz) continue;
+            const lvl::IceLoad r = lvl::ice_load(c, rho[j], double(a.qi[base + k]), double(a.ni[base + k]));
+            has[j] = r.ri > R1;                                      // M:3256
+            rq[j] = r.ri;
+            if (has[j]) lvl::ice_fall_speeds(c, rhof[j], r.lami, va[j], vb[j]);
+        }
+        carry_down_column<NJ, true>(va, vb, has, lane);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { fx[j] = va[j] * rq[j]; ftot[j] = ftot[j] + fx[j]; }
+        store_profile<T, NJ>(a.out[2], base, nz, lane, va);
+        store_profile<T, NJ>(a.out[3], base, nz, lane, vb);
+        store_profile<T, NJ>(a.out[7], base, nz, lane, fx);
+        if (count) ns_i = column_substeps<NJ>(va, dz, a.dt, nz, lane);
+
+        // ---- snow, M:1475-1483, block D and M:3285-3308 ----
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int k = 64 * j + lane;
+            va[j] = 0.; rq[j] = R1; has[j] = false;
+            if (k >= nz) continue;
+            const double qs = double(a.qs[base + k]);
+            if (qs > R1) rq[j] = qs * rho[j];                        // M:1475-1483
+            has[j] = rq[j] > R1;                                     // M:3288
+            if (!has[j]) continue;
+            const double boost = a.boost ? double(a.boost[base + k]) : temp[j] < T_0 ? 1.0 : 1.5;   // M:2027, M:1751
+            const double vts = lvl::snow_fall_speed(c, rhof[j], lvl::snow_level(temp[j], rq[j], c.oams));
+            va[j] = lvl::snow_boosted(vts, boost, temp[j], vtr[j]);
+        }
+        carry_down_column<NJ, false>(va, vb, has, lane);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { fx[j] = va[j] * rq[j]; ftot[j] = ftot[j] + fx[j]; }
+        store_profile<T, NJ>(a.out[4], base, nz, lane, va);
+        store_profile<T, NJ>(a.out[8], base, nz, lane, fx);
+        if (count) ns_s = column_substeps<NJ>(va, dz, a.dt, nz, lane);
+
+        // ---- graupel, M:1484-1492, block E (M:1633-1654) and M:3322-3334 ----
+        int k_0 = 0;                                                 // the highest level with temp >= 270.65, M:1634-1637
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const unsigned long long b = __ballot(64 * j + lane < nz && temp[j] >= 270.65);
+            if (b) k_0 = 64 * j + 63 - __builtin_clzll(b);
+        }
+        double n0[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int k = 64 * j + lane;
+            va[j] = 0.; rq[j] = R1; has[j] = false;
+            n0[j] = double(__builtin_inf());                         // levels past kte do not enter the minimum
+            if (k >= nz) continue;
+            const double qg = double(a.qg[base + k]);
+            if (qg > R1) rq[j] = qg * rho[j];                        // M:1484-1492
+            has[j] = rq[j] > R1;                                     // M:3325
+            n0[j] = lvl::graupel_n0_exp(k > k_0 && mvd[j] > 100.E-6, mvd[j], rq[j]);
+        }
+        double carry = gonv_max;                                     // N0_min = gonv_max, M:1633
+#pragma unroll
+        for (int j = NJ - 1; j >= 0; --j) {
+            double tail;
+            const double s = wave_suffix_min(n0[j], lane, tail);
+            n0[j] = fmin(s, carry);
+            carry = fmin(carry, tail);
+        }
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+            if (has[j]) va[j] = lvl::graupel_fall_speed(c, rhof[j], n0[j], rq[j], temp[j], vtr[j]);
+        carry_down_column<NJ, false>(va, vb, has, lane);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { fx[j] = va[j] * rq[j]; ftot[j] = ftot[j] + fx[j]; }
+        store_profile<T, NJ>(a.out[5], base, nz, lane, va);
+        store_profile<T, NJ>(a.out[9], base, nz, lane, fx);
+        if (count) ns_g = column_substeps<NJ>(va, dz, a.dt, nz, lane);
+    }
+    store_profile<T, NJ>(a.out[10], base, nz, lane, ftot);
+    if (count && lane < 4) a.nstep[col * 4 + lane] = lane == 0 ? ns_r : lane == 1 ? ns_i : lane == 2 ? ns_s : ns_g;
+}
 
 // the reflectivity alone; the kernel name rocprofv3 lists is kidmp::k_reflectivity<T, NJ>
 template <class T, int NJ>
@@ -413,6 +662,30 @@ template hipError_t launch_column_summary<double>(const ReflConsts &, const RadC
                                                   double *, hipStream_t);
 template hipError_t launch_column_summary<float>(const ReflConsts &, const RadConsts &, int64_t, int, const SummaryArgs<float> &,
                                                  double *, hipStream_t);
+
+template <class T>
+hipError_t launch_fall_speeds(const Consts *c, int64_t ncol, int nz, const FallArgs<T> &a, hipStream_t s)
+{
+    if (ncol <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((ncol + REFL_WAVES - 1) / REFL_WAVES)), block(REFL_THREADS);
+    switch ((nz + 63) / 64) {
+    case 1: hipLaunchKernelGGL((k_fall_speeds<T, 1>), grid, block, 0, s, c, a, ncol, nz); break;
+    case 2: hipLaunchKernelGGL((k_fall_speeds<T, 2>), grid, block, 0, s, c, a, ncol, nz); break;
+    case 3: hipLaunchKernelGGL((k_fall_speeds<T, 3>), grid, block, 0, s, c, a, ncol, nz); break;
+    case 4: hipLaunchKernelGGL((k_fall_speeds<T, 4>), grid, block, 0, s, c, a, ncol, nz); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+template hipError_t launch_fall_speeds<double>(const Consts *, int64_t, int, const FallArgs<double> &, hipStream_t);
+template hipError_t launch_fall_speeds<float>(const Consts *, int64_t, int, const FallArgs<float> &, hipStream_t);
+
+bool fall_consts_supported(const Consts &hc)
+{
+    // the exponents lvl:: takes as roots and integer powers (thompson_init, M:452-553, from bm_*, bv_*, mu_*)
+    return hc.obmr == 1. / 3. && hc.obmi == 1. / 3. && hc.oge1 == 0.25 && hc.cre[2] == 4. && hc.cre[5] == 5.
+           && hc.cre[11] == 2.5 && hc.cre[6] == 3.5 && hc.cse[0] == 3. && bm_s == 2.0 && bm_i == 3.0 && bm_r == 3.0 && bv_i == 1.0;
+}
 
 bool refl_consts_supported(const Consts &hc)
 {

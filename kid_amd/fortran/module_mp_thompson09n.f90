@@ -60,6 +60,7 @@ module module_mp_thompson09n
   public :: calc_effectRad, calc_effectRad_batch
   public :: mp_thompson_set_column_nc
   public :: column_summary_batch
+  public :: fall_speeds_batch
   public :: mp_thompson_kid_interface, mp_thompson_kid_staging
   logical, public :: is_aerosol_aware = .false.          ! M:28 (read at thompson_init)
   logical, public :: l_rate_diagnostics = .true.         ! replay the save_dg calls of M:2962-3124
@@ -91,6 +92,10 @@ module module_mp_thompson09n
   type, bind(C) :: kidmp_outputs                         ! kidmp_outputs / kidmp32_outputs: NULL = not wanted
      type(c_ptr) :: dbz, re_qc, re_qi, re_qs
   end type kidmp_outputs
+
+  type, bind(C) :: kidmp_fall_out                        ! kidmp_fall_out / kidmp32_fall_out: [ncol][nz] each, NULL = not wanted
+     type(c_ptr) :: vt_r, vt_nr, vt_i, vt_ni, vt_s, vt_g, flux_r, flux_i, flux_s, flux_g, flux_total
+  end type kidmp_fall_out
 
   type, bind(C) :: kidmp_kid_fields                      ! kidmp_kid_fields / kidmp32_kid_fields: KiD's fields, [ncol][nz] each
      type(c_ptr) :: theta, qv, qc, qr, nr, qi, ni, qs, qg
@@ -272,6 +277,30 @@ module module_mp_thompson09n
        type(c_ptr), value :: t, p, qv, qc, nc, qi, qr, nr, qs, qg, dz   ! real(c_float) [ncol][nz], dz [nz]
        type(c_ptr), value :: cfg, summary
      end function kidmp32_column_summary_host
+     ! block-O fall speeds and sedimentation fluxes (include/kidmp_fall.h): qi, ni, qs, qg, vts_boost may be NULL as the
+     ! header says; dz, dz_col_stride and dt are read only when nstep is not NULL; nstep [ncol][4] int32
+     integer(c_int) function kidmp_fall_speeds_host(ctx, ncol, nz, t, p, qv, qr, nr, qi, ni, qs, qg, vts_boost, dz, &
+          dz_col_stride, dt, out, nstep) bind(C, name='kidmp_fall_speeds_host')
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr, kidmp_fall_out
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol, dz_col_stride
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qr, nr, qi, ni, qs, qg, vts_boost, dz   ! real(c_double) [ncol][nz], dz [nz]
+       real(c_double), value :: dt
+       type(kidmp_fall_out), intent(in) :: out
+       type(c_ptr), value :: nstep
+     end function kidmp_fall_speeds_host
+     integer(c_int) function kidmp32_fall_speeds_host(ctx, ncol, nz, t, p, qv, qr, nr, qi, ni, qs, qg, vts_boost, dz, &
+          dz_col_stride, dt, out, nstep) bind(C, name='kidmp32_fall_speeds_host')
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr, kidmp_fall_out
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol, dz_col_stride
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qr, nr, qi, ni, qs, qg, vts_boost, dz   ! real(c_float) [ncol][nz], dz [nz]
+       real(c_double), value :: dt
+       type(kidmp_fall_out), intent(in) :: out
+       type(c_ptr), value :: nstep
+     end function kidmp32_fall_speeds_host
   end interface
 
 contains
@@ -591,6 +620,64 @@ contains
     end if
     call stop_on_error(rc, 'column_summary_batch')
   end subroutine column_summary_batch
+
+  ! Block O (M:3206-3354) of a state over ncol columns of KiD's (nz, ncol) storage in one call (include/kidmp_fall.h): the
+  ! mass- and number-weighted fall speeds of rain, ice, snow and graupel (m s-1), the sedimentation fluxes v*rho*q per
+  ! species and in total (kg m-2 s-1), and with dz(nz) and dt the substep counts nstep(4, ncol) (rain, ice, snow, graupel).
+  ! Every output is optional, in the array kind the arithmetic stores; at least one must be present.  qi, ni, qs and qg
+  ! may be left out in an iiwarm run; vts_boost left out means the value of a level without riming (1.0 below T_0, 1.5
+  ! elsewhere).  The inputs are not changed.  Default REAL 8 goes to kidmp_fall_speeds_host, REAL 4 to kidmp32_...
+  subroutine fall_speeds_batch(ncol, nz, t, p, qv, qr, nr, vt_r, vt_nr, vt_i, vt_ni, vt_s, vt_g, flux_r, flux_i, flux_s, &
+       flux_g, flux_total, qi, ni, qs, qg, vts_boost, dz, dt, nstep)
+    integer, intent(in) :: ncol, nz
+    real, dimension(nz,ncol), intent(in), target :: t, p, qv, qr, nr
+    real, dimension(nz,ncol), intent(out), optional, target :: vt_r, vt_nr, vt_i, vt_ni, vt_s, vt_g, flux_r, flux_i, flux_s, &
+         flux_g, flux_total
+    real, dimension(nz,ncol), intent(in), optional, target :: qi, ni, qs, qg, vts_boost
+    real, dimension(nz), intent(in), optional, target :: dz
+    real, intent(in), optional :: dt
+    integer(c_int32_t), dimension(4,ncol), intent(out), optional, target :: nstep
+    type(kidmp_fall_out) :: out
+    type(c_ptr) :: pqi, pni, pqs, pqg, pboost, pdz, pnstep
+    real(c_double) :: dt8
+    integer(c_int) :: rc
+    if (.not. c_associated(ctx)) call thompson_init
+    if (c_associated(mctx)) then
+       write(*,'(a)') ' module_mp_thompson09n: fall speeds are not available with kidmp_ndevices > 1'
+       stop 1
+    end if
+    pqi = c_null_ptr;  pni = c_null_ptr;  pqs = c_null_ptr;  pqg = c_null_ptr;  pboost = c_null_ptr
+    pdz = c_null_ptr;  pnstep = c_null_ptr;  dt8 = 0.0_c_double
+    if (present(qi)) pqi = c_loc(qi)
+    if (present(ni)) pni = c_loc(ni)
+    if (present(qs)) pqs = c_loc(qs)
+    if (present(qg)) pqg = c_loc(qg)
+    if (present(vts_boost)) pboost = c_loc(vts_boost)
+    if (present(dz)) pdz = c_loc(dz)
+    if (present(dt)) dt8 = real(dt, c_double)
+    if (present(nstep)) pnstep = c_loc(nstep)
+    out = kidmp_fall_out(c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
+         c_null_ptr, c_null_ptr, c_null_ptr)
+    if (present(vt_r)) out%vt_r = c_loc(vt_r)
+    if (present(vt_nr)) out%vt_nr = c_loc(vt_nr)
+    if (present(vt_i)) out%vt_i = c_loc(vt_i)
+    if (present(vt_ni)) out%vt_ni = c_loc(vt_ni)
+    if (present(vt_s)) out%vt_s = c_loc(vt_s)
+    if (present(vt_g)) out%vt_g = c_loc(vt_g)
+    if (present(flux_r)) out%flux_r = c_loc(flux_r)
+    if (present(flux_i)) out%flux_i = c_loc(flux_i)
+    if (present(flux_s)) out%flux_s = c_loc(flux_s)
+    if (present(flux_g)) out%flux_g = c_loc(flux_g)
+    if (present(flux_total)) out%flux_total = c_loc(flux_total)
+    if (kind(t) == c_double) then
+       rc = kidmp_fall_speeds_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), c_loc(qr), &
+            c_loc(nr), pqi, pni, pqs, pqg, pboost, pdz, 0_c_int64_t, dt8, out, pnstep)
+    else
+       rc = kidmp32_fall_speeds_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), c_loc(qr), &
+            c_loc(nr), pqi, pni, pqs, pqg, pboost, pdz, 0_c_int64_t, dt8, out, pnstep)
+    end if
+    call stop_on_error(rc, 'fall_speeds_batch')
+  end subroutine fall_speeds_batch
 
   ! A droplet number per column (kidmp_set_column_nc): column i of every following batched call uses Nt_c =
   ! set_nc_col(i)*1.e6 (M:381) in place of the namelist's set_Nc -- an Nd ensemble, or an aerosol gradient along x, in

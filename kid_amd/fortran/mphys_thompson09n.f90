@@ -46,6 +46,12 @@ module mphys_thompson09n
   ! are not run.  Needs one device, and a default REAL that is what kidmp_arith stores.  .false.: call sequence and
   ! results as without it.
   logical, public :: l_device_adapter = .false.
+  ! .true. (nx > 1): 'total_ppt_level' carries dt * flux_total of the post-step state, kg m-2 per step like pptrain --
+  ! the sedimentation flux v*rho*q of rain + ice + snow + graupel across every level (fall_speeds_batch, one more host
+  ! call per step) -- in the place of the zeros of U6; name, units string and dim='z,x' are unchanged.  Needs one device
+  ! and the host-side adapter (not l_device_adapter, which leaves no post-step state on the host).  .false.: call
+  ! sequence, save_dg sequence and every result as without it.
+  logical, public :: l_precip_flux = .false.
   real, allocatable, private, save :: nc_bound(:)          ! what is bound in the library (unallocated: nothing)
   integer:: ih, imom
   character(max_char_len) :: name, units
@@ -86,6 +92,16 @@ contains
     logical :: staged
     integer :: i, k, m, s
 
+    if (l_precip_flux) then                      ! refused before anything is initialised
+       if (kidmp_ndevices > 1) then
+          write(*,'(a)') ' mphys_thompson09n: l_precip_flux is not available with kidmp_ndevices > 1'
+          stop 1
+       end if
+       if (l_device_adapter) then
+          write(*,'(a)') ' mphys_thompson09n: l_precip_flux is not available with l_device_adapter'
+          stop 1
+       end if
+    end if
     if (micro_unset) then                        ! W:100-103 (ahead of the gather: the staging arrays belong to the library)
        call thompson_init
        micro_unset = .False.
@@ -283,8 +299,24 @@ contains
        ! save precip flux at all levels and columns, W:304-307.  The reference saves pptrain_2d_prof(nz,nx), an array it
        ! never assigns (W:191 is commented out), i.e. undefined values under a name every stock KiD output carries.
        ! Defined semantics here (U6): the name, units, dim='z,x' and shape of the reference, all values zero.
+       ! With l_precip_flux the array is assigned at last: dt * flux_total of the post-step state (cf. M:3395, W:191).
+       if (allocated(pptrain_2d_prof)) then
+          if (size(pptrain_2d_prof, 1) /= nz .or. size(pptrain_2d_prof, 2) /= nx) deallocate(pptrain_2d_prof)
+       end if
        if (.not. allocated(pptrain_2d_prof)) then
           allocate(pptrain_2d_prof(nz, nx))
+          pptrain_2d_prof = 0.0
+       end if
+       if (l_precip_flux) then
+          if (iiwarm) then
+             call fall_speeds_batch(nx, nz, st(:,:,S_T), fo(:,:,1), st(:,:,S_QV), st(:,:,S_QR), st(:,:,S_NR), &
+                  flux_total=pptrain_2d_prof)
+          else
+             call fall_speeds_batch(nx, nz, st(:,:,S_T), fo(:,:,1), st(:,:,S_QV), st(:,:,S_QR), st(:,:,S_NR), &
+                  flux_total=pptrain_2d_prof, qi=st(:,:,S_QI), ni=st(:,:,S_NI), qs=st(:,:,S_QS), qg=st(:,:,S_QG))
+          end if
+          pptrain_2d_prof = dt*pptrain_2d_prof
+       else
           pptrain_2d_prof = 0.0
        end if
        name = 'total_ppt_level'

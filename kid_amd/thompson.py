@@ -587,6 +587,17 @@ class ThompsonMP:
         from .summary import column_summary_host
         return column_summary_host(self, st, dz, cfg)
 
+    def fall_speeds(self, st, boost=None, dz=None, dt=None, want=None, stream=None):
+        """Block-O fall speeds and sedimentation fluxes of every level, and the substep counts when dz and dt are given
+        (include/kidmp_fall.h): kid_amd.fall.fall_speeds on this context."""
+        from .fall import FALL_NAMES, fall_speeds
+        return fall_speeds(self, st, boost, dz, dt, FALL_NAMES if want is None else want, stream)
+
+    def fall_speeds_host(self, st, boost=None, dz=None, dt=None, want=None):
+        """fall_speeds on numpy arrays: kid_amd.fall.fall_speeds_host on this context."""
+        from .fall import FALL_NAMES, fall_speeds_host
+        return fall_speeds_host(self, st, boost, dz, dt, FALL_NAMES if want is None else want)
+
     REFL_NAMES = ("t", "p", "qv", "qr", "nr", "qs", "qg")      # the inputs of calc_refl10cm that are read (qc1d is not)
 
     def reflectivity(self, st, out=None, stream=None):
