@@ -1,5 +1,6 @@
 // thompson_levels.h -- the per-level arithmetic of the column diagnostics, calc_effectRad (M:4834-4935), calc_refl10cm
-// (M:4946-5244) and the fall speeds of block O (M:3206-3354), as __device__ functions: the pointwise radii kernel
+// (M:4946-5244), the fall speeds of block O (M:3206-3354) and the Doppler moments of a vertically pointing radar
+// (include/kidmp_doppler.h), as __device__ functions: the pointwise radii kernel
 // (kidmp_diag.hip) and the wave-per-column kernels (thompson_reflectivity.hip) are built from these, so no statement
 // exists twice.
 //
@@ -28,6 +29,16 @@ struct FallConsts {
     double cie2, cig1, cig2, cig3, cig6, cig7, oig1, oig2;      // cloud ice
     double cse1, cse4, cse7, cse10, csg1, csg4, csg7, csg10, oams, sa[10], sb[10];   // snow
     double cgg1, cgg6, ogg3, lamg_fac;                          // graupel: lamg_fac = (cgg(3)*ogg2*ogg1)**obmg
+};
+
+// the gamma ratios of the Doppler moments (include/kidmp_doppler.h), which are not among thompson_init's c?g arrays:
+// formed on the host with tgamma from thompson_params.h (doppler_consts)
+struct DopplerConsts {
+    double cse1;                       // snow: the order of smoc, cse(1)
+    double gr1, gr2;                   // rain: Gamma(n+bv_r)/Gamma(n), Gamma(n+2bv_r)/Gamma(n), n = 7+mu_r
+    double gg1, gg2;                   // graupel: the same with bv_g, n = 7+mu_g
+    double ks0_1, ks1_1, ks0_2, ks1_2; // snow: Kap0 Gamma(5+b), Kap1 Gamma(5+mu_s+b) at b = bv_s and at b = 2 bv_s
+    double ia00;                       // snow: 1/(Kap0 Gamma(5) Lam0**-5 + Kap1 Gamma(5+mu_s) Lam1**-(5+mu_s))
 };
 
 namespace lvl {
@@ -112,16 +123,22 @@ __device__ inline double cbrt_any(double x)
     return fm::cbrt_pos(ldexp(x, -3 * q)) * ldexp(1., q);
 }
 
-// rain of a level with qr > R1: ze_rain and the median volume diameter; no 37.5 um / 2.5 mm limits here (cf. M:1661-1666)
-__device__ inline double rain_ze(const ReflConsts &c, double rho, double qr, double nr1, double &mvd_r)
+// rain of a level with qr > R1: ze_rain, the median volume diameter and the slope; no 37.5 um / 2.5 mm limits here
+// (cf. M:1661-1666)
+__device__ inline double rain_ze(const ReflConsts &c, double rho, double qr, double nr1, double &mvd_r, double &lamr)
 {
     const double rr = qr * rho;
     const double nr = fmax(R2, nr1 * rho);
-    const double lamr = cbrt_any(am_r * c.crg3 * c.org2 * nr / rr);       // **obmr
+    lamr = cbrt_any(am_r * c.crg3 * c.org2 * nr / rr);                    // **obmr
     const double ilamr = 1. / lamr;
     const double N0_r = nr * c.org2 * lamr;                               // lamr**cre(2), cre(2) = 1
     mvd_r = MVD_FAC * ilamr;
     return N0_r * c.crg4 * pw7(ilamr);                                    // ilamr**cre(4), M:5130
+}
+__device__ inline double rain_ze(const ReflConsts &c, double rho, double qr, double nr1, double &mvd_r)
+{
+    double lamr;
+    return rain_ze(c, rho, qr, nr1, mvd_r, lamr);
 }
 // snow of a level with qs > R2, M:5033-5038 and M:5131-5132
 __device__ inline double snow_ze(const ReflConsts &c, const SnowLevel &s) { return ZE_SNOW_FAC * snow_moment(c.sa, c.sb, c.cse3, s); }
@@ -135,14 +152,19 @@ __device__ inline double graupel_n0_exp(bool slw, double mvd_r, double rg)
     const double n0 = fm::exp10(zans1);
     return fmax(gonv_min, fmin(n0, gonv_max));
 }
-// graupel of a level with qg > R2 once the running minimum N0_exp is known, M:5099-5102 and M:5133-5135
-__device__ inline double graupel_ze(const ReflConsts &c, double N0_exp, double rg)
+// graupel of a level with qg > R2 once the running minimum N0_exp is known, M:5099-5102 and M:5133-5135; ilamg goes out too
+__device__ inline double graupel_ze(const ReflConsts &c, double N0_exp, double rg, double &ilamg)
 {
     const double lam_exp = fm::sqrt_pos(fm::sqrt_pos(N0_exp * am_g * c.cgg1 / rg));    // **oge1
     const double lamg = lam_exp * c.lamg_fac;
-    const double ilamg = 1. / lamg;
+    ilamg = 1. / lamg;
     const double N0_g = N0_exp / (c.cgg2 * lam_exp) * lamg;                             // lamg**cge(2), cge(2) = 1
     return ZE_GRAUPEL_FAC * N0_g * c.cgg4 * pw7(ilamg);                                 // ilamg**cge(4)
+}
+__device__ inline double graupel_ze(const ReflConsts &c, double N0_exp, double rg)
+{
+    double ilamg;
+    return graupel_ze(c, N0_exp, rg, ilamg);
 }
 __device__ inline double dbz_of(double ze) { return 10. * fm::log10(ze * 1.E18); }     // M:5196
 
@@ -250,6 +272,48 @@ __device__ inline int fall_substeps(double dt, double dz, double v)
 {
     const double x = dt / (dz / v) + 1.;
     return x < double(FALL_MAX_SUBSTEPS) ? int(x) : FALL_MAX_SUBSTEPS;    // a NaN counts as the cap
+}
+
+// ---- the Doppler moments (include/kidmp_doppler.h) at one level: the reflectivity-weighted mean vz = <v sigma>/<sigma>
+// and second moment v2 = <v**2 sigma>/<sigma> of the fall speed v(D) = rhof*av*D**bv*EXP(-fv*D) over the size distribution
+// calc_refl10cm gives the species, sigma ~ D**6 (rain, graupel) or D**(2 bm_s) (snow).  Closed forms; the exponents taken
+// as integers are pinned by doppler_consts_supported: mu_r = mu_g = 0 and bv_r = 1 (n = 7), bm_s = 2 (n = 5).  Every base
+// gives its logarithm once; vz and v2 share it. ----
+__device__ inline double pow_parts(const fm::Log2Parts &l, double y) { return fm::pow10_times_pow(0., l, y); }   // x**y, l = log2_parts(x)
+
+// rain: 7 lamr**7/(lamr+fv_r)**8 and 56 lamr**7/(lamr+2 fv_r)**9, formed from lamr/(lamr+f) <= 1 so that no power overflows
+__device__ inline void rain_doppler(const DopplerConsts &d, double rhof, double lamr, double &vz, double &v2)
+{
+    const double s1 = lamr + fv_r, s2 = lamr + 2. * fv_r;
+    const double va = rhof * av_r;
+    vz = va * d.gr1 * (pw7(lamr / s1) / s1);
+    v2 = va * va * d.gr2 * (pw7(lamr / s2) / (s2 * s2));
+}
+// graupel: Gamma(7+bv_g)/Gamma(7) ilamg**bv_g and Gamma(7+2 bv_g)/Gamma(7) ilamg**(2 bv_g); no MAX(vtg, vtrk) above T_0
+__device__ inline void graupel_doppler(const DopplerConsts &d, double rhof, double ilamg, double &vz, double &v2)
+{
+    const fm::Log2Parts l = fm::log2_parts(ilamg);
+    const double va = rhof * av_g;
+    vz = va * d.gg1 * pow_parts(l, bv_g);
+    v2 = va * va * d.gg2 * pow_parts(l, 2. * bv_g);
+}
+// snow: block O's t1..t4_vts form (M:3289-3299) at the reflectivity moment n = 2 bm_s + 1 = 5.  With Mrat = smob/smoc,
+//   A(b,f) = Kap0 Gamma(5+b) (Mrat Lam0 + f)**-(5+b) + Kap1 Mrat**mu_s Gamma(5+mu_s+b) (Mrat Lam1 + f)**-(5+mu_s+b)
+// and A(0,0) = Mrat**-5 * a00 with a00 a constant of the host.  No vts_boost, no above-freezing blend.
+__device__ inline void snow_doppler(const ReflConsts &c, const DopplerConsts &d, double rhof, const SnowLevel &s, double &vz, double &v2)
+{
+    const double smoc = snow_moment(c.sa, c.sb, d.cse1, s);
+    const double Mrat = s.smob / smoc;
+    const double mm = pow_parts(fm::log2_parts(Mrat), mu_s);
+    const double m2 = Mrat * Mrat, m5 = m2 * m2 * Mrat;
+    const double x0 = Mrat * Lam0, x1 = Mrat * Lam1;
+    const double a1 = d.ks0_1 * pow_parts(fm::log2_parts(x0 + fv_s), -(5. + bv_s))
+                    + d.ks1_1 * mm * pow_parts(fm::log2_parts(x1 + fv_s), -(5. + mu_s + bv_s));
+    const double a2 = d.ks0_2 * pow_parts(fm::log2_parts(x0 + 2. * fv_s), -(5. + 2. * bv_s))
+                    + d.ks1_2 * mm * pow_parts(fm::log2_parts(x1 + 2. * fv_s), -(5. + mu_s + 2. * bv_s));
+    const double va = rhof * av_s, ia00 = m5 * d.ia00;                   // 1/A(0,0)
+    vz = va * (a1 * ia00);
+    v2 = va * va * (a2 * ia00);
 }
 
 }  // namespace lvl

@@ -64,4 +64,20 @@ bool fall_consts_supported(const Consts &hc);
 template <class T>
 hipError_t launch_fall_speeds(const Consts *d_consts, int64_t ncol, int nz, const FallArgs<T> &a, hipStream_t stream);
 
+
+// The Doppler moments of a vertically pointing radar (include/kidmp_doppler.h): reflectivity, mean Doppler velocity and
+// spectrum width of every level, from calc_refl10cm's load and size distributions.  Null means: qs, qg -- zero; w -- zero;
+// an output -- not wanted.  out: dbz, vd, sw, vz_r, vz_s, vz_g, dbz_r, dbz_s, dbz_g.
+constexpr int DOPPLER_NOUT = 9;
+template <class T> struct DopplerArgs {
+    const T *t, *p, *qv, *qr, *nr, *qs, *qg, *w;
+    T *out[DOPPLER_NOUT];
+};
+// the exponents lvl:: takes as integer powers beyond those of refl_consts_supported
+bool doppler_consts_supported(const Consts &hc);
+DopplerConsts doppler_consts(const Consts &hc);
+template <class T>
+hipError_t launch_doppler_moments(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const DopplerArgs<T> &a,
+                                  hipStream_t stream);
+
 }  // namespace kidmp

@@ -21,6 +21,7 @@
 // per-level arithmetic of both diagnostics is thompson_levels.h, shared with the pointwise k_effective_radii.
 #include "thompson_reflectivity.h"
 
+#include <cmath>
 #include <type_traits>
 
 #include "thompson_levels.h"
@@ -516,6 +517,107 @@ k_fall_speeds(const Consts *__restrict__ hc, FallArgs<T> a, int64_t ncol, int nz
     if (count && lane < 4) a.nstep[col * 4 + lane] = lane == 0 ? ns_r : lane == 1 ? ns_i : lane == 2 ? ns_s : ns_g;
 }
 
+// One wavefront per column: the three radar moments of every level (include/kidmp_doppler.h).  The load, the ze_* and the
+// order of their sum are column_dbz's, through the same lvl:: functions; beside them the reflectivity-weighted first and
+// second moments of each species' fall speed.  Rain and snow are finished before the graupel scan and leave only their
+// sums behind; graupel follows the running minimum of its intercept.  Nothing but the fastmath tables is in LDS.
+template <class T, int NJ>
+__global__ void __launch_bounds__(REFL_THREADS)
+k_doppler_moments(ReflConsts c, DopplerConsts dc, DopplerArgs<T> a, int64_t ncol, int nz)
+{
+#if KFM_TABLES
+    fm::tab::load_tables(int(threadIdx.x), REFL_THREADS);
+    __syncthreads();
+#endif
+    const int lane = int(threadIdx.x) & 63;
+    const int64_t col = int64_t(blockIdx.x) * REFL_WAVES + (int(threadIdx.x) >> 6);
+    if (col >= ncol) return;                                         // whole wavefronts only: the scan needs every lane
+    const int64_t base = col * int64_t(nz);
+
+    // of rain and snow together: ze with the 1.E-22 of an absent species (dbz), ze of the present ones, ze*vz, ze*v2
+    double ze_rs[NJ], wt[NJ], m1[NJ], m2[NJ], rhof[NJ], rg[NJ], n0[NJ];
+    bool lqg[NJ], any[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        ze_rs[j] = wt[j] = m1[j] = m2[j] = rhof[j] = 0.;
+        rg[j] = R1;
+        lqg[j] = any[j] = false;
+        n0[j] = double(__builtin_inf());                             // levels past kte do not enter the minimum
+        if (k >= nz) continue;
+        const int64_t i = base + k;
+        // ---- load, M:4991-5028 ----
+        const double temp = double(a.t[i]);
+        const double qv = fmax(1.E-10, double(a.qv[i]));
+        const double rho = lvl::air_density(double(a.p[i]), temp, qv);
+        const double qr = double(a.qr[i]);
+        const double qs = a.qs ? double(a.qs[i]) : 0.;
+        const double qg = a.qg ? double(a.qg[i]) : 0.;
+        const bool L_qr = qr > R1, L_qs = qs > R2;
+        lqg[j] = qg > R2;
+        any[j] = L_qr || L_qs || lqg[j];
+        rhof[j] = fm::sqrt_pos(rho_not / rho);
+        double ze_rain = 1.E-22, ze_snow = 1.E-22, mvd_r = 50.E-6;
+        double vz_r = 0., v2_r = 0., vz_s = 0., v2_s = 0.;
+        if (L_qr) {
+            double lamr;
+            ze_rain = lvl::rain_ze(c, rho, qr, double(a.nr[i]), mvd_r, lamr);
+            lvl::rain_doppler(dc, rhof[j], lamr, vz_r, v2_r);
+        }
+        if (L_qs) {
+            const lvl::SnowLevel sl = lvl::snow_level(temp, qs * rho, c.oams);
+            ze_snow = lvl::snow_ze(c, sl);
+            lvl::snow_doppler(c, dc, rhof[j], sl, vz_s, v2_s);
+        }
+        if (lqg[j]) rg[j] = qg * rho;
+        ze_rs[j] = ze_rain + ze_snow;
+        wt[j] = (L_qr ? ze_rain : 0.) + (L_qs ? ze_snow : 0.);
+        m1[j] = ze_rain * vz_r + ze_snow * vz_s;                     // an absent species has vz = v2 = +0.0
+        m2[j] = ze_rain * v2_r + ze_snow * v2_s;
+        n0[j] = lvl::graupel_n0_exp(temp < 270.65 && L_qr && mvd_r > 100.E-6, mvd_r, rg[j]);
+        if (a.out[3]) a.out[3][i] = T(vz_r);
+        if (a.out[4]) a.out[4][i] = T(vz_s);
+        if (a.out[6]) a.out[6][i] = T(lvl::dbz_of(ze_rain));
+        if (a.out[7]) a.out[7][i] = T(lvl::dbz_of(ze_snow));
+    }
+
+    // ---- N0_min = MIN(N0_exp, N0_min) from kte down to kts (M:5097-5098) ----
+    double carry = gonv_max;
+#pragma unroll
+    for (int j = NJ - 1; j >= 0; --j) {
+        double tail;
+        const double s = wave_suffix_min(n0[j], lane, tail);
+        n0[j] = fmin(s, carry);
+        carry = fmin(carry, tail);
+    }
+
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        if (k >= nz) continue;
+        const int64_t i = base + k;
+        double ze_graupel = 1.E-22, vz_g = 0., v2_g = 0.;
+        if (lqg[j]) {
+            double ilamg;
+            ze_graupel = lvl::graupel_ze(c, n0[j], rg[j], ilamg);
+            lvl::graupel_doppler(dc, rhof[j], ilamg, vz_g, v2_g);
+        }
+        if (a.out[0]) a.out[0][i] = T(lvl::dbz_of(ze_rs[j] + ze_graupel));          // M:5196
+        if (a.out[5]) a.out[5][i] = T(vz_g);
+        if (a.out[8]) a.out[8][i] = T(lvl::dbz_of(ze_graupel));
+        double vd = 0., sw = 0.;                                     // a level with no species: +0.0, w is not applied
+        if (any[j]) {
+            const double W = wt[j] + (lqg[j] ? ze_graupel : 0.);
+            const double V = (m1[j] + ze_graupel * vz_g) / W;
+            const double var = (m2[j] + ze_graupel * v2_g) / W - V * V;
+            vd = V - (a.w ? double(a.w[i]) : 0.);
+            sw = var > 0. ? fm::sqrt_pos(var) : 0.;
+        }
+        if (a.out[1]) a.out[1][i] = T(vd);
+        if (a.out[2]) a.out[2][i] = T(sw);
+    }
+}
+
 // the reflectivity alone; the kernel name rocprofv3 lists is kidmp::k_reflectivity<T, NJ>
 template <class T, int NJ>
 __global__ void __launch_bounds__(REFL_THREADS)
@@ -679,6 +781,47 @@ hipError_t launch_fall_speeds(const Consts *c, int64_t ncol, int nz, const FallA
 }
 template hipError_t launch_fall_speeds<double>(const Consts *, int64_t, int, const FallArgs<double> &, hipStream_t);
 template hipError_t launch_fall_speeds<float>(const Consts *, int64_t, int, const FallArgs<float> &, hipStream_t);
+
+template <class T>
+hipError_t launch_doppler_moments(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const DopplerArgs<T> &a, hipStream_t s)
+{
+    if (ncol <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((ncol + REFL_WAVES - 1) / REFL_WAVES)), block(REFL_THREADS);
+    switch ((nz + 63) / 64) {
+    case 1: hipLaunchKernelGGL((k_doppler_moments<T, 1>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 2: hipLaunchKernelGGL((k_doppler_moments<T, 2>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 3: hipLaunchKernelGGL((k_doppler_moments<T, 3>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 4: hipLaunchKernelGGL((k_doppler_moments<T, 4>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+template hipError_t launch_doppler_moments<double>(const ReflConsts &, const DopplerConsts &, int64_t, int, const DopplerArgs<double> &, hipStream_t);
+template hipError_t launch_doppler_moments<float>(const ReflConsts &, const DopplerConsts &, int64_t, int, const DopplerArgs<float> &, hipStream_t);
+
+bool doppler_consts_supported(const Consts &hc)
+{
+    // beyond refl_consts_supported: n = 7 + mu_r = 7 + mu_g = 7 and bv_r = 1 (rain's integer powers), n = 2 bm_s + 1 = 5 and
+    // cse(1) = bm_s + 1 (snow)
+    return refl_consts_supported(hc) && mu_r == 0.0 && mu_g == 0.0 && bv_r == 1.0 && bm_s == 2.0 && hc.cse[0] == 3.;
+}
+
+DopplerConsts doppler_consts(const Consts &hc)
+{
+    DopplerConsts d{};
+    const double nr_ = 7. + mu_r, ng_ = 7. + mu_g, ns_ = 2. * bm_s + 1.;
+    d.cse1 = hc.cse[0];
+    d.gr1 = std::tgamma(nr_ + bv_r) / std::tgamma(nr_);
+    d.gr2 = std::tgamma(nr_ + 2. * bv_r) / std::tgamma(nr_);
+    d.gg1 = std::tgamma(ng_ + bv_g) / std::tgamma(ng_);
+    d.gg2 = std::tgamma(ng_ + 2. * bv_g) / std::tgamma(ng_);
+    d.ks0_1 = Kap0 * std::tgamma(ns_ + bv_s);
+    d.ks1_1 = Kap1 * std::tgamma(ns_ + mu_s + bv_s);
+    d.ks0_2 = Kap0 * std::tgamma(ns_ + 2. * bv_s);
+    d.ks1_2 = Kap1 * std::tgamma(ns_ + mu_s + 2. * bv_s);
+    d.ia00 = 1. / (Kap0 * std::tgamma(ns_) * std::pow(Lam0, -ns_) + Kap1 * std::tgamma(ns_ + mu_s) * std::pow(Lam1, -(ns_ + mu_s)));
+    return d;
+}
 
 bool fall_consts_supported(const Consts &hc)
 {

@@ -61,6 +61,7 @@ module module_mp_thompson09n
   public :: mp_thompson_set_column_nc
   public :: column_summary_batch
   public :: fall_speeds_batch
+  public :: doppler_moments_batch
   public :: mp_thompson_kid_interface, mp_thompson_kid_staging
   logical, public :: is_aerosol_aware = .false.          ! M:28 (read at thompson_init)
   logical, public :: l_rate_diagnostics = .true.         ! replay the save_dg calls of M:2962-3124
@@ -96,6 +97,9 @@ module module_mp_thompson09n
   type, bind(C) :: kidmp_fall_out                        ! kidmp_fall_out / kidmp32_fall_out: [ncol][nz] each, NULL = not wanted
      type(c_ptr) :: vt_r, vt_nr, vt_i, vt_ni, vt_s, vt_g, flux_r, flux_i, flux_s, flux_g, flux_total
   end type kidmp_fall_out
+  type, bind(C) :: kidmp_doppler_out                     ! kidmp_doppler_out / kidmp32_doppler_out: [ncol][nz] each, NULL = not wanted
+     type(c_ptr) :: dbz, vd, sw, vz_r, vz_s, vz_g, dbz_r, dbz_s, dbz_g
+  end type kidmp_doppler_out
 
   type, bind(C) :: kidmp_kid_fields                      ! kidmp_kid_fields / kidmp32_kid_fields: KiD's fields, [ncol][nz] each
      type(c_ptr) :: theta, qv, qc, qr, nr, qi, ni, qs, qg
@@ -301,6 +305,25 @@ module module_mp_thompson09n
        type(kidmp_fall_out), intent(in) :: out
        type(c_ptr), value :: nstep
      end function kidmp32_fall_speeds_host
+     ! the Doppler moments of a vertically pointing radar (include/kidmp_doppler.h): qs, qg and w may be NULL (zero)
+     integer(c_int) function kidmp_doppler_moments_host(ctx, ncol, nz, t, p, qv, qr, nr, qs, qg, w, out) &
+          bind(C, name='kidmp_doppler_moments_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr, kidmp_doppler_out
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qr, nr, qs, qg, w   ! real(c_double) [ncol][nz]
+       type(kidmp_doppler_out), intent(in) :: out
+     end function kidmp_doppler_moments_host
+     integer(c_int) function kidmp32_doppler_moments_host(ctx, ncol, nz, t, p, qv, qr, nr, qs, qg, w, out) &
+          bind(C, name='kidmp32_doppler_moments_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr, kidmp_doppler_out
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qr, nr, qs, qg, w   ! real(c_float) [ncol][nz]
+       type(kidmp_doppler_out), intent(in) :: out
+     end function kidmp32_doppler_moments_host
   end interface
 
 contains
@@ -678,6 +701,50 @@ contains
     end if
     call stop_on_error(rc, 'fall_speeds_batch')
   end subroutine fall_speeds_batch
+
+  ! The radar moments of a state over ncol columns of KiD's (nz, ncol) storage in one call (include/kidmp_doppler.h):
+  ! reflectivity dbz (dBZ), mean Doppler velocity vd and spectrum width sw (m s-1, positive downward), and the per-species
+  ! parts vz_r, vz_s, vz_g (m s-1) and dbz_r, dbz_s, dbz_g they are formed from.  Every output is optional, in the array
+  ! kind the arithmetic stores; at least one must be present.  qs and qg left out mean zero; w is the vertical air velocity
+  ! (positive upward), left out: still air.  A level without rain, snow and graupel has vd = sw = 0.  The inputs are not
+  ! changed.  Default REAL 8 goes to kidmp_doppler_moments_host, REAL 4 to kidmp32_...
+  subroutine doppler_moments_batch(ncol, nz, t, p, qv, qr, nr, dbz, vd, sw, vz_r, vz_s, vz_g, dbz_r, dbz_s, dbz_g, qs, qg, w)
+    integer, intent(in) :: ncol, nz
+    real, dimension(nz,ncol), intent(in), target :: t, p, qv, qr, nr
+    real, dimension(nz,ncol), intent(out), optional, target :: dbz, vd, sw, vz_r, vz_s, vz_g, dbz_r, dbz_s, dbz_g
+    real, dimension(nz,ncol), intent(in), optional, target :: qs, qg, w
+    type(kidmp_doppler_out) :: out
+    type(c_ptr) :: pqs, pqg, pw
+    integer(c_int) :: rc
+    if (.not. c_associated(ctx)) call thompson_init
+    if (c_associated(mctx)) then
+       write(*,'(a)') ' module_mp_thompson09n: Doppler moments are not available with kidmp_ndevices > 1'
+       stop 1
+    end if
+    pqs = c_null_ptr;  pqg = c_null_ptr;  pw = c_null_ptr
+    if (present(qs)) pqs = c_loc(qs)
+    if (present(qg)) pqg = c_loc(qg)
+    if (present(w)) pw = c_loc(w)
+    out = kidmp_doppler_out(c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
+         c_null_ptr)
+    if (present(dbz)) out%dbz = c_loc(dbz)
+    if (present(vd)) out%vd = c_loc(vd)
+    if (present(sw)) out%sw = c_loc(sw)
+    if (present(vz_r)) out%vz_r = c_loc(vz_r)
+    if (present(vz_s)) out%vz_s = c_loc(vz_s)
+    if (present(vz_g)) out%vz_g = c_loc(vz_g)
+    if (present(dbz_r)) out%dbz_r = c_loc(dbz_r)
+    if (present(dbz_s)) out%dbz_s = c_loc(dbz_s)
+    if (present(dbz_g)) out%dbz_g = c_loc(dbz_g)
+    if (kind(t) == c_double) then
+       rc = kidmp_doppler_moments_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), c_loc(qr), &
+            c_loc(nr), pqs, pqg, pw, out)
+    else
+       rc = kidmp32_doppler_moments_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), c_loc(qr), &
+            c_loc(nr), pqs, pqg, pw, out)
+    end if
+    call stop_on_error(rc, 'doppler_moments_batch')
+  end subroutine doppler_moments_batch
 
   ! A droplet number per column (kidmp_set_column_nc): column i of every following batched call uses Nt_c =
   ! set_nc_col(i)*1.e6 (M:381) in place of the namelist's set_Nc -- an Nd ensemble, or an aerosol gradient along x, in

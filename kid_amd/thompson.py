@@ -598,6 +598,17 @@ class ThompsonMP:
         from .fall import FALL_NAMES, fall_speeds_host
         return fall_speeds_host(self, st, boost, dz, dt, FALL_NAMES if want is None else want)
 
+    def doppler_moments(self, st, w=None, want=None, stream=None):
+        """Reflectivity, mean Doppler velocity and spectrum width of every level, with the per-species parts they are
+        formed from (include/kidmp_doppler.h): kid_amd.doppler.doppler_moments on this context."""
+        from .doppler import DOPPLER_NAMES, doppler_moments
+        return doppler_moments(self, st, w, DOPPLER_NAMES if want is None else want, stream)
+
+    def doppler_moments_host(self, st, w=None, want=None):
+        """doppler_moments on numpy arrays: kid_amd.doppler.doppler_moments_host on this context."""
+        from .doppler import DOPPLER_NAMES, doppler_moments_host
+        return doppler_moments_host(self, st, w, DOPPLER_NAMES if want is None else want)
+
     REFL_NAMES = ("t", "p", "qv", "qr", "nr", "qs", "qg")      # the inputs of calc_refl10cm that are read (qc1d is not)
 
     def reflectivity(self, st, out=None, stream=None):
