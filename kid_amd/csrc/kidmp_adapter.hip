@@ -5,25 +5,12 @@
 #include <cmath>
 
 #include "kidmp_ctx.h"
+#include "kidmp_stream.h"
 
 using namespace kidmp;
+using namespace kidmp::streaming;
 
 namespace {
-// 16 bytes of T (V = 2 doubles / 4 floats), or one element (V = 1) where nz or an address does not allow the wide form
-template <class T, int V> struct alignas(sizeof(T) * V) Vec { T v[V]; };
-
-// a null array is a literal zero operand: never read, and (0 + x), (x + 0) round as with an array of +0.0
-template <class T, int V> __device__ inline Vec<T, V> ld(const T *p, int64_t e)
-{
-    Vec<T, V> r;
-    if (p) r = *reinterpret_cast<const Vec<T, V> *>(p + e);
-    else
-#pragma unroll
-        for (int j = 0; j < V; ++j) r.v[j] = T(0);
-    return r;
-}
-template <class T, int V> __device__ inline void st(T *p, int64_t e, const Vec<T, V> &x) { *reinterpret_cast<Vec<T, V> *>(p + e) = x; }
-
 // KID_WORK_OF for device code
 __host__ __device__ constexpr int work_of(int m)
 {
@@ -119,14 +106,6 @@ __global__ __launch_bounds__(256) void k_kid_backout(const BackoutArgs<T> a)
         for (int m = 0; m < NF; ++m) st<T, V>(a.mphys[m], e, r[m]);
     }
 }
-
-// a grid sized to the chip (256 CUs, eight blocks of 256 lanes each), walked with a grid-stride loop
-unsigned grid_for(int64_t nvec)
-{
-    const int64_t g = (nvec + 255) / 256;
-    return unsigned(g < 1 ? 1 : g > 2048 ? 2048 : g);
-}
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 template <class T, class A> bool wide_ok(const A &a, int32_t nz, const void *const *more, int nmore)
 {

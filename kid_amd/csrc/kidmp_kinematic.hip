@@ -1,0 +1,326 @@
+// kidmp_kinematic.hip -- the entries of include/kidmp_kinematic.h: prescribed-w vertical advection of KiD's nine fields in
+// the adv / div form the adapter consumes (k_kid_advect) and the state update that closes the time loop (k_kid_update).
+// The scheme is the project's own, fixed to the operation.  Built with the library's plain flags
+// (IEEE division, no contraction): every operation below rounds once.
+#include "kidmp_ctx.h"
+#include "kidmp_stream.h"
+#include "../../include/kidmp_kinematic.h"
+
+using namespace kidmp;
+using namespace kidmp::streaming;
+
+namespace {
+constexpr int ADV_WAVES = 4;                             // columns (wavefronts) per workgroup
+constexpr int ADV_THREADS = 64 * ADV_WAVES;
+const char *const FIELD_NAMES[KID_NF] = {"theta", "qv", "qc", "qr", "nr", "qi", "ni", "qs", "qg"};
+
+template <class T> struct AdvectArgs {
+    const T *state[KID_NF];
+    T *adv[KID_NF], *div[KID_NF], *sum[KID_NF];          // null: not wanted
+    const T *w, *rho, *dz;
+    int64_t w_col_stride;
+    T *courant;
+    double dt;
+};
+template <class T> struct UpdateArgs {
+    T *state[KID_NF];                                    // null: skipped
+    const T *t[3][KID_NF];                               // null: a zero operand
+    int64_t n;
+    T dt;
+    int32_t clip;
+};
+
+// ---- a shift by one level across the whole wave ----
+// One DPP move per half: wave_shr:1 hands lane l the value of lane l - 1, wave_shl:1 that of lane l + 1; the one lane
+// without a source (0, or 63) keeps `edge`, which is where the neighbouring level group hands its end over.
+constexpr int DPP_WAVE_SHL1 = 0x130, DPP_WAVE_SHR1 = 0x138;
+template <int CTRL>
+__device__ inline double wave_shift(double edge, double v)
+{
+    const long long e = __double_as_longlong(edge), b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_update_dpp(int(e & 0xffffffffll), int(b & 0xffffffffll), CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(int(e >> 32), int(b >> 32), CTRL, 0xf, 0xf, false);
+    return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned int>(lo));
+}
+__device__ inline double readlane(double v, int lane)
+{
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_readlane(int(b & 0xffffffffll), lane);
+    const int hi = __builtin_amdgcn_readlane(int(b >> 32), lane);
+    return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned int>(lo));
+}
+// out[j] of level k = v of level k - 1; level 0 receives an unspecified finite value (the caller masks it)
+template <int NJ>
+__device__ inline void level_below(const double (&v)[NJ], double (&out)[NJ])
+{
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) out[j] = wave_shift<DPP_WAVE_SHR1>(j ? readlane(v[j - 1], 63) : 0., v[j]);
+}
+// out[j] of level k = v of level k + 1; the last lane of the last group receives an unspecified finite value
+template <int NJ>
+__device__ inline void level_above(const double (&v)[NJ], double (&out)[NJ])
+{
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) out[j] = wave_shift<DPP_WAVE_SHL1>(j + 1 < NJ ? readlane(v[j + 1], 0) : 0., v[j]);
+}
+__device__ inline double wave_max(double v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v = fmax(v, __shfl_xor(v, m, 64));
+    return v;
+}
+
+// One wavefront per column, level k = 64 j + lane.  Cell k owns its lower face k: the mass flux M and the Courant number c
+// of that face are formed once per column and kept in registers with what every member shares (den, the divergence
+// factor, the upwind side); then each present member is loaded once, its neighbours k-1, k-2 and k+1 come from the
+// neighbouring lanes, its face value and flux are formed once per lane and the flux of face k+1 comes from the lane
+// above.  The lane that holds level nz-1 forms the top face itself.  No LDS, no scratch.
+template <class T, int NJ>
+__global__ void __launch_bounds__(ADV_THREADS)
+k_kid_advect(const AdvectArgs<T> a, int64_t ncol, int nz)
+{
+    const int lane = int(threadIdx.x) & 63;
+    const int64_t col = int64_t(blockIdx.x) * ADV_WAVES + (int(threadIdx.x) >> 6);
+    if (col >= ncol) return;                                         // whole wavefronts only: the shifts need every lane
+    const int64_t base = col * int64_t(nz);
+    const T *const w = a.w + col * a.w_col_stride;
+
+    double M[NJ], Mup[NJ], den[NJ], hc[NJ], dM[NJ];                  // hc = 0.5*(1.0 - c) of face k
+    bool up[NJ], second[NJ];                                         // w[k] >= 0; uu of face k inside the column
+    double cmax = 0.;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        M[j] = Mup[j] = hc[j] = 0.;
+        den[j] = 1.;
+        up[j] = true;
+        second[j] = false;
+        if (k >= nz) continue;
+        const double rho = double(a.rho[k]), dz = double(a.dz[k]), wk = double(w[k]);
+        const double rho_lo = k ? double(a.rho[k - 1]) : rho, dz_lo = k ? double(a.dz[k - 1]) : dz;
+        const double rf = k ? 0.5 * (rho_lo + rho) : rho;
+        up[j] = wk >= 0.;
+        second[j] = up[j] ? k >= 2 : k + 1 < nz;
+        M[j] = rf * wk;
+        const double c = (fabs(wk) * a.dt) / (up[j] ? dz_lo : dz);
+        hc[j] = 0.5 * (1.0 - c);
+        den[j] = rho * dz;
+        cmax = fmax(cmax, c);
+        if (k == nz - 1) {                                           // the model top: rf = rho[nz-1], dz[nz-1]
+            const double wt = double(w[nz]);
+            Mup[j] = rho * wt;
+            cmax = fmax(cmax, (fabs(wt) * a.dt) / dz);
+        }
+    }
+    {
+        double above[NJ];
+        level_above<NJ>(M, above);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            if (64 * j + lane != nz - 1) Mup[j] = above[j];
+            dM[j] = (Mup[j] - M[j]) / den[j];
+        }
+    }
+    if (a.courant) {
+        cmax = wave_max(cmax);
+        if (lane == 0) a.courant[col] = T(cmax);
+    }
+
+#pragma unroll
+    for (int m = 0; m < KID_NF; ++m) {
+        if (!a.state[m] || !(a.adv[m] || a.div[m] || a.sum[m])) continue;
+        double q[NJ], q1[NJ], q2[NJ], qa[NJ], F[NJ], Fup[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int k = 64 * j + lane;
+            q[j] = k < nz ? double(a.state[m][base + k]) : 0.;
+        }
+        level_below<NJ>(q, q1);                                      // q[k-1]
+        level_below<NJ>(q1, q2);                                     // q[k-2]
+        level_above<NJ>(q, qa);                                      // q[k+1]
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int k = 64 * j + lane;
+            const double qu = up[j] ? q1[j] : q[j], qd = up[j] ? q[j] : q1[j], quu = up[j] ? q2[j] : qa[j];
+            const double dq = qd - qu, b = qu - quu, bd = b * dq;
+            const double s = second[j] && bd > 0. ? (2.0 * bd) / (b + dq) : 0.;
+            const double qf = k ? qu + hc[j] * s : q[j];             // qf[0] = q[0]
+            F[j] = M[j] * qf;
+        }
+        level_above<NJ>(F, Fup);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int k = 64 * j + lane;
+            if (k >= nz) continue;
+            if (k == nz - 1) Fup[j] = Mup[j] * q[j];                 // qf[nz] = q[nz-1]
+            const double adv = -((Fup[j] - F[j]) / den[j]);
+            const double div = q[j] * dM[j];
+            if (a.adv[m]) a.adv[m][base + k] = T(adv);
+            if (a.div[m]) a.div[m][base + k] = T(div);
+            if (a.sum[m]) a.sum[m][base + k] = T(adv + div);
+        }
+    }
+}
+
+// X = X + ((t1 + t2) + t3)*dt in T, then the clip of everything but theta: one element (V of them) per lane-slot
+template <class T, int V, int NF>
+__global__ __launch_bounds__(256) void k_kid_update(const UpdateArgs<T> a)
+{
+    const int64_t stride = int64_t(gridDim.x) * blockDim.x, nvec = a.n / V;
+    for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < nvec; i += stride) {
+        const int64_t e = i * V;
+#pragma unroll
+        for (int m = 0; m < NF; ++m) {
+            if (!a.state[m]) continue;
+            Vec<T, V> x = ld<T, V>(a.state[m], e);
+            const Vec<T, V> t1 = ld<T, V>(a.t[0][m], e), t2 = ld<T, V>(a.t[1][m], e), t3 = ld<T, V>(a.t[2][m], e);
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                x.v[j] = x.v[j] + ((t1.v[j] + t2.v[j]) + t3.v[j]) * a.dt;
+                if (m && a.clip) x.v[j] = x.v[j] < T(0) ? T(0) : x.v[j];
+            }
+            st<T, V>(a.state[m], e, x);
+        }
+    }
+}
+
+template <class T, class F> void members(const F *f, T *(&out)[KID_NF], int nf)
+{
+    for (int m = 0; m < KID_NF; ++m) out[m] = nullptr;
+    if (!f) return;
+    T *const p[KID_NF] = {f->theta, f->qv, f->qc, f->qr, f->nr, f->qi, f->ni, f->qs, f->qg};
+    for (int m = 0; m < nf; ++m) out[m] = p[m];
+}
+
+// what both entries refuse alike, before anything is touched; KIDMP_OK with ncol == 0 means: nothing to do
+int check_shape(kidmp_ctx *ctx, const std::string &w, int64_t ncol, int32_t nz, double dt)
+{
+    if (int rc = require_ready(ctx)) return rc;
+    if (ncol < 0) return fail(ctx, KIDMP_EINVAL, w + ": ncol < 0");
+    if (nz < 2 || nz > KIDMP_MAX_NZ) return fail(ctx, KIDMP_EINVAL, w + ": nz outside [2, KIDMP_MAX_NZ]");
+    if (!(dt > 0.)) return fail(ctx, KIDMP_EINVAL, w + ": dt must be > 0");
+    if (ncol > int64_t(0x7fffffff)) return fail(ctx, KIDMP_EINVAL, w + ": more columns than one launch takes");
+    return KIDMP_OK;
+}
+
+template <class T, class F>
+int advect_device(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, double dt, const F *state, const T *w, int64_t w_col_stride,
+                  const T *rho, const T *dz, const F *adv, const F *div, const F *sum, T *courant, void *stream)
+{
+    const std::string me(who);
+    if (int rc = check_shape(ctx, me, ncol, nz, dt)) return rc;
+    if (w_col_stride != 0 && w_col_stride < int64_t(nz) + 1) return fail(ctx, KIDMP_EINVAL, me + ": w_col_stride must be 0 or >= nz+1");
+    if (ncol == 0) return KIDMP_OK;                                  // an empty batch has nothing to point at
+    if (!state || !w || !rho || !dz) return fail(ctx, KIDMP_EINVAL, me + ": null argument (state, w, rho and dz are required)");
+    const int nf = ctx->cfg.iiwarm ? KID_NWARM : KID_NF;             // the frozen members are not looked at in a warm context
+    AdvectArgs<T> a{};
+    T *s[KID_NF];
+    members<T>(state, s, nf);
+    members<T>(adv, a.adv, nf);
+    members<T>(div, a.div, nf);
+    members<T>(sum, a.sum, nf);
+    bool any = courant != nullptr;
+    for (int m = 0; m < KID_NF; ++m) {
+        if (m < KID_NWARM && !s[m]) return fail(ctx, KIDMP_EINVAL, me + ": theta, qv, qc, qr and nr of state are required");
+        if (!s[m]) a.adv[m] = a.div[m] = a.sum[m] = nullptr;         // not advected: its outputs are not written
+        a.state[m] = s[m];
+        any = any || a.adv[m] || a.div[m] || a.sum[m];
+    }
+    if (!any) return fail(ctx, KIDMP_EINVAL, me + ": nothing requested: no output member of a present field and no courant");
+    GUARD(ctx);
+    for (int m = 0; m < KID_NF; ++m) {
+        if (int rc = check_device_array(ctx, who, a.state[m], FIELD_NAMES[m])) return rc;
+        if (int rc = check_device_array(ctx, who, a.adv[m], "a member of adv")) return rc;
+        if (int rc = check_device_array(ctx, who, a.div[m], "a member of div")) return rc;
+        if (int rc = check_device_array(ctx, who, a.sum[m], "a member of sum")) return rc;
+    }
+    const void *more[] = {w, rho, dz, courant};
+    const char *names[] = {"w", "rho", "dz", "courant"};
+    for (int i = 0; i < 4; ++i)
+        if (int rc = check_device_array(ctx, who, more[i], names[i])) return rc;
+    a.w = w; a.rho = rho; a.dz = dz; a.w_col_stride = w_col_stride; a.courant = courant; a.dt = dt;
+    const dim3 grid((unsigned)((ncol + ADV_WAVES - 1) / ADV_WAVES)), block(ADV_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    switch ((nz + 63) / 64) {
+    case 1: hipLaunchKernelGGL((k_kid_advect<T, 1>), grid, block, 0, st, a, ncol, nz); break;
+    case 2: hipLaunchKernelGGL((k_kid_advect<T, 2>), grid, block, 0, st, a, ncol, nz); break;
+    case 3: hipLaunchKernelGGL((k_kid_advect<T, 3>), grid, block, 0, st, a, ncol, nz); break;
+    default: hipLaunchKernelGGL((k_kid_advect<T, 4>), grid, block, 0, st, a, ncol, nz); break;
+    }
+    HIPTRY(ctx, hipGetLastError());
+    return KIDMP_OK;
+}
+
+template <class T, class F>
+int update_device(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, T dt, const F *state, const F *t1, const F *t2, const F *t3,
+                  int32_t clip, void *stream)
+{
+    const std::string me(who);
+    if (int rc = check_shape(ctx, me, ncol, nz, double(dt))) return rc;
+    if (ncol == 0) return KIDMP_OK;
+    if (!state) return fail(ctx, KIDMP_EINVAL, me + ": state is required");
+    const bool warm = ctx->cfg.iiwarm != 0;
+    const int nf = warm ? KID_NWARM : KID_NF;
+    UpdateArgs<T> a{};
+    members<T>(state, a.state, nf);
+    const F *const t[3] = {t1, t2, t3};
+    bool any = false;
+    for (int m = 0; m < KID_NF; ++m) any = any || a.state[m];
+    if (!any) return fail(ctx, KIDMP_EINVAL, me + ": nothing requested: state has no member");
+    for (int i = 0; i < 3; ++i) {
+        T *p[KID_NF];
+        members<T>(t[i], p, nf);
+        for (int m = 0; m < KID_NF; ++m) a.t[i][m] = a.state[m] ? p[m] : nullptr;
+    }
+    GUARD(ctx);
+    constexpr int V = 16 / int(sizeof(T));
+    bool wide = nz % V == 0;
+    for (int m = 0; m < KID_NF; ++m) {
+        if (int rc = check_device_array(ctx, who, a.state[m], FIELD_NAMES[m])) return rc;
+        wide = wide && aligned16(a.state[m]);
+        for (int i = 0; i < 3; ++i) {
+            if (int rc = check_device_array(ctx, who, a.t[i][m], "a member of a tendency")) return rc;
+            wide = wide && aligned16(a.t[i][m]);
+        }
+    }
+    a.n = ncol * int64_t(nz); a.dt = dt; a.clip = clip;
+    hipStream_t s = (hipStream_t)stream;
+    if (wide) {
+        if (warm) hipLaunchKernelGGL((k_kid_update<T, V, KID_NWARM>), dim3(grid_for(a.n / V)), dim3(256), 0, s, a);
+        else      hipLaunchKernelGGL((k_kid_update<T, V, KID_NF>), dim3(grid_for(a.n / V)), dim3(256), 0, s, a);
+    } else {
+        if (warm) hipLaunchKernelGGL((k_kid_update<T, 1, KID_NWARM>), dim3(grid_for(a.n)), dim3(256), 0, s, a);
+        else      hipLaunchKernelGGL((k_kid_update<T, 1, KID_NF>), dim3(grid_for(a.n)), dim3(256), 0, s, a);
+    }
+    HIPTRY(ctx, hipGetLastError());
+    return KIDMP_OK;
+}
+}  // namespace
+
+extern "C" {
+int kidmp_kid_advect_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, const kidmp_kid_fields *state,
+                            const double *w, int64_t w_col_stride, const double *rho, const double *dz,
+                            const kidmp_kid_fields *adv, const kidmp_kid_fields *div, const kidmp_kid_fields *sum, double *courant,
+                            void *stream)
+{
+    return advect_device<double>(ctx, "kidmp_kid_advect_device", ncol, nz, dt, state, w, w_col_stride, rho, dz, adv, div, sum, courant, stream);
+}
+int kidmp32_kid_advect_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, const kidmp32_kid_fields *state,
+                              const float *w, int64_t w_col_stride, const float *rho, const float *dz,
+                              const kidmp32_kid_fields *adv, const kidmp32_kid_fields *div, const kidmp32_kid_fields *sum, float *courant,
+                              void *stream)
+{
+    return advect_device<float>(ctx, "kidmp32_kid_advect_device", ncol, nz, dt, state, w, w_col_stride, rho, dz, adv, div, sum, courant, stream);
+}
+int kidmp_kid_update_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, const kidmp_kid_fields *state,
+                            const kidmp_kid_fields *t1, const kidmp_kid_fields *t2, const kidmp_kid_fields *t3, int32_t clip, void *stream)
+{
+    return update_device<double>(ctx, "kidmp_kid_update_device", ncol, nz, dt, state, t1, t2, t3, clip, stream);
+}
+int kidmp32_kid_update_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, float dt, const kidmp32_kid_fields *state,
+                              const kidmp32_kid_fields *t1, const kidmp32_kid_fields *t2, const kidmp32_kid_fields *t3, int32_t clip,
+                              void *stream)
+{
+    return update_device<float>(ctx, "kidmp32_kid_update_device", ncol, nz, dt, state, t1, t2, t3, clip, stream);
+}
+}  // extern "C"

@@ -829,6 +829,22 @@ class ThompsonMP:
         self._check(fn(*args, *code))
         return res
 
+    def kid_advect(self, state, w, rho, dz, dt, want=("sum",), courant=False, out=None, stream=None):
+        """Prescribed-w vertical advection of KiD's fields in the adapter's adv / div form (include/kidmp_kinematic.h):
+        kid_amd.kinematic.advect on this context."""
+        from .kinematic import advect
+        return advect(self, state, w, rho, dz, dt, want, courant, out, stream)
+
+    def kid_update(self, state, dt, *tendencies, clip=True, stream=None):
+        """state <- state + (t1 + t2 + t3)*dt in place, with the clip at zero: kid_amd.kinematic.update on this context."""
+        from .kinematic import update
+        return update(self, state, dt, *tendencies, clip=clip, stream=stream)
+
+    def kid_run(self, state, nsteps, dt, p0, r_on_cp, exner, dz, rho, w, fix_theta=False, on_step=None, stream=None, **kid_interface_options):
+        """A device-resident 1-D KiD case, advect -> kid_interface -> update per step: kid_amd.kinematic.run on this context."""
+        from .kinematic import run
+        return run(self, state, nsteps, dt, p0, r_on_cp, exner, dz, rho, w, fix_theta, on_step, stream, **kid_interface_options)
+
     def kernel_fingerprint(self, arith="p64"):
         """'src:<hash>;vgpr:<n>;lds:<bytes>;scratch:<bytes>' of this context's nz <= 120 column-step kernel, in the
         parity arithmetic (p64) or one of the binary32 ones (p32n, f32)."""
