@@ -11,3 +11,4 @@ from .summary import SUMMARY_INPUTS, SUMMARY_NAMES, column_summary, column_summa
 from .doppler import DOPPLER_INPUTS, DOPPLER_NAMES, doppler_moments, doppler_moments_host  # noqa: F401
 from .fall import FALL_INPUTS, FALL_NAMES, fall_speeds, fall_speeds_host  # noqa: F401
 from .kinematic import ADVECT_OUTPUTS, advect, run, update  # noqa: F401
+from .slab import advect_slab, run_slab, streamfunction_flow  # noqa: F401

@@ -1,0 +1,209 @@
+"""The kinematic half of a 2-D (x-z) KiD case on the device (include/kidmp_slab.h): prescribed-(u, w) advection of KiD's
+nine fields on a batch of independent slabs that are periodic in x, `streamfunction_flow`, which makes a mass-non-divergent
+flow for it, and `run_slab`, the device-resident loop over advect_slab, kid_interface and kinematic.update.  The advection
+scheme is the project's own, not KiD's.
+
+Only the two entries of kidmp_slab.h are declared here, on the object load_library() returned, the first time one of them
+is needed; the helpers and `update` are those of kid_amd.kinematic.  There is no fallback: without the library or the
+device a call raises KidmpError.
+"""
+import ctypes as C
+
+from . import kinematic as _kk
+from . import thompson as _th
+from .thompson import KID_FIELDS, KidmpError, _KidFields  # noqa: F401
+
+ADVECT_OUTPUTS = _kk.ADVECT_OUTPUTS
+
+
+def _declarations():
+    """name -> (restype, argtypes) of every entry of include/kidmp_slab.h."""
+    i32, i64, vp, rc, f, d = C.c_int32, C.c_int64, C.c_void_p, C.c_int, C.POINTER(_KidFields), C.c_double
+    advect = [vp, i64, i32, i32, d, d, f, vp, vp, i32, vp, vp, f, f, f, vp, vp]
+    return {"kidmp_kid_advect_slab_device": (rc, advect), "kidmp32_kid_advect_slab_device": (rc, advect)}
+
+
+def declare(L):
+    """Declare the entries of kidmp_slab.h on the loaded library `L`."""
+    for name, (restype, argtypes) in _declarations().items():
+        entry = getattr(L, name)
+        entry.restype, entry.argtypes = restype, argtypes
+    return L
+
+
+_declared = None
+
+
+def library():
+    """The library of load_library() with the slab entries declared."""
+    global _declared
+    L = _th.load_library()
+    if _declared is not L:
+        declare(L)
+        _declared = L
+    return L
+
+
+def _slab_shape(who, ncol, nx):
+    if isinstance(nx, bool) or not isinstance(nx, int):
+        _kk._refuse(who, "nx must be a whole number")
+    if nx < 3:
+        _kk._refuse(who, "nx must be >= 3 (the stencil i-2 .. i+2 must name distinct cells), got %d" % nx)
+    if ncol % nx != 0:
+        _kk._refuse(who, "ncol = %d is not a multiple of nx = %d" % (ncol, nx))
+    return ncol // nx
+
+
+def _flow(who, u, w, ncol, nx, nz):
+    """1 (one flow for every slab) or 0 (one per slab) from the shapes of u and w, which must agree; what the tensors are
+    is left to the caller's check."""
+    import torch
+    for name, a in (("u", u), ("w", w)):
+        if not isinstance(a, torch.Tensor):
+            _kk._refuse(who, "%s must be a torch tensor, got %s" % (name, type(a).__name__))
+    forms = []
+    for name, a, n in (("u", u, nz), ("w", w, nz + 1)):
+        if tuple(a.shape) == (nx, n):                          # nslab == 1: the two forms coincide and count as shared
+            forms.append(1)
+        elif tuple(a.shape) == (ncol, n):
+            forms.append(0)
+        else:
+            _kk._refuse(who, "%s must be [nx, %d] = [%d, %d] or [ncol, %d] = [%d, %d], got %s" % (name, n, nx, n, n, ncol, n, list(a.shape)))
+    if forms[0] != forms[1]:
+        _kk._refuse(who, "u and w must both be shared ([nx, ..]) or both per slab ([ncol, ..]), got %s and %s" % (list(u.shape), list(w.shape)))
+    return forms[0]
+
+
+def advect_slab(model, state, u, w, rho, dz, dx, dt, nx, want=("sum",), courant=False, out=None, stream=None):
+    """x-z advection tendencies of a device-resident KiD state on periodic slabs (kidmp[32]_kid_advect_slab_device): one
+    launch.
+
+    state   dict name -> CUDA tensor [ncol, nz] as for kinematic.advect; column s*nx + i is cell i of slab s, and
+            nslab = ncol / nx slabs are advected independently
+    u       x-face velocities in m/s, [nx, nz] for all slabs or [ncol, nz]: u[i, k] is at the left face of cell i
+    w       z-face velocities, [nx, nz+1] or [ncol, nz+1], shared or per slab as u is
+    rho, dz [nz] each, of the state's dtype; dx in m, dt in s
+    want, courant, out, stream   as for kinematic.advect; "courant" [ncol] is the unsplit stability number of each column
+    Returns {"adv": {member: tensor}, ...} for the names in `want`."""
+    import torch
+    who = "kid_advect_slab"
+    q, ncol, nz, check = _kk._state(who, model, state)
+    nslab = _slab_shape(who, ncol, nx)
+    want = _kk._wanted(who, want)
+    if not want and not courant:
+        _kk._refuse(who, "nothing requested: want is empty and courant is False")
+    dt = _kk._number(who, "dt", dt)
+    dx = _kk._number(who, "dx", dx)
+    shared = _flow(who, u, w, ncol, nx, nz)
+    f_state = _kk._members(who, model, state, "state", check, required=KID_FIELDS[:5])
+    check(u, "u", tuple(u.shape))
+    check(w, "w", tuple(w.shape))
+    check(rho, "rho", (nz,))
+    check(dz, "dz", (nz,))
+    keys = [k for k, _ in f_state]
+    if out is None:
+        res = {n: {k: torch.empty_like(q) for k in keys} for n in want}
+        if courant:
+            res["courant"] = torch.empty(ncol, dtype=q.dtype, device=q.device)
+    else:
+        res = out
+        if not isinstance(out, dict) or any(not isinstance(out.get(n), dict) for n in want) or (courant and out.get("courant") is None):
+            _kk._refuse(who, "out must be a dict returned by an earlier call with the same want and courant")
+        for n in want:
+            if sorted(out[n]) != sorted(keys):
+                _kk._refuse(who, "out[%r] must hold exactly the members %s" % (n, keys))
+            for k in keys:
+                check(out[n][k], "out[%r][%r]" % (n, k))
+        if courant:
+            check(out["courant"], "out['courant']", (ncol,))
+    c_state = _kk._fields(f_state)
+    c_out = {n: _kk._fields(res[n].items()) for n in want}
+    L = library()
+    fn = L.kidmp_kid_advect_slab_device if q.dtype == torch.float64 else L.kidmp32_kid_advect_slab_device
+    _kk._check(model, fn(model._h, nslab, nx, nz, dt, dx, C.byref(c_state), u.data_ptr(), w.data_ptr(), shared, rho.data_ptr(), dz.data_ptr(),
+                         *[C.byref(c_out[n]) if n in c_out else None for n in ADVECT_OUTPUTS],
+                         res["courant"].data_ptr() if courant else None, _th._stream(stream, q)))
+    return res
+
+
+def streamfunction_flow(psi, rho, dz, dx, nx=None):
+    """(u, w) of a stream function at the cell corners: plain torch, any device.
+
+    psi     [nx, nz+1], or [ncol, nz+1] with `nx` given (ncol = nslab*nx, each slab periodic on its own): psi[i, k] sits
+            at the left and lower corner of cell (i, k)
+    u = (-(psi[:, k+1] - psi[:, k])/dz[k])/rho[k]  at the left face of cell i;  w = ((psi[i+1] - psi[i])/dx)/rf[k]  at the
+    lower face, rf the face density of the 1-D entry (rho at both ends, the mean of the two cells inside).  The mass fluxes
+    rho*u*dz and rf*w*dx through a cell's four faces then sum to zero up to rounding.  Returns (u, w) shaped [.., nz] and
+    [.., nz+1] like psi: what advect_slab takes."""
+    import torch
+    who = "streamfunction_flow"
+    if not isinstance(psi, torch.Tensor) or psi.dim() != 2 or not all(isinstance(a, torch.Tensor) and a.dim() == 1 for a in (rho, dz)) \
+            or psi.shape[1] != rho.shape[0] + 1 or dz.shape != rho.shape:
+        _kk._refuse(who, "psi must be a tensor [nx, nz+1] or [ncol, nz+1] with rho and dz [nz]")
+    dx = _kk._number(who, "dx", dx)
+    n = psi.shape[0] if nx is None else nx
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1 or psi.shape[0] % n != 0:
+        _kk._refuse(who, "psi has %d columns, which is no multiple of nx = %r" % (psi.shape[0], nx))
+    dx = torch.full((), dx, dtype=psi.dtype, device=psi.device)  # a tensor: a Python divisor may be applied as a product with 1/dx
+    rf = torch.cat([rho[:1], 0.5 * (rho[:-1] + rho[1:]), rho[-1:]])
+    u = (-(psi[:, 1:] - psi[:, :-1]) / dz) / rho
+    p3 = psi.reshape(-1, n, psi.shape[1])
+    w = ((torch.roll(p3, -1, dims=1) - p3) / dx).reshape(psi.shape) / rf
+    return u.contiguous(), w.contiguous()
+
+
+def run_slab(model, state, nsteps, dt, p0, r_on_cp, exner, dz, rho, dx, nx, u, w, fix_theta=False, on_step=None, stream=None,
+             **kid_interface_options):
+    """An x-z KiD case on the device: `nsteps` times advect_slab(want="sum"), kid_interface(adv=sum), update(state, dt, sum,
+    mphys), with no host round trip and no synchronisation: kinematic.run with advect_slab in the place of advect.
+
+    state, exner, dz, rho, fix_theta, on_step, kid_interface_options   as for kinematic.run
+    dx, nx      as for advect_slab
+    u, w        as for advect_slab, or callables step -> such a tensor (no history is kept)
+    Everything is allocated once, before the first step.  Returns (state, ppt, courant): ppt [ncol, 4] the sum over the
+    steps of kid_interface's ppt, courant [ncol] of the last step."""
+    import torch
+    who = "kid_run_slab"
+    q, ncol, nz, check = _kk._state(who, model, state)
+    _slab_shape(who, ncol, nx)
+    _kk._number(who, "dt", dt)
+    _kk._number(who, "dx", dx)
+    if not callable(u) and not callable(w):
+        _flow(who, u, w, ncol, nx, nz)
+    _kk._members(who, model, state, "state", check, required=KID_FIELDS[:5])
+    for name, a, shape in (("exner", exner, (ncol, nz)), ("dz", dz, (nz,)), ("rho", rho, (nz,))):
+        check(a, name, shape)
+    bad = [k for k in kid_interface_options if k not in _kk._RUN_OPTIONS]
+    if bad:
+        _kk._refuse(who, "unknown options %s: kid_interface's %s may be passed on" % (bad, ", ".join(_kk._RUN_OPTIONS)))
+    if int(nsteps) != nsteps or nsteps < 0:
+        _kk._refuse(who, "nsteps must be a whole number >= 0")
+    keys = KID_FIELDS[:5] if model.iiwarm else KID_FIELDS
+    mphys = {k: torch.empty_like(q) for k in keys}
+    mphys["ppt"] = torch.empty((ncol, 4), dtype=q.dtype, device=q.device)
+    if kid_interface_options.get("dbz"):
+        mphys["dbz"] = torch.empty_like(q)
+    if kid_interface_options.get("radii"):
+        mphys["radii"] = tuple(torch.empty_like(q) for _ in range(3))
+    work = model.kid_workspace(ncol, nz, q.dtype)
+    adv = {"sum": {k: torch.empty_like(q) for k in keys if state.get(k) is not None},
+           "courant": torch.zeros(ncol, dtype=q.dtype, device=q.device)}
+    ppt = torch.zeros((ncol, 4), dtype=q.dtype, device=q.device)
+    moved = {k: v for k, v in state.items() if not (fix_theta and k == "theta")}
+    ctx = torch.cuda.stream(torch.cuda.ExternalStream(stream, device=q.device)) if stream is not None else None
+    if ctx is not None:
+        ctx.__enter__()
+    try:
+        for step in range(int(nsteps)):
+            adv = advect_slab(model, state, u(step) if callable(u) else u, w(step) if callable(w) else w, rho, dz, dx, dt, nx,
+                              "sum", True, adv, stream)
+            mphys = model.kid_interface(state, dt, p0, r_on_cp, exner, dz, adv=adv["sum"], work=work, out=mphys, stream=stream,
+                                        **kid_interface_options)
+            _kk.update(model, moved, dt, adv["sum"], mphys, stream=stream)
+            ppt += mphys["ppt"]
+            if on_step is not None:
+                on_step(step, state, mphys)
+    finally:
+        if ctx is not None:
+            ctx.__exit__(None, None, None)
+    return state, ppt, adv["courant"]

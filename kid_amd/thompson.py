@@ -845,6 +845,18 @@ class ThompsonMP:
         from .kinematic import run
         return run(self, state, nsteps, dt, p0, r_on_cp, exner, dz, rho, w, fix_theta, on_step, stream, **kid_interface_options)
 
+    def kid_advect_slab(self, state, u, w, rho, dz, dx, dt, nx, want=("sum",), courant=False, out=None, stream=None):
+        """Prescribed-(u, w) advection on periodic x-z slabs in the adapter's adv / div form (include/kidmp_slab.h):
+        kid_amd.slab.advect_slab on this context."""
+        from .slab import advect_slab
+        return advect_slab(self, state, u, w, rho, dz, dx, dt, nx, want, courant, out, stream)
+
+    def kid_run_slab(self, state, nsteps, dt, p0, r_on_cp, exner, dz, rho, dx, nx, u, w, fix_theta=False, on_step=None, stream=None,
+                     **kid_interface_options):
+        """A device-resident x-z KiD case, advect_slab -> kid_interface -> update per step: kid_amd.slab.run_slab on this context."""
+        from .slab import run_slab
+        return run_slab(self, state, nsteps, dt, p0, r_on_cp, exner, dz, rho, dx, nx, u, w, fix_theta, on_step, stream, **kid_interface_options)
+
     def kernel_fingerprint(self, arith="p64"):
         """'src:<hash>;vgpr:<n>;lds:<bytes>;scratch:<bytes>' of this context's nz <= 120 column-step kernel, in the
         parity arithmetic (p64) or one of the binary32 ones (p32n, f32)."""
