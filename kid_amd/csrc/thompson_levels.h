@@ -69,6 +69,15 @@ __device__ inline double snow_moment(const double *a, const double *b, double x,
     return fm::pow10_times_pow(loga_, s.l2, b_);
 }
 
+// nu_c = MIN(15, NINT(1000.E6/nc) + 2) (M:1400, M:1690, M:4876-4880) of a positive nc, without forming an integer out of range
+__device__ inline int cloud_nu_c(double nc)
+{
+    if (nc < 100.) return 15;
+    if (nc > 1.E10) return 2;
+    const int inu_c = int(lround(1000.E6 / nc)) + 2;
+    return inu_c < 15 ? inu_c : 15;
+}
+
 // ---- calc_effectRad at one level.  Each function reports whether the level holds the species (the reference CYCLEs
 // otherwise, M:4874 / 4889 / 4897) and, if so, returns the radius in `re`. ----
 // Nt_c: c.Nt_c, or the column's own where a per-column droplet number is bound (kidmp_set_column_nc)
@@ -78,10 +87,7 @@ __device__ inline bool cloud_water_radius(const RadConsts &c, double Nt_c, doubl
     const double rc = fmax(R1, qc * rho);
     const double nc = c.aero ? fmax(R2, nc1 * rho) : Nt_c;              // .NOT. is_aerosol_aware, M:4863
     if (rc <= R1 || nc <= R2) return false;                             // M:4873-4884
-    int inu_c;
-    if (nc < 100.) inu_c = 15;
-    else if (nc > 1.E10) inu_c = 2;
-    else { inu_c = int(lround(1000.E6 / nc)) + 2; inu_c = inu_c < 15 ? inu_c : 15; }
+    const int inu_c = cloud_nu_c(nc);
     const double g_ratio = double((inu_c + 1) * (inu_c + 2) * (inu_c + 3));   // 24, 60, 120 ... 4896 = (n+1)(n+2)(n+3)
     const double lamc = fm::cbrt_pos(nc * am_r_ * g_ratio / rc);
     re = fmax(2.51E-6, fmin(0.5 * double(3. + inu_c) / lamc, 50.E-6));
@@ -314,6 +320,90 @@ __device__ inline void snow_doppler(const ReflConsts &c, const DopplerConsts &d,
     const double va = rhof * av_s, ia00 = m5 * d.ia00;                   // 1/A(0,0)
     vz = va * (a1 * ia00);
     v2 = va * va * (a2 * ia00);
+}
+
+// ---- the size spectra (include/kidmp_spectra.h) at one level: the slope and intercept of each species' distribution as
+// mp_thompson loads the state, and one bin of it as the reference's table builders form it (M:3768, M:3967-3975,
+// M:4157-4164, M:4206-4221).  Beyond fall_consts_supported the integer exponents are pinned by spectra_consts_supported:
+// mu_r = mu_g = mu_i = 0 (cre(2) = cge(2) = cie(1) = 1), cce(1,n) = n + 1, cce(2,n) = bm_r + n + 1 with bm_r = 3. ----
+// An exponential term whose argument exceeds SPECTRA_EXP_MAX is exact +0.0: fm::exp is written for |x| < 700, and below
+// that EXP(-x) is a normal number.  A NaN argument gives +0.0 too.
+constexpr double SPECTRA_EXP_MAX = 700.;
+__device__ inline double exp_neg(double x) { return x <= SPECTRA_EXP_MAX ? fm::exp(-x) : 0.; }
+
+// N0_r = nr*org2*lamr**cre(2) (M:1664, M:3757), N0_i = ni*oig1*lami**cie(1) (M:4206): cre(2) = cie(1) = 1
+__device__ inline double rain_intercept(const FallConsts &c, const RainLoad &r) { return r.nr * c.org2 * r.lamr; }
+__device__ inline double ice_intercept(const FallConsts &c, const IceLoad &r) { return r.ni * c.oig1 * r.lami; }
+
+// graupel of a level with rg > R1 once the running minimum N0_exp is known: lamg and N0_g of block E (M:1650-1653), cge(2) = 1
+__device__ inline void graupel_slope(const FallConsts &c, double cgg2, double N0_exp, double rg, double &lamg, double &N0_g)
+{
+    const double lam_exp = fm::sqrt_pos(fm::sqrt_pos(N0_exp * am_g * c.cgg1 / rg));    // **oge1
+    lamg = lam_exp * c.lamg_fac;
+    N0_g = N0_exp / (cgg2 * lam_exp) * lamg;
+}
+
+// cloud water as loaded, M:1395-1410, then nu_c and lamc as block G forms them from the loaded number (M:1690-1692).
+// Nt_c: the context's, or the column's own (kidmp_set_column_nc); aero: the droplet number is the caller's nc1, limited
+// through xDc (M:1402-1409).  A level without cloud water, or a droplet number that is not above R2 (calc_effectRad's
+// test, M:4873), has has = false and nothing else is read.  The gamma functions of integers are taken exactly, as
+// calc_effectRad takes its g_ratio (M:4852): ccg(2,n)*ocg1(n) = (n+1)(n+2)(n+3) and ccg(1,n) = n!, where thompson_init's
+// WGAMMA is off by up to 9e-12 at n = 15 -- sixteen times that in lamc**cce(1,n).
+struct CloudLoad { double nc, lamc, n0; int nu; bool has; };
+__device__ inline double cloud_g_ratio(int nu) { return double((nu + 1) * (nu + 2) * (nu + 3)); }
+__device__ inline double cloud_slope(int nu, double rc, double nc) { return cbrt_any(nc * am_r * cloud_g_ratio(nu) / rc); }
+__device__ inline CloudLoad cloud_load(bool aero, double Nt_c, double rho, double qc, double nc1)
+{
+    CloudLoad r{0., 0., 0., 0, qc > R1};
+    if (!r.has) return r;
+    const double rc = qc * rho;
+    r.nc = Nt_c;                                                           // .NOT. is_aerosol_aware, M:1410
+    if (aero) {
+        r.nc = fmax(2., nc1 * rho);
+        const int nu = cloud_nu_c(r.nc);
+        double lamc = cloud_slope(nu, rc, r.nc);
+        const double xDc = (bm_r + nu + 1.) / lamc;
+        if (xDc < D0c) lamc = (bm_r + nu + 1.) / D0c;                     // cce(2,nu_c)
+        else if (xDc > D0r * 2.) lamc = (bm_r + nu + 1.) / (D0r * 2.);
+        r.nc = fmin(Nt_c_max, rc / cloud_g_ratio(nu) / am_r * cube(lamc));  // ccg(1,nu_c)*ocg2(nu_c) = 1/g_ratio
+    }
+    r.has = r.nc > R2;
+    if (!r.has) return r;
+    r.nu = cloud_nu_c(r.nc);
+    r.lamc = cloud_slope(r.nu, rc, r.nc);
+    double pw = r.lamc, b = r.lamc;                                        // lamc**cce(1,nu_c) = lamc * lamc**nu_c, nu_c in 2..15
+    for (int e = r.nu; e > 0; e >>= 1) {                                   // (binary powering: at most 4 squarings)
+        if (e & 1) pw *= b;
+        b *= b;
+    }
+    double fact = 2.;                                                      // ccg(1,nu_c) = nu_c!
+    for (int i = 3; i <= r.nu; ++i) fact *= double(i);
+    r.n0 = r.nc / fact * pw;                                               // nc*ocg1(nu_c)*lamc**cce(1,nu_c), M:4158
+    return r;
+}
+
+// snow of a level with rs > R1: what M:3967-3971 hands the bin loop.  s = snow_level(temp, rs, oams), smoc its cse(1) moment
+struct SnowSpectrum { double Mrat, k1m0, slam1, slam2; };
+__device__ inline SnowSpectrum snow_spectrum(const SnowLevel &s, double smoc)
+{
+    const double r = s.smob / smoc;
+    SnowSpectrum o;
+    o.Mrat = s.smob * r * r * r;
+    o.k1m0 = Kap1 * pow_parts(fm::log2_parts(r), mu_s);
+    o.slam1 = r * Lam0;
+    o.slam2 = r * Lam1;
+    return o;
+}
+// one bin: D and dD are the bin's diameter and width, Dmu = D**mu_s
+__device__ inline double snow_bin(const SnowSpectrum &s, double D, double Dmu, double dD)
+{ return s.Mrat * (Kap0 * exp_neg(s.slam1 * D) + s.k1m0 * Dmu * exp_neg(s.slam2 * D)) * dD; }
+// rain, graupel, cloud ice: N0 * D**0 * EXP(-lam*D) * dD
+__device__ inline double exp_bin(double n0, double lam, double D, double dD) { return n0 * exp_neg(lam * D) * dD; }
+// cloud water: N0_c * D**nu_c * EXP(-lamc*D) * dD with D**nu_c picked from D, D**2, D**4, D**8 (nu_c in 2..15)
+__device__ inline double cloud_bin(double n0, double lam, int nu, double D, double D2, double D4, double D8, double dD)
+{
+    const double Dnu = ((nu & 1 ? D : 1.) * (nu & 2 ? D2 : 1.)) * ((nu & 4 ? D4 : 1.) * (nu & 8 ? D8 : 1.));
+    return n0 * Dnu * exp_neg(lam * D) * dD;
 }
 
 }  // namespace lvl

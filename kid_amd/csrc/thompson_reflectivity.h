@@ -65,6 +65,26 @@ template <class T>
 hipError_t launch_fall_speeds(const Consts *d_consts, int64_t ncol, int nz, const FallArgs<T> &a, hipStream_t stream);
 
 
+// The size spectra (include/kidmp_spectra.h): each species' distribution parameters [ncol][nz] and its numbers per bin
+// [ncol][nb][nz].  Species in the order c, i, r, s, g; par in the order of kidmp_spectra_out.  Null means: nc -- Nt_c (the
+// context is not aerosol-aware); qi and ni, qs, qg -- the species is absent everywhere (iiwarm); an output -- not wanted;
+// set_nc_col -- the context's Nt_c.  D, dD: device arrays of nb[x] doubles, read only where spec[x] is wanted.
+constexpr int SPECTRA_NPAR = 11, SPECTRA_NSPEC = 5;
+constexpr int SPECTRA_LAM_C = 0, SPECTRA_LAM_I = 3, SPECTRA_LAM_R = 5, SPECTRA_SMOB = 7, SPECTRA_LAM_G = 9;   // each followed by its n0 / smoc (and nu_c)
+constexpr int SPECTRA_MAX_SHARES = 16, SPECTRA_MIN_BLOCKS = 1024;
+template <class T> struct SpectraArgs {
+    const T *t, *p, *qv, *qc, *nc, *qi, *ni, *qr, *nr, *qs, *qg;
+    T *par[SPECTRA_NPAR];
+    T *spec[SPECTRA_NSPEC];
+    const double *D[SPECTRA_NSPEC], *dD[SPECTRA_NSPEC];
+    int32_t nb[SPECTRA_NSPEC];
+    const double *set_nc_col;                        // null, or the batch's share of a bound per-column droplet number (cm**-3)
+    int aero;                                        // the context's is_aerosol_aware: nc is read and size-limited (M:1398-1409)
+};
+bool spectra_consts_supported(const Consts &hc);
+template <class T>
+hipError_t launch_size_spectra(const Consts *d_consts, int64_t ncol, int nz, const SpectraArgs<T> &a, hipStream_t stream);
+
 // The Doppler moments of a vertically pointing radar (include/kidmp_doppler.h): reflectivity, mean Doppler velocity and
 // spectrum width of every level, from calc_refl10cm's load and size distributions.  Null means: qs, qg -- zero; w -- zero;
 // an output -- not wanted.  out: dbz, vd, sw, vz_r, vz_s, vz_g, dbz_r, dbz_s, dbz_g.

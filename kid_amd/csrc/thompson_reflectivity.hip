@@ -357,6 +357,71 @@ __device__ inline void store_profile(T *__restrict__ out, int64_t base, int nz, 
     }
 }
 
+// Block E's intercept of every level of the column (M:1633-1647): k_0 is the highest level with temp >= 270.65
+// (M:1634-1637), mvd the limited median volume diameter of the level's rain (0: none), rg the graupel content (R1: none);
+// n0 receives the running minimum from the top down (N0_min = gonv_max above the top, M:1633).  Whole wavefronts only.
+template <int NJ>
+__device__ inline void graupel_intercepts(const double (&temp)[NJ], const double (&mvd)[NJ], const double (&rg)[NJ], int nz, int lane,
+                                          double (&n0)[NJ])
+{
+    int k_0 = 0;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const unsigned long long b = __ballot(64 * j + lane < nz && temp[j] >= 270.65);
+        if (b) k_0 = 64 * j + 63 - __builtin_clzll(b);
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        n0[j] = double(__builtin_inf());                             // levels past kte do not enter the minimum
+        if (k < nz) n0[j] = lvl::graupel_n0_exp(k > k_0 && mvd[j] > 100.E-6, mvd[j], rg[j]);
+    }
+    double carry = gonv_max;
+#pragma unroll
+    for (int j = NJ - 1; j >= 0; --j) {
+        double tail;
+        const double s = wave_suffix_min(n0[j], lane, tail);
+        n0[j] = fmin(s, carry);
+        carry = fmin(carry, tail);
+    }
+}
+
+// ---- the size spectra (include/kidmp_spectra.h) ----
+// The rows of one species that this block owns: the species' nb bins are dealt to the gridDim.y blocks of a column group in
+// contiguous shares, and every bin is formed from the level's parameters and the bin's own D, dD alone, so its bits do not
+// depend on the share it falls into.  out is [ncol][nb][nz]: one contiguous row of nz values per bin.  bin(j, D, dD, Dmu)
+// gives the value of the lane's level of group j; live[j] is wave-uniform: no level of group j holds the species, and the
+// row is +0.0 without an exponential.  POW: Dmu = D**mu_s, formed once per bin -- 64 bins at a time, one per lane, and
+// handed round with v_readlane.  D and dD are wave-uniform loads.
+template <class T, int NJ, bool POW, class F>
+__device__ __forceinline__ void store_bins(T *__restrict__ out, const double *__restrict__ D, const double *__restrict__ dD, int nb,
+                                           int64_t col, int nz, int lane, const double (&n0)[NJ], F &&bin)
+{
+    if (!out) return;
+    const int per = (nb + int(gridDim.y) - 1) / int(gridDim.y);
+    const int b0 = int(blockIdx.y) * per, b1 = b0 + per < nb ? b0 + per : nb;
+    bool live[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) live[j] = __ballot(n0[j] > 0.) != 0;
+    for (int bb = b0; bb < b1; bb += 64) {
+        double mine = 0.;
+        if (POW && bb + lane < b1) mine = fm::pow(D[bb + lane], mu_s);
+        const int be = bb + 64 < b1 ? bb + 64 : b1;
+        for (int b = bb; b < be; ++b) {
+            const double Db = D[b], dDb = dD[b];
+            const double Dmu = POW ? readlane(mine, b - bb) : 0.;
+            T *__restrict__ row = out + (col * int64_t(nb) + b) * int64_t(nz);
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const int k = 64 * j + lane;
+                double v = 0.;
+                if (live[j]) v = bin(j, Db, dDb, Dmu);
+                if (k < nz) row[k] = T(v);
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // what block O reads, picked from the context's Consts: on the device from its copy in HBM (scalar loads on demand: as
@@ -477,32 +542,17 @@ k_fall_speeds(const Consts *__restrict__ hc, FallArgs<T> a, int64_t ncol, int nz
         if (count) ns_s = column_substeps<NJ>(va, dz, a.dt, nz, lane);
 
         // ---- graupel, M:1484-1492, block E (M:1633-1654) and M:3322-3334 ----
-        int k_0 = 0;                                                 // the highest level with temp >= 270.65, M:1634-1637
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const unsigned long long b = __ballot(64 * j + lane < nz && temp[j] >= 270.65);
-            if (b) k_0 = 64 * j + 63 - __builtin_clzll(b);
-        }
         double n0[NJ];
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const int k = 64 * j + lane;
             va[j] = 0.; rq[j] = R1; has[j] = false;
-            n0[j] = double(__builtin_inf());                         // levels past kte do not enter the minimum
             if (k >= nz) continue;
             const double qg = double(a.qg[base + k]);
             if (qg > R1) rq[j] = qg * rho[j];                        // M:1484-1492
             has[j] = rq[j] > R1;                                     // M:3325
-            n0[j] = lvl::graupel_n0_exp(k > k_0 && mvd[j] > 100.E-6, mvd[j], rq[j]);
         }
-        double carry = gonv_max;                                     // N0_min = gonv_max, M:1633
-#pragma unroll
-        for (int j = NJ - 1; j >= 0; --j) {
-            double tail;
-            const double s = wave_suffix_min(n0[j], lane, tail);
-            n0[j] = fmin(s, carry);
-            carry = fmin(carry, tail);
-        }
+        graupel_intercepts<NJ>(temp, mvd, rq, nz, lane, n0);
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
             if (has[j]) va[j] = lvl::graupel_fall_speed(c, rhof[j], n0[j], rq[j], temp[j], vtr[j]);
@@ -515,6 +565,151 @@ k_fall_speeds(const Consts *__restrict__ hc, FallArgs<T> a, int64_t ncol, int nz
     }
     store_profile<T, NJ>(a.out[10], base, nz, lane, ftot);
     if (count && lane < 4) a.nstep[col * 4 + lane] = lane == 0 ? ns_r : lane == 1 ? ns_i : lane == 2 ? ns_s : ns_g;
+}
+
+// One wavefront per column and share of the bins: the size distributions of the state as mp_thompson loads it, on diameter
+// bins (include/kidmp_spectra.h).  Species by species -- rain first, whose median volume diameter the graupel intercept
+// reads -- the level's slope and intercept are formed once in registers, stored by the column's first share if asked for,
+// and the species' bins follow at once, so that only one species' parameters are live at a time.  The load is
+// k_fall_speeds' own, through the same lvl:: functions.  Nothing but the fastmath tables is in LDS.
+template <class T, int NJ>
+__global__ void __launch_bounds__(REFL_THREADS)
+k_size_spectra(const Consts *__restrict__ hc, SpectraArgs<T> a, int64_t ncol, int nz)
+{
+#if KFM_TABLES
+    fm::tab::load_tables(int(threadIdx.x), REFL_THREADS);
+    __syncthreads();
+#endif
+    const int lane = int(threadIdx.x) & 63;
+    const int64_t col = int64_t(blockIdx.x) * REFL_WAVES + (int(threadIdx.x) >> 6);
+    if (col >= ncol) return;                                         // whole wavefronts only: the scan needs every lane
+    const int64_t base = col * int64_t(nz);
+    const bool first = blockIdx.y == 0;                              // the share that stores the parameters
+    T *const *par = a.par;
+    const auto params = [&](int v, const double (&x)[NJ]) __attribute__((always_inline)) { if (first) store_profile<T, NJ>(par[v], base, nz, lane, x); };
+    const auto wants = [&](int sp, int p0, int p1, int p2) __attribute__((always_inline)) { return a.spec[sp] || par[p0] || par[p1] || (p2 >= 0 && par[p2]); };
+
+    double temp[NJ], rho[NJ], mvd[NJ], n0[NJ], lam[NJ];
+
+    // ---- load (M:1387-1391) and rain (M:1447-1474) ----
+    // (each species picks its own few constants from the context's copy in HBM just before it needs them: all fifty of
+    //  fall_consts at once, beside the forty pointers of the arguments, do not fit the scalar registers)
+    FallConsts c{};
+    c.crg2 = hc->crg[1]; c.crg3 = hc->crg[2]; c.org2 = hc->org2; c.org3 = hc->org3;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        temp[j] = 0.; rho[j] = 1.; mvd[j] = 0.; n0[j] = lam[j] = 0.;
+        if (k >= nz) continue;
+        const int64_t i = base + k;
+        temp[j] = double(a.t[i]);
+        rho[j] = lvl::air_density(double(a.p[i]), temp[j], fmax(1.E-10, double(a.qv[i])));
+        const lvl::RainLoad r = lvl::rain_load(c, rho[j], double(a.qr[i]), double(a.nr[i]));
+        if (!r.has) continue;
+        mvd[j] = r.mvd;                                              // 0: no rain (block E asks L_qr, M:1639)
+        lam[j] = r.lamr;
+        n0[j] = lvl::rain_intercept(c, r);
+    }
+    params(SPECTRA_LAM_R, lam);
+    params(SPECTRA_LAM_R + 1, n0);
+    store_bins<T, NJ, false>(a.spec[2], a.D[2], a.dD[2], a.nb[2], col, nz, lane, n0,
+                             [&](int j, double D, double dD, double) __attribute__((always_inline)) { return n0[j] > 0. ? lvl::exp_bin(n0[j], lam[j], D, dD) : 0.; });
+
+    // ---- cloud ice, M:1420-1445 ----
+    if (wants(1, SPECTRA_LAM_I, SPECTRA_LAM_I + 1, -1)) {
+        c.cie2 = hc->cie[1]; c.cig1 = hc->cig[0]; c.cig2 = hc->cig[1]; c.oig1 = hc->oig1; c.oig2 = hc->oig2;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int k = 64 * j + lane;
+            n0[j] = lam[j] = 0.;
+            if (k >= nz || !a.qi) continue;
+            const lvl::IceLoad r = lvl::ice_load(c, rho[j], double(a.qi[base + k]), double(a.ni[base + k]));
+            if (!r.has) continue;
+            lam[j] = r.lami;
+            n0[j] = lvl::ice_intercept(c, r);
+        }
+        params(SPECTRA_LAM_I, lam);
+        params(SPECTRA_LAM_I + 1, n0);
+        store_bins<T, NJ, false>(a.spec[1], a.D[1], a.dD[1], a.nb[1], col, nz, lane, n0,
+                                 [&](int j, double D, double dD, double) __attribute__((always_inline)) { return n0[j] > 0. ? lvl::exp_bin(n0[j], lam[j], D, dD) : 0.; });
+    }
+
+    // ---- snow, M:1475-1483 and block D ----
+    if (wants(3, SPECTRA_SMOB, SPECTRA_SMOB + 1, -1)) {
+        lvl::SnowSpectrum sp[NJ];
+        c.oams = hc->oams; c.cse1 = hc->cse[0];
+#pragma unroll
+        for (int i = 0; i < 10; ++i) { c.sa[i] = hc->sa[i]; c.sb[i] = hc->sb[i]; }
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int k = 64 * j + lane;
+            n0[j] = lam[j] = 0.;                                     // smob, smoc
+            sp[j] = lvl::SnowSpectrum{0., 0., 0., 0.};
+            if (k >= nz || !a.qs) continue;
+            const double qs = double(a.qs[base + k]);
+            if (!(qs > R1)) continue;
+            const lvl::SnowLevel sl = lvl::snow_level(temp[j], qs * rho[j], c.oams);
+            n0[j] = sl.smob;
+            lam[j] = lvl::snow_moment(c.sa, c.sb, c.cse1, sl);      // M:1590-1600
+            sp[j] = lvl::snow_spectrum(sl, lam[j]);
+        }
+        params(SPECTRA_SMOB, n0);
+        params(SPECTRA_SMOB + 1, lam);
+        store_bins<T, NJ, true>(a.spec[3], a.D[3], a.dD[3], a.nb[3], col, nz, lane, n0,
+                                [&](int j, double D, double dD, double Dmu) __attribute__((always_inline)) { return n0[j] > 0. ? lvl::snow_bin(sp[j], D, Dmu, dD) : 0.; });
+    }
+
+    // ---- graupel, M:1484-1492 and block E (M:1633-1654) ----
+    if (wants(4, SPECTRA_LAM_G, SPECTRA_LAM_G + 1, -1)) {
+        double rg[NJ];
+        bool has[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int k = 64 * j + lane;
+            rg[j] = R1; has[j] = false;
+            if (k >= nz || !a.qg) continue;
+            const double qg = double(a.qg[base + k]);
+            has[j] = qg > R1;
+            if (has[j]) rg[j] = qg * rho[j];
+        }
+        graupel_intercepts<NJ>(temp, mvd, rg, nz, lane, n0);
+        const double cgg2 = hc->cgg[1];
+        c.cgg1 = hc->cgg[0]; c.lamg_fac = hc->lamg_fac;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const double n0_exp = n0[j];
+            n0[j] = lam[j] = 0.;
+            if (has[j]) lvl::graupel_slope(c, cgg2, n0_exp, rg[j], lam[j], n0[j]);
+        }
+        params(SPECTRA_LAM_G, lam);
+        params(SPECTRA_LAM_G + 1, n0);
+        store_bins<T, NJ, false>(a.spec[4], a.D[4], a.dD[4], a.nb[4], col, nz, lane, n0,
+                                 [&](int j, double D, double dD, double) __attribute__((always_inline)) { return n0[j] > 0. ? lvl::exp_bin(n0[j], lam[j], D, dD) : 0.; });
+    }
+
+    // ---- cloud water, M:1395-1410 and M:1690-1692 ----
+    if (wants(0, SPECTRA_LAM_C, SPECTRA_LAM_C + 1, SPECTRA_LAM_C + 2)) {
+        const double Nt_c = a.set_nc_col ? a.set_nc_col[col] * 1.e6 : hc->Nt_c;
+        int nu[NJ];
+        double fnu[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int k = 64 * j + lane;
+            n0[j] = lam[j] = fnu[j] = 0.; nu[j] = 0;
+            if (k >= nz) continue;
+            const lvl::CloudLoad r = lvl::cloud_load(a.aero != 0, Nt_c, rho[j], double(a.qc[base + k]), a.nc ? double(a.nc[base + k]) : 0.);
+            if (!r.has) continue;
+            lam[j] = r.lamc; n0[j] = r.n0; nu[j] = r.nu; fnu[j] = double(r.nu);
+        }
+        params(SPECTRA_LAM_C, lam);
+        params(SPECTRA_LAM_C + 1, n0);
+        params(SPECTRA_LAM_C + 2, fnu);
+        store_bins<T, NJ, false>(a.spec[0], a.D[0], a.dD[0], a.nb[0], col, nz, lane, n0,
+                                 [&](int j, double D, double dD, double) __attribute__((always_inline)) {
+                                     const double D2 = D * D, D4 = D2 * D2;
+                                     return n0[j] > 0. ? lvl::cloud_bin(n0[j], lam[j], nu[j], D, D2, D4, D4 * D4, dD) : 0.;
+                                 });
+    }
 }
 
 // One wavefront per column: the three radar moments of every level (include/kidmp_doppler.h).  The load, the ze_* and the
@@ -781,6 +976,41 @@ hipError_t launch_fall_speeds(const Consts *c, int64_t ncol, int nz, const FallA
 }
 template hipError_t launch_fall_speeds<double>(const Consts *, int64_t, int, const FallArgs<double> &, hipStream_t);
 template hipError_t launch_fall_speeds<float>(const Consts *, int64_t, int, const FallArgs<float> &, hipStream_t);
+
+template <class T>
+hipError_t launch_size_spectra(const Consts *c, int64_t ncol, int nz, const SpectraArgs<T> &a, hipStream_t s)
+{
+    if (ncol <= 0) return hipSuccess;
+    const int64_t nblk = (ncol + REFL_WAVES - 1) / REFL_WAVES;
+    // few columns and many bins: a column's bins go to several blocks, up to SPECTRA_MAX_SHARES, until the grid holds
+    // SPECTRA_MIN_BLOCKS workgroups (four to a compute unit)
+    int maxnb = 1;
+    for (int x = 0; x < SPECTRA_NSPEC; ++x)
+        if (a.spec[x] && a.nb[x] > maxnb) maxnb = a.nb[x];
+    int64_t shares = (SPECTRA_MIN_BLOCKS + nblk - 1) / nblk;
+    shares = shares > SPECTRA_MAX_SHARES ? SPECTRA_MAX_SHARES : shares;
+    shares = shares > maxnb ? maxnb : shares;
+    const dim3 grid((unsigned)nblk, (unsigned)shares), block(REFL_THREADS);
+    switch ((nz + 63) / 64) {
+    case 1: hipLaunchKernelGGL((k_size_spectra<T, 1>), grid, block, 0, s, c, a, ncol, nz); break;
+    case 2: hipLaunchKernelGGL((k_size_spectra<T, 2>), grid, block, 0, s, c, a, ncol, nz); break;
+    case 3: hipLaunchKernelGGL((k_size_spectra<T, 3>), grid, block, 0, s, c, a, ncol, nz); break;
+    case 4: hipLaunchKernelGGL((k_size_spectra<T, 4>), grid, block, 0, s, c, a, ncol, nz); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+template hipError_t launch_size_spectra<double>(const Consts *, int64_t, int, const SpectraArgs<double> &, hipStream_t);
+template hipError_t launch_size_spectra<float>(const Consts *, int64_t, int, const SpectraArgs<float> &, hipStream_t);
+
+bool spectra_consts_supported(const Consts &hc)
+{
+    // beyond fall_consts_supported: mu_r = mu_g = mu_i = 0 (no D**mu factor; cre(2) = cge(2) = cie(1) = 1), and the
+    // cloud-water exponents cce(1,n) = n + 1, cce(2,n) = bm_r + n + 1 taken as integers
+    bool ok = fall_consts_supported(hc) && mu_r == 0.0 && mu_g == 0.0 && mu_i == 0.0 && hc.cre[1] == 1. && hc.cge[1] == 1. && hc.cie[0] == 1.;
+    for (int n = 1; n <= 15; ++n) ok = ok && hc.cce[0][n - 1] == n + 1. && hc.cce[1][n - 1] == bm_r + n + 1.;
+    return ok;
+}
 
 template <class T>
 hipError_t launch_doppler_moments(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const DopplerArgs<T> &a, hipStream_t s)

@@ -62,6 +62,7 @@ module module_mp_thompson09n
   public :: column_summary_batch
   public :: fall_speeds_batch
   public :: doppler_moments_batch
+  public :: size_spectra_batch
   public :: mp_thompson_kid_interface, mp_thompson_kid_staging
   logical, public :: is_aerosol_aware = .false.          ! M:28 (read at thompson_init)
   logical, public :: l_rate_diagnostics = .true.         ! replay the save_dg calls of M:2962-3124
@@ -100,6 +101,17 @@ module module_mp_thompson09n
   type, bind(C) :: kidmp_doppler_out                     ! kidmp_doppler_out / kidmp32_doppler_out: [ncol][nz] each, NULL = not wanted
      type(c_ptr) :: dbz, vd, sw, vz_r, vz_s, vz_g, dbz_r, dbz_s, dbz_g
   end type kidmp_doppler_out
+
+  type, bind(C) :: kidmp_spectra_out                     ! kidmp_spectra_out / kidmp32_spectra_out: [ncol][nz] each, NULL = not wanted
+     type(c_ptr) :: lam_c, n0_c, nu_c, lam_i, n0_i, lam_r, n0_r, smob, smoc, lam_g, n0_g
+  end type kidmp_spectra_out
+  type, bind(C) :: kidmp_spectra_bins                    ! kidmp_spectra_bins / kidmp32_spectra_bins: [ncol][nb][nz] each, NULL = not wanted
+     type(c_ptr) :: n_c, n_i, n_r, n_s, n_g
+  end type kidmp_spectra_bins
+  type, bind(C) :: kidmp_spectra_grids                   ! by species c, i, r, s, g: D and dD both NULL = the scheme's own 100 bins
+     type(c_ptr) :: D(5), dD(5)
+     integer(c_int32_t) :: nb(5)
+  end type kidmp_spectra_grids
 
   type, bind(C) :: kidmp_kid_fields                      ! kidmp_kid_fields / kidmp32_kid_fields: KiD's fields, [ncol][nz] each
      type(c_ptr) :: theta, qv, qc, qr, nr, qi, ni, qs, qg
@@ -305,6 +317,29 @@ module module_mp_thompson09n
        type(kidmp_fall_out), intent(in) :: out
        type(c_ptr), value :: nstep
      end function kidmp32_fall_speeds_host
+     ! the size spectra (include/kidmp_spectra.h): nc, qi, ni, qs, qg may be NULL as the header says
+     integer(c_int) function kidmp_size_spectra_host(ctx, ncol, nz, t, p, qv, qc, nc, qi, ni, qr, nr, qs, qg, par, bins, grids) &
+          bind(C, name='kidmp_size_spectra_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr, kidmp_spectra_out, kidmp_spectra_bins, kidmp_spectra_grids
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qc, nc, qi, ni, qr, nr, qs, qg   ! real(c_double) [ncol][nz]
+       type(kidmp_spectra_out), intent(in) :: par
+       type(kidmp_spectra_bins), intent(in) :: bins
+       type(kidmp_spectra_grids), intent(in) :: grids
+     end function kidmp_size_spectra_host
+     integer(c_int) function kidmp32_size_spectra_host(ctx, ncol, nz, t, p, qv, qc, nc, qi, ni, qr, nr, qs, qg, par, bins, grids) &
+          bind(C, name='kidmp32_size_spectra_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr, kidmp_spectra_out, kidmp_spectra_bins, kidmp_spectra_grids
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qc, nc, qi, ni, qr, nr, qs, qg   ! real(c_float) [ncol][nz]
+       type(kidmp_spectra_out), intent(in) :: par
+       type(kidmp_spectra_bins), intent(in) :: bins
+       type(kidmp_spectra_grids), intent(in) :: grids
+     end function kidmp32_size_spectra_host
      ! the Doppler moments of a vertically pointing radar (include/kidmp_doppler.h): qs, qg and w may be NULL (zero)
      integer(c_int) function kidmp_doppler_moments_host(ctx, ncol, nz, t, p, qv, qr, nr, qs, qg, w, out) &
           bind(C, name='kidmp_doppler_moments_host')
@@ -701,6 +736,95 @@ contains
     end if
     call stop_on_error(rc, 'fall_speeds_batch')
   end subroutine fall_speeds_batch
+
+  ! The size distributions of a state over ncol columns of KiD's (nz, ncol) storage in one call (include/kidmp_spectra.h):
+  ! per species (cloud water c, cloud ice i, rain r, snow s, graupel g) the spectrum n_x(nz, nb, ncol), particles per m3 of
+  ! air in each diameter bin, and the parameters of the distribution (nz, ncol): slope and intercept lam_x, n0_x (nu_c for
+  ! cloud water; smob and smoc for snow).  Every output is optional, in the array kind the arithmetic stores; at least one
+  ! must be present.  A spectrum is put on the grid D_x(nb), dD_x(nb) (m, always REAL 8; 1 <= nb <= 256) when both are
+  ! given, else on the scheme's own 100 bins, and its second extent must be that nb.  nc is read only by an aerosol-aware
+  ! run; qi, ni, qs and qg may be left out in an iiwarm run or when no frozen output is asked for.  The inputs are not
+  ! changed.  Default REAL 8 goes to kidmp_size_spectra_host, REAL 4 to kidmp32_...
+  subroutine size_spectra_batch(ncol, nz, t, p, qv, qc, qr, nr, n_c, n_i, n_r, n_s, n_g, lam_c, n0_c, nu_c, lam_i, n0_i, &
+       lam_r, n0_r, smob, smoc, lam_g, n0_g, nc, qi, ni, qs, qg, D_c, dD_c, D_i, dD_i, D_r, dD_r, D_s, dD_s, D_g, dD_g)
+    integer, intent(in) :: ncol, nz
+    real, dimension(nz,ncol), intent(in), target :: t, p, qv, qc, qr, nr
+    real, dimension(:,:,:), intent(inout), optional, target, contiguous :: n_c, n_i, n_r, n_s, n_g
+    real, dimension(nz,ncol), intent(out), optional, target :: lam_c, n0_c, nu_c, lam_i, n0_i, lam_r, n0_r, smob, smoc, lam_g, n0_g
+    real, dimension(nz,ncol), intent(in), optional, target :: nc, qi, ni, qs, qg
+    real(c_double), dimension(:), intent(in), optional, target, contiguous :: D_c, dD_c, D_i, dD_i, D_r, dD_r, D_s, dD_s, D_g, dD_g
+    type(kidmp_spectra_out) :: par
+    type(kidmp_spectra_bins) :: bins
+    type(kidmp_spectra_grids) :: grids
+    type(c_ptr) :: pnc, pqi, pni, pqs, pqg, pn(5)
+    integer(c_int) :: rc
+    integer :: x
+    if (.not. c_associated(ctx)) call thompson_init
+    if (c_associated(mctx)) then
+       write(*,'(a)') ' module_mp_thompson09n: size spectra are not available with kidmp_ndevices > 1'
+       stop 1
+    end if
+    pnc = c_null_ptr;  pqi = c_null_ptr;  pni = c_null_ptr;  pqs = c_null_ptr;  pqg = c_null_ptr
+    if (present(nc)) pnc = c_loc(nc)
+    if (present(qi)) pqi = c_loc(qi)
+    if (present(ni)) pni = c_loc(ni)
+    if (present(qs)) pqs = c_loc(qs)
+    if (present(qg)) pqg = c_loc(qg)
+    do x = 1, 5
+       grids%D(x) = c_null_ptr;  grids%dD(x) = c_null_ptr;  grids%nb(x) = 0_c_int32_t
+    end do
+    call species(1, n_c, D_c, dD_c)
+    call species(2, n_i, D_i, dD_i)
+    call species(3, n_r, D_r, dD_r)
+    call species(4, n_s, D_s, dD_s)
+    call species(5, n_g, D_g, dD_g)
+    bins = kidmp_spectra_bins(pn(1), pn(2), pn(3), pn(4), pn(5))
+    par = kidmp_spectra_out(c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
+         c_null_ptr, c_null_ptr, c_null_ptr)
+    if (present(lam_c)) par%lam_c = c_loc(lam_c)
+    if (present(n0_c)) par%n0_c = c_loc(n0_c)
+    if (present(nu_c)) par%nu_c = c_loc(nu_c)
+    if (present(lam_i)) par%lam_i = c_loc(lam_i)
+    if (present(n0_i)) par%n0_i = c_loc(n0_i)
+    if (present(lam_r)) par%lam_r = c_loc(lam_r)
+    if (present(n0_r)) par%n0_r = c_loc(n0_r)
+    if (present(smob)) par%smob = c_loc(smob)
+    if (present(smoc)) par%smoc = c_loc(smoc)
+    if (present(lam_g)) par%lam_g = c_loc(lam_g)
+    if (present(n0_g)) par%n0_g = c_loc(n0_g)
+    if (kind(t) == c_double) then
+       rc = kidmp_size_spectra_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), c_loc(qc), &
+            pnc, pqi, pni, c_loc(qr), c_loc(nr), pqs, pqg, par, bins, grids)
+    else
+       rc = kidmp32_size_spectra_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), c_loc(qc), &
+            pnc, pqi, pni, c_loc(qr), c_loc(nr), pqs, pqg, par, bins, grids)
+    end if
+    call stop_on_error(rc, 'size_spectra_batch')
+  contains
+    ! one species: the spectrum's address and, when the caller gives one, its grid; the extents are checked here, where
+    ! they are known
+    subroutine species(x, n, D, dD)
+      integer, intent(in) :: x
+      real, dimension(:,:,:), intent(inout), optional, target, contiguous :: n
+      real(c_double), dimension(:), intent(in), optional, target, contiguous :: D, dD
+      pn(x) = c_null_ptr
+      if (.not. present(n)) return
+      if (present(D) .neqv. present(dD)) call bad('a grid needs both D and dD')
+      if (size(n, 1) /= nz .or. size(n, 3) /= ncol) call bad('a spectrum must be (nz, nb, ncol)')
+      if (present(D)) then
+         if (size(D) /= size(n, 2) .or. size(dD) /= size(n, 2)) call bad('D, dD and the spectrum differ in the number of bins')
+         grids%D(x) = c_loc(D);  grids%dD(x) = c_loc(dD);  grids%nb(x) = int(size(D), c_int32_t)
+      else if (size(n, 2) /= 100) then
+         call bad('a spectrum on the scheme''s own grid has 100 bins')
+      end if
+      pn(x) = c_loc(n)
+    end subroutine species
+    subroutine bad(msg)
+      character(*), intent(in) :: msg
+      write(*,'(2a)') ' module_mp_thompson09n: size_spectra_batch: ', msg
+      stop 1
+    end subroutine bad
+  end subroutine size_spectra_batch
 
   ! The radar moments of a state over ncol columns of KiD's (nz, ncol) storage in one call (include/kidmp_doppler.h):
   ! reflectivity dbz (dBZ), mean Doppler velocity vd and spectrum width sw (m s-1, positive downward), and the per-species

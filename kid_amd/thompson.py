@@ -598,6 +598,17 @@ class ThompsonMP:
         from .fall import FALL_NAMES, fall_speeds_host
         return fall_speeds_host(self, st, boost, dz, dt, FALL_NAMES if want is None else want)
 
+    def size_spectra(self, st, want=None, grids=None, out=None, stream=None):
+        """The size distributions of every level on diameter bins, and their parameters (include/kidmp_spectra.h):
+        kid_amd.spectra.size_spectra on this context."""
+        from .spectra import SPECTRA_SPECIES, size_spectra
+        return size_spectra(self, st, SPECTRA_SPECIES if want is None else want, grids, out, stream)
+
+    def size_spectra_host(self, st, want=None, grids=None, out=None):
+        """size_spectra on numpy arrays: kid_amd.spectra.size_spectra_host on this context."""
+        from .spectra import SPECTRA_SPECIES, size_spectra_host
+        return size_spectra_host(self, st, SPECTRA_SPECIES if want is None else want, grids, out)
+
     def doppler_moments(self, st, w=None, want=None, stream=None):
         """Reflectivity, mean Doppler velocity and spectrum width of every level, with the per-species parts they are
         formed from (include/kidmp_doppler.h): kid_amd.doppler.doppler_moments on this context."""
