@@ -28,14 +28,22 @@ template <class T> struct GatherArgs {
     int32_t nz;
     T dt, p0, expo, Nt_c;                            // expo = 1./r_on_cp, formed in T
     const double *set_nc_col;                        // kidmp_set_column_nc: the batch's first column, or null
+    // AERO (include/kidmp_aerosol.h): nc, nwfa, nifa with their forcing, and the cell-centre updraft
+    const T *aer[KID_NA], *aer_adv[KID_NA], *aer_div[KID_NA];
+    const T *w;
+    int64_t w_col_stride;
 };
 template <class T> struct BackoutArgs {
     const T *state[KID_NF], *adv[KID_NF], *div[KID_NF];
     const T *exner;
-    const T *work[KID_NWORK];
+    T *work[KID_NWORK];                              // read; AERO with a surface source: level 0 of profile 9 is written
     T *mphys[KID_NF];
     int64_t n;
     T dt;
+    const T *aer[KID_NA], *aer_adv[KID_NA], *aer_div[KID_NA];       // AERO, as in GatherArgs
+    T *aer_mphys[KID_NA];
+    const T *nwfa_src;
+    int32_t nz;
 };
 
 // p = p0 * exner**(1./r_on_cp) (W:62).  binary64: the device libm's pow (under 1 ulp).  binary32: pow in binary64 rounded
@@ -44,8 +52,9 @@ __device__ inline double pres_of(double p0, double exner, double expo) { return 
 __device__ inline float pres_of(float p0, float exner, float expo) { return p0 * float(pow(double(exner), double(expo))); }
 
 // W:46-97 + U2.  One element (V of them) per lane-slot; NF = KID_NWARM in an iiwarm context, where the four frozen
-// profiles are exact zeros (W:46-52) and their inputs are not looked at.
-template <class T, int V, int NF>
+// profiles are exact zeros (W:46-52) and their inputs are not looked at.  AERO: profiles 8, 9 and 10 are the caller's nc,
+// nwfa and nifa moved on like the other moments instead of the U2 defaults, and profile 13 is the caller's updraft.
+template <class T, int V, int NF, bool AERO>
 __global__ __launch_bounds__(256) void k_kid_gather(const GatherArgs<T> a)
 {
     const int64_t stride = int64_t(gridDim.x) * blockDim.x, tid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -58,31 +67,47 @@ __global__ __launch_bounds__(256) void k_kid_gather(const GatherArgs<T> a)
 #pragma unroll
         for (int m = 0; m < NF; ++m) { x[m] = ld<T, V>(a.state[m], e); xa[m] = ld<T, V>(a.adv[m], e); xd[m] = ld<T, V>(a.div[m], e); }
         const Vec<T, V> ex = ld<T, V>(a.exner, e), dz = ld<T, V>(a.dz, e - col * a.nz);
-        const T Nt_c = a.set_nc_col ? T(a.set_nc_col[col] * 1.e6) : a.Nt_c;      // as k_default_aerosols
-        Vec<T, V> g[NF], p, nc, nwfa, nifa, zero;
+        Vec<T, V> g[NF], p, n3[KID_NA], w, zero;                                 // n3: nc, nwfa, nifa
+        if constexpr (AERO) {
+            Vec<T, V> y[KID_NA], ya[KID_NA], yd[KID_NA];
+#pragma unroll
+            for (int m = 0; m < KID_NA; ++m) { y[m] = ld<T, V>(a.aer[m], e); ya[m] = ld<T, V>(a.aer_adv[m], e); yd[m] = ld<T, V>(a.aer_div[m], e); }
+            w = ld<T, V>(a.w, col * a.w_col_stride + (e - col * a.nz));          // (wide: the stride is a multiple of V)
+#pragma unroll
+            for (int j = 0; j < V; ++j)
+#pragma unroll
+                for (int m = 0; m < KID_NA; ++m) n3[m].v[j] = y[m].v[j] + (ya[m].v[j] + yd[m].v[j]) * a.dt;   // as W:60-93
+        }
+        const T Nt_c = !AERO && a.set_nc_col ? T(a.set_nc_col[col] * 1.e6) : a.Nt_c;      // as k_default_aerosols
 #pragma unroll
         for (int j = 0; j < V; ++j) {
 #pragma unroll
             for (int m = 0; m < NF; ++m) g[m].v[j] = x[m].v[j] + (xa[m].v[j] + xd[m].v[j]) * a.dt;    // W:60-93
             g[0].v[j] = g[0].v[j] * ex.v[j];                                     // t = (theta + ...)*exner, W:60
             p.v[j] = pres_of(a.p0, ex.v[j], a.expo);
-            const T rho = T(0.622) * p.v[j] / (T(Rgas) * g[0].v[j] * (g[1].v[j] + T(0.622)));   // M:959
-            nc.v[j] = Nt_c / rho;                                                // M:960
-            nwfa.v[j] = T(11.1E6) / rho;                                         // M:961
-            nifa.v[j] = T(naIN1) * T(0.01) / rho;                                // M:962
             zero.v[j] = T(0);
+            if constexpr (!AERO) {
+                const T rho = T(0.622) * p.v[j] / (T(Rgas) * g[0].v[j] * (g[1].v[j] + T(0.622)));   // M:959
+                n3[0].v[j] = Nt_c / rho;                                         // M:960
+                n3[1].v[j] = T(11.1E6) / rho;                                    // M:961
+                n3[2].v[j] = T(naIN1) * T(0.01) / rho;                           // M:962
+                w.v[j] = T(0);
+            }
         }
 #pragma unroll
         for (int m = 0; m < NF; ++m) st<T, V>(a.work[work_of(m)], e, g[m]);
 #pragma unroll
         for (int m = NF; m < KID_NF; ++m) st<T, V>(a.work[work_of(m)], e, zero);
-        st<T, V>(a.work[8], e, nc); st<T, V>(a.work[9], e, nwfa); st<T, V>(a.work[10], e, nifa);
-        st<T, V>(a.work[12], e, p); st<T, V>(a.work[13], e, zero); st<T, V>(a.work[14], e, dz);
+#pragma unroll
+        for (int m = 0; m < KID_NA; ++m) st<T, V>(a.work[KID_AER_WORK0 + m], e, n3[m]);
+        st<T, V>(a.work[12], e, p); st<T, V>(a.work[13], e, w); st<T, V>(a.work[14], e, dz);
     }
 }
 
-// W:198-245 on the post-step workspace
-template <class T, int V, int NF>
+// W:198-245 on the post-step workspace.  AERO: first the surface source of M:1001 into level 0 of profile 9 (the V
+// elements of a lane-slot share a column, so level 0 is element 0 of the slot that begins a column), then the three
+// aerosol tendencies like the others.
+template <class T, int V, int NF, bool AERO>
 __global__ __launch_bounds__(256) void k_kid_backout(const BackoutArgs<T> a)
 {
     const int64_t stride = int64_t(gridDim.x) * blockDim.x, nvec = a.n / V;
@@ -104,6 +129,28 @@ __global__ __launch_bounds__(256) void k_kid_backout(const BackoutArgs<T> a)
         }
 #pragma unroll
         for (int m = 0; m < NF; ++m) st<T, V>(a.mphys[m], e, r[m]);
+        if constexpr (AERO) {
+            Vec<T, V> y[KID_NA], ya[KID_NA], yd[KID_NA], y1[KID_NA];
+#pragma unroll
+            for (int m = 0; m < KID_NA; ++m) {
+                y[m] = ld<T, V>(a.aer[m], e); ya[m] = ld<T, V>(a.aer_adv[m], e); yd[m] = ld<T, V>(a.aer_div[m], e);
+                y1[m] = ld<T, V>(a.work[KID_AER_WORK0 + m], e);
+            }
+            if (a.nwfa_src) {
+                const int64_t col = a.n <= 0x7fffffff ? int64_t(int32_t(e) / a.nz) : e / a.nz;
+                if (e == col * a.nz) {
+                    y1[1].v[0] = y1[1].v[0] + a.nwfa_src[col] * a.dt;
+                    a.work[KID_AER_WORK0 + 1][e] = y1[1].v[0];
+                }
+            }
+#pragma unroll
+            for (int m = 0; m < KID_NA; ++m) {
+                Vec<T, V> s;
+#pragma unroll
+                for (int j = 0; j < V; ++j) s.v[j] = (y1[m].v[j] - y[m].v[j]) / a.dt - (ya[m].v[j] + yd[m].v[j]);
+                st<T, V>(a.aer_mphys[m], e, s);
+            }
+        }
     }
 }
 
@@ -117,34 +164,37 @@ template <class T, class A> bool wide_ok(const A &a, int32_t nz, const void *con
         if (!aligned16(a.work[v])) return false;
     for (int i = 0; i < nmore; ++i)
         if (!aligned16(more[i])) return false;
+    for (int m = 0; m < KID_NA; ++m)                     // null unless AERO
+        if (!aligned16(a.aer[m]) || !aligned16(a.aer_adv[m]) || !aligned16(a.aer_div[m])) return false;
     return true;
 }
 
-template <class T> hipError_t launch_gather(const GatherArgs<T> &a, bool warm, hipStream_t s)
+template <class T> hipError_t launch_gather(const GatherArgs<T> &a, bool warm, bool aero, hipStream_t s)
 {
     constexpr int V = 16 / int(sizeof(T));
-    const void *more[] = {a.exner, a.dz};
-    if (wide_ok<T>(a, a.nz, more, 2)) {
-        if (warm) hipLaunchKernelGGL((k_kid_gather<T, V, KID_NWARM>), dim3(grid_for(a.n / V)), dim3(256), 0, s, a);
-        else      hipLaunchKernelGGL((k_kid_gather<T, V, KID_NF>), dim3(grid_for(a.n / V)), dim3(256), 0, s, a);
-    } else {
-        if (warm) hipLaunchKernelGGL((k_kid_gather<T, 1, KID_NWARM>), dim3(grid_for(a.n)), dim3(256), 0, s, a);
-        else      hipLaunchKernelGGL((k_kid_gather<T, 1, KID_NF>), dim3(grid_for(a.n)), dim3(256), 0, s, a);
-    }
+    const void *more[] = {a.exner, a.dz, a.w};
+    const bool wide = wide_ok<T>(a, a.nz, more, 3) && a.w_col_stride % V == 0;
+    const dim3 grid(wide ? grid_for(a.n / V) : grid_for(a.n)), block(256);
+#define KID_GATHER(W, NF_) do { if (aero) hipLaunchKernelGGL((k_kid_gather<T, W, NF_, true>), grid, block, 0, s, a); \
+                                else      hipLaunchKernelGGL((k_kid_gather<T, W, NF_, false>), grid, block, 0, s, a); } while (0)
+    if (wide) { if (warm) KID_GATHER(V, KID_NWARM); else KID_GATHER(V, KID_NF); }
+    else      { if (warm) KID_GATHER(1, KID_NWARM); else KID_GATHER(1, KID_NF); }
+#undef KID_GATHER
     return hipGetLastError();
 }
-template <class T> hipError_t launch_backout(const BackoutArgs<T> &a, int32_t nz, bool warm, hipStream_t s)
+template <class T> hipError_t launch_backout(const BackoutArgs<T> &a, int32_t nz, bool warm, bool aero, hipStream_t s)
 {
     constexpr int V = 16 / int(sizeof(T));
-    const void *more[KID_NF + 1] = {a.exner};
+    const void *more[KID_NF + KID_NA + 1] = {a.exner};
     for (int m = 0; m < KID_NF; ++m) more[m + 1] = a.mphys[m];
-    if (wide_ok<T>(a, nz, more, KID_NF + 1)) {
-        if (warm) hipLaunchKernelGGL((k_kid_backout<T, V, KID_NWARM>), dim3(grid_for(a.n / V)), dim3(256), 0, s, a);
-        else      hipLaunchKernelGGL((k_kid_backout<T, V, KID_NF>), dim3(grid_for(a.n / V)), dim3(256), 0, s, a);
-    } else {
-        if (warm) hipLaunchKernelGGL((k_kid_backout<T, 1, KID_NWARM>), dim3(grid_for(a.n)), dim3(256), 0, s, a);
-        else      hipLaunchKernelGGL((k_kid_backout<T, 1, KID_NF>), dim3(grid_for(a.n)), dim3(256), 0, s, a);
-    }
+    for (int m = 0; m < KID_NA; ++m) more[KID_NF + 1 + m] = a.aer_mphys[m];
+    const bool wide = wide_ok<T>(a, nz, more, KID_NF + KID_NA + 1);
+    const dim3 grid(wide ? grid_for(a.n / V) : grid_for(a.n)), block(256);
+#define KID_BACKOUT(W, NF_) do { if (aero) hipLaunchKernelGGL((k_kid_backout<T, W, NF_, true>), grid, block, 0, s, a); \
+                                 else      hipLaunchKernelGGL((k_kid_backout<T, W, NF_, false>), grid, block, 0, s, a); } while (0)
+    if (wide) { if (warm) KID_BACKOUT(V, KID_NWARM); else KID_BACKOUT(V, KID_NF); }
+    else      { if (warm) KID_BACKOUT(1, KID_NWARM); else KID_BACKOUT(1, KID_NF); }
+#undef KID_BACKOUT
     return hipGetLastError();
 }
 
@@ -159,18 +209,35 @@ int kid_device(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, T dt, 
     if (int rc = kid_check<T, F>(ctx, who, ncol, nz, double(dt), state, adv, div, exner, dz, mphys, ppt, o, arith, c)) return rc;
     if (ncol == 0) return KIDMP_OK;
     c.dt = dt; c.p0 = p0; c.r_on_cp = r_on_cp; c.rates = rates; c.nstep = nstep;
+    return kid_device_call<T>(ctx, who, c, work, work_bytes, stream, gather_only);
+}
+}  // namespace
+
+template <class T>
+int kidmp::kid_device_call(kidmp_ctx *ctx, const char *who, const KidCall<T> &c, void *work, size_t work_bytes, void *stream, bool gather_only)
+{
     const std::string w(who);
-    if (!work || work_bytes < size_t(KID_NWORK) * kid_stride(ncol, nz, sizeof(T)))
+    if (!work || work_bytes < size_t(KID_NWORK) * kid_stride(c.ncol, c.nz, sizeof(T)))
         return fail(ctx, KIDMP_EINVAL, w + ": the workspace is missing or smaller than kidmp_kid_workspace_bytes(ncol, nz)");
     if (!aligned16(work)) return fail(ctx, KIDMP_EINVAL, w + ": the workspace must be 16-byte aligned");
     GUARD(ctx);
-    const void *ptrs[] = {c.state.f[0], c.mphys.f[0], exner, dz, ppt, work, rates, nstep};
+    const void *ptrs[] = {c.state.f[0], c.mphys.f[0], c.exner, c.dz, c.ppt, work, c.rates, c.nstep};
     const char *names[] = {"state", "mphys", "exner", "dz", "ppt", "work", "rates", "nstep"};
     for (int i = 0; i < 8; ++i)
         if (int rc = check_on_device(ctx, ptrs[i], names[i])) return rc;
+    if (c.aer.on) {
+        const void *more[] = {c.aer.state[0], c.aer.state[1], c.aer.state[2], c.aer.adv[0], c.aer.adv[1], c.aer.adv[2],
+                              c.aer.div[0], c.aer.div[1], c.aer.div[2], c.aer.mphys[0], c.aer.mphys[1], c.aer.mphys[2],
+                              c.aer.w, c.aer.nwfa_src};
+        const char *what[] = {"aer->nc", "aer->nwfa", "aer->nifa", "aer_adv->nc", "aer_adv->nwfa", "aer_adv->nifa", "aer_div->nc",
+                              "aer_div->nwfa", "aer_div->nifa", "aer_mphys->nc", "aer_mphys->nwfa", "aer_mphys->nifa", "w", "nwfa_src"};
+        for (int i = 0; i < 14; ++i)
+            if (int rc = check_on_device(ctx, more[i], what[i])) return rc;
+    }
     return kid_enqueue<T>(ctx, c, work, (hipStream_t)stream, -1, gather_only);
 }
-}  // namespace
+template int kidmp::kid_device_call<double>(kidmp_ctx *, const char *, const KidCall<double> &, void *, size_t, void *, bool);
+template int kidmp::kid_device_call<float>(kidmp_ctx *, const char *, const KidCall<float> &, void *, size_t, void *, bool);
 
 template <class T, class F>
 int kidmp::kid_check(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, double dt, const F *state, const F *adv, const F *div,
@@ -230,13 +297,21 @@ int kidmp::kid_enqueue(kidmp_ctx *ctx, const KidCall<T> &c, void *work, hipStrea
     g.n = b.n = c.ncol * int64_t(c.nz); g.ncol = c.ncol; g.nz = c.nz;
     g.dt = b.dt = c.dt; g.p0 = c.p0; g.expo = T(1) / c.r_on_cp; g.Nt_c = T(ctx->hc.Nt_c);
     g.set_nc_col = ctx->d_nc_col ? ctx->d_nc_col + (nc_first > 0 ? nc_first : 0) : nullptr;
-    HIPTRY(ctx, launch_gather<T>(g, warm, s));
+    const bool aero = c.aer.on;
+    if (aero) {
+        for (int m = 0; m < KID_NA; ++m) {
+            g.aer[m] = b.aer[m] = c.aer.state[m]; g.aer_adv[m] = b.aer_adv[m] = c.aer.adv[m]; g.aer_div[m] = b.aer_div[m] = c.aer.div[m];
+            b.aer_mphys[m] = c.aer.mphys[m];
+        }
+        g.w = c.aer.w; g.w_col_stride = c.aer.w_col_stride; b.nwfa_src = c.aer.nwfa_src; b.nz = c.nz;
+    }
+    HIPTRY(ctx, launch_gather<T>(g, warm, aero, s));
     if (gather_only) return KIDMP_OK;
     if (int rc = step_device<T>(ctx, c.ncol, c.nz, c.dt, w, w[12], w[13], w[14], c.ppt, c.rates, c.nstep, c.arith, s, nc_first)) return rc;
     if (c.out.dbz || c.out.re_qc)                                // of the post-step state, as the host pipeline forms them
         HIPTRY(ctx, launch_outputs<T>(ctx, c.ncol, c.nz, {w[11], w[12], w[0], w[1], w[8], w[2], w[6], w[3], w[7], w[4], w[5]}, c.out, s,
                                       nc_first > 0 ? nc_first : 0));
-    HIPTRY(ctx, launch_backout<T>(b, c.nz, warm, s));
+    HIPTRY(ctx, launch_backout<T>(b, c.nz, warm, aero, s));
     return KIDMP_OK;
 }
 template int kidmp::kid_enqueue<double>(kidmp_ctx *, const KidCall<double> &, void *, hipStream_t, int64_t, bool);

@@ -1,5 +1,5 @@
 // kidmp_ctx.h -- internal to the units behind include/kidmp.h (not installed): the context, the error and device-guard
-// helpers of every entry point, and what the units kidmp_{capi,diag,host,tables,multi,adapter,stats,summary,fall,doppler,kinematic,slab,spectra}.hip offer one another.
+// helpers of every entry point, and what the units kidmp_{capi,diag,host,tables,multi,adapter,stats,summary,fall,doppler,kinematic,slab,spectra,aerosol}.hip offer one another.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -199,12 +199,22 @@ int host_pipeline(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, T *const 
 constexpr int KID_NF = 9, KID_NWARM = 5, KID_NWORK = 15;                 // theta, qv, qc, qr, nr | qi, ni, qs, qg
 constexpr int KID_WORK_OF[KID_NF] = {11, 0, 1, 3, 7, 2, 6, 4, 5};
 template <class T> struct KidFields { T *f[KID_NF]; };
+// the aerosol-aware call of include/kidmp_aerosol.h: nc, nwfa, nifa are gathered into profiles KID_AER_WORK0 .. + 2 and
+// backed out like the other moments, w goes to profile 13; on == false: the U2 defaults and w = 0
+constexpr int KID_NA = 3, KID_AER_WORK0 = 8;
+template <class T> struct KidAerosols {
+    bool on;
+    T *state[KID_NA], *adv[KID_NA], *div[KID_NA], *mphys[KID_NA];   // a null member of adv / div is a zero operand
+    const T *w; int64_t w_col_stride;                // cell-centre updraft [ncol][nz] (stride 0: one profile), null: zeros
+    const T *nwfa_src;                               // [ncol], null: no surface source (M:1001)
+};
 template <class T> struct KidCall {
     int64_t ncol; int32_t nz; T dt, p0, r_on_cp;
     KidFields<T> state, adv, div, mphys;             // a null member of adv / div is a zero operand
     const T *exner, *dz;
     T *ppt; double *rates; int32_t *nstep; ColumnOutputs<T> out;
     int32_t arith;
+    KidAerosols<T> aer;
 };
 inline size_t kid_stride(int64_t ncol, int32_t nz, size_t elem)      // bytes from one workspace profile to the next; 0: bad arguments
 { return ncol < 0 || nz < 1 || nz > KIDMP_MAX_NZ ? 0 : (size_t(ncol) * size_t(nz) * elem + 255) / 256 * 256; }
@@ -214,6 +224,28 @@ int kid_check(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, double 
               const T *exner, const T *dz, const F *mphys, T *ppt, const ColumnOutputs<T> &out, int32_t arith, KidCall<T> &call);
 // gather (gather_only: that alone), step, outputs, back-out on `s`, nothing else: `c` holds device pointers; nc_first as for step_device
 template <class T> int kid_enqueue(kidmp_ctx *ctx, const KidCall<T> &c, void *work, hipStream_t s, int64_t nc_first, bool gather_only = false);
+// what a device entry does once kid_check has passed and `c` is filled: the workspace and device checks, then kid_enqueue
+template <class T>
+int kid_device_call(kidmp_ctx *ctx, const char *who, const KidCall<T> &c, void *work, size_t work_bytes, void *stream, bool gather_only);
 // kidmp_host.hip
 template <class T> int kid_host(kidmp_ctx *ctx, const KidCall<T> &host);
+
+// kidmp_kinematic.hip / kidmp_slab.hip: the bodies of the advection and update entries for N members (N = KID_NF behind
+// kidmp_kinematic.h and kidmp_slab.h, KID_NA behind kidmp_aerosol.h), one launch each.  The first `nreq` members of
+// `state` are required (`required` is what the refusal says); `names` are the members' names in messages.
+template <class T, int N> struct KidMembers { T *state[N], *adv[N], *div[N], *sum[N]; };
+template <class T, int N>
+int kid_advect_members(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, double dt, const KidMembers<T, N> &f, int nreq,
+                       const char *required, const char *const *names, const T *w, int64_t w_col_stride, const T *rho, const T *dz,
+                       T *courant, void *stream);
+struct KidSlabShape { int64_t nslab; int32_t nx, nz; double dt, dx; int32_t shared_flow; };
+template <class T, int N>
+int kid_advect_slab_members(kidmp_ctx *ctx, const char *who, const KidSlabShape &g, const KidMembers<T, N> &f, int nreq,
+                            const char *required, const char *const *names, const T *u, const T *w, const T *rho, const T *dz,
+                            T *courant, void *stream);
+// state <- state + ((t[0] + t[1]) + t[2])*dt; bit m of clip_mask: member m becomes max(X, +0.0); nloop <= N members are walked
+template <class T, int N> struct KidUpdate { T *state[N]; const T *t[3][N]; };
+template <class T, int N>
+int kid_update_members(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, T dt, const KidUpdate<T, N> &f, int nloop,
+                       const char *const *names, uint32_t clip_mask, void *stream);
 }  // namespace kidmp

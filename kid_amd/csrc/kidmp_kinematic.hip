@@ -16,20 +16,20 @@ constexpr int ADV_WAVES = 4;                             // columns (wavefronts)
 constexpr int ADV_THREADS = 64 * ADV_WAVES;
 const char *const FIELD_NAMES[KID_NF] = {"theta", "qv", "qc", "qr", "nr", "qi", "ni", "qs", "qg"};
 
-template <class T> struct AdvectArgs {
-    const T *state[KID_NF];
-    T *adv[KID_NF], *div[KID_NF], *sum[KID_NF];          // null: not wanted
+template <class T, int N> struct AdvectArgs {            // N members: KiD's nine fields, or the three aerosols
+    const T *state[N];
+    T *adv[N], *div[N], *sum[N];                         // null: not wanted
     const T *w, *rho, *dz;
     int64_t w_col_stride;
     T *courant;
     double dt;
 };
-template <class T> struct UpdateArgs {
-    T *state[KID_NF];                                    // null: skipped
-    const T *t[3][KID_NF];                               // null: a zero operand
+template <class T, int N> struct UpdateArgs {
+    T *state[N];                                         // null: skipped
+    const T *t[3][N];                                    // null: a zero operand
     int64_t n;
     T dt;
-    int32_t clip;
+    uint32_t clip;                                       // bit m: member m is clipped (never theta)
 };
 
 // One wavefront per column, level k = 64 j + lane.  Cell k owns its lower face k: the mass flux M and the Courant number c
@@ -37,9 +37,9 @@ template <class T> struct UpdateArgs {
 // factor, the upwind side); then each present member is loaded once, its neighbours k-1, k-2 and k+1 come from the
 // neighbouring lanes, its face value and flux are formed once per lane and the flux of face k+1 comes from the lane
 // above.  The lane that holds level nz-1 forms the top face itself.  No LDS, no scratch.
-template <class T, int NJ>
+template <class T, int NJ, int N>
 __global__ void __launch_bounds__(ADV_THREADS)
-k_kid_advect(const AdvectArgs<T> a, int64_t ncol, int nz)
+k_kid_advect(const AdvectArgs<T, N> a, int64_t ncol, int nz)
 {
     const int lane = int(threadIdx.x) & 63;
     const int64_t col = int64_t(blockIdx.x) * ADV_WAVES + (int(threadIdx.x) >> 6);
@@ -89,7 +89,7 @@ k_kid_advect(const AdvectArgs<T> a, int64_t ncol, int nz)
     }
 
 #pragma unroll
-    for (int m = 0; m < KID_NF; ++m) {
+    for (int m = 0; m < N; ++m) {
         if (!a.state[m] || !(a.adv[m] || a.div[m] || a.sum[m])) continue;
         double q[NJ], q1[NJ], q2[NJ], qa[NJ], F[NJ], Fup[NJ];
 #pragma unroll
@@ -125,8 +125,8 @@ k_kid_advect(const AdvectArgs<T> a, int64_t ncol, int nz)
 }
 
 // X = X + ((t1 + t2) + t3)*dt in T, then the clip of everything but theta: one element (V of them) per lane-slot
-template <class T, int V, int NF>
-__global__ __launch_bounds__(256) void k_kid_update(const UpdateArgs<T> a)
+template <class T, int V, int NF, int N>
+__global__ __launch_bounds__(256) void k_kid_update(const UpdateArgs<T, N> a)
 {
     const int64_t stride = int64_t(gridDim.x) * blockDim.x, nvec = a.n / V;
     for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < nvec; i += stride) {
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256) void k_kid_update(const UpdateArgs<T> a)
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 x.v[j] = x.v[j] + ((t1.v[j] + t2.v[j]) + t3.v[j]) * a.dt;
-                if (m && a.clip) x.v[j] = x.v[j] < T(0) ? T(0) : x.v[j];
+                if (a.clip >> m & 1u) x.v[j] = x.v[j] < T(0) ? T(0) : x.v[j];
             }
             st<T, V>(a.state[m], e, x);
         }
@@ -169,95 +169,128 @@ template <class T, class F>
 int advect_device(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, double dt, const F *state, const T *w, int64_t w_col_stride,
                   const T *rho, const T *dz, const F *adv, const F *div, const F *sum, T *courant, void *stream)
 {
-    const std::string me(who);
-    if (int rc = check_shape(ctx, me, ncol, nz, dt)) return rc;
-    if (w_col_stride != 0 && w_col_stride < int64_t(nz) + 1) return fail(ctx, KIDMP_EINVAL, me + ": w_col_stride must be 0 or >= nz+1");
-    if (ncol == 0) return KIDMP_OK;                                  // an empty batch has nothing to point at
-    if (!state || !w || !rho || !dz) return fail(ctx, KIDMP_EINVAL, me + ": null argument (state, w, rho and dz are required)");
-    const int nf = ctx->cfg.iiwarm ? KID_NWARM : KID_NF;             // the frozen members are not looked at in a warm context
-    AdvectArgs<T> a{};
-    T *s[KID_NF];
-    members<T>(state, s, nf);
-    members<T>(adv, a.adv, nf);
-    members<T>(div, a.div, nf);
-    members<T>(sum, a.sum, nf);
-    bool any = courant != nullptr;
-    for (int m = 0; m < KID_NF; ++m) {
-        if (m < KID_NWARM && !s[m]) return fail(ctx, KIDMP_EINVAL, me + ": theta, qv, qc, qr and nr of state are required");
-        if (!s[m]) a.adv[m] = a.div[m] = a.sum[m] = nullptr;         // not advected: its outputs are not written
-        a.state[m] = s[m];
-        any = any || a.adv[m] || a.div[m] || a.sum[m];
-    }
-    if (!any) return fail(ctx, KIDMP_EINVAL, me + ": nothing requested: no output member of a present field and no courant");
-    GUARD(ctx);
-    for (int m = 0; m < KID_NF; ++m) {
-        if (int rc = check_device_array(ctx, who, a.state[m], FIELD_NAMES[m])) return rc;
-        if (int rc = check_device_array(ctx, who, a.adv[m], "a member of adv")) return rc;
-        if (int rc = check_device_array(ctx, who, a.div[m], "a member of div")) return rc;
-        if (int rc = check_device_array(ctx, who, a.sum[m], "a member of sum")) return rc;
-    }
-    const void *more[] = {w, rho, dz, courant};
-    const char *names[] = {"w", "rho", "dz", "courant"};
-    for (int i = 0; i < 4; ++i)
-        if (int rc = check_device_array(ctx, who, more[i], names[i])) return rc;
-    a.w = w; a.rho = rho; a.dz = dz; a.w_col_stride = w_col_stride; a.courant = courant; a.dt = dt;
-    const dim3 grid((unsigned)((ncol + ADV_WAVES - 1) / ADV_WAVES)), block(ADV_THREADS);
-    hipStream_t st = (hipStream_t)stream;
-    switch ((nz + 63) / 64) {
-    case 1: hipLaunchKernelGGL((k_kid_advect<T, 1>), grid, block, 0, st, a, ncol, nz); break;
-    case 2: hipLaunchKernelGGL((k_kid_advect<T, 2>), grid, block, 0, st, a, ncol, nz); break;
-    case 3: hipLaunchKernelGGL((k_kid_advect<T, 3>), grid, block, 0, st, a, ncol, nz); break;
-    default: hipLaunchKernelGGL((k_kid_advect<T, 4>), grid, block, 0, st, a, ncol, nz); break;
-    }
-    HIPTRY(ctx, hipGetLastError());
-    return KIDMP_OK;
+    const int nf = ctx && ctx->cfg.iiwarm ? KID_NWARM : KID_NF;      // the frozen members are not looked at in a warm context
+    KidMembers<T, KID_NF> f{};
+    members<T>(state, f.state, nf);
+    members<T>(adv, f.adv, nf);
+    members<T>(div, f.div, nf);
+    members<T>(sum, f.sum, nf);
+    return kid_advect_members<T, KID_NF>(ctx, who, ncol, nz, dt, f, KID_NWARM, "theta, qv, qc, qr and nr of state are required",
+                                         FIELD_NAMES, w, w_col_stride, rho, dz, courant, stream);
 }
 
 template <class T, class F>
 int update_device(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, T dt, const F *state, const F *t1, const F *t2, const F *t3,
                   int32_t clip, void *stream)
 {
-    const std::string me(who);
-    if (int rc = check_shape(ctx, me, ncol, nz, double(dt))) return rc;
-    if (ncol == 0) return KIDMP_OK;
-    if (!state) return fail(ctx, KIDMP_EINVAL, me + ": state is required");
-    const bool warm = ctx->cfg.iiwarm != 0;
+    const bool warm = ctx && ctx->cfg.iiwarm != 0;
     const int nf = warm ? KID_NWARM : KID_NF;
-    UpdateArgs<T> a{};
-    members<T>(state, a.state, nf);
+    KidUpdate<T, KID_NF> f{};
+    members<T>(state, f.state, nf);
     const F *const t[3] = {t1, t2, t3};
-    bool any = false;
-    for (int m = 0; m < KID_NF; ++m) any = any || a.state[m];
-    if (!any) return fail(ctx, KIDMP_EINVAL, me + ": nothing requested: state has no member");
     for (int i = 0; i < 3; ++i) {
         T *p[KID_NF];
         members<T>(t[i], p, nf);
-        for (int m = 0; m < KID_NF; ++m) a.t[i][m] = a.state[m] ? p[m] : nullptr;
+        for (int m = 0; m < KID_NF; ++m) f.t[i][m] = p[m];
     }
+    return kid_update_members<T, KID_NF>(ctx, who, ncol, nz, dt, f, nf, FIELD_NAMES, clip ? 0x1feu : 0u, stream);   // not theta
+}
+}  // namespace
+
+template <class T, int N>
+int kidmp::kid_advect_members(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, double dt, const KidMembers<T, N> &f, int nreq,
+                              const char *required, const char *const *names, const T *w, int64_t w_col_stride, const T *rho,
+                              const T *dz, T *courant, void *stream)
+{
+    const std::string me(who);
+    if (int rc = check_shape(ctx, me, ncol, nz, dt)) return rc;
+    if (w_col_stride != 0 && w_col_stride < int64_t(nz) + 1) return fail(ctx, KIDMP_EINVAL, me + ": w_col_stride must be 0 or >= nz+1");
+    if (ncol == 0) return KIDMP_OK;                                  // an empty batch has nothing to point at
+    if (!w || !rho || !dz) return fail(ctx, KIDMP_EINVAL, me + ": null argument (state, w, rho and dz are required)");
+    AdvectArgs<T, N> a{};
+    bool any = courant != nullptr;
+    for (int m = 0; m < N; ++m) {
+        if (m < nreq && !f.state[m]) return fail(ctx, KIDMP_EINVAL, me + ": " + required);
+        a.state[m] = f.state[m];
+        if (f.state[m]) { a.adv[m] = f.adv[m]; a.div[m] = f.div[m]; a.sum[m] = f.sum[m]; }   // not advected: its outputs are not written
+        any = any || a.adv[m] || a.div[m] || a.sum[m];
+    }
+    if (!any) return fail(ctx, KIDMP_EINVAL, me + ": nothing requested: no output member of a present field and no courant");
+    GUARD(ctx);
+    for (int m = 0; m < N; ++m) {
+        if (int rc = check_device_array(ctx, who, a.state[m], names[m])) return rc;
+        if (int rc = check_device_array(ctx, who, a.adv[m], "a member of adv")) return rc;
+        if (int rc = check_device_array(ctx, who, a.div[m], "a member of div")) return rc;
+        if (int rc = check_device_array(ctx, who, a.sum[m], "a member of sum")) return rc;
+    }
+    const void *more[] = {w, rho, dz, courant};
+    const char *what[] = {"w", "rho", "dz", "courant"};
+    for (int i = 0; i < 4; ++i)
+        if (int rc = check_device_array(ctx, who, more[i], what[i])) return rc;
+    a.w = w; a.rho = rho; a.dz = dz; a.w_col_stride = w_col_stride; a.courant = courant; a.dt = dt;
+    const dim3 grid((unsigned)((ncol + ADV_WAVES - 1) / ADV_WAVES)), block(ADV_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    switch ((nz + 63) / 64) {
+    case 1: hipLaunchKernelGGL((k_kid_advect<T, 1, N>), grid, block, 0, st, a, ncol, nz); break;
+    case 2: hipLaunchKernelGGL((k_kid_advect<T, 2, N>), grid, block, 0, st, a, ncol, nz); break;
+    case 3: hipLaunchKernelGGL((k_kid_advect<T, 3, N>), grid, block, 0, st, a, ncol, nz); break;
+    default: hipLaunchKernelGGL((k_kid_advect<T, 4, N>), grid, block, 0, st, a, ncol, nz); break;
+    }
+    HIPTRY(ctx, hipGetLastError());
+    return KIDMP_OK;
+}
+
+template <class T, int N>
+int kidmp::kid_update_members(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, T dt, const KidUpdate<T, N> &f, int nloop,
+                              const char *const *names, uint32_t clip_mask, void *stream)
+{
+    const std::string me(who);
+    if (int rc = check_shape(ctx, me, ncol, nz, double(dt))) return rc;
+    if (ncol == 0) return KIDMP_OK;
+    UpdateArgs<T, N> a{};
+    bool any = false;
+    for (int m = 0; m < N; ++m) { a.state[m] = f.state[m]; any = any || a.state[m]; }
+    if (!any) return fail(ctx, KIDMP_EINVAL, me + ": nothing requested: state has no member");
+    for (int i = 0; i < 3; ++i)
+        for (int m = 0; m < N; ++m) a.t[i][m] = a.state[m] ? f.t[i][m] : nullptr;
     GUARD(ctx);
     constexpr int V = 16 / int(sizeof(T));
     bool wide = nz % V == 0;
-    for (int m = 0; m < KID_NF; ++m) {
-        if (int rc = check_device_array(ctx, who, a.state[m], FIELD_NAMES[m])) return rc;
+    for (int m = 0; m < N; ++m) {
+        if (int rc = check_device_array(ctx, who, a.state[m], names[m])) return rc;
         wide = wide && aligned16(a.state[m]);
         for (int i = 0; i < 3; ++i) {
             if (int rc = check_device_array(ctx, who, a.t[i][m], "a member of a tendency")) return rc;
             wide = wide && aligned16(a.t[i][m]);
         }
     }
-    a.n = ncol * int64_t(nz); a.dt = dt; a.clip = clip;
+    a.n = ncol * int64_t(nz); a.dt = dt; a.clip = clip_mask;
     hipStream_t s = (hipStream_t)stream;
-    if (wide) {
-        if (warm) hipLaunchKernelGGL((k_kid_update<T, V, KID_NWARM>), dim3(grid_for(a.n / V)), dim3(256), 0, s, a);
-        else      hipLaunchKernelGGL((k_kid_update<T, V, KID_NF>), dim3(grid_for(a.n / V)), dim3(256), 0, s, a);
+    const dim3 grid(wide ? grid_for(a.n / V) : grid_for(a.n)), block(256);
+    if constexpr (N == KID_NF) {
+        if (wide) {
+            if (nloop == KID_NWARM) hipLaunchKernelGGL((k_kid_update<T, V, KID_NWARM, N>), grid, block, 0, s, a);
+            else                    hipLaunchKernelGGL((k_kid_update<T, V, KID_NF, N>), grid, block, 0, s, a);
+        } else {
+            if (nloop == KID_NWARM) hipLaunchKernelGGL((k_kid_update<T, 1, KID_NWARM, N>), grid, block, 0, s, a);
+            else                    hipLaunchKernelGGL((k_kid_update<T, 1, KID_NF, N>), grid, block, 0, s, a);
+        }
     } else {
-        if (warm) hipLaunchKernelGGL((k_kid_update<T, 1, KID_NWARM>), dim3(grid_for(a.n)), dim3(256), 0, s, a);
-        else      hipLaunchKernelGGL((k_kid_update<T, 1, KID_NF>), dim3(grid_for(a.n)), dim3(256), 0, s, a);
+        if (wide) hipLaunchKernelGGL((k_kid_update<T, V, N, N>), grid, block, 0, s, a);
+        else      hipLaunchKernelGGL((k_kid_update<T, 1, N, N>), grid, block, 0, s, a);
     }
     HIPTRY(ctx, hipGetLastError());
     return KIDMP_OK;
 }
-}  // namespace
+
+#define KIDMP_INSTANTIATE(T, N) \
+    template int kidmp::kid_advect_members<T, N>(kidmp_ctx *, const char *, int64_t, int32_t, double, const KidMembers<T, N> &, int, \
+        const char *, const char *const *, const T *, int64_t, const T *, const T *, T *, void *); \
+    template int kidmp::kid_update_members<T, N>(kidmp_ctx *, const char *, int64_t, int32_t, T, const KidUpdate<T, N> &, int, \
+        const char *const *, uint32_t, void *);
+KIDMP_INSTANTIATE(double, KID_NA)
+KIDMP_INSTANTIATE(float, KID_NA)
+#undef KIDMP_INSTANTIATE
 
 extern "C" {
 int kidmp_kid_advect_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, const kidmp_kid_fields *state,

@@ -14,9 +14,9 @@ constexpr int SLAB_WAVES = 4;                            // W: consecutive cells
 constexpr int SLAB_THREADS = 64 * SLAB_WAVES;
 const char *const FIELD_NAMES[KID_NF] = {"theta", "qv", "qc", "qr", "nr", "qi", "ni", "qs", "qg"};
 
-template <class T> struct SlabArgs {
-    const T *state[KID_NF];
-    T *adv[KID_NF], *div[KID_NF], *sum[KID_NF];          // null: not wanted
+template <class T, int N> struct SlabArgs {              // N members: KiD's nine fields, or the three aerosols
+    const T *state[N];
+    T *adv[N], *div[N], *sum[N];                         // null: not wanted
     const T *u, *w, *rho, *dz;
     T *courant;
     double dt, dx;
@@ -33,9 +33,9 @@ template <class T> struct SlabArgs {
 // A stage of the strip in LDS, W = 8 and x faces shared between neighbouring waves were all measured and were no faster
 // (the kernel is bound by its binary64 arithmetic), so there is no LDS and no barrier here, and
 // a wave beyond the slab's end (nx no multiple of W) may simply leave.  No scratch.
-template <class T, int NJ>
+template <class T, int NJ, int N>
 __global__ void __launch_bounds__(SLAB_THREADS)
-k_kid_advect_slab(const SlabArgs<T> a)
+k_kid_advect_slab(const SlabArgs<T, N> a)
 {
     const int lane = int(threadIdx.x) & 63;
     const int nx = a.nx, nz = a.nz;
@@ -112,7 +112,7 @@ k_kid_advect_slab(const SlabArgs<T> a)
     }
 
 #pragma unroll
-    for (int m = 0; m < KID_NF; ++m) {
+    for (int m = 0; m < N; ++m) {
         if (!a.state[m] || !(a.adv[m] || a.div[m] || a.sum[m])) continue;
         double q[NJ], q1[NJ], q2[NJ], qa[NJ], F[NJ], Fup[NJ], dFx[NJ];
 #pragma unroll
@@ -176,57 +176,72 @@ int advect_slab_device(kidmp_ctx *ctx, const char *who, int64_t nslab, int32_t n
                        const T *u, const T *w, int32_t shared_flow, const T *rho, const T *dz, const F *adv, const F *div, const F *sum,
                        T *courant, void *stream)
 {
+    const int nf = ctx && ctx->cfg.iiwarm ? KID_NWARM : KID_NF;      // the frozen members are not looked at in a warm context
+    KidMembers<T, KID_NF> f{};
+    members<T>(state, f.state, nf);
+    members<T>(adv, f.adv, nf);
+    members<T>(div, f.div, nf);
+    members<T>(sum, f.sum, nf);
+    return kid_advect_slab_members<T, KID_NF>(ctx, who, {nslab, nx, nz, dt, dx, shared_flow}, f, KID_NWARM,
+                                              "theta, qv, qc, qr and nr of state are required", FIELD_NAMES, u, w, rho, dz, courant, stream);
+}
+}  // namespace
+
+template <class T, int N>
+int kidmp::kid_advect_slab_members(kidmp_ctx *ctx, const char *who, const KidSlabShape &g, const KidMembers<T, N> &f, int nreq,
+                                   const char *required, const char *const *names, const T *u, const T *w, const T *rho, const T *dz,
+                                   T *courant, void *stream)
+{
     const std::string me(who);
+    const int64_t nslab = g.nslab;
+    const int32_t nx = g.nx, nz = g.nz;
     if (int rc = require_ready(ctx)) return rc;
     if (nslab < 0) return fail(ctx, KIDMP_EINVAL, me + ": nslab < 0");
     if (nx < 3) return fail(ctx, KIDMP_EINVAL, me + ": nx < 3 (the stencil i-2 .. i+2 must name distinct cells)");
     if (nz < 2 || nz > KIDMP_MAX_NZ) return fail(ctx, KIDMP_EINVAL, me + ": nz outside [2, KIDMP_MAX_NZ]");
-    if (!(dt > 0.)) return fail(ctx, KIDMP_EINVAL, me + ": dt must be > 0");
-    if (!(dx > 0.)) return fail(ctx, KIDMP_EINVAL, me + ": dx must be > 0");
+    if (!(g.dt > 0.)) return fail(ctx, KIDMP_EINVAL, me + ": dt must be > 0");
+    if (!(g.dx > 0.)) return fail(ctx, KIDMP_EINVAL, me + ": dx must be > 0");
     if (nslab > int64_t(0x7fffffff) / nx) return fail(ctx, KIDMP_EINVAL, me + ": more columns than one launch takes");
     if (nslab == 0) return KIDMP_OK;                                 // an empty batch has nothing to point at
-    if (!state || !u || !w || !rho || !dz) return fail(ctx, KIDMP_EINVAL, me + ": null argument (state, u, w, rho and dz are required)");
-    const int nf = ctx->cfg.iiwarm ? KID_NWARM : KID_NF;             // the frozen members are not looked at in a warm context
-    SlabArgs<T> a{};
-    T *s[KID_NF];
-    members<T>(state, s, nf);
-    members<T>(adv, a.adv, nf);
-    members<T>(div, a.div, nf);
-    members<T>(sum, a.sum, nf);
+    if (!u || !w || !rho || !dz) return fail(ctx, KIDMP_EINVAL, me + ": null argument (state, u, w, rho and dz are required)");
+    SlabArgs<T, N> a{};
     bool any = courant != nullptr;
-    for (int m = 0; m < KID_NF; ++m) {
-        if (m < KID_NWARM && !s[m]) return fail(ctx, KIDMP_EINVAL, me + ": theta, qv, qc, qr and nr of state are required");
-        if (!s[m]) a.adv[m] = a.div[m] = a.sum[m] = nullptr;         // not advected: its outputs are not written
-        a.state[m] = s[m];
+    for (int m = 0; m < N; ++m) {
+        if (m < nreq && !f.state[m]) return fail(ctx, KIDMP_EINVAL, me + ": " + required);
+        a.state[m] = f.state[m];
+        if (f.state[m]) { a.adv[m] = f.adv[m]; a.div[m] = f.div[m]; a.sum[m] = f.sum[m]; }   // not advected: its outputs are not written
         any = any || a.adv[m] || a.div[m] || a.sum[m];
     }
     if (!any) return fail(ctx, KIDMP_EINVAL, me + ": nothing requested: no output member of a present field and no courant");
     GUARD(ctx);
-    for (int m = 0; m < KID_NF; ++m) {
-        if (int rc = check_device_array(ctx, who, a.state[m], FIELD_NAMES[m])) return rc;
+    for (int m = 0; m < N; ++m) {
+        if (int rc = check_device_array(ctx, who, a.state[m], names[m])) return rc;
         if (int rc = check_device_array(ctx, who, a.adv[m], "a member of adv")) return rc;
         if (int rc = check_device_array(ctx, who, a.div[m], "a member of div")) return rc;
         if (int rc = check_device_array(ctx, who, a.sum[m], "a member of sum")) return rc;
     }
     const void *more[] = {u, w, rho, dz, courant};
-    const char *names[] = {"u", "w", "rho", "dz", "courant"};
+    const char *what[] = {"u", "w", "rho", "dz", "courant"};
     for (int i = 0; i < 5; ++i)
-        if (int rc = check_device_array(ctx, who, more[i], names[i])) return rc;
-    a.u = u; a.w = w; a.rho = rho; a.dz = dz; a.courant = courant; a.dt = dt; a.dx = dx;
-    a.nx = nx; a.nz = nz; a.shared_flow = shared_flow != 0;
+        if (int rc = check_device_array(ctx, who, more[i], what[i])) return rc;
+    a.u = u; a.w = w; a.rho = rho; a.dz = dz; a.courant = courant; a.dt = g.dt; a.dx = g.dx;
+    a.nx = nx; a.nz = nz; a.shared_flow = g.shared_flow != 0;
     a.nstrip = uint32_t((nx + SLAB_WAVES - 1) / SLAB_WAVES);
     const dim3 grid((unsigned)(nslab * a.nstrip)), block(SLAB_THREADS);      // <= nslab*nx <= 0x7fffffff
     hipStream_t st = (hipStream_t)stream;
     switch ((nz + 63) / 64) {
-    case 1: hipLaunchKernelGGL((k_kid_advect_slab<T, 1>), grid, block, 0, st, a); break;
-    case 2: hipLaunchKernelGGL((k_kid_advect_slab<T, 2>), grid, block, 0, st, a); break;
-    case 3: hipLaunchKernelGGL((k_kid_advect_slab<T, 3>), grid, block, 0, st, a); break;
-    default: hipLaunchKernelGGL((k_kid_advect_slab<T, 4>), grid, block, 0, st, a); break;
+    case 1: hipLaunchKernelGGL((k_kid_advect_slab<T, 1, N>), grid, block, 0, st, a); break;
+    case 2: hipLaunchKernelGGL((k_kid_advect_slab<T, 2, N>), grid, block, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((k_kid_advect_slab<T, 3, N>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((k_kid_advect_slab<T, 4, N>), grid, block, 0, st, a); break;
     }
     HIPTRY(ctx, hipGetLastError());
     return KIDMP_OK;
 }
-}  // namespace
+template int kidmp::kid_advect_slab_members<double, KID_NA>(kidmp_ctx *, const char *, const KidSlabShape &, const KidMembers<double, KID_NA> &,
+    int, const char *, const char *const *, const double *, const double *, const double *, const double *, double *, void *);
+template int kidmp::kid_advect_slab_members<float, KID_NA>(kidmp_ctx *, const char *, const KidSlabShape &, const KidMembers<float, KID_NA> &,
+    int, const char *, const char *const *, const float *, const float *, const float *, const float *, float *, void *);
 
 extern "C" {
 int kidmp_kid_advect_slab_device(kidmp_ctx *ctx, int64_t nslab, int32_t nx, int32_t nz, double dt, double dx,

@@ -868,6 +868,41 @@ class ThompsonMP:
         from .slab import run_slab
         return run_slab(self, state, nsteps, dt, p0, r_on_cp, exner, dz, rho, dx, nx, u, w, fix_theta, on_step, stream, **kid_interface_options)
 
+    # ---- prognostic aerosols in the KiD path (include/kidmp_aerosol.h): kid_amd.aerosol on this context ----
+    def kid_interface_aero(self, state, dt, p0, r_on_cp, exner, dz, **options):
+        """The KiD adapter with nc, nwfa and nifa as state and the updraft w: kid_amd.aerosol.kid_interface_aero."""
+        from .aerosol import kid_interface_aero
+        return kid_interface_aero(self, state, dt, p0, r_on_cp, exner, dz, **options)
+
+    def kid_advect_aero(self, state, w, rho, dz, dt, want=("sum",), out=None, stream=None):
+        """Vertical advection of the aerosols: kid_amd.aerosol.advect_aero."""
+        from .aerosol import advect_aero
+        return advect_aero(self, state, w, rho, dz, dt, want, out, stream)
+
+    def kid_advect_slab_aero(self, state, u, w, rho, dz, dx, dt, nx, want=("sum",), out=None, stream=None):
+        """x-z advection of the aerosols on periodic slabs: kid_amd.aerosol.advect_slab_aero."""
+        from .aerosol import advect_slab_aero
+        return advect_slab_aero(self, state, u, w, rho, dz, dx, dt, nx, want, out, stream)
+
+    def kid_update_aero(self, state, dt, *tendencies, clip=True, stream=None):
+        """nc, nwfa, nifa <- A + (t1 + t2 + t3)*dt in place, with the clip at zero: kid_amd.aerosol.update_aero."""
+        from .aerosol import update_aero
+        return update_aero(self, state, dt, *tendencies, clip=clip, stream=stream)
+
+    def kid_run_aero(self, state, nsteps, dt, p0, r_on_cp, exner, dz, rho, w, nwfa_source=None, fix_theta=False, on_step=None, stream=None,
+                     **kid_interface_options):
+        """A device-resident 1-D KiD case with prognostic aerosols: kid_amd.aerosol.run_aero."""
+        from .aerosol import run_aero
+        return run_aero(self, state, nsteps, dt, p0, r_on_cp, exner, dz, rho, w, nwfa_source, fix_theta, on_step, stream,
+                        **kid_interface_options)
+
+    def kid_run_slab_aero(self, state, nsteps, dt, p0, r_on_cp, exner, dz, rho, dx, nx, u, w, nwfa_source=None, fix_theta=False,
+                          on_step=None, stream=None, **kid_interface_options):
+        """A device-resident x-z KiD case with prognostic aerosols: kid_amd.aerosol.run_slab_aero."""
+        from .aerosol import run_slab_aero
+        return run_slab_aero(self, state, nsteps, dt, p0, r_on_cp, exner, dz, rho, dx, nx, u, w, nwfa_source, fix_theta, on_step, stream,
+                             **kid_interface_options)
+
     def kernel_fingerprint(self, arith="p64"):
         """'src:<hash>;vgpr:<n>;lds:<bytes>;scratch:<bytes>' of this context's nz <= 120 column-step kernel, in the
         parity arithmetic (p64) or one of the binary32 ones (p32n, f32)."""
