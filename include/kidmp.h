@@ -485,6 +485,19 @@ int kidmp_cache_read_file(const char *path, int32_t ntab, double *const *tabs, i
 #define KIDMP_MATH_IEEE_DIV 9  /* IEEE x / y, for comparison                        */
 #define KIDMP_MATH_RCP    10   /* the kernel's 1 / y (seed, one cubically convergent step) */
 int kidmp_math_probe(kidmp_ctx *ctx, int32_t fn, int64_t n, const double *x, const double *y, double *out);
+/* The same on three operands and in either arithmetic, from a unit compiled with the column kernel's own flags (so its
+ * plain division is the kernel's binary32 one).  fn: the codes above, unchanged in meaning, and the ones below.
+ * binary32 != 0: every operand is narrowed to float (exact when the caller passes binary32-representable values), the
+ * float overload of fastmath.h is evaluated and the result widened; KIDMP_MATH_RCP_SEED is then the raw v_rcp_f32.
+ * KIDMP_MATH_DIV, KIDMP_MATH_IEEE_DIV, KIDMP_MATH_RCP and the two mixed-type powers exist in binary64 only: KIDMP_EINVAL with binary32 != 0.
+ * All arrays are host arrays of n doubles and all four are required, whichever of them fn reads. */
+#define KIDMP_MATH_POW10_TIMES_POW 11  /* 10**x * y**z in one exponential (pow10_times_pow(x, log2_parts(y), z)) */
+#define KIDMP_MATH_PLAIN_DIV 12        /* x / y as the column kernel's flags compile it                           */
+#define KIDMP_MATH_PLAIN_RCP 13        /* 1 / y likewise                                                          */
+#define KIDMP_MATH_POW_DF    14        /* pow(double x, float y): DOUBLE**REAL, evaluated in binary64             */
+#define KIDMP_MATH_POW_FD    15        /* pow(float x, double y): REAL**DOUBLE, evaluated in binary64             */
+int kidmp_math_probe_ex(kidmp_ctx *ctx, int32_t fn, int32_t binary32, int64_t n, const double *x, const double *y,
+                        const double *z, double *out);
 
 /* Seconds spent in table construction during kidmp_init (host wall clock). */
 double kidmp_init_seconds(const kidmp_ctx *ctx);

@@ -1,0 +1,96 @@
+// kidmp_mathprobe.hip -- kidmp_math_probe_ex: device evaluation of every function of fastmath.h, binary64 and binary32,
+// and of the plain binary32 division, for the accuracy tests.
+// Built with HIPFLAGS + COLFLAGS, the flags of the three column objects (-fapprox-func -freciprocal-math): what this
+// unit's `x / y` and `1 / y` compile to is what the column kernel's REAL operands get (operator/(A, Qden<B>) and
+// frcp<float> of thompson_column.hip).  kidmp_math_probe (kidmp_diag.hip, plain HIPFLAGS) stays as the reference point.
+#include "kidmp_ctx.h"
+#include "fastmath.h"
+
+using namespace kidmp;
+
+namespace {
+// IEEE binary64 division inside a unit whose flags turn `a / b` into a reciprocal and Newton steps: the scale / fmas /
+// fixup sequence that the compiler emits for a plain fp64 quotient without those flags, written out
+__device__ inline double ieee_div(double a, double b)
+{
+    bool scaled_den, vcc;
+    const double d = __builtin_amdgcn_div_scale(a, b, false, &scaled_den);
+    const double n = __builtin_amdgcn_div_scale(a, b, true, &vcc);
+    double y = __builtin_amdgcn_rcp(d);
+    y = __builtin_fma(y, __builtin_fma(-d, y, 1.0), y);
+    y = __builtin_fma(y, __builtin_fma(-d, y, 1.0), y);
+    const double q = n * y;
+    return __builtin_amdgcn_div_fixup(__builtin_amdgcn_div_fmas(__builtin_fma(-d, q, n), y, q, vcc), b, a);
+}
+
+__device__ inline double rcp_seed(double b) { return __builtin_amdgcn_rcp(b); }    // raw v_rcp_f64
+__device__ inline float rcp_seed(float b) { return __builtin_amdgcn_rcpf(b); }     // raw v_rcp_f32
+
+// the codes that exist in both arithmetics, T = double or float (operands narrowed exactly: the caller passes
+// binary32-representable values)
+template <class T> __device__ inline T eval(int fn, T x, T y, T z)
+{
+    switch (fn) {
+    case KIDMP_MATH_LOG:      return fm::log(x);
+    case KIDMP_MATH_LOG10:    return fm::log10(x);
+    case KIDMP_MATH_EXP:      return fm::exp(x);
+    case KIDMP_MATH_EXP10:    return fm::exp10(x);
+    case KIDMP_MATH_SQRT:     return fm::sqrt_pos(x);
+    case KIDMP_MATH_CBRT:     return fm::cbrt_pos(x);
+    case KIDMP_MATH_POW:      return fm::pow(x, y);
+    case KIDMP_MATH_RCP_SEED: return rcp_seed(y);
+    case KIDMP_MATH_POW10_TIMES_POW: return fm::pow10_times_pow(x, fm::log2_parts(y), z);
+    case KIDMP_MATH_PLAIN_DIV: return x / y;                                       // as the column objects compile it
+    case KIDMP_MATH_PLAIN_RCP: return T(1) / y;
+    }
+    return T(0);
+}
+
+__global__ void k_math_probe_ex(int fn, int binary32, int64_t n, const double *x, const double *y, const double *z, double *out)
+{
+    const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+#if KFM_TABLES
+    fm::tab::load_tables(int(threadIdx.x), int(blockDim.x));
+    __syncthreads();
+#endif
+    if (i >= n) return;
+    double r;
+    switch (fn) {
+    case KIDMP_MATH_DIV:    r = fm::div(x[i], y[i]); break;                        // binary64 only (refused otherwise)
+    case KIDMP_MATH_RCP:    r = fm::rcp(y[i]); break;
+    case KIDMP_MATH_IEEE_DIV: r = ieee_div(x[i], y[i]); break;
+    case KIDMP_MATH_POW_DF: r = fm::pow(x[i], float(y[i])); break;                 // DOUBLE**REAL
+    case KIDMP_MATH_POW_FD: r = fm::pow(float(x[i]), y[i]); break;                 // REAL**DOUBLE
+    default:
+        r = binary32 ? double(eval<float>(fn, float(x[i]), float(y[i]), float(z[i]))) : eval<double>(fn, x[i], y[i], z[i]);
+    }
+    out[i] = r;
+}
+}  // namespace
+
+int kidmp_math_probe_ex(kidmp_ctx *ctx, int32_t fn, int32_t binary32, int64_t n, const double *x, const double *y, const double *z,
+                        double *out)
+{
+    if (int rc = require_ready(ctx)) return rc;
+    if (n < 0 || !x || !y || !z || !out || fn < 0 || fn > KIDMP_MATH_POW_FD)
+        return fail(ctx, KIDMP_EINVAL, "kidmp_math_probe_ex: bad argument");
+    const bool only64 = fn == KIDMP_MATH_DIV || fn == KIDMP_MATH_IEEE_DIV || fn == KIDMP_MATH_RCP || fn == KIDMP_MATH_POW_DF || fn == KIDMP_MATH_POW_FD;
+    if (binary32 && only64)
+        return fail(ctx, KIDMP_EINVAL, "kidmp_math_probe_ex: the three fp64 divisions and the mixed-type powers have no binary32 form");
+    if (n == 0) return KIDMP_OK;
+    GUARD(ctx);
+    double *d = nullptr;
+    HIPTRY(ctx, hipMalloc(&d, size_t(n) * 4 * sizeof(double)));
+    hipError_t e = hipMemcpy(d, x, size_t(n) * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + n, y, size_t(n) * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + 2 * n, z, size_t(n) * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_math_probe_ex, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, fn, binary32 != 0, n, d, d + n,
+                           d + 2 * n, d + 3 * n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, d + 3 * n, size_t(n) * sizeof(double), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    HIPTRY(ctx, e);
+    return KIDMP_OK;
+}

@@ -103,6 +103,7 @@ def _declarations():
         "kidmp_batch_step_host_multi": (rc, step64 + [_dp]),
         "kidmp_batch_step_host_multi_diag": (rc, step64 + [_dp, _dp]),
         "kidmp_math_probe": (rc, [_vp, i32, i64, _dp, _dp, _dp]),
+        "kidmp_math_probe_ex": (rc, [_vp, i32, i32, i64, _dp, _dp, _dp, _dp]),
         "kidmp_get_table": (i64, [_vp, text, _dp, i64]),
         "kidmp_get_const": (i64, [_vp, text, _dp, i64]),
         "kidmp_save_table_cache": (rc, [_vp, text]),
@@ -920,6 +921,28 @@ class ThompsonMP:
         out = np.empty_like(x)
         self._check(load_library().kidmp_math_probe(self._h, self.MATH_FUNCS.index(fn), x.size, _np_ptr(x), _np_ptr(y),
                                                     _np_ptr(out)))
+        return out
+
+    MATH_FUNCS_EX = MATH_FUNCS + ("pow10_times_pow", "plain_div", "plain_rcp", "pow_df", "pow_fd")
+
+    def math_probe_ex(self, fn, x, y=None, z=None, binary32=False):
+        """math_probe on up to three operands, in binary64 or (binary32=True) through the float overloads, from a unit
+        built with the column kernel's flags: "plain_div" / "plain_rcp" are the kernel's binary32 x / y and 1 / y.
+        "pow10_times_pow": 10**x * y**z.  "pow_df" / "pow_fd": pow(double x, float y) / pow(float x, double y).
+        Operands that the device narrows to float must be binary32-representable."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.ascontiguousarray(x if y is None else y, dtype=np.float64)
+        z = np.ascontiguousarray(x if z is None else z, dtype=np.float64)
+        if not (x.shape == y.shape == z.shape):
+            raise ValueError("math_probe_ex: x, y and z must have one shape")
+        narrowed = (x, y, z) if binary32 else {"pow_df": (y,), "pow_fd": (x,)}.get(fn, ())
+        for a in narrowed:
+            with np.errstate(over="ignore"):
+                if not np.array_equal(a.astype(np.float32).astype(np.float64), a):
+                    raise ValueError("math_probe_ex: an operand the device narrows to binary32 is not binary32-representable")
+        out = np.empty_like(x)
+        self._check(load_library().kidmp_math_probe_ex(self._h, self.MATH_FUNCS_EX.index(fn), int(bool(binary32)), x.size,
+                                                       _np_ptr(x), _np_ptr(y), _np_ptr(z), _np_ptr(out)))
         return out
 
     def table(self, name, shape=None):

@@ -12,6 +12,7 @@ import pytest
 import cases
 import kat_cases as kc
 from parity import FLOORS, OUT
+from test_gpu_variants import _resample
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -100,3 +101,84 @@ def test_kat_b_native_through_the_p32n_kernel(gpu_warm):
     for g, n, pp in zip(got, native, p64):
         assert abs(g / n - 1) < 2.5e-5, (got, native)     # measured 4e-6, 1.5e-5, 1.1e-5 (binary32 special-function units, not libm)
         assert abs(g - n) < 0.5 * abs(pp - n), (g, n, pp)
+
+
+# ---- the binary32 builds at other level counts: every level-group count (<1,64>, <2,128>, <3,192>, <4,256> launches) and
+#      both sides of each threshold, in contexts that are NOT aerosol-aware
+OTHER_NZ = [2, 37, 64, 65, 121, 128, 129, 192, 193, 256]
+_shared = {}
+
+
+def _columns32(nz):
+    """64 binary32 columns on nz levels: the three KAT columns resampled as test_gpu_variants does, each perturbed with
+    the recipe of cases._perturb under a fixed seed."""
+    rng = np.random.Generator(np.random.PCG64(cases.SEED + 32 + nz))
+    parts = [cases._perturb(_resample(col, nz), n, rng) for col, n in ((kc.kat_a(True), 22), (kc.kat_a(False), 21), (kc.kat_c(), 21))]
+    return _to32({k: np.concatenate([p[k] for p in parts]) for k in cases.KEYS})
+
+
+def _stepped(iiwarm, nz, m, o):
+    """(inputs, P32n oracle result and ppt, p32n kernel result and ppt) of one context and level count, computed once and
+    shared by the tests below; nobody writes into them."""
+    key = (bool(iiwarm), nz)
+    if key not in _shared:
+        st = _columns32(nz)
+        ref = {k: v.copy() for k, v in st.items()}
+        rppt = o.batch_step_p32n(ref, 10.0)
+        got = {k: v.copy() for k, v in st.items()}
+        gppt, _, _ = m.batch_step32_host(got, 10.0, arith="p32n")
+        _shared[key] = (st, ref, rppt, got, gppt)
+    return _shared[key]
+
+
+@pytest.mark.parametrize("nz", OTHER_NZ)
+@pytest.mark.parametrize("iiwarm", [True, False], ids=["warm", "mixed"])
+def test_p32n_kernel_against_the_p32n_oracle_at_other_level_counts(iiwarm, nz, gpu_warm, gpu_mixed, oracle_warm, oracle_mixed):
+    """The bounds of test_p32n_kernel_against_the_p32n_oracle (nz = 120), unchanged, at every level-group count."""
+    m, o = (gpu_warm, oracle_warm) if iiwarm else (gpu_mixed, oracle_mixed)
+    st, ref, rppt, got, gppt = _stepped(iiwarm, nz, m, o)
+    med, q99, q9999, mx = _stats(got, ref)
+    pe = np.abs(gppt.astype(np.float64) - rppt) / np.maximum(np.abs(rppt), 1e-8)
+    print("nz %3d %s p32n gpu vs p32n oracle: median %.1e q99 %.1e q99.99 %.1e max %.1e ppt %.1e"
+          % (nz, "warm" if iiwarm else "mixed", med, q99, q9999, mx, float(pe.max())))
+    assert all(np.isfinite(got[k]).all() for k in OUT)
+    assert float(pe.max()) < 1e-4, float(pe.max())
+    assert med < 3e-7 and q99 < 1e-4, (med, q99, q9999, mx)
+
+
+@pytest.mark.parametrize("nz", OTHER_NZ)
+@pytest.mark.parametrize("iiwarm", [True, False], ids=["warm", "mixed"])
+def test_f32_kernel_stays_near_the_p32n_kernel_at_other_level_counts(iiwarm, nz, gpu_warm, gpu_mixed, oracle_warm, oracle_mixed):
+    """The all-binary32 build against the p32n result of the same launch shape: the statistic, the bound and the
+    invariants of test_binary32_builds_stay_near_the_p64_result."""
+    m, o = (gpu_warm, oracle_warm) if iiwarm else (gpu_mixed, oracle_mixed)
+    st, _, _, p32n, _ = _stepped(iiwarm, nz, m, o)
+    got = {k: v.copy() for k, v in st.items()}
+    ppt, _, _ = m.batch_step32_host(got, 10.0, arith="f32")
+    med, q99, q9999, mx = _stats(got, p32n)
+    print("nz %3d %s f32 vs p32n: median %.1e q99 %.1e q99.99 %.1e max %.1e" % (nz, "warm" if iiwarm else "mixed", med, q99, q9999, mx))
+    assert all(np.isfinite(got[k]).all() for k in OUT)
+    assert (got["qv"] >= f32(1e-10)).all() and (ppt >= 0).all()
+    for q in ("qc", "qi", "qr", "qs", "qg"):
+        assert ((got[q] == 0) | (got[q] > f32(1e-12))).all(), q
+    assert med < 1e-6 and q99 < 2e-3, (med, q99)
+
+
+@pytest.mark.parametrize("arith", ["p32n", "f32"])
+@pytest.mark.parametrize("ncol", [1, 3, 5, 6])
+def test_binary32_columns_keep_their_bits_in_a_smaller_batch(ncol, arith, gpu_mixed):
+    """A workgroup steps four columns: the first ncol columns of a 12-column batch, stepped alone (every remainder of
+    ncol mod 4), end with the bits they had in the batch of 12."""
+    if "twelve" not in _shared:
+        ec, c5 = cases.edge_cases(), cases.config5(3)
+        _shared["twelve"] = _to32({k: np.concatenate([ec[k], c5[k]]) for k in cases.KEYS})
+    st = _shared["twelve"]
+    if ("twelve", arith) not in _shared:
+        full = {k: v.copy() for k, v in st.items()}
+        _shared[("twelve", arith)] = (full, gpu_mixed.batch_step32_host(full, 10.0, arith=arith)[0])
+    full, fppt = _shared[("twelve", arith)]
+    part = {k: v[:ncol].copy() for k, v in st.items()}                    # (a slice alone would be a view into the shared input)
+    pppt = gpu_mixed.batch_step32_host(part, 10.0, arith=arith)[0]
+    for k in OUT:
+        assert np.array_equal(part[k].view(np.uint32), full[k][:ncol].view(np.uint32)), k
+    assert np.array_equal(pppt.view(np.uint32), fppt[:ncol].view(np.uint32))

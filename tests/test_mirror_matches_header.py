@@ -65,7 +65,7 @@ def _is_pointer(t):
 
 
 def test_the_header_has_the_prototypes_this_test_was_written_for():
-    assert len(_prototypes()) == 66
+    assert len(_prototypes()) == 67
 
 
 def test_every_prototype_is_declared_with_its_argument_count_and_types(declared):
