@@ -10,7 +10,9 @@
  * THE SCHEME IS THE PROJECT'S OWN.  The KiD driver's advection code (ULTIMATE) is not part of the reference this library
  * was written against, so nothing here is a port and nothing is bit-compatible with a KiD build: it is a flux-form
  * upwind scheme with a van Leer limiter, fixed to the operation so that a restatement in any IEEE binary64 arithmetic
- * gives the same bits.  Binary64, every operation rounded once (no contraction, IEEE division), in this order:
+ * gives the same bits.  It is the scheme of a new context; kidmp_advection.h offers ULTIMATE QUICKEST as a second one, which
+ * changes qf of an interior face and nothing else.  Binary64, every operation rounded once (no contraction, IEEE division),
+ * in this order:
  *
  *   rf[0] = rho[0];  rf[nz] = rho[nz-1];  rf[f] = 0.5*(rho[f-1] + rho[f])      (0 < f < nz)
  *   M[f]  = rf[f]*w[f]

@@ -15,6 +15,7 @@
  *
  * THE SCHEME IS THE PROJECT'S OWN, as in kidmp_kinematic.h (KiD's ULTIMATE is not part of the reference this library was
  * written against): the 1-D entry's flux-form upwind scheme with a van Leer limiter, applied unsplit in both directions.
+ * It is the scheme of a new context; kidmp_advection.h offers ULTIMATE QUICKEST as a second one, which changes qf in z and x.
  * Binary64, every operation rounded once (no contraction, IEEE division), in this order:
  *
  *   z part:  advz[i,k], divz[i,k] and the face Courant numbers cz[i,f] (f = 0 .. nz) are EXACTLY adv[k], div[k] and c of

@@ -12,6 +12,7 @@ from .doppler import DOPPLER_INPUTS, DOPPLER_NAMES, doppler_moments, doppler_mom
 from .fall import FALL_INPUTS, FALL_NAMES, fall_speeds, fall_speeds_host  # noqa: F401
 from .spectra import SPECTRA_INPUTS, SPECTRA_PARAMS, SPECTRA_SPECIES, default_grid, size_spectra, size_spectra_host  # noqa: F401
 from .kinematic import ADVECT_OUTPUTS, advect, run, update  # noqa: F401
+from .advection import SCHEMES as ADVECTION_SCHEMES  # noqa: F401
 from .slab import advect_slab, run_slab, streamfunction_flow  # noqa: F401
 from .aerosol import (AEROSOL_FIELDS, advect_aero, advect_slab_aero, kid_interface_aero, run_aero, run_slab_aero,  # noqa: F401
                       update_aero)

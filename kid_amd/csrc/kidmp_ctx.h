@@ -51,6 +51,8 @@ struct kidmp_ctx {
     // kidmp_set_column_nc: the bound per-column set_Nc (cm**-3, binary64) in HBM, owned by the context; null = unbound
     double *d_nc_col = nullptr;
     int64_t nc_count = 0;
+    // kidmp_set_advection (include/kidmp_advection.h): the scheme an advection entry reads when it is called
+    int32_t advection = 0;                           // KIDMP_ADVECT_VANLEER
 };
 
 namespace kidmp {

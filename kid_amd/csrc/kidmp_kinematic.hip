@@ -1,8 +1,10 @@
 // kidmp_kinematic.hip -- the entries of include/kidmp_kinematic.h: prescribed-w vertical advection of KiD's nine fields in
 // the adv / div form the adapter consumes (k_kid_advect) and the state update that closes the time loop (k_kid_update).
-// The scheme is the project's own, fixed to the operation.  Built with the library's plain flags
-// (IEEE division, no contraction): every operation below rounds once.
+// The schemes (van Leer; ULTIMATE QUICKEST, section 4.6g, include/kidmp_advection.h, whose two
+// entries are at the end) are fixed to the operation.  Built with the library's plain flags (IEEE division, no
+// contraction): every operation below rounds once.
 #include "kidmp_ctx.h"
+#include "kidmp_face.h"
 #include "kidmp_stream.h"
 #include "kidmp_wave.h"
 #include "../../include/kidmp_kinematic.h"
@@ -36,8 +38,9 @@ template <class T, int N> struct UpdateArgs {
 // of that face are formed once per column and kept in registers with what every member shares (den, the divergence
 // factor, the upwind side); then each present member is loaded once, its neighbours k-1, k-2 and k+1 come from the
 // neighbouring lanes, its face value and flux are formed once per lane and the flux of face k+1 comes from the lane
-// above.  The lane that holds level nz-1 forms the top face itself.  No LDS, no scratch.
-template <class T, int NJ, int N>
+// above.  The lane that holds level nz-1 forms the top face itself.  No LDS, no scratch.  S: the scheme of the interior
+// faces' value (kidmp_face.h), whose per-face coefficients g and rc join hc in the per-column registers.
+template <class T, int NJ, int N, int S>
 __global__ void __launch_bounds__(ADV_THREADS)
 k_kid_advect(const AdvectArgs<T, N> a, int64_t ncol, int nz)
 {
@@ -47,13 +50,15 @@ k_kid_advect(const AdvectArgs<T, N> a, int64_t ncol, int nz)
     const int64_t base = col * int64_t(nz);
     const T *const w = a.w + col * a.w_col_stride;
 
+    constexpr int NG = face::coef_count<S>(NJ);
     double M[NJ], Mup[NJ], den[NJ], hc[NJ], dM[NJ];                  // hc = 0.5*(1.0 - c) of face k
+    double g[NG], rc[NG];                                            // ULTIMATE: (1.0 - c*c)/6.0 and 1.0/c of face k
     bool up[NJ], second[NJ];                                         // w[k] >= 0; uu of face k inside the column
     double cmax = 0.;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int k = 64 * j + lane;
-        M[j] = Mup[j] = hc[j] = 0.;
+        M[j] = Mup[j] = hc[j] = g[j % NG] = rc[j % NG] = 0.;
         den[j] = 1.;
         up[j] = true;
         second[j] = false;
@@ -65,7 +70,7 @@ k_kid_advect(const AdvectArgs<T, N> a, int64_t ncol, int nz)
         second[j] = up[j] ? k >= 2 : k + 1 < nz;
         M[j] = rf * wk;
         const double c = (fabs(wk) * a.dt) / (up[j] ? dz_lo : dz);
-        hc[j] = 0.5 * (1.0 - c);
+        face::coef<S>(c, hc[j], g[j % NG], rc[j % NG]);
         den[j] = rho * dz;
         cmax = fmax(cmax, c);
         if (k == nz - 1) {                                           // the model top: rf = rho[nz-1], dz[nz-1]
@@ -104,9 +109,9 @@ k_kid_advect(const AdvectArgs<T, N> a, int64_t ncol, int nz)
         for (int j = 0; j < NJ; ++j) {
             const int k = 64 * j + lane;
             const double qu = up[j] ? q1[j] : q[j], qd = up[j] ? q[j] : q1[j], quu = up[j] ? q2[j] : qa[j];
-            const double dq = qd - qu, b = qu - quu, bd = b * dq;
-            const double s = second[j] && bd > 0. ? (2.0 * bd) / (b + dq) : 0.;
-            const double qf = k ? qu + hc[j] * s : q[j];             // qf[0] = q[0]
+            // formed before the select, not in its arm: there the division would make the select a branch
+            const double qi = face::value<S>(hc[j], g[j % NG], rc[j % NG], second[j], qu, qd, quu);
+            const double qf = k ? qi : q[j];                         // qf[0] = q[0]
             F[j] = M[j] * qf;
         }
         level_above<NJ>(F, Fup);
@@ -143,6 +148,17 @@ __global__ __launch_bounds__(256) void k_kid_update(const UpdateArgs<T, N> a)
             }
             st<T, V>(a.state[m], e, x);
         }
+    }
+}
+
+template <class T, int N, int S>
+void launch_advect(dim3 grid, dim3 block, hipStream_t st, const AdvectArgs<T, N> &a, int64_t ncol, int nz)
+{
+    switch ((nz + 63) / 64) {
+    case 1: hipLaunchKernelGGL((k_kid_advect<T, 1, N, S>), grid, block, 0, st, a, ncol, nz); break;
+    case 2: hipLaunchKernelGGL((k_kid_advect<T, 2, N, S>), grid, block, 0, st, a, ncol, nz); break;
+    case 3: hipLaunchKernelGGL((k_kid_advect<T, 3, N, S>), grid, block, 0, st, a, ncol, nz); break;
+    default: hipLaunchKernelGGL((k_kid_advect<T, 4, N, S>), grid, block, 0, st, a, ncol, nz); break;
     }
 }
 
@@ -230,12 +246,8 @@ int kidmp::kid_advect_members(kidmp_ctx *ctx, const char *who, int64_t ncol, int
     a.w = w; a.rho = rho; a.dz = dz; a.w_col_stride = w_col_stride; a.courant = courant; a.dt = dt;
     const dim3 grid((unsigned)((ncol + ADV_WAVES - 1) / ADV_WAVES)), block(ADV_THREADS);
     hipStream_t st = (hipStream_t)stream;
-    switch ((nz + 63) / 64) {
-    case 1: hipLaunchKernelGGL((k_kid_advect<T, 1, N>), grid, block, 0, st, a, ncol, nz); break;
-    case 2: hipLaunchKernelGGL((k_kid_advect<T, 2, N>), grid, block, 0, st, a, ncol, nz); break;
-    case 3: hipLaunchKernelGGL((k_kid_advect<T, 3, N>), grid, block, 0, st, a, ncol, nz); break;
-    default: hipLaunchKernelGGL((k_kid_advect<T, 4, N>), grid, block, 0, st, a, ncol, nz); break;
-    }
+    if (ctx->advection == KIDMP_ADVECT_ULTIMATE) launch_advect<T, N, KIDMP_ADVECT_ULTIMATE>(grid, block, st, a, ncol, nz);
+    else                                         launch_advect<T, N, KIDMP_ADVECT_VANLEER>(grid, block, st, a, ncol, nz);
     HIPTRY(ctx, hipGetLastError());
     return KIDMP_OK;
 }
@@ -293,6 +305,16 @@ KIDMP_INSTANTIATE(float, KID_NA)
 #undef KIDMP_INSTANTIATE
 
 extern "C" {
+int kidmp_set_advection(kidmp_ctx *ctx, int32_t scheme)
+{
+    if (!ctx) return fail(nullptr, KIDMP_ESTATE, "kidmp_set_advection: no context");
+    if (scheme != KIDMP_ADVECT_VANLEER && scheme != KIDMP_ADVECT_ULTIMATE)
+        return fail(ctx, KIDMP_EINVAL, "kidmp_set_advection: scheme must be KIDMP_ADVECT_VANLEER or KIDMP_ADVECT_ULTIMATE");
+    ctx->advection = scheme;
+    return KIDMP_OK;
+}
+int kidmp_advection(const kidmp_ctx *ctx) { return ctx ? int(ctx->advection) : fail(nullptr, KIDMP_ESTATE, "kidmp_advection: no context"); }
+
 int kidmp_kid_advect_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, double dt, const kidmp_kid_fields *state,
                             const double *w, int64_t w_col_stride, const double *rho, const double *dz,
                             const kidmp_kid_fields *adv, const kidmp_kid_fields *div, const kidmp_kid_fields *sum, double *courant,

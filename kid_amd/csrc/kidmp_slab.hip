@@ -1,8 +1,9 @@
 // kidmp_slab.hip -- the entries of include/kidmp_slab.h: prescribed-(u, w) advection of KiD's nine fields on a batch of
-// periodic x-z slabs in the adv / div form the adapter consumes (k_kid_advect_slab).  The scheme is the project's own
-// (DESIGN.md section 4.6d): the 1-D entry's in z, the same limiter in x, fixed to the operation.  Built with the library's
+// periodic x-z slabs in the adv / div form the adapter consumes (k_kid_advect_slab).  The schemes (DESIGN.md sections 4.6d
+// and 4.6g) are the 1-D entry's in z with the same face value in x, fixed to the operation.  Built with the library's
 // plain flags (IEEE division, no contraction): every operation below rounds once.
 #include "kidmp_ctx.h"
+#include "kidmp_face.h"
 #include "kidmp_wave.h"
 #include "../../include/kidmp_slab.h"
 
@@ -27,13 +28,13 @@ template <class T, int N> struct SlabArgs {              // N members: KiD's nin
 // One wavefront per column, level k = 64 j + lane, as in k_kid_advect; a workgroup owns W consecutive cells of one slab,
 // the grid is nslab x ceil(nx / W).  The z part is k_kid_advect's, operation for operation.  What every member shares is
 // formed once per column and kept in registers: in z the faces' M, hc, dM and den, in x the mass flux Mx, 0.5*(1 - cx)
-// and the upwind side of the cell's two faces i and i+1, dMx and denx.  Then each present member is loaded once; its
-// neighbours in z come from the neighbouring lanes, its neighbours in x (cells i-2 .. i+2, periodic) are plain loads
+// (and what else the scheme S of kidmp_face.h shares) and the upwind side of the cell's two faces i and i+1, dMx and
+// denx.  Then each present member is loaded once; its neighbours in z come from the neighbouring lanes, its neighbours in x (cells i-2 .. i+2, periodic) are plain loads
 // that the caches serve: the waves of a workgroup and of its neighbours read the same columns at about the same time.
 // A stage of the strip in LDS, W = 8 and x faces shared between neighbouring waves were all measured and were no faster
 // (the kernel is bound by its binary64 arithmetic), so there is no LDS and no barrier here, and
 // a wave beyond the slab's end (nx no multiple of W) may simply leave.  No scratch.
-template <class T, int NJ, int N>
+template <class T, int NJ, int N, int S>
 __global__ void __launch_bounds__(SLAB_THREADS)
 k_kid_advect_slab(const SlabArgs<T, N> a)
 {
@@ -54,9 +55,12 @@ k_kid_advect_slab(const SlabArgs<T, N> a)
     const T *const w = a.w + fcol * (int64_t(nz) + 1);
     const T *const u0 = a.u + fcol * int64_t(nz), *const u1 = a.u + fcol_r * int64_t(nz);
 
+    constexpr int NG = face::coef_count<S>(NJ);
     double M[NJ], Mup[NJ], den[NJ], hc[NJ], dM[NJ];                  // z, as in k_kid_advect: hc = 0.5*(1.0 - c) of face k
+    double g[NG], rc[NG];
     bool up[NJ], second[NJ];
     double Mx0[NJ], Mx1[NJ], hx0[NJ], hx1[NJ], dMx[NJ], denx[NJ];    // x: faces i (0) and i+1 (1) of this cell
+    double gx0[NG], gx1[NG], rx0[NG], rx1[NG];
     bool ux0[NJ], ux1[NJ];
     {
         double cz[NJ], czup[NJ], cxm[NJ], above[NJ], cabove[NJ];
@@ -65,6 +69,7 @@ k_kid_advect_slab(const SlabArgs<T, N> a)
             const int k = 64 * j + lane;
             M[j] = Mup[j] = hc[j] = cz[j] = czup[j] = cxm[j] = 0.;
             Mx0[j] = Mx1[j] = hx0[j] = hx1[j] = 0.;
+            g[j % NG] = rc[j % NG] = gx0[j % NG] = gx1[j % NG] = rx0[j % NG] = rx1[j % NG] = 0.;
             den[j] = denx[j] = 1.;
             up[j] = ux0[j] = ux1[j] = true;
             second[j] = false;
@@ -76,7 +81,7 @@ k_kid_advect_slab(const SlabArgs<T, N> a)
             second[j] = up[j] ? k >= 2 : k + 1 < nz;
             M[j] = rf * wk;
             cz[j] = (fabs(wk) * a.dt) / (up[j] ? dz_lo : dz);
-            hc[j] = 0.5 * (1.0 - cz[j]);
+            face::coef<S>(cz[j], hc[j], g[j % NG], rc[j % NG]);
             den[j] = rho * dz;
             if (k == nz - 1) {                                       // the model top: rf = rho[nz-1], dz[nz-1]
                 const double wt = double(w[nz]);
@@ -89,8 +94,8 @@ k_kid_advect_slab(const SlabArgs<T, N> a)
             Mx0[j] = rho * ul;
             Mx1[j] = rho * ur;
             const double cx0 = (fabs(ul) * a.dt) / a.dx, cx1 = (fabs(ur) * a.dt) / a.dx;
-            hx0[j] = 0.5 * (1.0 - cx0);
-            hx1[j] = 0.5 * (1.0 - cx1);
+            face::coef<S>(cx0, hx0[j], gx0[j % NG], rx0[j % NG]);
+            face::coef<S>(cx1, hx1[j], gx1[j % NG], rx1[j % NG]);
             denx[j] = rho * a.dx;
             cxm[j] = fmax(cx0, cx1);
         }
@@ -127,9 +132,9 @@ k_kid_advect_slab(const SlabArgs<T, N> a)
         for (int j = 0; j < NJ; ++j) {
             const int k = 64 * j + lane;
             const double qu = up[j] ? q1[j] : q[j], qd = up[j] ? q[j] : q1[j], quu = up[j] ? q2[j] : qa[j];
-            const double dq = qd - qu, b = qu - quu, bd = b * dq;
-            const double s = second[j] && bd > 0. ? (2.0 * bd) / (b + dq) : 0.;
-            const double qf = k ? qu + hc[j] * s : q[j];             // qf[0] = q[0]
+            // formed before the select, not in its arm: there the division would make the select a branch
+            const double qi = face::value<S>(hc[j], g[j % NG], rc[j % NG], second[j], qu, qd, quu);
+            const double qf = k ? qi : q[j];                         // qf[0] = q[0]
             F[j] = M[j] * qf;
             // the x faces of this cell: i between cells i-1 and i, i+1 between cells i and i+1
             const bool in = k < nz;
@@ -142,9 +147,8 @@ k_kid_advect_slab(const SlabArgs<T, N> a)
                 const double xu = f ? (pos ? q[j] : r1) : (pos ? l1 : q[j]);
                 const double xd = f ? (pos ? r1 : q[j]) : (pos ? q[j] : l1);
                 const double xuu = f ? (pos ? l1 : r2) : (pos ? l2 : r1);
-                const double dqx = xd - xu, bx = xu - xuu, bdx = bx * dqx;
-                const double sx = bdx > 0. ? (2.0 * bdx) / (bx + dqx) : 0.;
-                Fx[f] = (f ? Mx1[j] : Mx0[j]) * (xu + (f ? hx1[j] : hx0[j]) * sx);
+                Fx[f] = (f ? Mx1[j] : Mx0[j]) * face::value<S>(f ? hx1[j] : hx0[j], f ? gx1[j % NG] : gx0[j % NG], f ? rx1[j % NG] : rx0[j % NG],
+                                                                  true, xu, xd, xuu);
             }
             dFx[j] = Fx[1] - Fx[0];
         }
@@ -160,6 +164,16 @@ k_kid_advect_slab(const SlabArgs<T, N> a)
             if (a.div[m]) a.div[m][base + k] = T(div);
             if (a.sum[m]) a.sum[m][base + k] = T(adv + div);
         }
+    }
+}
+
+template <class T, int N, int S> void launch_slab(dim3 grid, dim3 block, hipStream_t st, const SlabArgs<T, N> &a)
+{
+    switch ((a.nz + 63) / 64) {
+    case 1: hipLaunchKernelGGL((k_kid_advect_slab<T, 1, N, S>), grid, block, 0, st, a); break;
+    case 2: hipLaunchKernelGGL((k_kid_advect_slab<T, 2, N, S>), grid, block, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((k_kid_advect_slab<T, 3, N, S>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((k_kid_advect_slab<T, 4, N, S>), grid, block, 0, st, a); break;
     }
 }
 
@@ -229,12 +243,8 @@ int kidmp::kid_advect_slab_members(kidmp_ctx *ctx, const char *who, const KidSla
     a.nstrip = uint32_t((nx + SLAB_WAVES - 1) / SLAB_WAVES);
     const dim3 grid((unsigned)(nslab * a.nstrip)), block(SLAB_THREADS);      // <= nslab*nx <= 0x7fffffff
     hipStream_t st = (hipStream_t)stream;
-    switch ((nz + 63) / 64) {
-    case 1: hipLaunchKernelGGL((k_kid_advect_slab<T, 1, N>), grid, block, 0, st, a); break;
-    case 2: hipLaunchKernelGGL((k_kid_advect_slab<T, 2, N>), grid, block, 0, st, a); break;
-    case 3: hipLaunchKernelGGL((k_kid_advect_slab<T, 3, N>), grid, block, 0, st, a); break;
-    default: hipLaunchKernelGGL((k_kid_advect_slab<T, 4, N>), grid, block, 0, st, a); break;
-    }
+    if (ctx->advection == KIDMP_ADVECT_ULTIMATE) launch_slab<T, N, KIDMP_ADVECT_ULTIMATE>(grid, block, st, a);
+    else                                         launch_slab<T, N, KIDMP_ADVECT_VANLEER>(grid, block, st, a);
     HIPTRY(ctx, hipGetLastError());
     return KIDMP_OK;
 }

@@ -1,7 +1,7 @@
 """The kinematic half of a 1-D KiD case on the device (include/kidmp_kinematic.h): prescribed-w vertical advection of
 KiD's nine fields in the adv / div form the adapter consumes, the state update that closes the time loop, and `run`, the
-device-resident loop over both and kid_interface.  The advection scheme is the project's own, not
-KiD's.
+device-resident loop over both and kid_interface.  The advection scheme is the context's (kid_amd.advection): the project's
+own van Leer scheme unless ULTIMATE QUICKEST (section 4.6g) was selected; neither is KiD's code.
 
 The four entries of kidmp_kinematic.h are declared here, on the object load_library() returned, the first time one of them
 is needed: include/kidmp.h and its mirror in thompson.py stay what they are.  There is no fallback: without the library or

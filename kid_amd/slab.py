@@ -1,7 +1,7 @@
 """The kinematic half of a 2-D (x-z) KiD case on the device (include/kidmp_slab.h): prescribed-(u, w) advection of KiD's
 nine fields on a batch of independent slabs that are periodic in x, `streamfunction_flow`, which makes a mass-non-divergent
 flow for it, and `run_slab`, the device-resident loop over advect_slab, kid_interface and kinematic.update.  The advection
-scheme is the project's own, not KiD's.
+scheme is the context's (kid_amd.advection): van Leer or ULTIMATE QUICKEST (4.6g), neither KiD's code.
 
 Only the two entries of kidmp_slab.h are declared here, on the object load_library() returned, the first time one of them
 is needed; the helpers and `update` are those of kid_amd.kinematic.  There is no fallback: without the library or the

@@ -904,6 +904,18 @@ class ThompsonMP:
         return run_slab_aero(self, state, nsteps, dt, p0, r_on_cp, exner, dz, rho, dx, nx, u, w, nwfa_source, fix_theta, on_step, stream,
                              **kid_interface_options)
 
+    # ---- the advection scheme of the KiD path (include/kidmp_advection.h): kid_amd.advection on this context ----
+    def set_advection(self, name):
+        """Select the scheme of every later kid_advect*, kid_run* call: "vanleer" (a new context's) or "ultimate"."""
+        from .advection import set_scheme
+        return set_scheme(self, name)
+
+    @property
+    def advection(self):
+        """The name of the scheme this context advects with."""
+        from .advection import scheme
+        return scheme(self)
+
     def kernel_fingerprint(self, arith="p64"):
         """'src:<hash>;vgpr:<n>;lds:<bytes>;scratch:<bytes>' of this context's nz <= 120 column-step kernel, in the
         parity arithmetic (p64) or one of the binary32 ones (p32n, f32)."""
