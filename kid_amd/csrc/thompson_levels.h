@@ -131,15 +131,20 @@ __device__ inline double cbrt_any(double x)
 
 // rain of a level with qr > R1: ze_rain, the median volume diameter and the slope; no 37.5 um / 2.5 mm limits here
 // (cf. M:1661-1666)
-__device__ inline double rain_ze(const ReflConsts &c, double rho, double qr, double nr1, double &mvd_r, double &lamr)
+__device__ inline double rain_ze(const ReflConsts &c, double rho, double qr, double nr1, double &mvd_r, double &lamr, double &N0_r)
 {
     const double rr = qr * rho;
     const double nr = fmax(R2, nr1 * rho);
     lamr = cbrt_any(am_r * c.crg3 * c.org2 * nr / rr);                    // **obmr
     const double ilamr = 1. / lamr;
-    const double N0_r = nr * c.org2 * lamr;                               // lamr**cre(2), cre(2) = 1
+    N0_r = nr * c.org2 * lamr;                                            // lamr**cre(2), cre(2) = 1
     mvd_r = MVD_FAC * ilamr;
     return N0_r * c.crg4 * pw7(ilamr);                                    // ilamr**cre(4), M:5130
+}
+__device__ inline double rain_ze(const ReflConsts &c, double rho, double qr, double nr1, double &mvd_r, double &lamr)
+{
+    double N0_r;
+    return rain_ze(c, rho, qr, nr1, mvd_r, lamr, N0_r);
 }
 __device__ inline double rain_ze(const ReflConsts &c, double rho, double qr, double nr1, double &mvd_r)
 {
@@ -159,13 +164,18 @@ __device__ inline double graupel_n0_exp(bool slw, double mvd_r, double rg)
     return fmax(gonv_min, fmin(n0, gonv_max));
 }
 // graupel of a level with qg > R2 once the running minimum N0_exp is known, M:5099-5102 and M:5133-5135; ilamg goes out too
-__device__ inline double graupel_ze(const ReflConsts &c, double N0_exp, double rg, double &ilamg)
+__device__ inline double graupel_ze(const ReflConsts &c, double N0_exp, double rg, double &ilamg, double &lamg, double &N0_g)
 {
     const double lam_exp = fm::sqrt_pos(fm::sqrt_pos(N0_exp * am_g * c.cgg1 / rg));    // **oge1
-    const double lamg = lam_exp * c.lamg_fac;
+    lamg = lam_exp * c.lamg_fac;
     ilamg = 1. / lamg;
-    const double N0_g = N0_exp / (c.cgg2 * lam_exp) * lamg;                             // lamg**cge(2), cge(2) = 1
+    N0_g = N0_exp / (c.cgg2 * lam_exp) * lamg;                                          // lamg**cge(2), cge(2) = 1
     return ZE_GRAUPEL_FAC * N0_g * c.cgg4 * pw7(ilamg);                                 // ilamg**cge(4)
+}
+__device__ inline double graupel_ze(const ReflConsts &c, double N0_exp, double rg, double &ilamg)
+{
+    double lamg, N0_g;
+    return graupel_ze(c, N0_exp, rg, ilamg, lamg, N0_g);
 }
 __device__ inline double graupel_ze(const ReflConsts &c, double N0_exp, double rg)
 {
@@ -306,11 +316,16 @@ __device__ inline void graupel_doppler(const DopplerConsts &d, double rhof, doub
 // snow: block O's t1..t4_vts form (M:3289-3299) at the reflectivity moment n = 2 bm_s + 1 = 5.  With Mrat = smob/smoc,
 //   A(b,f) = Kap0 Gamma(5+b) (Mrat Lam0 + f)**-(5+b) + Kap1 Mrat**mu_s Gamma(5+mu_s+b) (Mrat Lam1 + f)**-(5+mu_s+b)
 // and A(0,0) = Mrat**-5 * a00 with a00 a constant of the host.  No vts_boost, no above-freezing blend.
-__device__ inline void snow_doppler(const ReflConsts &c, const DopplerConsts &d, double rhof, const SnowLevel &s, double &vz, double &v2)
+__device__ inline double snow_mrat(const ReflConsts &c, const DopplerConsts &d, const SnowLevel &s)
 {
     const double smoc = snow_moment(c.sa, c.sb, d.cse1, s);
-    const double Mrat = s.smob / smoc;
-    const double mm = pow_parts(fm::log2_parts(Mrat), mu_s);
+    return s.smob / smoc;
+}
+__device__ inline double snow_mrat_mu(double Mrat) { return pow_parts(fm::log2_parts(Mrat), mu_s); }    // Mrat**mu_s
+__device__ inline void snow_doppler(const ReflConsts &c, const DopplerConsts &d, double rhof, const SnowLevel &s, double &vz, double &v2)
+{
+    const double Mrat = snow_mrat(c, d, s);
+    const double mm = snow_mrat_mu(Mrat);
     const double m2 = Mrat * Mrat, m5 = m2 * m2 * Mrat;
     const double x0 = Mrat * Lam0, x1 = Mrat * Lam1;
     const double a1 = d.ks0_1 * pow_parts(fm::log2_parts(x0 + fv_s), -(5. + bv_s))
@@ -405,6 +420,32 @@ __device__ inline double cloud_bin(double n0, double lam, int nu, double D, doub
     const double Dnu = ((nu & 1 ? D : 1.) * (nu & 2 ? D2 : 1.)) * ((nu & 4 ? D4 : 1.) * (nu & 8 ? D8 : 1.));
     return n0 * Dnu * exp_neg(lam * D) * dD;
 }
+
+// ---- the Doppler spectrum (include/kidmp_dspectrum.h): the reflectivity z_b of one diameter bin at one level, in the
+// units of ze, and what depends on the bin alone.  Rain and graupel: z_b = (A * exp_neg(lam*D_b)) * G_b with A = N0_r or
+// ZE_GRAUPEL_FAC*N0_g and G_b = D_b**6 * dD_b.  Snow: z_b = (zs * (Kap0*exp_neg(x0*D_b) + (k1*D_b**mu_s)*exp_neg(x1*D_b))) * G_b
+// with zs = ze_s*(Mrat**5*ia00), x0 = Mrat*Lam0, x1 = Mrat*Lam1, k1 = Kap1*Mrat**mu_s and G_b = D_b**4 * dD_b.
+// The fall speed of the bin in still air of density rho_not is vfac_b = av*D_b**bv*exp_neg(fv*D_b) (bv_r = 1; graupel has
+// no exponential): the level multiplies by rhof. ----
+struct SnowEcho { double zs, x0, x1, k1; };
+__device__ inline SnowEcho snow_echo(const DopplerConsts &d, double ze_s, double Mrat)
+{
+    const double m2 = Mrat * Mrat, m5 = m2 * m2 * Mrat;
+    SnowEcho o;
+    o.zs = ze_s * (m5 * d.ia00);
+    o.x0 = Mrat * Lam0;
+    o.x1 = Mrat * Lam1;
+    o.k1 = Kap1 * snow_mrat_mu(Mrat);
+    return o;
+}
+__device__ inline double exp_echo(double A, double lam, double D, double G) { return (A * exp_neg(lam * D)) * G; }
+__device__ inline double snow_echo_bin(const SnowEcho &s, double D, double Dmu, double G)
+{ return (s.zs * (Kap0 * exp_neg(s.x0 * D) + (s.k1 * Dmu) * exp_neg(s.x1 * D))) * G; }
+__device__ inline double rain_bin_speed(double D) { return av_r * D * exp_neg(fv_r * D); }                    // bv_r = 1
+__device__ inline double snow_bin_speed(double D) { return av_s * fm::pow(D, bv_s) * exp_neg(fv_s * D); }
+__device__ inline double graupel_bin_speed(double D) { return av_g * fm::pow(D, bv_g); }
+__device__ inline double pw6_times(double D, double dD) { const double D2 = D * D; return D2 * D2 * D2 * dD; }
+__device__ inline double pw4_times(double D, double dD) { const double D2 = D * D; return D2 * D2 * dD; }
 
 }  // namespace lvl
 }  // namespace kidmp

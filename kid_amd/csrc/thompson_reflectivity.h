@@ -100,4 +100,26 @@ template <class T>
 hipError_t launch_doppler_moments(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const DopplerArgs<T> &a,
                                   hipStream_t stream);
 
+// The Doppler spectrum (include/kidmp_dspectrum.h): the reflectivity of every level on a uniform velocity grid, from
+// k_doppler_moments' load.  Null means: qs, qg -- zero; w -- zero; an output -- not wanted.  out: total, rain, snow,
+// graupel [ncol][nv][nz], below, above [ncol][nz].  D, dD: device arrays of nb[x] doubles by species rain, snow, graupel.
+// idv = 1/dv.  One launch; the velocity axis is walked in tiles of DSPECTRUM_TILE slots held in LDS.
+// (-DKIDMP_DSPECTRUM_TILE=n builds another tile for tools/bench_doppler_spectrum.py --lib; the results do not depend on it)
+#ifndef KIDMP_DSPECTRUM_TILE
+#define KIDMP_DSPECTRUM_TILE 24
+#endif
+constexpr int DSPECTRUM_NOUT = 6, DSPECTRUM_NSPEC = 3, DSPECTRUM_TILE = KIDMP_DSPECTRUM_TILE, DSPECTRUM_MAX_NV = 256;
+static_assert(DSPECTRUM_TILE >= 2 && DSPECTRUM_TILE <= 30, "four waves' tiles and the fastmath tables share 64 KiB of LDS");
+template <class T> struct DSpectrumArgs {
+    const T *t, *p, *qv, *qr, *nr, *qs, *qg, *w;
+    T *out[DSPECTRUM_NOUT];
+    const double *D[DSPECTRUM_NSPEC], *dD[DSPECTRUM_NSPEC];
+    int32_t nb[DSPECTRUM_NSPEC];
+    double v0, idv;
+    int32_t nv;
+};
+template <class T>
+hipError_t launch_doppler_spectrum(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const DSpectrumArgs<T> &a,
+                                   hipStream_t stream);
+
 }  // namespace kidmp

@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "thompson_levels.h"
+#include "kidmp_dspectrum_slot.h"
 
 namespace kidmp {
 
@@ -712,6 +713,58 @@ k_size_spectra(const Consts *__restrict__ hc, SpectraArgs<T> a, int64_t ncol, in
     }
 }
 
+// ---- what k_doppler_moments and k_doppler_spectrum share: calc_refl10cm's load of one level (M:4991-5028) with the
+// slopes and intercepts that column_dbz leaves inside lvl::rain_ze and lvl::graupel_ze ----
+// An absent species: ze = 1.E-22 (M:5127-5136), lamr = N0_r = 0, sl zero.  n0_exp is the level's graupel intercept before
+// the running minimum.  A: DopplerArgs or DSpectrumArgs (t, p, qv, qr, nr; qs, qg null = zero).
+struct RadarLevel {
+    bool L_qr, L_qs, L_qg;
+    double rhof, rg, n0_exp, ze_rain, ze_snow, lamr, N0_r;
+    lvl::SnowLevel sl;
+};
+template <class A>
+__device__ __forceinline__ RadarLevel radar_level(const ReflConsts &c, const A &a, int64_t i)
+{
+    RadarLevel r;
+    const double temp = double(a.t[i]);
+    const double qv = fmax(1.E-10, double(a.qv[i]));
+    const double rho = lvl::air_density(double(a.p[i]), temp, qv);
+    const double qr = double(a.qr[i]);
+    const double qs = a.qs ? double(a.qs[i]) : 0.;
+    const double qg = a.qg ? double(a.qg[i]) : 0.;
+    r.L_qr = qr > R1;
+    r.L_qs = qs > R2;
+    r.L_qg = qg > R2;
+    r.rhof = fm::sqrt_pos(rho_not / rho);
+    r.ze_rain = r.ze_snow = 1.E-22;
+    r.lamr = r.N0_r = 0.;
+    r.sl = lvl::SnowLevel{};
+    r.rg = R1;
+    double mvd_r = 50.E-6;
+    if (r.L_qr) r.ze_rain = lvl::rain_ze(c, rho, qr, double(a.nr[i]), mvd_r, r.lamr, r.N0_r);
+    if (r.L_qs) {
+        r.sl = lvl::snow_level(temp, qs * rho, c.oams);
+        r.ze_snow = lvl::snow_ze(c, r.sl);
+    }
+    if (r.L_qg) r.rg = qg * rho;
+    r.n0_exp = lvl::graupel_n0_exp(temp < 270.65 && r.L_qr && mvd_r > 100.E-6, mvd_r, r.rg);
+    return r;
+}
+// N0_min = MIN(N0_exp, N0_min) from kte down to kts (M:5097-5098): n0 holds N0_exp (+inf past kte) and receives the
+// running minimum, the level groups chained from the top through a wave-uniform carry.  Whole wavefronts only.
+template <int NJ>
+__device__ __forceinline__ void graupel_running_min(double (&n0)[NJ], int lane)
+{
+    double carry = gonv_max;
+#pragma unroll
+    for (int j = NJ - 1; j >= 0; --j) {
+        double tail;
+        const double s = wave_suffix_min(n0[j], lane, tail);
+        n0[j] = fmin(s, carry);
+        carry = fmin(carry, tail);
+    }
+}
+
 // One wavefront per column: the three radar moments of every level (include/kidmp_doppler.h).  The load, the ze_* and the
 // order of their sum are column_dbz's, through the same lvl:: functions; beside them the reflectivity-weighted first and
 // second moments of each species' fall speed.  Rain and snow are finished before the graupel scan and leave only their
@@ -741,50 +794,28 @@ k_doppler_moments(ReflConsts c, DopplerConsts dc, DopplerArgs<T> a, int64_t ncol
         n0[j] = double(__builtin_inf());                             // levels past kte do not enter the minimum
         if (k >= nz) continue;
         const int64_t i = base + k;
-        // ---- load, M:4991-5028 ----
-        const double temp = double(a.t[i]);
-        const double qv = fmax(1.E-10, double(a.qv[i]));
-        const double rho = lvl::air_density(double(a.p[i]), temp, qv);
-        const double qr = double(a.qr[i]);
-        const double qs = a.qs ? double(a.qs[i]) : 0.;
-        const double qg = a.qg ? double(a.qg[i]) : 0.;
-        const bool L_qr = qr > R1, L_qs = qs > R2;
-        lqg[j] = qg > R2;
+        const RadarLevel r = radar_level(c, a, i);                   // ---- load, M:4991-5028 ----
+        const bool L_qr = r.L_qr, L_qs = r.L_qs;
+        const double ze_rain = r.ze_rain, ze_snow = r.ze_snow;
+        lqg[j] = r.L_qg;
         any[j] = L_qr || L_qs || lqg[j];
-        rhof[j] = fm::sqrt_pos(rho_not / rho);
-        double ze_rain = 1.E-22, ze_snow = 1.E-22, mvd_r = 50.E-6;
+        rhof[j] = r.rhof;
+        rg[j] = r.rg;
         double vz_r = 0., v2_r = 0., vz_s = 0., v2_s = 0.;
-        if (L_qr) {
-            double lamr;
-            ze_rain = lvl::rain_ze(c, rho, qr, double(a.nr[i]), mvd_r, lamr);
-            lvl::rain_doppler(dc, rhof[j], lamr, vz_r, v2_r);
-        }
-        if (L_qs) {
-            const lvl::SnowLevel sl = lvl::snow_level(temp, qs * rho, c.oams);
-            ze_snow = lvl::snow_ze(c, sl);
-            lvl::snow_doppler(c, dc, rhof[j], sl, vz_s, v2_s);
-        }
-        if (lqg[j]) rg[j] = qg * rho;
+        if (L_qr) lvl::rain_doppler(dc, rhof[j], r.lamr, vz_r, v2_r);
+        if (L_qs) lvl::snow_doppler(c, dc, rhof[j], r.sl, vz_s, v2_s);
         ze_rs[j] = ze_rain + ze_snow;
         wt[j] = (L_qr ? ze_rain : 0.) + (L_qs ? ze_snow : 0.);
         m1[j] = ze_rain * vz_r + ze_snow * vz_s;                     // an absent species has vz = v2 = +0.0
         m2[j] = ze_rain * v2_r + ze_snow * v2_s;
-        n0[j] = lvl::graupel_n0_exp(temp < 270.65 && L_qr && mvd_r > 100.E-6, mvd_r, rg[j]);
+        n0[j] = r.n0_exp;
         if (a.out[3]) a.out[3][i] = T(vz_r);
         if (a.out[4]) a.out[4][i] = T(vz_s);
         if (a.out[6]) a.out[6][i] = T(lvl::dbz_of(ze_rain));
         if (a.out[7]) a.out[7][i] = T(lvl::dbz_of(ze_snow));
     }
 
-    // ---- N0_min = MIN(N0_exp, N0_min) from kte down to kts (M:5097-5098) ----
-    double carry = gonv_max;
-#pragma unroll
-    for (int j = NJ - 1; j >= 0; --j) {
-        double tail;
-        const double s = wave_suffix_min(n0[j], lane, tail);
-        n0[j] = fmin(s, carry);
-        carry = fmin(carry, tail);
-    }
+    graupel_running_min<NJ>(n0, lane);
 
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -810,6 +841,155 @@ k_doppler_moments(ReflConsts c, DopplerConsts dc, DopplerArgs<T> a, int64_t ncol
         }
         if (a.out[1]) a.out[1][i] = T(vd);
         if (a.out[2]) a.out[2][i] = T(sw);
+    }
+}
+
+// ---- the Doppler spectrum (include/kidmp_dspectrum.h) ----
+// what a level keeps for its bins: the three species' factors of lvl::exp_echo / lvl::snow_echo_bin
+struct EchoLevel {
+    double rhof, w, n0r, lamr, n0g, lamg;
+    lvl::SnowEcho s;
+    bool pr, ps, pg;
+};
+__device__ inline double wave_min(double v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v = fmin(v, __shfl_xor(v, m, 64));
+    return v;
+}
+
+// One species' bins of one level group into the slots [t0, t1) of the wave's tile, `acc` laid out [slot - t0][lane]:
+// every lane owns a column of the tile, so no two lanes meet and the order of the additions to a slot is the order of
+// the bins.  Slots are counted from `below` = 0: slot s holds velocity bin s - 1, slot nv + 1 is `above`.
+// What depends on the bin alone is formed once per bin, 64 bins at a time and one per lane, and handed round with
+// v_readlane.  Each of those lanes also bounds the slots its bin can reach at any level of the group, from the group's
+// extremes of rhof and w: the position (rhof*vfac - w - v0)*idv is monotone in rhof and in w under rounding, so the bound
+// holds exactly, and a bin that cannot reach the tile is passed over before its exponential.  The bound only prunes;
+// whether a lane deposits is decided by its own slot, so the result does not depend on the tile.
+template <int SP, class T>
+__device__ __forceinline__ void deposit_species(double *__restrict__ acc, int t0, int t1, const EchoLevel &L, bool present,
+                                                const DSpectrumArgs<T> &a, int lane)
+{
+    if (!__ballot(present)) return;
+    const double inf = double(__builtin_inf());
+    const bool wild = __ballot(present && !(fabs(L.rhof) < inf && fabs(L.w) < inf)) != 0;   // NaN or infinite: no bound
+    const double rmin = wave_min(present ? L.rhof : inf), rmax = wave_max(present ? L.rhof : -inf);
+    const double wmin = wave_min(present ? L.w : inf), wmax = wave_max(present ? L.w : -inf);
+    const double *__restrict__ D = a.D[SP], *__restrict__ dD = a.dD[SP];
+    const int nb = a.nb[SP], nv = a.nv, top = nv + 1;
+    for (int bb = 0; bb < nb; bb += 64) {
+        double mD = 0., mG = 0., mV = 0., mMu = 0.;
+        bool reach = false;
+        if (bb + lane < nb) {
+            mD = D[bb + lane];
+            const double dDb = dD[bb + lane];
+            if (SP == 0) { mG = lvl::pw6_times(mD, dDb); mV = lvl::rain_bin_speed(mD); }
+            if (SP == 1) { mG = lvl::pw4_times(mD, dDb); mV = lvl::snow_bin_speed(mD); mMu = fm::pow(mD, mu_s); }
+            if (SP == 2) { mG = lvl::pw6_times(mD, dDb); mV = lvl::graupel_bin_speed(mD); }
+            int lo = 0, hi = top;
+            if (!wild && mV >= 0.) {
+                lo = dspectrum_slot((rmin * mV - wmax - a.v0) * a.idv, nv).j + 1;
+                hi = dspectrum_slot((rmax * mV - wmin - a.v0) * a.idv, nv).j + 2;
+            }
+            reach = hi >= t0 && lo < t1;
+        }
+        unsigned long long hit = __ballot(reach);
+        while (hit) {
+            const int b = __builtin_ctzll(hit);
+            hit &= hit - 1;
+            const double Db = readlane(mD, b), Gb = readlane(mG, b), Vb = readlane(mV, b);
+            const double Dmu = SP == 1 ? readlane(mMu, b) : 0.;
+            const DSpectrumSlot s = dspectrum_slot((L.rhof * Vb - L.w - a.v0) * a.idv, nv);
+            const int s0 = s.j + 1, s1 = s.j + 2;                    // 0 .. nv, 1 .. nv + 1
+            const bool in0 = s0 >= t0 && s0 < t1, in1 = s1 >= t0 && s1 < t1;
+            if (present && (in0 || in1)) {
+                double z = 0.;
+                if (SP == 0) z = lvl::exp_echo(L.n0r, L.lamr, Db, Gb);
+                if (SP == 1) z = lvl::snow_echo_bin(L.s, Db, Dmu, Gb);
+                if (SP == 2) z = lvl::exp_echo(L.n0g, L.lamg, Db, Gb);
+                if (in0) acc[(s0 - t0) * 64 + lane] += (1. - s.f) * z;
+                if (in1) acc[(s1 - t0) * 64 + lane] += s.f * z;
+            }
+        }
+    }
+}
+
+// One wavefront per column: the Doppler spectrum of every level (include/kidmp_dspectrum.h).  The load and the scan are
+// k_doppler_moments' (radar_level, graupel_running_min); every level keeps the factors of its three species in registers.
+// Then, per level group and per requested spectrum (total with below and above, rain, snow, graupel: one pass each), the
+// nv + 2 slots are walked in tiles of DSPECTRUM_TILE: the tile's accumulators are a lane-private column in LDS, zeroed,
+// filled species by species in the order rain, snow, graupel with the bins ascending, and written out as one row store
+// per velocity bin.  No atomics; a slot's additions come in one order whatever the tile, the pass and the grid.
+template <class T, int NJ>
+__global__ void __launch_bounds__(REFL_THREADS)
+k_doppler_spectrum(ReflConsts c, DopplerConsts dc, DSpectrumArgs<T> a, int64_t ncol, int nz)
+{
+    __shared__ double s_acc[REFL_WAVES][DSPECTRUM_TILE * 64];
+#if KFM_TABLES
+    fm::tab::load_tables(int(threadIdx.x), REFL_THREADS);
+    __syncthreads();
+#endif
+    const int lane = int(threadIdx.x) & 63;
+    const int64_t col = int64_t(blockIdx.x) * REFL_WAVES + (int(threadIdx.x) >> 6);
+    if (col >= ncol) return;                                         // whole wavefronts only: the scan needs every lane
+    const int64_t base = col * int64_t(nz);
+    double *__restrict__ acc = s_acc[int(threadIdx.x) >> 6];
+
+    EchoLevel lv[NJ];
+    double rg[NJ], n0[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        lv[j] = EchoLevel{};
+        rg[j] = R1;
+        n0[j] = double(__builtin_inf());                             // levels past kte do not enter the minimum
+        if (k >= nz) continue;
+        const int64_t i = base + k;
+        const RadarLevel r = radar_level(c, a, i);
+        lv[j].rhof = r.rhof;
+        lv[j].pr = r.L_qr; lv[j].ps = r.L_qs; lv[j].pg = r.L_qg;
+        if (r.L_qr || r.L_qs || r.L_qg) lv[j].w = a.w ? double(a.w[i]) : 0.;     // a level with no species: w is not read
+        lv[j].n0r = r.N0_r; lv[j].lamr = r.lamr;
+        if (r.L_qs) lv[j].s = lvl::snow_echo(dc, r.ze_snow, lvl::snow_mrat(c, dc, r.sl));
+        rg[j] = r.rg;
+        n0[j] = r.n0_exp;
+    }
+    graupel_running_min<NJ>(n0, lane);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        if (!lv[j].pg) continue;
+        double ilamg, N0_g;
+        lvl::graupel_ze(c, n0[j], rg[j], ilamg, lv[j].lamg, N0_g);
+        lv[j].n0g = lvl::ZE_GRAUPEL_FAC * N0_g;
+    }
+
+    const int nv = a.nv, nslot = nv + 2;
+    for (int j = 0; j < NJ; ++j) {
+        EchoLevel L = lv[0];
+#pragma unroll
+        for (int jj = 1; jj < NJ; ++jj)
+            if (j == jj) L = lv[jj];
+        const int k = 64 * j + lane;
+        for (int pass = 0; pass < 4; ++pass) {
+            const bool edges = pass == 0 && (a.out[4] || a.out[5]);
+            T *__restrict__ spec = a.out[pass];
+            if (!spec && !edges) continue;
+            for (int t0 = 0; t0 < nslot; t0 += DSPECTRUM_TILE) {
+                const int t1 = t0 + DSPECTRUM_TILE < nslot ? t0 + DSPECTRUM_TILE : nslot;
+                if (!spec && t0 > 0 && t1 < nslot) continue;         // below and above alone: the first and the last tile
+                for (int s = 0; s < t1 - t0; ++s) acc[s * 64 + lane] = 0.;
+                if (pass == 0 || pass == 1) deposit_species<0, T>(acc, t0, t1, L, L.pr, a, lane);
+                if (pass == 0 || pass == 2) deposit_species<1, T>(acc, t0, t1, L, L.ps, a, lane);
+                if (pass == 0 || pass == 3) deposit_species<2, T>(acc, t0, t1, L, L.pg, a, lane);
+                if (k < nz)
+                    for (int s = t0; s < t1; ++s) {
+                        const double v = acc[(s - t0) * 64 + lane];
+                        if (s == 0) { if (edges && a.out[4]) a.out[4][base + k] = T(v); }
+                        else if (s == nslot - 1) { if (edges && a.out[5]) a.out[5][base + k] = T(v); }
+                        else if (spec) spec[(col * int64_t(nv) + (s - 1)) * int64_t(nz) + k] = T(v);
+                    }
+            }
+        }
     }
 }
 
@@ -1028,6 +1208,24 @@ hipError_t launch_doppler_moments(const ReflConsts &c, const DopplerConsts &dc, 
 }
 template hipError_t launch_doppler_moments<double>(const ReflConsts &, const DopplerConsts &, int64_t, int, const DopplerArgs<double> &, hipStream_t);
 template hipError_t launch_doppler_moments<float>(const ReflConsts &, const DopplerConsts &, int64_t, int, const DopplerArgs<float> &, hipStream_t);
+
+template <class T>
+hipError_t launch_doppler_spectrum(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const DSpectrumArgs<T> &a, hipStream_t s)
+{
+    if (ncol <= 0) return hipSuccess;
+    if (a.nv < 1 || a.nv > DSPECTRUM_MAX_NV) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((ncol + REFL_WAVES - 1) / REFL_WAVES)), block(REFL_THREADS);
+    switch ((nz + 63) / 64) {
+    case 1: hipLaunchKernelGGL((k_doppler_spectrum<T, 1>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 2: hipLaunchKernelGGL((k_doppler_spectrum<T, 2>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 3: hipLaunchKernelGGL((k_doppler_spectrum<T, 3>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 4: hipLaunchKernelGGL((k_doppler_spectrum<T, 4>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+template hipError_t launch_doppler_spectrum<double>(const ReflConsts &, const DopplerConsts &, int64_t, int, const DSpectrumArgs<double> &, hipStream_t);
+template hipError_t launch_doppler_spectrum<float>(const ReflConsts &, const DopplerConsts &, int64_t, int, const DSpectrumArgs<float> &, hipStream_t);
 
 bool doppler_consts_supported(const Consts &hc)
 {

@@ -63,6 +63,7 @@ module module_mp_thompson09n
   public :: fall_speeds_batch
   public :: doppler_moments_batch
   public :: size_spectra_batch
+  public :: doppler_spectrum_batch
   public :: mp_thompson_kid_interface, mp_thompson_kid_staging
   logical, public :: is_aerosol_aware = .false.          ! M:28 (read at thompson_init)
   logical, public :: l_rate_diagnostics = .true.         ! replay the save_dg calls of M:2962-3124
@@ -112,6 +113,14 @@ module module_mp_thompson09n
      type(c_ptr) :: D(5), dD(5)
      integer(c_int32_t) :: nb(5)
   end type kidmp_spectra_grids
+
+  type, bind(C) :: kidmp_dspectrum_out                   ! kidmp_dspectrum_out / kidmp32_dspectrum_out: NULL = not wanted
+     type(c_ptr) :: total, rain, snow, graupel, below, above
+  end type kidmp_dspectrum_out
+  type, bind(C) :: kidmp_dspectrum_grids                 ! by species r, s, g: D and dD both NULL = the scheme's own 100 bins
+     type(c_ptr) :: D(3), dD(3)
+     integer(c_int32_t) :: nb(3)
+  end type kidmp_dspectrum_grids
 
   type, bind(C) :: kidmp_kid_fields                      ! kidmp_kid_fields / kidmp32_kid_fields: KiD's fields, [ncol][nz] each
      type(c_ptr) :: theta, qv, qc, qr, nr, qi, ni, qs, qg
@@ -359,6 +368,29 @@ module module_mp_thompson09n
        type(c_ptr), value :: t, p, qv, qr, nr, qs, qg, w   ! real(c_float) [ncol][nz]
        type(kidmp_doppler_out), intent(in) :: out
      end function kidmp32_doppler_moments_host
+     ! the Doppler spectrum on a uniform velocity grid (include/kidmp_dspectrum.h): qs, qg and w may be NULL (zero)
+     integer(c_int) function kidmp_doppler_spectrum_host(ctx, ncol, nz, t, p, qv, qr, nr, qs, qg, w, v0, dv, nv, grids, out) &
+          bind(C, name='kidmp_doppler_spectrum_host')
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr, kidmp_dspectrum_grids, kidmp_dspectrum_out
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz, nv
+       type(c_ptr), value :: t, p, qv, qr, nr, qs, qg, w
+       real(c_double), value :: v0, dv
+       type(kidmp_dspectrum_grids), intent(in) :: grids
+       type(kidmp_dspectrum_out), intent(in) :: out
+     end function kidmp_doppler_spectrum_host
+     integer(c_int) function kidmp32_doppler_spectrum_host(ctx, ncol, nz, t, p, qv, qr, nr, qs, qg, w, v0, dv, nv, grids, out) &
+          bind(C, name='kidmp32_doppler_spectrum_host')
+       import :: c_int, c_int32_t, c_int64_t, c_double, c_ptr, kidmp_dspectrum_grids, kidmp_dspectrum_out
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz, nv
+       type(c_ptr), value :: t, p, qv, qr, nr, qs, qg, w
+       real(c_double), value :: v0, dv
+       type(kidmp_dspectrum_grids), intent(in) :: grids
+       type(kidmp_dspectrum_out), intent(in) :: out
+     end function kidmp32_doppler_spectrum_host
   end interface
 
 contains
@@ -869,6 +901,82 @@ contains
     end if
     call stop_on_error(rc, 'doppler_moments_batch')
   end subroutine doppler_moments_batch
+
+  ! The Doppler spectrum of a state over ncol columns of KiD's (nz, ncol) storage in one call (include/kidmp_dspectrum.h):
+  ! the reflectivity (m6 m-3 per bin) of rain, snow and graupel together (total) and apart, as spectra (nz, nv, ncol) on the
+  ! uniform velocity grid v0 + j*dv, j = 0 .. nv-1 (m s-1, positive downward, always REAL 8; 1 <= nv <= 256), and what total
+  ! holds outside the grid, below and above (nz, ncol).  Every output is optional, in the array kind the arithmetic stores;
+  ! at least one must be present, and the second extent of a spectrum must be nv.  qs and qg left out mean zero; w is the
+  ! vertical air velocity (positive upward), left out: still air.  A species is put on the diameter grid D_x(nb), dD_x(nb)
+  ! (m, always REAL 8; 1 <= nb <= 256) when both are given, else on the scheme's own 100 bins.  The inputs are not
+  ! changed.  Default REAL 8 goes to kidmp_doppler_spectrum_host, REAL 4 to kidmp32_...
+  subroutine doppler_spectrum_batch(ncol, nz, t, p, qv, qr, nr, v0, dv, nv, total, rain, snow, graupel, below, above, qs, qg, w, &
+       D_r, dD_r, D_s, dD_s, D_g, dD_g)
+    integer, intent(in) :: ncol, nz, nv
+    real, dimension(nz,ncol), intent(in), target :: t, p, qv, qr, nr
+    real(c_double), intent(in) :: v0, dv
+    real, dimension(:,:,:), intent(inout), optional, target, contiguous :: total, rain, snow, graupel
+    real, dimension(nz,ncol), intent(out), optional, target :: below, above
+    real, dimension(nz,ncol), intent(in), optional, target :: qs, qg, w
+    real(c_double), dimension(:), intent(in), optional, target, contiguous :: D_r, dD_r, D_s, dD_s, D_g, dD_g
+    type(kidmp_dspectrum_out) :: out
+    type(kidmp_dspectrum_grids) :: grids
+    type(c_ptr) :: pqs, pqg, pw
+    integer(c_int) :: rc
+    integer :: x
+    if (.not. c_associated(ctx)) call thompson_init
+    if (c_associated(mctx)) then
+       write(*,'(a)') ' module_mp_thompson09n: Doppler spectra are not available with kidmp_ndevices > 1'
+       stop 1
+    end if
+    pqs = c_null_ptr;  pqg = c_null_ptr;  pw = c_null_ptr
+    if (present(qs)) pqs = c_loc(qs)
+    if (present(qg)) pqg = c_loc(qg)
+    if (present(w)) pw = c_loc(w)
+    do x = 1, 3
+       grids%D(x) = c_null_ptr;  grids%dD(x) = c_null_ptr;  grids%nb(x) = 0_c_int32_t
+    end do
+    call grid(1, D_r, dD_r)
+    call grid(2, D_s, dD_s)
+    call grid(3, D_g, dD_g)
+    out = kidmp_dspectrum_out(c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr)
+    call spectrum(out%total, total)
+    call spectrum(out%rain, rain)
+    call spectrum(out%snow, snow)
+    call spectrum(out%graupel, graupel)
+    if (present(below)) out%below = c_loc(below)
+    if (present(above)) out%above = c_loc(above)
+    if (kind(t) == c_double) then
+       rc = kidmp_doppler_spectrum_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), c_loc(qr), &
+            c_loc(nr), pqs, pqg, pw, v0, dv, int(nv, c_int32_t), grids, out)
+    else
+       rc = kidmp32_doppler_spectrum_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), c_loc(qr), &
+            c_loc(nr), pqs, pqg, pw, v0, dv, int(nv, c_int32_t), grids, out)
+    end if
+    call stop_on_error(rc, 'doppler_spectrum_batch')
+  contains
+    ! one spectrum's address; its extents are checked here, where they are known
+    subroutine spectrum(ptr, s)
+      type(c_ptr), intent(inout) :: ptr
+      real, dimension(:,:,:), intent(inout), optional, target, contiguous :: s
+      if (.not. present(s)) return
+      if (size(s, 1) /= nz .or. size(s, 2) /= nv .or. size(s, 3) /= ncol) call bad('a spectrum must be (nz, nv, ncol)')
+      ptr = c_loc(s)
+    end subroutine spectrum
+    subroutine grid(x, D, dD)
+      integer, intent(in) :: x
+      real(c_double), dimension(:), intent(in), optional, target, contiguous :: D, dD
+      if (present(D) .neqv. present(dD)) call bad('a grid needs both D and dD')
+      if (.not. present(D)) return
+      if (size(D) /= size(dD)) call bad('D and dD differ in the number of bins')
+      grids%D(x) = c_loc(D);  grids%dD(x) = c_loc(dD);  grids%nb(x) = int(size(D), c_int32_t)
+    end subroutine grid
+    subroutine bad(msg)
+      character(*), intent(in) :: msg
+      write(*,'(2a)') ' module_mp_thompson09n: doppler_spectrum_batch: ', msg
+      stop 1
+    end subroutine bad
+  end subroutine doppler_spectrum_batch
 
   ! A droplet number per column (kidmp_set_column_nc): column i of every following batched call uses Nt_c =
   ! set_nc_col(i)*1.e6 (M:381) in place of the namelist's set_Nc -- an Nd ensemble, or an aerosol gradient along x, in

@@ -621,6 +621,17 @@ class ThompsonMP:
         from .doppler import DOPPLER_NAMES, doppler_moments_host
         return doppler_moments_host(self, st, w, DOPPLER_NAMES if want is None else want)
 
+    def doppler_spectrum(self, st, v0, dv, nv, w=None, grids=None, want=("total",), out=None, stream=None):
+        """The Doppler spectrum of every level on a uniform velocity grid (include/kidmp_dspectrum.h):
+        kid_amd.dspectrum.doppler_spectrum on this context."""
+        from .dspectrum import doppler_spectrum
+        return doppler_spectrum(self, st, v0, dv, nv, w, grids, want, out, stream)
+
+    def doppler_spectrum_host(self, st, v0, dv, nv, w=None, grids=None, want=("total",), out=None):
+        """doppler_spectrum on numpy arrays: kid_amd.dspectrum.doppler_spectrum_host on this context."""
+        from .dspectrum import doppler_spectrum_host
+        return doppler_spectrum_host(self, st, v0, dv, nv, w, grids, want, out)
+
     REFL_NAMES = ("t", "p", "qv", "qr", "nr", "qs", "qg")      # the inputs of calc_refl10cm that are read (qc1d is not)
 
     def reflectivity(self, st, out=None, stream=None):
