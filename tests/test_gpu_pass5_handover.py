@@ -18,6 +18,7 @@ import pytest
 import cases
 import kat_cases as kc
 from parity import MAX_SENSITIVE_FRAC, branch_aware_compare, assert_parity
+from rates_parity import assert_rates
 
 T_0, R1 = 273.15, 1e-12
 NZS = [2, 17, 64, 65, 120, 121, 200]          # 121 and 200: one column per workgroup, the band is the wave's own column
@@ -93,10 +94,10 @@ def _allowed(n_levels):
 
 def _run(m, o, st, dt, rates=False, **kw):
     got = {k: v.copy() for k, v in st.items()}
-    gppt, _ = m.batch_step_host(got, dt, want_rates=rates)
+    gppt, grates = m.batch_step_host(got, dt, want_rates=rates)
     v = assert_parity(o, st, dt, got, gppt, **kw)
     print(st["qv"].shape, dt, v)
-    return got
+    return (got, grates) if rates else got
 
 
 @pytest.mark.slow
@@ -156,8 +157,13 @@ def test_handover_more_substeps(gpu_mixed, oracle_mixed):
 @pytest.mark.gpu
 @pytest.mark.parametrize("nz", [120, 121])
 def test_handover_rates_instantiation(gpu_mixed, oracle_mixed, nz):
-    """The kernel compiled with the rate diagnostics (256 VGPRs, two waves per SIMD) takes the same hand-over."""
-    _run(gpu_mixed, oracle_mixed, _batch(nz, 5), 10.0, rates=True, max_branch_frac=0.2)
+    """The kernel compiled with the rate diagnostics (256 VGPRs, two waves per SIMD) takes the same hand-over, and the
+    rates it stores on the way are the oracle's (rates_parity.assert_rates; every other level count:
+    test_gpu_rates_shapes.py)."""
+    st = _batch(nz, 5)
+    _, rates = _run(gpu_mixed, oracle_mixed, st, 10.0, rates=True, max_branch_frac=0.2)
+    v = assert_rates(oracle_mixed.column_step, st, 10.0, rates)
+    print("rates", nz, {k: x for k, x in v.items() if k != "cmp"})
 
 
 @pytest.mark.gpu

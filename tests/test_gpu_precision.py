@@ -53,7 +53,8 @@ def test_p32n_kernel_against_the_p32n_oracle(name, iiwarm, gpu_warm, gpu_mixed, 
 @pytest.mark.parametrize("arith,bound", [("p32n", 2e-3), ("f32", 2e-3)])
 def test_binary32_builds_stay_near_the_p64_result(arith, bound, gpu_mixed, oracle_mixed):
     """One step from identical (binary32-representable) inputs: both builds differ from P64 at binary32 rounding
-    level (99th percentile), and every invariant of the step holds."""
+    level (99th percentile), and every invariant of the step holds.  (The rates are only asked to be finite here; their
+    values are held to the P32n oracle in test_gpu_rates_shapes.test_p32n_rates_against_the_p32n_oracle.)"""
     st32 = _to32(cases.config5(512))
     st64 = {k: np.ascontiguousarray(v.astype(np.float64)) for k, v in st32.items()}
     oracle_mixed.batch_step(st64, 10.0)
