@@ -1,0 +1,208 @@
+// kidmp_lidar.hip -- the entries of include/kidmp_lidar.h: extinction, backscatter, optical depth and attenuated
+// backscatter of device arrays in one launch of k_lidar_profiles (thompson_reflectivity.hip), and of host arrays in chunks
+// through the context's staging memory.
+#include "kidmp_ctx.h"
+#include "../../include/kidmp_lidar.h"
+
+#include <cmath>
+
+using namespace kidmp;
+
+static_assert(sizeof(kidmp_lidar_out) == LIDAR_NOUT * sizeof(double *) && sizeof(kidmp32_lidar_out) == LIDAR_NOUT * sizeof(float *)
+                  && LIDAR_SUMMARY_N == KIDMP_LIDAR_SUMMARY_N && sizeof(kidmp_lidar_cfg) == (SPECTRA_NSPEC + 4) * sizeof(double),
+              "include/kidmp_lidar.h");
+
+namespace {
+constexpr int NIN = 11;                                   // t, p, qv, qc, nc, qi, ni, qr, nr, qs, qg
+const char *const IN_NAMES[NIN] = {"t", "p", "qv", "qc", "nc", "qi", "ni", "qr", "nr", "qs", "qg"};
+const char *const OUT_NAMES[LIDAR_NOUT] = {"ext_c", "ext_i", "ext_r", "ext_s", "ext_g", "ext", "bsc", "bsc_mol", "tau_up", "tau_dn",
+                                           "att_up", "att_dn", "sr_up", "sr_dn"};
+constexpr bool REQUIRED[NIN] = {true, true, true, true, false, false, false, true, true, false, false};
+constexpr bool FROZEN_IN[NIN] = {false, false, false, false, false, true, true, false, false, true, true};
+const kidmp_lidar_cfg DEFAULT_CFG = {{18.8, 25., 18.8, 25., 25.}, 0.7, 6.2446e-32, 2.e-5, 2.5e-3};
+
+template <class T> struct LidarCall {
+    const T *in[NIN];
+    const T *dz;
+    int64_t dz_col_stride;
+    T *out[LIDAR_NOUT];
+    double *summary;
+};
+template <class T, class O>
+LidarCall<T> lidar_call(const T *t, const T *p, const T *qv, const T *qc, const T *nc, const T *qi, const T *ni, const T *qr, const T *nr,
+                        const T *qs, const T *qg, const T *dz, int64_t dz_col_stride, const O *out, double *summary)
+{
+    LidarCall<T> c{{t, p, qv, qc, nc, qi, ni, qr, nr, qs, qg}, dz, dz_col_stride, {}, summary};
+    if (out) {
+        T *const o[LIDAR_NOUT] = {out->ext_c, out->ext_i, out->ext_r, out->ext_s, out->ext_g, out->ext, out->bsc, out->bsc_mol,
+                                  out->tau_up, out->tau_dn, out->att_up, out->att_dn, out->sr_up, out->sr_dn};
+        for (int v = 0; v < LIDAR_NOUT; ++v) c.out[v] = o[v];
+    }
+    return c;
+}
+// whether the call goes beyond the profiles that need no neighbour: then the kernel scans and reads dz
+template <class T> bool needs_depth(const LidarCall<T> &a)
+{
+    bool any = a.summary != nullptr;
+    for (int v = LIDAR_NLOCAL; v < LIDAR_NOUT; ++v) any = any || a.out[v];
+    return any;
+}
+
+// what the device and the host entries check alike, before anything is touched; use receives the configuration
+template <class T>
+int check_lidar(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, const LidarCall<T> &a, const kidmp_lidar_cfg *cfg, kidmp_lidar_cfg &use)
+{
+    const std::string w(who);
+    if (int rc = require_ready(ctx)) return rc;
+    if (ncol < 0) return fail(ctx, KIDMP_EINVAL, w + ": ncol < 0");
+    if (int rc = check_nc_count(ctx, who, ncol)) return rc;
+    if (nz < 2 || nz > KIDMP_MAX_NZ) return fail(ctx, KIDMP_EINVAL, w + ": nz outside [2, KIDMP_MAX_NZ]");
+    if (a.dz_col_stride != 0 && a.dz_col_stride < nz) return fail(ctx, KIDMP_EINVAL, w + ": dz_col_stride must be 0 or >= nz");
+    use = cfg ? *cfg : DEFAULT_CFG;
+    bool finite = std::isfinite(use.eta) && std::isfinite(use.c_mol) && std::isfinite(use.beta_detect) && std::isfinite(use.trans_lost);
+    for (int x = 0; x < SPECTRA_NSPEC; ++x) finite = finite && std::isfinite(use.s_ratio[x]);
+    if (!finite) return fail(ctx, KIDMP_EINVAL, w + ": a member of cfg is not finite");
+    for (int x = 0; x < SPECTRA_NSPEC; ++x)
+        if (!(use.s_ratio[x] > 0.)) return fail(ctx, KIDMP_EINVAL, w + ": a lidar ratio must be positive");
+    if (!(use.eta > 0. && use.eta <= 1.)) return fail(ctx, KIDMP_EINVAL, w + ": eta outside (0, 1]");
+    if (use.c_mol < 0.) return fail(ctx, KIDMP_EINVAL, w + ": c_mol < 0");
+    if (use.c_mol == 0. && (a.out[LIDAR_SR_UP] || a.out[LIDAR_SR_DN]))
+        return fail(ctx, KIDMP_EINVAL, w + ": a scattering ratio needs c_mol > 0");
+    if (ncol == 0) return KIDMP_OK;                       // an empty batch has nothing to point at
+    bool any = a.summary != nullptr;
+    for (int v = 0; v < LIDAR_NOUT; ++v) any = any || a.out[v];
+    if (!any) return fail(ctx, KIDMP_EINVAL, w + ": nothing requested: every profile and the summary are NULL");
+    for (int v = 0; v < NIN; ++v)
+        if (REQUIRED[v] && !a.in[v]) return fail(ctx, KIDMP_EINVAL, w + ": null array argument");
+    if (needs_depth(a) && !a.dz) return fail(ctx, KIDMP_EINVAL, w + ": optical depths need dz");
+    if (!ctx->cfg.iiwarm)
+        for (int v = 0; v < NIN; ++v)
+            if (FROZEN_IN[v] && !a.in[v]) return fail(ctx, KIDMP_EINVAL, w + ": a mixed-phase context needs qi, ni, qs and qg");
+    if (ctx->cfg.is_aerosol_aware && !a.in[4]) return fail(ctx, KIDMP_EINVAL, w + ": an aerosol-aware context needs nc");
+    if (!lidar_consts_supported(ctx->hc)) return fail(ctx, KIDMP_ESTATE, w + ": size-distribution exponents differ from the closed forms'");
+    return KIDMP_OK;
+}
+
+// one launch over device pointers; nc_first: the batch's first column within a bound per-column droplet number.  An
+// iiwarm context reads no frozen input; a context that is not aerosol-aware does not read nc.
+template <class T>
+hipError_t enqueue_lidar(kidmp_ctx *ctx, int64_t ncol, int nz, const LidarCall<T> &a, const kidmp_lidar_cfg &g, int64_t nc_first, hipStream_t s)
+{
+    const bool warm = ctx->cfg.iiwarm != 0, aero = ctx->cfg.is_aerosol_aware != 0;
+    const T *const *q = a.in;
+    LidarArgs<T> args{q[0], q[1], q[2], q[3], aero ? q[4] : nullptr, warm ? nullptr : q[5], warm ? nullptr : q[6], q[7], q[8],
+                      warm ? nullptr : q[9], warm ? nullptr : q[10], a.dz, a.dz_col_stride, {}, a.summary,
+                      {g.s_ratio[0], g.s_ratio[1], g.s_ratio[2], g.s_ratio[3], g.s_ratio[4]}, g.eta, g.c_mol, g.beta_detect, g.trans_lost,
+                      ctx->d_nc_col ? ctx->d_nc_col + nc_first : nullptr, aero ? 1 : 0};
+    for (int v = 0; v < LIDAR_NOUT; ++v) args.out[v] = a.out[v];
+    return launch_lidar_profiles<T>(ctx->d_consts, ncol, nz, args, s);
+}
+
+template <class T>
+int lidar_device(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, const LidarCall<T> &a, const kidmp_lidar_cfg *cfg, void *stream)
+{
+    kidmp_lidar_cfg g;
+    if (int rc = check_lidar<T>(ctx, who, ncol, nz, a, cfg, g)) return rc;
+    if (ncol == 0) return KIDMP_OK;
+    GUARD(ctx);
+    const bool warm = ctx->cfg.iiwarm != 0;
+    for (int v = 0; v < NIN; ++v)
+        if (!(warm && FROZEN_IN[v]))
+            if (int rc = check_device_array(ctx, who, a.in[v], IN_NAMES[v])) return rc;
+    if (int rc = check_device_array(ctx, who, a.dz, "dz")) return rc;
+    for (int v = 0; v < LIDAR_NOUT; ++v)
+        if (int rc = check_device_array(ctx, who, a.out[v], OUT_NAMES[v])) return rc;
+    if (int rc = check_device_array(ctx, who, a.summary, "summary")) return rc;
+    HIPTRY(ctx, enqueue_lidar<T>(ctx, ncol, nz, a, g, 0, (hipStream_t)stream));
+    return KIDMP_OK;
+}
+
+// host arrays: chunks of columns through the context's staging memory on its compute stream, one after the other
+// (summary_host of kidmp_summary.hip).  A column's result does not depend on its batch, so any chunking gives the same
+// bits.  Only what the kernel reads goes up and only what was asked for comes down.
+template <class T>
+int lidar_host(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, const LidarCall<T> &h, const kidmp_lidar_cfg *cfg)
+{
+    kidmp_lidar_cfg g;
+    if (int rc = check_lidar<T>(ctx, who, ncol, nz, h, cfg, g)) return rc;
+    if (ncol == 0) return KIDMP_OK;
+    GUARD(ctx);
+    const bool warm = ctx->cfg.iiwarm != 0, aero = ctx->cfg.is_aerosol_aware != 0, depth = needs_depth(h);
+    const int64_t CH = pick_host_chunk(ctx, ncol);
+    const size_t b_prof = (size_t(CH) * size_t(nz) * sizeof(T) + 255) / 256 * 256;
+    const size_t b_sum = (size_t(CH) * KIDMP_LIDAR_SUMMARY_N * sizeof(double) + 255) / 256 * 256;
+    bool up[NIN];
+    int slots = depth ? 1 : 0;
+    for (int v = 0; v < NIN; ++v) {
+        up[v] = h.in[v] && !(warm && FROZEN_IN[v]) && !(v == 4 && !aero);
+        slots += up[v];
+    }
+    for (int v = 0; v < LIDAR_NOUT; ++v) slots += h.out[v] != nullptr;
+    if (int rc = ensure_stage(ctx, size_t(slots) * b_prof + (h.summary ? b_sum : 0))) return rc;
+    char *next = reinterpret_cast<char *>(ctx->d_stage);
+    auto slot = [&](bool wanted) { T *p = wanted ? reinterpret_cast<T *>(next) : nullptr; if (wanted) next += b_prof; return p; };
+    LidarCall<T> d{};
+    for (int v = 0; v < NIN; ++v) d.in[v] = slot(up[v]);
+    T *const d_dz = slot(depth);
+    d.dz = d_dz;
+    d.dz_col_stride = h.dz_col_stride ? nz : 0;           // staged rows are packed
+    for (int v = 0; v < LIDAR_NOUT; ++v) d.out[v] = slot(h.out[v] != nullptr);
+    d.summary = h.summary ? reinterpret_cast<double *>(next) : nullptr;
+    hipError_t e = hipSuccess;
+    if (depth && !h.dz_col_stride) e = hipMemcpyAsync(d_dz, h.dz, size_t(nz) * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
+    for (int64_t c0 = 0; c0 < ncol && e == hipSuccess; c0 += CH) {
+        const int64_t n = c0 + CH <= ncol ? CH : ncol - c0;
+        const size_t off = size_t(c0) * size_t(nz), cnt = size_t(n) * size_t(nz);
+        for (int v = 0; v < NIN && e == hipSuccess; ++v)
+            if (up[v]) e = hipMemcpyAsync(const_cast<T *>(d.in[v]), h.in[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess && depth && h.dz_col_stride)
+            e = hipMemcpy2DAsync(d_dz, size_t(nz) * sizeof(T), h.dz + size_t(c0) * size_t(h.dz_col_stride),
+                                 size_t(h.dz_col_stride) * sizeof(T), size_t(nz) * sizeof(T), size_t(n), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = enqueue_lidar<T>(ctx, n, nz, d, g, c0, ctx->stream);
+        for (int v = 0; v < LIDAR_NOUT && e == hipSuccess; ++v)
+            if (h.out[v]) e = hipMemcpyAsync(h.out[v] + off, d.out[v], cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && h.summary)
+            e = hipMemcpyAsync(h.summary + size_t(c0) * KIDMP_LIDAR_SUMMARY_N, d.summary, size_t(n) * KIDMP_LIDAR_SUMMARY_N * sizeof(double),
+                               hipMemcpyDeviceToHost, ctx->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(ctx->stream);        // no copy may still be in flight towards the caller's arrays
+    HIPTRY(ctx, e);
+    HIPTRY(ctx, es);
+    return KIDMP_OK;
+}
+}  // namespace
+
+extern "C" {
+int kidmp_lidar_profiles_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const double *t, const double *p, const double *qv,
+                                const double *qc, const double *nc, const double *qi, const double *ni, const double *qr, const double *nr,
+                                const double *qs, const double *qg, const double *dz, int64_t dz_col_stride, const kidmp_lidar_cfg *cfg,
+                                const kidmp_lidar_out *out, double *summary, void *stream)
+{
+    return lidar_device<double>(ctx, "kidmp_lidar_profiles_device", ncol, nz,
+                                lidar_call<double>(t, p, qv, qc, nc, qi, ni, qr, nr, qs, qg, dz, dz_col_stride, out, summary), cfg, stream);
+}
+int kidmp32_lidar_profiles_device(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const float *t, const float *p, const float *qv,
+                                  const float *qc, const float *nc, const float *qi, const float *ni, const float *qr, const float *nr,
+                                  const float *qs, const float *qg, const float *dz, int64_t dz_col_stride, const kidmp_lidar_cfg *cfg,
+                                  const kidmp32_lidar_out *out, double *summary, void *stream)
+{
+    return lidar_device<float>(ctx, "kidmp32_lidar_profiles_device", ncol, nz,
+                               lidar_call<float>(t, p, qv, qc, nc, qi, ni, qr, nr, qs, qg, dz, dz_col_stride, out, summary), cfg, stream);
+}
+int kidmp_lidar_profiles_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const double *t, const double *p, const double *qv,
+                              const double *qc, const double *nc, const double *qi, const double *ni, const double *qr, const double *nr,
+                              const double *qs, const double *qg, const double *dz, int64_t dz_col_stride, const kidmp_lidar_cfg *cfg,
+                              const kidmp_lidar_out *out, double *summary)
+{
+    return lidar_host<double>(ctx, "kidmp_lidar_profiles_host", ncol, nz,
+                              lidar_call<double>(t, p, qv, qc, nc, qi, ni, qr, nr, qs, qg, dz, dz_col_stride, out, summary), cfg);
+}
+int kidmp32_lidar_profiles_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const float *t, const float *p, const float *qv,
+                                const float *qc, const float *nc, const float *qi, const float *ni, const float *qr, const float *nr,
+                                const float *qs, const float *qg, const float *dz, int64_t dz_col_stride, const kidmp_lidar_cfg *cfg,
+                                const kidmp32_lidar_out *out, double *summary)
+{
+    return lidar_host<float>(ctx, "kidmp32_lidar_profiles_host", ncol, nz,
+                             lidar_call<float>(t, p, qv, qc, nc, qi, ni, qr, nr, qs, qg, dz, dz_col_stride, out, summary), cfg);
+}
+}  // extern "C"

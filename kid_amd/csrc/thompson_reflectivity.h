@@ -85,6 +85,26 @@ bool spectra_consts_supported(const Consts &hc);
 template <class T>
 hipError_t launch_size_spectra(const Consts *d_consts, int64_t ncol, int nz, const SpectraArgs<T> &a, hipStream_t stream);
 
+// The lidar operator (include/kidmp_lidar.h): extinction, backscatter, optical depth and attenuated backscatter of every
+// level, and eight numbers per column, from the size spectra's load.  Null means: nc -- Nt_c (the context is not
+// aerosol-aware); qi and ni, qs, qg -- the species is absent everywhere (iiwarm); an output or the summary -- not wanted;
+// dz -- not read when nothing past out[LIDAR_NLOCAL - 1] and no summary is wanted.  out in the order of kidmp_lidar_out.
+constexpr int LIDAR_NOUT = 14, LIDAR_NLOCAL = 8, LIDAR_SUMMARY_N = 8;      // out[0..7] need no neighbour: no scan
+constexpr int LIDAR_TAU_UP = 8, LIDAR_TAU_DN = 9, LIDAR_ATT_UP = 10, LIDAR_ATT_DN = 11, LIDAR_SR_UP = 12, LIDAR_SR_DN = 13;
+template <class T> struct LidarArgs {
+    const T *t, *p, *qv, *qc, *nc, *qi, *ni, *qr, *nr, *qs, *qg, *dz;
+    int64_t dz_col_stride;
+    T *out[LIDAR_NOUT];
+    double *summary;                                 // [ncol][LIDAR_SUMMARY_N]
+    double s_ratio[SPECTRA_NSPEC], eta, c_mol, beta_detect, trans_lost;
+    const double *set_nc_col;
+    int aero;
+};
+// beyond spectra_consts_supported: bm_s = 2 (snow's extinction is its moment smob) and mu_r = mu_g = mu_i = 0
+bool lidar_consts_supported(const Consts &hc);
+template <class T>
+hipError_t launch_lidar_profiles(const Consts *d_consts, int64_t ncol, int nz, const LidarArgs<T> &a, hipStream_t stream);
+
 // The Doppler moments of a vertically pointing radar (include/kidmp_doppler.h): reflectivity, mean Doppler velocity and
 // spectrum width of every level, from calc_refl10cm's load and size distributions.  Null means: qs, qg -- zero; w -- zero;
 // an output -- not wanted.  out: dbz, vd, sw, vz_r, vz_s, vz_g, dbz_r, dbz_s, dbz_g.

@@ -81,6 +81,49 @@ __device__ inline double wave_suffix_min(double v, int lane, double &tail)
     return v;
 }
 
+// inclusive sum scan over the wave, Kogge-Stone over __shfl_up: lane l receives v[0] + ... + v[l], in an order that l alone
+// fixes.  DOWN is its mirror image over __shfl_down: lane l receives v[l] + ... + v[63].  `total` receives the sum of the
+// whole wave as the last (DOWN: the first) lane holds it, wave-uniform.  Whole wavefronts only.
+template <bool DOWN>
+__device__ inline double wave_prefix_sum(double v, int lane, double &total)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double o = DOWN ? __shfl_down(v, d, 64) : __shfl_up(v, d, 64);
+        if (DOWN ? lane + d < 64 : lane >= d) v += o;
+    }
+    total = readlane(v, DOWN ? 0 : 63);
+    return v;
+}
+// The exclusive sums of a column: up[j] = the sum of v over the levels below the lane's level of group j, dn[j] = over the
+// levels above it.  The level groups are chained through a wave-uniform carry, upward for up and from the top for dn (a
+// reversed scan, not total minus prefix: nothing cancels, dn is exact +0.0 at the top level and never negative).  Levels
+// past nz must hold +0.0.  The order of every sum is a pure function of the level and of NJ.
+template <int NJ>
+__device__ inline void column_depths(const double (&v)[NJ], int lane, bool want_up, bool want_dn, double (&up)[NJ], double (&dn)[NJ])
+{
+    double carry = 0.;
+    if (want_up) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            double total;
+            const double below = __shfl_up(wave_prefix_sum<false>(v[j], lane, total), 1, 64);
+            up[j] = carry + (lane > 0 ? below : 0.);
+            carry = carry + total;
+        }
+    }
+    carry = 0.;
+    if (want_dn) {
+#pragma unroll
+        for (int j = NJ - 1; j >= 0; --j) {
+            double total;
+            const double above = __shfl_down(wave_prefix_sum<true>(v[j], lane, total), 1, 64);
+            dn[j] = carry + (lane < 63 ? above : 0.);
+            carry = carry + total;
+        }
+    }
+}
+
 // calc_effectRad of one level in the driver's form (M:1111-1116): a level without the species receives the preset.  The
 // driver's clamps after the call (M:1118-1120) change nothing after the subroutine's own and are not computed.
 // calc_effectRad does not clamp qv (M:4860) where calc_refl10cm does (M:4992): below 1e-10 the radii get a density of
@@ -423,6 +466,123 @@ __device__ __forceinline__ void store_bins(T *__restrict__ out, const double *__
     }
 }
 
+// ---- the state as mp_thompson loads it, species by species: what k_size_spectra and k_lidar_profiles share, so that the
+// load is stated once (include/kidmp_spectra.h).  A: SpectraArgs or LidarArgs (t, p, qv, qc, nc, qi, ni, qr, nr, qs, qg,
+// set_nc_col, aero; a null frozen input: the species is absent everywhere).  A level whose species is absent, and a lane
+// whose level does not exist, keep exact +0.0 in all of the species' own values.  Whole wavefronts only. ----
+// M:1387-1391: temperature, pressure and the density from qv' = max(1e-10, qv); idle lanes: temp = pres = 0, rho = 1
+template <int NJ, class A>
+__device__ __forceinline__ void load_air(const A &a, int64_t base, int nz, int lane, double (&temp)[NJ], double (&pres)[NJ], double (&rho)[NJ])
+{
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        temp[j] = 0.; pres[j] = 0.; rho[j] = 1.;
+        if (k >= nz) continue;
+        const int64_t i = base + k;
+        temp[j] = double(a.t[i]);
+        pres[j] = double(a.p[i]);
+        rho[j] = lvl::air_density(pres[j], temp[j], fmax(1.E-10, double(a.qv[i])));
+    }
+}
+// rain, M:1447-1474: its slope, its intercept and the limited median volume diameter that block E reads (0: no rain, M:1639)
+template <int NJ, class A>
+__device__ __forceinline__ void load_rain(const Consts *__restrict__ hc, FallConsts &c, const A &a, int64_t base, int nz, int lane,
+                                          const double (&rho)[NJ], double (&mvd)[NJ], double (&lam)[NJ], double (&n0)[NJ])
+{
+    c.crg2 = hc->crg[1]; c.crg3 = hc->crg[2]; c.org2 = hc->org2; c.org3 = hc->org3;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        mvd[j] = 0.; n0[j] = lam[j] = 0.;
+        if (k >= nz) continue;
+        const lvl::RainLoad r = lvl::rain_load(c, rho[j], double(a.qr[base + k]), double(a.nr[base + k]));
+        if (!r.has) continue;
+        mvd[j] = r.mvd;
+        lam[j] = r.lamr;
+        n0[j] = lvl::rain_intercept(c, r);
+    }
+}
+// cloud ice, M:1420-1445
+template <int NJ, class A>
+__device__ __forceinline__ void load_ice(const Consts *__restrict__ hc, FallConsts &c, const A &a, int64_t base, int nz, int lane,
+                                         const double (&rho)[NJ], double (&lam)[NJ], double (&n0)[NJ])
+{
+    c.cie2 = hc->cie[1]; c.cig1 = hc->cig[0]; c.cig2 = hc->cig[1]; c.oig1 = hc->oig1; c.oig2 = hc->oig2;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        n0[j] = lam[j] = 0.;
+        if (k >= nz || !a.qi) continue;
+        const lvl::IceLoad r = lvl::ice_load(c, rho[j], double(a.qi[base + k]), double(a.ni[base + k]));
+        if (!r.has) continue;
+        lam[j] = r.lami;
+        n0[j] = lvl::ice_intercept(c, r);
+    }
+}
+// snow, M:1475-1483 and block D: smob; at(j, sl) is called at every level that holds snow, for what else the caller forms
+// from the level's Field fit
+template <int NJ, class A, class F>
+__device__ __forceinline__ void load_snow(const Consts *__restrict__ hc, FallConsts &c, const A &a, int64_t base, int nz, int lane,
+                                          const double (&temp)[NJ], const double (&rho)[NJ], double (&smob)[NJ], F &&at)
+{
+    c.oams = hc->oams;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        smob[j] = 0.;
+        if (k >= nz || !a.qs) continue;
+        const double qs = double(a.qs[base + k]);
+        if (!(qs > R1)) continue;
+        const lvl::SnowLevel sl = lvl::snow_level(temp[j], qs * rho[j], c.oams);
+        smob[j] = sl.smob;
+        at(j, sl);
+    }
+}
+// graupel, M:1484-1492 and block E (M:1633-1654): the intercept is the running minimum from the top down over all levels
+template <int NJ, class A>
+__device__ __forceinline__ void load_graupel(const Consts *__restrict__ hc, FallConsts &c, const A &a, int64_t base, int nz, int lane,
+                                             const double (&temp)[NJ], const double (&rho)[NJ], const double (&mvd)[NJ], double (&lam)[NJ],
+                                             double (&n0)[NJ])
+{
+    double rg[NJ];
+    bool has[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        rg[j] = R1; has[j] = false;
+        if (k >= nz || !a.qg) continue;
+        const double qg = double(a.qg[base + k]);
+        has[j] = qg > R1;
+        if (has[j]) rg[j] = qg * rho[j];
+    }
+    graupel_intercepts<NJ>(temp, mvd, rg, nz, lane, n0);
+    const double cgg2 = hc->cgg[1];
+    c.cgg1 = hc->cgg[0]; c.lamg_fac = hc->lamg_fac;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const double n0_exp = n0[j];
+        n0[j] = lam[j] = 0.;
+        if (has[j]) lvl::graupel_slope(c, cgg2, n0_exp, rg[j], lam[j], n0[j]);
+    }
+}
+// cloud water, M:1395-1410 and M:1690-1692: the loaded number nc, nu_c, lamc and the intercept
+template <int NJ, class A>
+__device__ __forceinline__ void load_cloud(const Consts *__restrict__ hc, const A &a, int64_t col, int64_t base, int nz, int lane,
+                                           const double (&rho)[NJ], double (&lam)[NJ], double (&n0)[NJ], double (&nc)[NJ], int (&nu)[NJ])
+{
+    const double Nt_c = a.set_nc_col ? a.set_nc_col[col] * 1.e6 : hc->Nt_c;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        n0[j] = lam[j] = nc[j] = 0.; nu[j] = 0;
+        if (k >= nz) continue;
+        const lvl::CloudLoad r = lvl::cloud_load(a.aero != 0, Nt_c, rho[j], double(a.qc[base + k]), a.nc ? double(a.nc[base + k]) : 0.);
+        if (!r.has) continue;
+        lam[j] = r.lamc; n0[j] = r.n0; nc[j] = r.nc; nu[j] = r.nu;
+    }
+}
+
 }  // namespace
 
 // what block O reads, picked from the context's Consts: on the device from its copy in HBM (scalar loads on demand: as
@@ -572,7 +732,8 @@ k_fall_speeds(const Consts *__restrict__ hc, FallArgs<T> a, int64_t ncol, int nz
 // bins (include/kidmp_spectra.h).  Species by species -- rain first, whose median volume diameter the graupel intercept
 // reads -- the level's slope and intercept are formed once in registers, stored by the column's first share if asked for,
 // and the species' bins follow at once, so that only one species' parameters are live at a time.  The load is
-// k_fall_speeds' own, through the same lvl:: functions.  Nothing but the fastmath tables is in LDS.
+// k_fall_speeds' own, through the same lvl:: functions, stated once in load_air .. load_cloud above, which
+// k_lidar_profiles calls as well.  Nothing but the fastmath tables is in LDS.
 template <class T, int NJ>
 __global__ void __launch_bounds__(REFL_THREADS)
 k_size_spectra(const Consts *__restrict__ hc, SpectraArgs<T> a, int64_t ncol, int nz)
@@ -590,118 +751,57 @@ k_size_spectra(const Consts *__restrict__ hc, SpectraArgs<T> a, int64_t ncol, in
     const auto params = [&](int v, const double (&x)[NJ]) __attribute__((always_inline)) { if (first) store_profile<T, NJ>(par[v], base, nz, lane, x); };
     const auto wants = [&](int sp, int p0, int p1, int p2) __attribute__((always_inline)) { return a.spec[sp] || par[p0] || par[p1] || (p2 >= 0 && par[p2]); };
 
-    double temp[NJ], rho[NJ], mvd[NJ], n0[NJ], lam[NJ];
+    double temp[NJ], pres[NJ], rho[NJ], mvd[NJ], n0[NJ], lam[NJ];
 
-    // ---- load (M:1387-1391) and rain (M:1447-1474) ----
     // (each species picks its own few constants from the context's copy in HBM just before it needs them: all fifty of
     //  fall_consts at once, beside the forty pointers of the arguments, do not fit the scalar registers)
     FallConsts c{};
-    c.crg2 = hc->crg[1]; c.crg3 = hc->crg[2]; c.org2 = hc->org2; c.org3 = hc->org3;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int k = 64 * j + lane;
-        temp[j] = 0.; rho[j] = 1.; mvd[j] = 0.; n0[j] = lam[j] = 0.;
-        if (k >= nz) continue;
-        const int64_t i = base + k;
-        temp[j] = double(a.t[i]);
-        rho[j] = lvl::air_density(double(a.p[i]), temp[j], fmax(1.E-10, double(a.qv[i])));
-        const lvl::RainLoad r = lvl::rain_load(c, rho[j], double(a.qr[i]), double(a.nr[i]));
-        if (!r.has) continue;
-        mvd[j] = r.mvd;                                              // 0: no rain (block E asks L_qr, M:1639)
-        lam[j] = r.lamr;
-        n0[j] = lvl::rain_intercept(c, r);
-    }
+    load_air<NJ>(a, base, nz, lane, temp, pres, rho);
+    load_rain<NJ>(hc, c, a, base, nz, lane, rho, mvd, lam, n0);
     params(SPECTRA_LAM_R, lam);
     params(SPECTRA_LAM_R + 1, n0);
     store_bins<T, NJ, false>(a.spec[2], a.D[2], a.dD[2], a.nb[2], col, nz, lane, n0,
                              [&](int j, double D, double dD, double) __attribute__((always_inline)) { return n0[j] > 0. ? lvl::exp_bin(n0[j], lam[j], D, dD) : 0.; });
 
-    // ---- cloud ice, M:1420-1445 ----
     if (wants(1, SPECTRA_LAM_I, SPECTRA_LAM_I + 1, -1)) {
-        c.cie2 = hc->cie[1]; c.cig1 = hc->cig[0]; c.cig2 = hc->cig[1]; c.oig1 = hc->oig1; c.oig2 = hc->oig2;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int k = 64 * j + lane;
-            n0[j] = lam[j] = 0.;
-            if (k >= nz || !a.qi) continue;
-            const lvl::IceLoad r = lvl::ice_load(c, rho[j], double(a.qi[base + k]), double(a.ni[base + k]));
-            if (!r.has) continue;
-            lam[j] = r.lami;
-            n0[j] = lvl::ice_intercept(c, r);
-        }
+        load_ice<NJ>(hc, c, a, base, nz, lane, rho, lam, n0);
         params(SPECTRA_LAM_I, lam);
         params(SPECTRA_LAM_I + 1, n0);
         store_bins<T, NJ, false>(a.spec[1], a.D[1], a.dD[1], a.nb[1], col, nz, lane, n0,
                                  [&](int j, double D, double dD, double) __attribute__((always_inline)) { return n0[j] > 0. ? lvl::exp_bin(n0[j], lam[j], D, dD) : 0.; });
     }
 
-    // ---- snow, M:1475-1483 and block D ----
     if (wants(3, SPECTRA_SMOB, SPECTRA_SMOB + 1, -1)) {
         lvl::SnowSpectrum sp[NJ];
-        c.oams = hc->oams; c.cse1 = hc->cse[0];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { lam[j] = 0.; sp[j] = lvl::SnowSpectrum{0., 0., 0., 0.}; }
+        c.cse1 = hc->cse[0];
 #pragma unroll
         for (int i = 0; i < 10; ++i) { c.sa[i] = hc->sa[i]; c.sb[i] = hc->sb[i]; }
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int k = 64 * j + lane;
-            n0[j] = lam[j] = 0.;                                     // smob, smoc
-            sp[j] = lvl::SnowSpectrum{0., 0., 0., 0.};
-            if (k >= nz || !a.qs) continue;
-            const double qs = double(a.qs[base + k]);
-            if (!(qs > R1)) continue;
-            const lvl::SnowLevel sl = lvl::snow_level(temp[j], qs * rho[j], c.oams);
-            n0[j] = sl.smob;
-            lam[j] = lvl::snow_moment(c.sa, c.sb, c.cse1, sl);      // M:1590-1600
+        load_snow<NJ>(hc, c, a, base, nz, lane, temp, rho, n0, [&](int j, const lvl::SnowLevel &sl) __attribute__((always_inline)) {
+            lam[j] = lvl::snow_moment(c.sa, c.sb, c.cse1, sl);      // smoc, M:1590-1600
             sp[j] = lvl::snow_spectrum(sl, lam[j]);
-        }
+        });
         params(SPECTRA_SMOB, n0);
         params(SPECTRA_SMOB + 1, lam);
         store_bins<T, NJ, true>(a.spec[3], a.D[3], a.dD[3], a.nb[3], col, nz, lane, n0,
                                 [&](int j, double D, double dD, double Dmu) __attribute__((always_inline)) { return n0[j] > 0. ? lvl::snow_bin(sp[j], D, Dmu, dD) : 0.; });
     }
 
-    // ---- graupel, M:1484-1492 and block E (M:1633-1654) ----
     if (wants(4, SPECTRA_LAM_G, SPECTRA_LAM_G + 1, -1)) {
-        double rg[NJ];
-        bool has[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int k = 64 * j + lane;
-            rg[j] = R1; has[j] = false;
-            if (k >= nz || !a.qg) continue;
-            const double qg = double(a.qg[base + k]);
-            has[j] = qg > R1;
-            if (has[j]) rg[j] = qg * rho[j];
-        }
-        graupel_intercepts<NJ>(temp, mvd, rg, nz, lane, n0);
-        const double cgg2 = hc->cgg[1];
-        c.cgg1 = hc->cgg[0]; c.lamg_fac = hc->lamg_fac;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const double n0_exp = n0[j];
-            n0[j] = lam[j] = 0.;
-            if (has[j]) lvl::graupel_slope(c, cgg2, n0_exp, rg[j], lam[j], n0[j]);
-        }
+        load_graupel<NJ>(hc, c, a, base, nz, lane, temp, rho, mvd, lam, n0);
         params(SPECTRA_LAM_G, lam);
         params(SPECTRA_LAM_G + 1, n0);
         store_bins<T, NJ, false>(a.spec[4], a.D[4], a.dD[4], a.nb[4], col, nz, lane, n0,
                                  [&](int j, double D, double dD, double) __attribute__((always_inline)) { return n0[j] > 0. ? lvl::exp_bin(n0[j], lam[j], D, dD) : 0.; });
     }
 
-    // ---- cloud water, M:1395-1410 and M:1690-1692 ----
     if (wants(0, SPECTRA_LAM_C, SPECTRA_LAM_C + 1, SPECTRA_LAM_C + 2)) {
-        const double Nt_c = a.set_nc_col ? a.set_nc_col[col] * 1.e6 : hc->Nt_c;
         int nu[NJ];
-        double fnu[NJ];
+        double ncl[NJ], fnu[NJ];
+        load_cloud<NJ>(hc, a, col, base, nz, lane, rho, lam, n0, ncl, nu);
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int k = 64 * j + lane;
-            n0[j] = lam[j] = fnu[j] = 0.; nu[j] = 0;
-            if (k >= nz) continue;
-            const lvl::CloudLoad r = lvl::cloud_load(a.aero != 0, Nt_c, rho[j], double(a.qc[base + k]), a.nc ? double(a.nc[base + k]) : 0.);
-            if (!r.has) continue;
-            lam[j] = r.lamc; n0[j] = r.n0; nu[j] = r.nu; fnu[j] = double(r.nu);
-        }
+        for (int j = 0; j < NJ; ++j) fnu[j] = double(nu[j]);
         params(SPECTRA_LAM_C, lam);
         params(SPECTRA_LAM_C + 1, n0);
         params(SPECTRA_LAM_C + 2, fnu);
@@ -711,6 +811,156 @@ k_size_spectra(const Consts *__restrict__ hc, SpectraArgs<T> a, int64_t ncol, in
                                      return n0[j] > 0. ? lvl::cloud_bin(n0[j], lam[j], nu[j], D, D2, D4, D4 * D4, dD) : 0.;
                                  });
     }
+}
+
+// One wavefront per column: the lidar operator of include/kidmp_lidar.h.  The load is k_size_spectra's, through the same
+// functions, in the order of the total (c, i, r, s, g; rain before graupel, whose intercept reads rain's diameter), one
+// species' slope and intercept live at a time.  The profiles that need no neighbour (the extinctions, bsc, bsc_mol) are
+// stored first; a call that asks for nothing else ends there, without a scan and without an exponential.  Otherwise the
+// optical depths are two pairs of wave scans (column_depths) of dtau and dtau_mol, the attenuated backscatter follows per
+// level, and the eight numbers of the column come from wave_sum, ballots and height_below as in k_column_summary.
+// Nothing but the fastmath tables is in LDS.
+template <class T, int NJ>
+__global__ void __launch_bounds__(REFL_THREADS)
+k_lidar_profiles(const Consts *__restrict__ hc, LidarArgs<T> a, int64_t ncol, int nz)
+{
+#if KFM_TABLES
+    fm::tab::load_tables(int(threadIdx.x), REFL_THREADS);
+    __syncthreads();
+#endif
+    const int lane = int(threadIdx.x) & 63;
+    const int64_t col = int64_t(blockIdx.x) * REFL_WAVES + (int(threadIdx.x) >> 6);
+    if (col >= ncol) return;                                         // whole wavefronts only: the scans need every lane
+    const int64_t base = col * int64_t(nz);
+    T *const *out = a.out;
+    const bool want_sr_up = out[LIDAR_SR_UP] != nullptr, want_sr_dn = out[LIDAR_SR_DN] != nullptr, summary = a.summary != nullptr;
+    const bool want_up = out[LIDAR_TAU_UP] || out[LIDAR_ATT_UP] || want_sr_up || summary;
+    const bool want_dn = out[LIDAR_TAU_DN] || out[LIDAR_ATT_DN] || want_sr_dn || summary;
+    const bool totals = out[5] || out[6] || want_up || want_dn;      // ext and bsc take every species
+    const auto wants = [&](int x) __attribute__((always_inline)) { return totals || out[x]; };
+
+    double temp[NJ], pres[NJ], rho[NJ], mvd[NJ], lam[NJ], n0[NJ], e[NJ], ext[NJ], bsc[NJ];
+    FallConsts c{};
+    load_air<NJ>(a, base, nz, lane, temp, pres, rho);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) ext[j] = bsc[j] = mvd[j] = 0.;
+    // ext = (((ext_c + ext_i) + ext_r) + ext_s) + ext_g and bsc likewise of ext_x / S_x; an absent species adds +0.0
+    const auto add = [&](int x) __attribute__((always_inline)) {
+        store_profile<T, NJ>(out[x], base, nz, lane, e);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { ext[j] = x == 0 ? e[j] : ext[j] + e[j]; bsc[j] = x == 0 ? e[j] / a.s_ratio[0] : bsc[j] + e[j] / a.s_ratio[x]; }
+    };
+    if (wants(0)) {
+        int nu[NJ];
+        double ncl[NJ];
+        load_cloud<NJ>(hc, a, col, base, nz, lane, rho, lam, n0, ncl, nu);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) e[j] = lam[j] > 0. ? lvl::cloud_extinction(ncl[j], nu[j], lam[j]) : 0.;
+        add(0);
+    }
+    if (wants(1)) {
+        load_ice<NJ>(hc, c, a, base, nz, lane, rho, lam, n0);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) e[j] = lam[j] > 0. ? lvl::exp_extinction(n0[j], lam[j]) : 0.;
+        add(1);
+    }
+    if (wants(2) || wants(4)) {
+        load_rain<NJ>(hc, c, a, base, nz, lane, rho, mvd, lam, n0);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) e[j] = lam[j] > 0. ? lvl::exp_extinction(n0[j], lam[j]) : 0.;
+        add(2);
+    }
+    if (wants(3)) {
+        load_snow<NJ>(hc, c, a, base, nz, lane, temp, rho, n0, [](int, const lvl::SnowLevel &) __attribute__((always_inline)) {});
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) e[j] = n0[j] > 0. ? lvl::snow_extinction(n0[j]) : 0.;
+        add(3);
+    }
+    if (wants(4)) {
+        load_graupel<NJ>(hc, c, a, base, nz, lane, temp, rho, mvd, lam, n0);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) e[j] = lam[j] > 0. ? lvl::exp_extinction(n0[j], lam[j]) : 0.;
+        add(4);
+    }
+    double bm[NJ];                                                   // bsc_mol = c_mol * N, N = p/(k_B T) molecules per m3
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) bm[j] = 64 * j + lane < nz ? a.c_mol * (pres[j] / (lvl::LIDAR_K_B * temp[j])) : 0.;
+    store_profile<T, NJ>(out[5], base, nz, lane, ext);
+    store_profile<T, NJ>(out[6], base, nz, lane, bsc);
+    store_profile<T, NJ>(out[7], base, nz, lane, bm);
+    if (!(want_up || want_dn)) return;                               // wave-uniform
+
+    // ---- optical depth: dtau = (eta ext + ext_mol) dz, dtau_mol = ext_mol dz; levels past nz hold +0.0 ----
+    const T *__restrict__ dzc = a.dz + col * a.dz_col_stride;
+    double dz[NJ], dt[NJ], dm[NJ], tu[NJ], td[NJ], mu[NJ], md[NJ], part = 0., mol = 0.;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        dz[j] = k < nz ? double(dzc[k]) : 0.;
+        const double em = (8. * lvl::LIDAR_PI / 3.) * bm[j];
+        dt[j] = (a.eta * ext[j] + em) * dz[j];
+        dm[j] = em * dz[j];
+        part += ext[j] * dz[j];
+        mol += dm[j];
+        tu[j] = td[j] = mu[j] = md[j] = 0.;
+    }
+    column_depths<NJ>(dt, lane, want_up, want_dn, tu, td);
+    if (want_sr_up || want_sr_dn) column_depths<NJ>(dm, lane, want_sr_up, want_sr_dn, mu, md);
+    store_profile<T, NJ>(out[LIDAR_TAU_UP], base, nz, lane, tu);
+    store_profile<T, NJ>(out[LIDAR_TAU_DN], base, nz, lane, td);
+
+    if (!(out[LIDAR_ATT_UP] || out[LIDAR_ATT_DN] || want_sr_up || want_sr_dn || summary)) return;   // the depths alone: no exponential
+
+    // ---- layer-mean attenuated backscatter and the scattering ratio ----
+    double au[NJ], ad[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const double b = bsc[j] + bm[j], g = lvl::layer_mean(2. * dt[j]);
+        au[j] = want_up ? b * lvl::exp_neg(2. * tu[j]) * g : 0.;
+        ad[j] = want_dn ? b * lvl::exp_neg(2. * td[j]) * g : 0.;
+    }
+    store_profile<T, NJ>(out[LIDAR_ATT_UP], base, nz, lane, au);
+    store_profile<T, NJ>(out[LIDAR_ATT_DN], base, nz, lane, ad);
+    if (want_sr_up || want_sr_dn) {
+        double su[NJ], sd[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const double gm = lvl::layer_mean(2. * dm[j]);
+            su[j] = want_sr_up ? au[j] / (bm[j] * lvl::exp_neg(2. * mu[j]) * gm) : 0.;
+            sd[j] = want_sr_dn ? ad[j] / (bm[j] * lvl::exp_neg(2. * md[j]) * gm) : 0.;
+        }
+        store_profile<T, NJ>(out[LIDAR_SR_UP], base, nz, lane, su);
+        store_profile<T, NJ>(out[LIDAR_SR_DN], base, nz, lane, sd);
+    }
+    if (!summary) return;
+
+    // ---- the column's eight numbers: sums as in k_column_summary, levels by ballot, heights as masked sums of dz ----
+    part = wave_sum(part);
+    mol = wave_sum(mol);
+    bool det_up[NJ], det_dn[NJ], lost_up[NJ], lost_dn[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const bool level = 64 * j + lane < nz;
+        det_up[j] = level && au[j] >= a.beta_detect;
+        det_dn[j] = level && ad[j] >= a.beta_detect;
+        lost_up[j] = level && lvl::exp_neg(2. * (tu[j] + dt[j])) < a.trans_lost;
+        lost_dn[j] = level && lvl::exp_neg(2. * (td[j] + dt[j])) < a.trans_lost;
+    }
+    int n_up, n_dn, n_lost;
+    const int k_base = lowest_level<NJ>(det_up), k_lost_up = lowest_level<NJ>(lost_up);
+    const int k_top = highest_level<NJ>(det_dn, n_dn), k_lost_dn = highest_level<NJ>(lost_dn, n_lost);
+    highest_level<NJ>(det_up, n_up);
+    const double nan = __builtin_nan("");
+    const double slot[LIDAR_SUMMARY_N] = {part, mol,
+                                          k_base < 0 ? nan : height_below<NJ>(dz, lane, k_base),
+                                          k_lost_up < 0 ? nan : height_below<NJ>(dz, lane, k_lost_up + 1),
+                                          k_top < 0 ? nan : height_below<NJ>(dz, lane, k_top + 1),
+                                          k_lost_dn < 0 ? nan : height_below<NJ>(dz, lane, k_lost_dn),
+                                          double(n_up), double(n_dn)};
+    double v = slot[0];
+#pragma unroll
+    for (int s = 1; s < LIDAR_SUMMARY_N; ++s) v = lane == s ? slot[s] : v;
+    if (lane < LIDAR_SUMMARY_N) a.summary[col * LIDAR_SUMMARY_N + lane] = v;     // one 64-byte line
 }
 
 // ---- what k_doppler_moments and k_doppler_spectrum share: calc_refl10cm's load of one level (M:4991-5028) with the
@@ -1190,6 +1440,29 @@ bool spectra_consts_supported(const Consts &hc)
     bool ok = fall_consts_supported(hc) && mu_r == 0.0 && mu_g == 0.0 && mu_i == 0.0 && hc.cre[1] == 1. && hc.cge[1] == 1. && hc.cie[0] == 1.;
     for (int n = 1; n <= 15; ++n) ok = ok && hc.cce[0][n - 1] == n + 1. && hc.cce[1][n - 1] == bm_r + n + 1.;
     return ok;
+}
+
+template <class T>
+hipError_t launch_lidar_profiles(const Consts *c, int64_t ncol, int nz, const LidarArgs<T> &a, hipStream_t s)
+{
+    if (ncol <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((ncol + REFL_WAVES - 1) / REFL_WAVES)), block(REFL_THREADS);
+    switch ((nz + 63) / 64) {
+    case 1: hipLaunchKernelGGL((k_lidar_profiles<T, 1>), grid, block, 0, s, c, a, ncol, nz); break;
+    case 2: hipLaunchKernelGGL((k_lidar_profiles<T, 2>), grid, block, 0, s, c, a, ncol, nz); break;
+    case 3: hipLaunchKernelGGL((k_lidar_profiles<T, 3>), grid, block, 0, s, c, a, ncol, nz); break;
+    case 4: hipLaunchKernelGGL((k_lidar_profiles<T, 4>), grid, block, 0, s, c, a, ncol, nz); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+template hipError_t launch_lidar_profiles<double>(const Consts *, int64_t, int, const LidarArgs<double> &, hipStream_t);
+template hipError_t launch_lidar_profiles<float>(const Consts *, int64_t, int, const LidarArgs<float> &, hipStream_t);
+
+bool lidar_consts_supported(const Consts &hc)
+{
+    // beyond spectra_consts_supported: ext_s = (pi/2) smob needs bm_s = 2, and pi N0/lam**3 needs mu = 0 with Gamma(3) = 2
+    return spectra_consts_supported(hc) && bm_s == 2.0 && mu_r == 0.0 && mu_g == 0.0 && mu_i == 0.0;
 }
 
 template <class T>

@@ -64,6 +64,7 @@ module module_mp_thompson09n
   public :: doppler_moments_batch
   public :: size_spectra_batch
   public :: doppler_spectrum_batch
+  public :: lidar_profiles_batch
   public :: mp_thompson_kid_interface, mp_thompson_kid_staging
   logical, public :: is_aerosol_aware = .false.          ! M:28 (read at thompson_init)
   logical, public :: l_rate_diagnostics = .true.         ! replay the save_dg calls of M:2962-3124
@@ -102,6 +103,9 @@ module module_mp_thompson09n
   type, bind(C) :: kidmp_doppler_out                     ! kidmp_doppler_out / kidmp32_doppler_out: [ncol][nz] each, NULL = not wanted
      type(c_ptr) :: dbz, vd, sw, vz_r, vz_s, vz_g, dbz_r, dbz_s, dbz_g
   end type kidmp_doppler_out
+  type, bind(C) :: kidmp_lidar_out                       ! kidmp_lidar_out / kidmp32_lidar_out: [ncol][nz] each, NULL = not wanted
+     type(c_ptr) :: ext_c, ext_i, ext_r, ext_s, ext_g, ext, bsc, bsc_mol, tau_up, tau_dn, att_up, att_dn, sr_up, sr_dn
+  end type kidmp_lidar_out
 
   type, bind(C) :: kidmp_spectra_out                     ! kidmp_spectra_out / kidmp32_spectra_out: [ncol][nz] each, NULL = not wanted
      type(c_ptr) :: lam_c, n0_c, nu_c, lam_i, n0_i, lam_r, n0_r, smob, smoc, lam_g, n0_g
@@ -368,6 +372,28 @@ module module_mp_thompson09n
        type(c_ptr), value :: t, p, qv, qr, nr, qs, qg, w   ! real(c_float) [ncol][nz]
        type(kidmp_doppler_out), intent(in) :: out
      end function kidmp32_doppler_moments_host
+     ! the lidar operator (include/kidmp_lidar.h): nc, qi, ni, qs, qg, cfg (nine doubles) and summary [ncol][8] (real(c_double)
+     ! in both) may be NULL; dz_col_stride 0 = one dz profile for all columns
+     integer(c_int) function kidmp_lidar_profiles_host(ctx, ncol, nz, t, p, qv, qc, nc, qi, ni, qr, nr, qs, qg, dz, &
+          dz_col_stride, cfg, out, summary) bind(C, name='kidmp_lidar_profiles_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr, kidmp_lidar_out
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol, dz_col_stride
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qc, nc, qi, ni, qr, nr, qs, qg, dz   ! real(c_double) [ncol][nz], dz [nz]
+       type(c_ptr), value :: cfg, summary
+       type(kidmp_lidar_out), intent(in) :: out
+     end function kidmp_lidar_profiles_host
+     integer(c_int) function kidmp32_lidar_profiles_host(ctx, ncol, nz, t, p, qv, qc, nc, qi, ni, qr, nr, qs, qg, dz, &
+          dz_col_stride, cfg, out, summary) bind(C, name='kidmp32_lidar_profiles_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr, kidmp_lidar_out
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol, dz_col_stride
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qc, nc, qi, ni, qr, nr, qs, qg, dz   ! real(c_float) [ncol][nz], dz [nz]
+       type(c_ptr), value :: cfg, summary
+       type(kidmp_lidar_out), intent(in) :: out
+     end function kidmp32_lidar_profiles_host
      ! the Doppler spectrum on a uniform velocity grid (include/kidmp_dspectrum.h): qs, qg and w may be NULL (zero)
      integer(c_int) function kidmp_doppler_spectrum_host(ctx, ncol, nz, t, p, qv, qr, nr, qs, qg, w, v0, dv, nv, grids, out) &
           bind(C, name='kidmp_doppler_spectrum_host')
@@ -901,6 +927,77 @@ contains
     end if
     call stop_on_error(rc, 'doppler_moments_batch')
   end subroutine doppler_moments_batch
+
+  ! The lidar operator of include/kidmp_lidar.h over ncol columns of KiD's (nz, ncol) storage in one call: the extinction of
+  ! the five species, of all particles and their backscatter, the molecular backscatter, the optical depth and the
+  ! layer-mean attenuated backscatter seen from the ground (_up) and from space (_dn), and the scattering ratios.  Every
+  ! output is optional, the profiles in the array kind the arithmetic stores; summary(s+1, i) is slot s of column i, always
+  ! real(c_double); at least one must be present.  dz(nz) is KiD's one profile of layer depths.  nc may be left out unless
+  ! is_aerosol_aware, qi, ni, qs and qg in an iiwarm run.  A member of the configuration left out keeps the library's
+  ! convention (s_ratio = 18.8, 25, 18.8, 25, 25 for c, i, r, s, g; eta 0.7; c_mol 6.2446e-32; beta_detect 2e-5; trans_lost
+  ! 2.5e-3).  The inputs are not changed.  Default REAL 8 goes to kidmp_lidar_profiles_host, REAL 4 to kidmp32_...
+  subroutine lidar_profiles_batch(ncol, nz, t, p, qv, qc, qr, nr, dz, ext_c, ext_i, ext_r, ext_s, ext_g, ext, bsc, bsc_mol, &
+       tau_up, tau_dn, att_up, att_dn, sr_up, sr_dn, summary, nc, qi, ni, qs, qg, s_ratio, eta, c_mol, beta_detect, trans_lost)
+    integer, intent(in) :: ncol, nz
+    real, dimension(nz,ncol), intent(in), target :: t, p, qv, qc, qr, nr
+    real, dimension(nz), intent(in), target :: dz
+    real, dimension(nz,ncol), intent(out), optional, target :: ext_c, ext_i, ext_r, ext_s, ext_g, ext, bsc, bsc_mol, &
+         tau_up, tau_dn, att_up, att_dn, sr_up, sr_dn
+    real(c_double), dimension(8,ncol), intent(out), optional, target :: summary
+    real, dimension(nz,ncol), intent(in), optional, target :: nc, qi, ni, qs, qg
+    real(c_double), intent(in), optional :: s_ratio(5), eta, c_mol, beta_detect, trans_lost
+    real(c_double), target :: cfg(9)                       ! kidmp_lidar_cfg: nine doubles
+    type(kidmp_lidar_out) :: out
+    type(c_ptr) :: pnc, pqi, pni, pqs, pqg, pcfg, psum
+    integer(c_int) :: rc
+    if (.not. c_associated(ctx)) call thompson_init
+    if (c_associated(mctx)) then
+       write(*,'(a)') ' module_mp_thompson09n: lidar profiles are not available with kidmp_ndevices > 1'
+       stop 1
+    end if
+    pnc = c_null_ptr;  pqi = c_null_ptr;  pni = c_null_ptr;  pqs = c_null_ptr;  pqg = c_null_ptr
+    pcfg = c_null_ptr;  psum = c_null_ptr
+    if (present(nc)) pnc = c_loc(nc)
+    if (present(qi)) pqi = c_loc(qi)
+    if (present(ni)) pni = c_loc(ni)
+    if (present(qs)) pqs = c_loc(qs)
+    if (present(qg)) pqg = c_loc(qg)
+    if (present(summary)) psum = c_loc(summary)
+    if (present(s_ratio) .or. present(eta) .or. present(c_mol) .or. present(beta_detect) .or. present(trans_lost)) then
+       cfg = (/ 18.8_c_double, 25.0_c_double, 18.8_c_double, 25.0_c_double, 25.0_c_double, 0.7_c_double, 6.2446e-32_c_double, &
+            2.0e-5_c_double, 2.5e-3_c_double /)
+       if (present(s_ratio)) cfg(1:5) = s_ratio
+       if (present(eta)) cfg(6) = eta
+       if (present(c_mol)) cfg(7) = c_mol
+       if (present(beta_detect)) cfg(8) = beta_detect
+       if (present(trans_lost)) cfg(9) = trans_lost
+       pcfg = c_loc(cfg)
+    end if
+    out = kidmp_lidar_out(c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
+         c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr)
+    if (present(ext_c)) out%ext_c = c_loc(ext_c)
+    if (present(ext_i)) out%ext_i = c_loc(ext_i)
+    if (present(ext_r)) out%ext_r = c_loc(ext_r)
+    if (present(ext_s)) out%ext_s = c_loc(ext_s)
+    if (present(ext_g)) out%ext_g = c_loc(ext_g)
+    if (present(ext)) out%ext = c_loc(ext)
+    if (present(bsc)) out%bsc = c_loc(bsc)
+    if (present(bsc_mol)) out%bsc_mol = c_loc(bsc_mol)
+    if (present(tau_up)) out%tau_up = c_loc(tau_up)
+    if (present(tau_dn)) out%tau_dn = c_loc(tau_dn)
+    if (present(att_up)) out%att_up = c_loc(att_up)
+    if (present(att_dn)) out%att_dn = c_loc(att_dn)
+    if (present(sr_up)) out%sr_up = c_loc(sr_up)
+    if (present(sr_dn)) out%sr_dn = c_loc(sr_dn)
+    if (kind(t) == c_double) then
+       rc = kidmp_lidar_profiles_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), c_loc(qc), &
+            pnc, pqi, pni, c_loc(qr), c_loc(nr), pqs, pqg, c_loc(dz), 0_c_int64_t, pcfg, out, psum)
+    else
+       rc = kidmp32_lidar_profiles_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), c_loc(qc), &
+            pnc, pqi, pni, c_loc(qr), c_loc(nr), pqs, pqg, c_loc(dz), 0_c_int64_t, pcfg, out, psum)
+    end if
+    call stop_on_error(rc, 'lidar_profiles_batch')
+  end subroutine lidar_profiles_batch
 
   ! The Doppler spectrum of a state over ncol columns of KiD's (nz, ncol) storage in one call (include/kidmp_dspectrum.h):
   ! the reflectivity (m6 m-3 per bin) of rain, snow and graupel together (total) and apart, as spectra (nz, nv, ncol) on the

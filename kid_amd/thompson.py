@@ -621,6 +621,17 @@ class ThompsonMP:
         from .doppler import DOPPLER_NAMES, doppler_moments_host
         return doppler_moments_host(self, st, w, DOPPLER_NAMES if want is None else want)
 
+    def lidar_profiles(self, st, dz=None, cfg=None, want=None, summary=False, stream=None):
+        """Extinction, backscatter, optical depth and attenuated backscatter of every level as a lidar on the ground and
+        one in space see them (include/kidmp_lidar.h): kid_amd.lidar.lidar_profiles on this context."""
+        from .lidar import LIDAR_NAMES, lidar_profiles
+        return lidar_profiles(self, st, dz, cfg, LIDAR_NAMES if want is None else want, summary, stream)
+
+    def lidar_profiles_host(self, st, dz=None, cfg=None, want=None, summary=False):
+        """lidar_profiles on numpy arrays: kid_amd.lidar.lidar_profiles_host on this context."""
+        from .lidar import LIDAR_NAMES, lidar_profiles_host
+        return lidar_profiles_host(self, st, dz, cfg, LIDAR_NAMES if want is None else want, summary)
+
     def doppler_spectrum(self, st, v0, dv, nv, w=None, grids=None, want=("total",), out=None, stream=None):
         """The Doppler spectrum of every level on a uniform velocity grid (include/kidmp_dspectrum.h):
         kid_amd.dspectrum.doppler_spectrum on this context."""
