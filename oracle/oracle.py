@@ -88,6 +88,9 @@ def lib():
         for f in ("th_oracle_rslf", "th_oracle_rsif", "th_oracle_gammp"):
             getattr(L, f).restype = C.c_double
             getattr(L, f).argtypes = [C.c_double, C.c_double]
+        for f in ("th_oracle_u4_count", "th_oracle_u4_count_p32n"):
+            getattr(L, f).restype = C.c_long
+            getattr(L, f).argtypes = []
         L.th_oracle_gammln.restype = C.c_double
         L.th_oracle_gammln.argtypes = [C.c_double]
         _lib = L
@@ -261,6 +264,12 @@ class Oracle:
 
     def integer(self, name):
         return lib().th_oracle_int(self._h, name.encode())
+
+
+def u4_count(p32n=False):
+    """Reads of t_Efrw / t_Efsw whose second index had to be clamped to 1..100 (U4: the reference reads out of bounds
+    there) since the library was loaded; take the difference around a step."""
+    return int((lib().th_oracle_u4_count_p32n if p32n else lib().th_oracle_u4_count)())
 
 
 def rslf(p, t):

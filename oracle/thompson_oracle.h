@@ -14,13 +14,15 @@
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may
  * load this library.  The shipped path (kid_amd/) never links or calls it.
  *
- * PARITY PINNING: the reference cannot be built in this image under the rules
- * of this project (it USEs five KiD modules that are not in the mount and
- * needs a source patch for undefined behaviour U1), and it ships no golden
- * vectors.  The oracle is pinned against the known-answer values that the
- * survey recorded from the reference itself (KAT-A/B/C,
- * 6-7 significant digits); see tests/test_oracle_kat.py.  Beyond those
- * digits parity is UNPINNED.
+ * PARITY PINNING: the reference itself is built from source against the KiD
+ * stand-ins of tests/fortran/kid_stubs.f90 (`make ref`, ref_driver.f90) and what
+ * it computes is recorded in tests/golden/reference_*.npz; the oracle is held
+ * to those records in tests/test_reference_goldens.py (P64 within 7.4e-13 on
+ * every recorded output; at a level on a residue-decided test of M:3587 /
+ * M:3596 against the forced outcome the Fortran took), and to the known-answer values that the survey
+ * recorded earlier (KAT-A/B/C, 6-7 significant digits)
+ * in tests/test_oracle_kat.py.  Beyond the recorded columns, and at the
+ * reference's undefined behaviour U1 / U4, parity is UNPINNED.
  */
 #ifndef THOMPSON_ORACLE_H
 #define THOMPSON_ORACLE_H
@@ -180,6 +182,9 @@ const double *th_oracle_const(const th_oracle *o, const char *name, int *n);
 const double *th_oracle_table(const th_oracle *o, const char *name,
                               int *ndim, int dims[4]);
 int th_oracle_int(const th_oracle *o, const char *name);
+/* reads of t_Efrw / t_Efsw whose second index the oracle had to clamp (U4) since the library was loaded, all contexts */
+long th_oracle_u4_count(void);
+long th_oracle_u4_count_p32n(void);
 
 /* scalar helpers exposed for unit tests */
 double th_oracle_rslf(double p, double t);     /* M:4656-4686 */

@@ -394,6 +394,16 @@ double P(th_oracle_view_const)(const th_oracle *c, const char *name, int idx)
 }
 
 static inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+/* U4: the second index of t_Efrw / t_Efsw, clamped to 1..nbc; u4_count counts the reads the clamp changed, i.e. the ones
+ * the reference takes out of bounds (read through th_oracle_u4_count: a column that reaches one has no reference value) */
+static long u4_count;
+static inline int u4_index(int j)
+{
+    const int c = clampi(j, 1, nbc);
+    if (c != j) __atomic_fetch_add(&u4_count, 1, __ATOMIC_RELAXED);
+    return c;
+}
+long P(th_oracle_u4_count)(void) { return __atomic_load_n(&u4_count, __ATOMIC_RELAXED); }
 
 #ifndef TH_P32N
 int th_oracle_mp_thompson(const th_oracle *o,
@@ -767,7 +777,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
             idx = 1 + (int)(nbr * log(mvd_r[k] / o->Dr[1]) / log(o->Dr[nbr] / o->Dr[1]));
             idx = idx < nbr ? idx : nbr;
             if (idx < 1) idx = 1;
-            Ef_rw = EFRW(o->t_Efrw, idx, clampi((int)(mvd_c[k] * 1.E6), 1, nbc));
+            Ef_rw = EFRW(o->t_Efrw, idx, u4_index((int)(mvd_c[k] * 1.E6)));
             prr_rcw[k] = rhof[k] * o->t1_qr_qc * Ef_rw * rc[k] * N0_r[k] * pow(lamr + fv_r, -cre[9]);
             prr_rcw[k] = MIND(rc[k] * odts, prr_rcw[k]);
             pnc_rcw[k] = rhof[k] * o->t1_qr_qc * Ef_rw * nc[k] * N0_r[k] * pow(lamr + fv_r, -cre[9]);
@@ -865,7 +875,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
                     idx = 1 + (int)(nbs * log(xDs / o->Ds[1]) / log(o->Ds[nbs] / o->Ds[1]));
                     idx = idx < nbs ? idx : nbs;
                     if (idx < 1) idx = 1;
-                    Ef_sw = EFSW(o->t_Efsw, idx, clampi((int)(mvd_c[k] * 1.E6), 1, nbc));
+                    Ef_sw = EFSW(o->t_Efsw, idx, u4_index((int)(mvd_c[k] * 1.E6)));
                     prs_scw[k] = rhof[k] * o->t1_qs_qc * Ef_sw * rc[k] * smoe[k];
                     pnc_scw[k] = rhof[k] * o->t1_qs_qc * Ef_sw * nc[k] * smoe[k];
                     pnc_scw[k] = MIND(nc[k] * odts, pnc_scw[k]);

@@ -1,7 +1,9 @@
-! Minimal stand-ins for the KiD driver modules that the build-owned drop-in
-! modules (kid_amd/fortran/*.f90) USE.  TEST SCAFFOLDING for OUR OWN code only:
-! the real KiD driver is not in the reference mount; nothing here is used to
-! build or run the reference.
+! Minimal stand-ins for the KiD driver modules (the real KiD driver is not in the
+! reference mount).  TEST SCAFFOLDING with two users: the build-owned drop-in
+! modules (kid_amd/fortran/*.f90), and -- since these are exactly the modules the
+! reference's two files USE -- the reference itself, compiled unmodified against
+! them by `make -C oracle ref` and run by oracle/ref_driver.f90 to record
+! tests/golden/reference_*.npz.
 module typeKind
   integer, parameter :: wp = kind(1.0)
 end module typeKind

@@ -83,7 +83,16 @@ def _copy(st):
     return {k: np.ascontiguousarray(v.copy()) for k, v in st.items()}
 
 
-def branch_aware_compare(oracle, st, dt, got, got_ppt=None, nperturb=2, keys=OUT, depletion=0.0):
+def against_record(record, ref, keys=OUT):
+    """What `got` is compared with when an outside record is given (tests/golden/reference_*.npz: what the reference
+    Fortran itself computed): the record, except at its NaN entries -- results the reference leaves undefined (U1:
+    output qc and nc at level kts) -- where the oracle's defined-semantics value stands in."""
+    return {k: np.where(np.isnan(np.asarray(record[k], dtype=np.float64)), ref[k], np.asarray(record[k], dtype=np.float64))
+            for k in keys}
+
+
+def branch_aware_compare(oracle, st, dt, got, got_ppt=None, nperturb=2, keys=OUT, depletion=0.0, record=None,
+                         record_ppt=None):
     """Level-by-level comparison of `got` (the HIP result after one step from `st`) with the oracle that leaves
     no level unchecked.  Returns a dict of [ncol, nz] arrays and the oracle outputs:
       err    error against the oracle; at levels on one of the reference's residue-decided tests (M:3587 /
@@ -91,12 +100,19 @@ def branch_aware_compare(oracle, st, dt, got, got_ppt=None, nperturb=2, keys=OUT
              each taken over ALL variables of the level at once
       flags  the oracle's flags (bit 0: M:3587, bit 1: M:3596)
       sens   the oracle's own response at the level (same metric) to ulp-sized perturbations of T and q
-      ref, ppt_ref, ppt_err"""
+      ref, ppt_ref, ppt_err
+    With `record` (and `record_ppt`) the errors are taken against that outside record (against_record) instead of the
+    oracle's step; the oracle then supplies only the flags, the two admissible outcomes and the sensitivity.  At a
+    residue-decided level `got` must then equal the record or the other admissible outcome, and the record itself is
+    held there too: "record_err" is, at those levels, the smaller of the RECORD's errors against the two outcomes
+    (zero elsewhere, where `err` already is the distance to the record)."""
     ref = _copy(st)
     ppt_ref, flags = oracle.batch_step(ref, dt, want_illcond=True)
-    err = level_err(got, ref, keys, st, depletion)
+    target = ref if record is None else against_record(record, ref, keys)
+    err = level_err(got, target, keys, st, depletion)
     flagged = flags != 0
     refs = [ref]
+    record_err = None if record is None else np.zeros_like(err)
     if flagged.any():
         e2 = []
         for force in (1, 2):
@@ -104,7 +120,13 @@ def branch_aware_compare(oracle, st, dt, got, got_ppt=None, nperturb=2, keys=OUT
             oracle.batch_step(r, dt, force=force)
             refs.append(r)
             e2.append(level_err(got, r, keys, st, depletion))
-        err = np.where(flagged, np.minimum(e2[0], e2[1]), err)
+        best = np.minimum(e2[0], e2[1])
+        if record is not None:               # `err` so far is the distance to the record: one more admissible answer
+            best = np.minimum(best, err)
+        err = np.where(flagged, best, err)
+        if record is not None:
+            r2 = [level_err(target, r, keys, st, depletion) for r in refs[1:]]
+            record_err = np.where(flagged, np.minimum(r2[0], r2[1]), 0.0)
     sens = np.zeros_like(err)
     for ft, fq in _PERT[:nperturb]:
         pert = _copy(st)
@@ -126,8 +148,9 @@ def branch_aware_compare(oracle, st, dt, got, got_ppt=None, nperturb=2, keys=OUT
         sens = np.maximum(sens, s)
     ppt_err = None
     if got_ppt is not None:
-        ppt_err = np.abs(np.asarray(got_ppt) - ppt_ref) / np.maximum(np.abs(ppt_ref), FLOORS["ppt"])
-    return dict(err=err, flags=flags, sens=sens, ref=ref, ppt_ref=ppt_ref, ppt_err=ppt_err)
+        ppt_target = ppt_ref if record_ppt is None else np.asarray(record_ppt, dtype=np.float64)
+        ppt_err = np.abs(np.asarray(got_ppt) - ppt_target) / np.maximum(np.abs(ppt_target), FLOORS["ppt"])
+    return dict(err=err, flags=flags, sens=sens, ref=ref, ppt_ref=ppt_ref, ppt_err=ppt_err, record_err=record_err)
 
 
 def verdict(cmp, tol=TOL, sens_factor=10.0, sens_cut=1e-11):
@@ -170,7 +193,7 @@ MAX_SENSITIVE_FRAC = 0.02   # at most this share of the levels may lean on the s
 
 def assert_parity(oracle, st, dt, got, got_ppt, tol=TOL, sens_factor=10.0, tol_ppt=None, depletion=0.0,
                   max_branch_frac=None, min_cols_within=None, tol_cols=TOL, ceiling=ABS_CEILING,
-                  max_sensitive_frac=MAX_SENSITIVE_FRAC, quantile=None):
+                  max_sensitive_frac=MAX_SENSITIVE_FRAC, quantile=None, record=None, record_ppt=None):
     """The parity assertion of the -m gpu tests: EVERY level within max(tol, sens_factor x the oracle's own
     sensitivity there), levels on the reference's residue-decided tests against the better of their two admissible
     outcomes; precipitation within tol_ppt.  The sensitivity allowance is itself bounded: no level beyond
@@ -178,9 +201,14 @@ def assert_parity(oracle, st, dt, got, got_ppt, tol=TOL, sens_factor=10.0, tol_p
     `tol` at all (i.e. passing only because of the allowance).  Optionally: at most max_branch_frac of the levels on
     residue-decided tests, and at least min_cols_within of the columns with every level within tol_cols; `quantile` =
     (q, bound): the q-quantile of the level errors (no allowance of any kind) must not exceed bound.
+    `record` / `record_ppt`: compare with that outside record instead of the oracle's step (branch_aware_compare).
     Returns the verdict dict."""
-    cmp = branch_aware_compare(oracle, st, dt, got, got_ppt, depletion=depletion)
+    cmp = branch_aware_compare(oracle, st, dt, got, got_ppt, depletion=depletion, record=record, record_ppt=record_ppt)
     v = verdict(cmp, tol=tol, sens_factor=sens_factor)
+    if record is not None:                   # the record itself on the residue-decided levels: one of the two outcomes
+        v["max_record_err"] = float(cmp["record_err"].max())
+        assert (cmp["record_err"] <= np.maximum(tol, sens_factor * cmp["sens"])).all(), v
+        assert v["max_record_err"] <= max(tol, ceiling), v
     assert v["n_unmatched"] == 0, v
     assert v["max_err_any"] <= max(tol, ceiling), v
     assert v["n_beyond_tol"] <= int(np.ceil(max_sensitive_frac * v["n_levels"])), v

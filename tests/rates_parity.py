@@ -38,14 +38,15 @@ def oracle_rates(oracle_column_step, st, dt):
     return ref, dry
 
 
-def rates_compare(oracle_column_step, st, dt, got_rates, nperturb=2):
+def rates_compare(oracle_column_step, st, dt, got_rates, nperturb=2, record=None):
     """`got_rates` [ncol, 36, nz] (the HIP result of one step from `st`) against the oracle, column by column.
     Returns a dict of [ncol, 36, nz] arrays:
       err   the element metric of got_rates against the oracle
       sens  the oracle's own response, same metric, to the first `nperturb` probes of parity._PERT (T scaled by
             1 +- 2 eps, the six mixing ratios by 1 -+ 2 eps: the probes of branch_aware_compare)
       ref   the oracle's rates
-    and `dry` [ncol]: the oracle's no_micro verdict."""
+    and `dry` [ncol]: the oracle's no_micro verdict.  With `record` [ncol, 36, nz] (what the reference Fortran itself
+    logged, tests/golden/reference_*.npz) `err` is taken against that record; the oracle supplies only `sens`."""
     got_rates = np.asarray(got_rates)
     ref, dry = oracle_rates(oracle_column_step, st, dt)
     assert got_rates.shape == ref.shape, (got_rates.shape, ref.shape)
@@ -56,7 +57,9 @@ def rates_compare(oracle_column_step, st, dt, got_rates, nperturb=2):
         for k in ("qv", "qc", "qi", "qr", "qs", "qg"):
             pert[k] *= fq
         sens = np.maximum(sens, rates_metric(oracle_rates(oracle_column_step, pert, dt)[0], ref))
-    return dict(err=rates_metric(got_rates, ref), sens=sens, ref=ref, dry=dry)
+    target = ref if record is None else np.asarray(record, dtype=np.float64)
+    assert target.shape == ref.shape, (target.shape, ref.shape)
+    return dict(err=rates_metric(got_rates, target), sens=sens, ref=ref, dry=dry)
 
 
 def rates_verdict(cmp, tol=TOL, sens_factor=10.0):
@@ -71,12 +74,12 @@ def rates_verdict(cmp, tol=TOL, sens_factor=10.0):
 
 
 def assert_rates(oracle_column_step, st, dt, got_rates, tol=TOL, sens_factor=10.0, ceiling=ABS_CEILING,
-                 max_beyond_frac=MAX_BEYOND_FRAC):
+                 max_beyond_frac=MAX_BEYOND_FRAC, record=None):
     """The rate assertion of the -m gpu tests, parity.assert_parity restated for the rate buffer with the project's own
     constants: EVERY element within max(tol, sens_factor x the oracle's own response there), none beyond
     max(tol, ceiling) however the oracle responds, and at most max_beyond_frac of the elements beyond `tol` at all.
     Returns the verdict with the comparison under "cmp"."""
-    cmp = rates_compare(oracle_column_step, st, dt, got_rates)
+    cmp = rates_compare(oracle_column_step, st, dt, got_rates, record=record)
     v = rates_verdict(cmp, tol=tol, sens_factor=sens_factor)
     assert v["n_unmatched"] == 0, v
     assert v["max_err_any"] <= max(tol, ceiling), v

@@ -1,6 +1,6 @@
 """The HIP path against the reference's OWN recorded outputs (-m gpu): the known-answer soundings of SURVEY.md section 9h
 (KAT-A warm / mixed over 200 calls, KAT-C over 3 calls) through kidmp_column_step, every quoted digit (6-7).  These are
-the only reference-generated values there are (the mount holds no fixtures and the reference cannot be rebuilt here):
+the reference-generated values the survey recorded (tests/test_gpu_reference.py holds the records of a later build from source):
 tests/test_oracle_kat.py pins the oracle on them, this file pins the product path on them directly.  KAT-B (the KiD
 adapter, 360 steps) runs through the Fortran drop-in in tests/test_fortran_gpu.py."""
 import numpy as np

@@ -2,8 +2,8 @@
 
 The numbers below are what the reference Fortran (P64 build) produced for these exact
 soundings during the survey (KAT-A/B/C; 6-7 significant digits).
-They are the only reference-generated values available: the mount holds no tests or
-golden vectors, and the reference cannot be rebuilt in this image."""
+The mount holds no tests or golden vectors; what a build of the reference from source
+computes on single steps is held in tests/test_reference_goldens.py."""
 import numpy as np
 import pytest
 
