@@ -11,6 +11,7 @@ from .summary import SUMMARY_INPUTS, SUMMARY_NAMES, column_summary, column_summa
 from .doppler import DOPPLER_INPUTS, DOPPLER_NAMES, doppler_moments, doppler_moments_host  # noqa: F401
 from .lidar import LIDAR_INPUTS, LIDAR_NAMES, LIDAR_SUMMARY_NAMES, LidarCfg, lidar_profiles, lidar_profiles_host  # noqa: F401
 from .fall import FALL_INPUTS, FALL_NAMES, fall_speeds, fall_speeds_host  # noqa: F401
+from .brightband import BRIGHTBAND_INPUTS, BRIGHTBAND_NAMES, BrightBandCfg, bright_band, bright_band_host  # noqa: F401
 from .dspectrum import DSPECTRUM_INPUTS, DSPECTRUM_NAMES, doppler_spectrum, doppler_spectrum_host, velocity_grid  # noqa: F401
 from .spectra import SPECTRA_INPUTS, SPECTRA_PARAMS, SPECTRA_SPECIES, default_grid, size_spectra, size_spectra_host  # noqa: F401
 from .kinematic import ADVECT_OUTPUTS, advect, run, update  # noqa: F401

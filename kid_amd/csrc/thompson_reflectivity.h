@@ -7,6 +7,7 @@
 
 #include "thompson_params.h"
 #include "thompson_levels.h"
+#include "kidmp_brightband_mix.h"
 
 namespace kidmp {
 
@@ -141,5 +142,23 @@ template <class T> struct DSpectrumArgs {
 template <class T>
 hipError_t launch_doppler_spectrum(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const DSpectrumArgs<T> &a,
                                    hipStream_t stream);
+
+// The bright band (include/kidmp_brightband.h): calc_refl10cm with melting snow and graupel below the melting level, from
+// k_doppler_moments' load.  Null means: qs, qg -- zero; an output -- not wanted.  out: dbz, dbz_s, dbz_g, enh_s, enh_g,
+// fmelt_s, fmelt_g [ncol][nz]; k0 [ncol].  D, dD: device arrays of nb[x] doubles by species snow, graupel.  warm: an iiwarm
+// context, no melting level.  One launch; the lanes sweep the diameter bins of each active (level, species) pair.
+constexpr int BRIGHTBAND_NOUT = 7, BRIGHTBAND_NSPEC = 2, BRIGHTBAND_MAX_BINS = 256;
+template <class T> struct BrightBandArgs {
+    const T *t, *p, *qv, *qr, *nr, *qs, *qg;
+    T *out[BRIGHTBAND_NOUT];
+    int32_t *k0;
+    const double *D[BRIGHTBAND_NSPEC], *dD[BRIGHTBAND_NSPEC];
+    int32_t nb[BRIGHTBAND_NSPEC];
+    BBMix mix;
+    int warm;
+};
+template <class T>
+hipError_t launch_bright_band(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const BrightBandArgs<T> &a,
+                              hipStream_t stream);
 
 }  // namespace kidmp

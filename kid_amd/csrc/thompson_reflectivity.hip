@@ -3,7 +3,8 @@
 //
 // Only the live part of the reference is computed.  Dead as shipped: rc (qc1d is never read), rhof, smoc, the melting-level
 // search k_0/melti (M:5107-5121) and the whole wet-snow/graupel block (M:5140-5192): with nrbins = 0 (M:204) its bin loops
-// are empty and its ze_* assignments are commented out, so there is no bright band and none is added here.
+// are empty and its ze_* assignments are commented out, so calc_refl10cm has no bright band; k_bright_band below is an
+// entry of its own that rebuilds that block (include/kidmp_brightband.h).
 //
 // Layout: one wavefront per column (four per workgroup), lanes over levels: level k = 64 j + lane in level group j,
 // NJ = ceil(nz/64) groups per lane.  Every level is independent except the graupel intercept, which is a top-down running
@@ -966,10 +967,11 @@ k_lidar_profiles(const Consts *__restrict__ hc, LidarArgs<T> a, int64_t ncol, in
 // ---- what k_doppler_moments and k_doppler_spectrum share: calc_refl10cm's load of one level (M:4991-5028) with the
 // slopes and intercepts that column_dbz leaves inside lvl::rain_ze and lvl::graupel_ze ----
 // An absent species: ze = 1.E-22 (M:5127-5136), lamr = N0_r = 0, sl zero.  n0_exp is the level's graupel intercept before
-// the running minimum.  A: DopplerArgs or DSpectrumArgs (t, p, qv, qr, nr; qs, qg null = zero).
+// the running minimum.  A: DopplerArgs, DSpectrumArgs or BrightBandArgs (t, p, qv, qr, nr; qs, qg null = zero).  temp and
+// rs = qs*rho (R1 without snow, M:5019) are what the melting layer reads beside them.
 struct RadarLevel {
     bool L_qr, L_qs, L_qg;
-    double rhof, rg, n0_exp, ze_rain, ze_snow, lamr, N0_r;
+    double temp, rs, rhof, rg, n0_exp, ze_rain, ze_snow, lamr, N0_r;
     lvl::SnowLevel sl;
 };
 template <class A>
@@ -989,11 +991,13 @@ __device__ __forceinline__ RadarLevel radar_level(const ReflConsts &c, const A &
     r.ze_rain = r.ze_snow = 1.E-22;
     r.lamr = r.N0_r = 0.;
     r.sl = lvl::SnowLevel{};
-    r.rg = R1;
+    r.rg = r.rs = R1;
+    r.temp = temp;
     double mvd_r = 50.E-6;
     if (r.L_qr) r.ze_rain = lvl::rain_ze(c, rho, qr, double(a.nr[i]), mvd_r, r.lamr, r.N0_r);
     if (r.L_qs) {
-        r.sl = lvl::snow_level(temp, qs * rho, c.oams);
+        r.rs = qs * rho;
+        r.sl = lvl::snow_level(temp, r.rs, c.oams);
         r.ze_snow = lvl::snow_ze(c, r.sl);
     }
     if (r.L_qg) r.rg = qg * rho;
@@ -1241,6 +1245,188 @@ k_doppler_spectrum(ReflConsts c, DopplerConsts dc, DSpectrumArgs<T> a, int64_t n
             }
         }
     }
+}
+
+// ---- the bright band (include/kidmp_brightband.h) ----
+// sum over the wave in the order the header fixes: a butterfly over xor 32, 16, ..., 1; every lane ends with the same bits
+__device__ inline double wave_sum_down(double v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+constexpr int BB_STRIDES = BRIGHTBAND_MAX_BINS / 64;
+
+// One species' active levels of the column: the lanes sweep the diameter bins, lane l taking bins l, l + 64, ...  What
+// depends on the bin alone -- D, dD, D**mu_s, the mass, the unmelted particle's ice and envelope, its dry weight -- is
+// formed once per lane and kept in registers.  Per level group the ballot of active levels is walked by bit scans, lowest
+// level first; the level's parameters arrive wave-uniform through v_readlane: fm and p0, p1, p2 = snow's Mrat, k1m0 and
+// smob/smoc (lvl::SnowSpectrum) or graupel's N0_g and lamg.  enh receives the level's ratio in the lane that owns it.
+// The order in which the pairs are taken changes no bit: every pair has accumulators of its own.
+template <int SP, int NJ, class T>
+__device__ __forceinline__ void bright_band_species(const BrightBandArgs<T> &a, int lane, const double (&fmelt)[NJ],
+                                                    const double (&p0)[NJ], const double (&p1)[NJ], const double (&p2)[NJ],
+                                                    double (&enh)[NJ])
+{
+    const double *__restrict__ D = a.D[SP], *__restrict__ dD = a.dD[SP];
+    const int nb = a.nb[SP];
+    double bD[BB_STRIDES], bdD[BB_STRIDES], bMu[BB_STRIDES];
+    BBBin bb[BB_STRIDES];
+#pragma unroll
+    for (int q = 0; q < BB_STRIDES; ++q) {
+        const int b = 64 * q + lane;
+        bD[q] = bdD[q] = bMu[q] = 0.;
+        bb[q] = BBBin{};
+        if (b >= nb) continue;
+        const double d = D[b];
+        bD[q] = d;
+        bdD[q] = dD[b];
+        if (SP == 0) bMu[q] = fm::pow(d, mu_s);
+        bb[q] = bb_bin(a.mix, SP == 0 ? am_s * (d * d) : am_g * (d * d * d), d);
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        unsigned long long act = __ballot(fmelt[j] > 0.);
+        while (act) {
+            const int l = __builtin_ctzll(act);
+            act &= act - 1;
+            const double f = readlane(fmelt[j], l), u0 = readlane(p0[j], l), u1 = readlane(p1[j], l), u2 = readlane(p2[j], l);
+            lvl::SnowSpectrum ss{};
+            if (SP == 0) { ss.Mrat = u0; ss.k1m0 = u1; ss.slam1 = u2 * Lam0; ss.slam2 = u2 * Lam1; }
+            double wet = 0., dry = 0.;
+#pragma unroll
+            for (int q = 0; q < BB_STRIDES; ++q) {
+                if (64 * q >= nb) break;                             // wave-uniform
+                if (64 * q + lane >= nb) continue;
+                const double n = SP == 0 ? lvl::snow_bin(ss, bD[q], bMu[q], bdD[q]) : lvl::exp_bin(u0, u1, bD[q], bdD[q]);
+                wet += n * bb_wet(a.mix, bb[q], f);
+                dry += n * bb[q].dry;
+            }
+            wet = wave_sum_down(wet);
+            dry = wave_sum_down(dry);
+            const double e = dry > 0. ? wet / dry : 1.;
+            if (lane == l) enh[j] = e;
+        }
+    }
+}
+
+// One wavefront per column: calc_refl10cm with the melting layer (include/kidmp_brightband.h).  The load and the scan are
+// k_doppler_moments' (radar_level, graupel_running_min), lanes over levels.  The melting level comes from ballots, the top
+// level group first; rs and rg of that level are handed round with v_readlane.  A column without a melting level stores
+// the dry profiles and does nothing else; otherwise the few active (level, species) pairs below the melting level are
+// integrated with the lanes over the diameter bins (bright_band_species).  No atomics, no scratch, nothing but the
+// fastmath tables in LDS.
+template <class T, int NJ>
+__global__ void __launch_bounds__(REFL_THREADS)
+k_bright_band(ReflConsts c, DopplerConsts dc, BrightBandArgs<T> a, int64_t ncol, int nz)
+{
+#if KFM_TABLES
+    fm::tab::load_tables(int(threadIdx.x), REFL_THREADS);
+    __syncthreads();
+#endif
+    const int lane = int(threadIdx.x) & 63;
+    const int64_t col = int64_t(blockIdx.x) * REFL_WAVES + (int(threadIdx.x) >> 6);
+    if (col >= ncol) return;                                         // whole wavefronts only: the scans need every lane
+    const int64_t base = col * int64_t(nz);
+
+    double ze_r[NJ], ze_s[NJ], ze_g[NJ], rs[NJ], rg[NJ], n0[NJ];
+    double s0[NJ], s1[NJ], s2[NJ], g0[NJ], g1[NJ];                   // snow: tc0, smob, then Mrat, k1m0, smob/smoc; graupel: N0_g, lamg
+    bool lqs[NJ], lqg[NJ], warm_rain[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        ze_r[j] = ze_s[j] = ze_g[j] = 1.E-22;
+        rs[j] = rg[j] = R1;
+        s0[j] = s1[j] = s2[j] = g0[j] = g1[j] = 0.;
+        lqs[j] = lqg[j] = warm_rain[j] = false;
+        n0[j] = double(__builtin_inf());                             // levels past kte do not enter the minimum
+        if (k >= nz) continue;
+        const RadarLevel r = radar_level(c, a, base + k);            // ---- load, M:4991-5028 ----
+        ze_r[j] = r.ze_rain;
+        ze_s[j] = r.ze_snow;
+        rs[j] = r.rs;
+        rg[j] = r.rg;
+        lqs[j] = r.L_qs;
+        lqg[j] = r.L_qg;
+        warm_rain[j] = k <= nz - 2 && r.temp > 273.15 && r.L_qr;     // M:5112
+        s0[j] = r.sl.tc0;
+        s1[j] = r.sl.smob;
+        n0[j] = r.n0_exp;
+    }
+    graupel_running_min<NJ>(n0, lane);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        if (!lqg[j]) continue;
+        double ilamg;
+        ze_g[j] = lvl::graupel_ze(c, n0[j], rg[j], ilamg, g1[j], g0[j]);
+    }
+
+    // ---- the melting level, M:5109-5118: the highest k with warm rain under snow or graupel; k0 = k + 1 ----
+    unsigned long long ms[NJ], mg[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) { ms[j] = __ballot(lqs[j]); mg[j] = __ballot(lqg[j]); }
+    int k0 = -1;
+    if (!a.warm) {
+#pragma unroll
+        for (int j = NJ - 1; j >= 0; --j) {
+            unsigned long long above = (ms[j] | mg[j]) >> 1;         // bit l: level 64 j + l + 1 holds snow or graupel
+            const int ju = j + 1 < NJ ? j + 1 : j;
+            if (j + 1 < NJ) above |= (ms[ju] | mg[ju]) << 63;
+            const unsigned long long hit = __ballot(warm_rain[j]) & above;
+            if (hit && k0 < 0) k0 = 64 * j + 64 - __builtin_clzll(hit);
+        }
+    }
+
+    double fms[NJ], fmg[NJ], es[NJ], eg[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) { fms[j] = fmg[j] = 0.; es[j] = eg[j] = 1.; }
+    if (k0 >= 0) {
+        bool snow0 = false, graupel0 = false;                        // L_qs(k_0), L_qg(k_0)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+            if ((k0 >> 6) == j) { snow0 = (ms[j] >> (k0 & 63)) & 1; graupel0 = (mg[j] >> (k0 & 63)) & 1; }
+        const double rs0 = level_of<NJ>(rs, k0), rg0 = level_of<NJ>(rg, k0);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int k = 64 * j + lane;
+            if (k < k0 && lqs[j] && snow0) fms[j] = fmax(0.05, fmin(1. - rs[j] / rs0, 0.99));       // M:5152
+            if (k < k0 && lqg[j] && graupel0) fmg[j] = fmax(0.05, fmin(1. - rg[j] / rg0, 0.99));    // M:5176
+        }
+        if (snow0 && (a.out[0] || a.out[1] || a.out[3])) {
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                if (!(fms[j] > 0.)) continue;
+                lvl::SnowLevel sl;
+                sl.tc0 = s0[j];
+                sl.smob = s1[j];
+                sl.l2 = fm::log2_parts(sl.smob);
+                const double smoc = lvl::snow_moment(c.sa, c.sb, dc.cse1, sl);
+                const lvl::SnowSpectrum ss = lvl::snow_spectrum(sl, smoc);
+                s0[j] = ss.Mrat;
+                s1[j] = ss.k1m0;
+                s2[j] = sl.smob / smoc;                              // slam1 = s2*Lam0, slam2 = s2*Lam1
+            }
+            bright_band_species<0, NJ, T>(a, lane, fms, s0, s1, s2, es);
+        }
+        if (graupel0 && (a.out[0] || a.out[2] || a.out[4]))
+            bright_band_species<1, NJ, T>(a, lane, fmg, g0, g1, g1, eg);
+    }
+
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        if (k >= nz) continue;
+        const int64_t i = base + k;
+        const double zs = ze_s[j] * es[j], zg = ze_g[j] * eg[j];
+        if (a.out[0]) a.out[0][i] = T(lvl::dbz_of(ze_r[j] + zs + zg));               // M:5196
+        if (a.out[1]) a.out[1][i] = T(lvl::dbz_of(zs));
+        if (a.out[2]) a.out[2][i] = T(lvl::dbz_of(zg));
+        if (a.out[3]) a.out[3][i] = T(es[j]);
+        if (a.out[4]) a.out[4][i] = T(eg[j]);
+        if (a.out[5]) a.out[5][i] = T(fms[j]);
+        if (a.out[6]) a.out[6][i] = T(fmg[j]);
+    }
+    if (a.k0 && lane == 0) a.k0[col] = k0;
 }
 
 // the reflectivity alone; the kernel name rocprofv3 lists is kidmp::k_reflectivity<T, NJ>
@@ -1499,6 +1685,25 @@ hipError_t launch_doppler_spectrum(const ReflConsts &c, const DopplerConsts &dc,
 }
 template hipError_t launch_doppler_spectrum<double>(const ReflConsts &, const DopplerConsts &, int64_t, int, const DSpectrumArgs<double> &, hipStream_t);
 template hipError_t launch_doppler_spectrum<float>(const ReflConsts &, const DopplerConsts &, int64_t, int, const DSpectrumArgs<float> &, hipStream_t);
+
+template <class T>
+hipError_t launch_bright_band(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const BrightBandArgs<T> &a, hipStream_t s)
+{
+    if (ncol <= 0) return hipSuccess;
+    for (int x = 0; x < BRIGHTBAND_NSPEC; ++x)
+        if (a.nb[x] < 1 || a.nb[x] > BRIGHTBAND_MAX_BINS) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((ncol + REFL_WAVES - 1) / REFL_WAVES)), block(REFL_THREADS);
+    switch ((nz + 63) / 64) {
+    case 1: hipLaunchKernelGGL((k_bright_band<T, 1>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 2: hipLaunchKernelGGL((k_bright_band<T, 2>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 3: hipLaunchKernelGGL((k_bright_band<T, 3>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 4: hipLaunchKernelGGL((k_bright_band<T, 4>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+template hipError_t launch_bright_band<double>(const ReflConsts &, const DopplerConsts &, int64_t, int, const BrightBandArgs<double> &, hipStream_t);
+template hipError_t launch_bright_band<float>(const ReflConsts &, const DopplerConsts &, int64_t, int, const BrightBandArgs<float> &, hipStream_t);
 
 bool doppler_consts_supported(const Consts &hc)
 {

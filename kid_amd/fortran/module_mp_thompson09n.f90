@@ -64,6 +64,7 @@ module module_mp_thompson09n
   public :: doppler_moments_batch
   public :: size_spectra_batch
   public :: doppler_spectrum_batch
+  public :: bright_band_batch
   public :: lidar_profiles_batch
   public :: mp_thompson_kid_interface, mp_thompson_kid_staging
   logical, public :: is_aerosol_aware = .false.          ! M:28 (read at thompson_init)
@@ -125,6 +126,18 @@ module module_mp_thompson09n
      type(c_ptr) :: D(3), dD(3)
      integer(c_int32_t) :: nb(3)
   end type kidmp_dspectrum_grids
+
+  type, bind(C) :: kidmp_brightband_out                  ! kidmp_brightband_out / kidmp32_brightband_out: NULL = not wanted
+     type(c_ptr) :: dbz, dbz_s, dbz_g, enh_s, enh_g, fmelt_s, fmelt_g, k0
+  end type kidmp_brightband_out
+  type, bind(C) :: kidmp_brightband_grids                ! by species s, g: D and dD both NULL = the scheme's own 100 bins
+     type(c_ptr) :: D(2), dD(2)
+     integer(c_int32_t) :: nb(2)
+  end type kidmp_brightband_grids
+  type, bind(C) :: kidmp_brightband_cfg                  ! kidmp_brightband_cfg; kidmp_brightband_defaults fills it
+     real(c_double) :: eps_w_re, eps_w_im, eps_i, rho_w, rho_i, kw2
+     integer(c_int32_t) :: topology
+  end type kidmp_brightband_cfg
 
   type, bind(C) :: kidmp_kid_fields                      ! kidmp_kid_fields / kidmp32_kid_fields: KiD's fields, [ncol][nz] each
      type(c_ptr) :: theta, qv, qc, qr, nr, qi, ni, qs, qg
@@ -417,6 +430,31 @@ module module_mp_thompson09n
        type(kidmp_dspectrum_grids), intent(in) :: grids
        type(kidmp_dspectrum_out), intent(in) :: out
      end function kidmp32_doppler_spectrum_host
+     ! the reflectivity with its melting layer (include/kidmp_brightband.h): qs and qg may be NULL (zero), cfg NULL = defaults
+     subroutine kidmp_brightband_defaults(cfg) bind(C, name='kidmp_brightband_defaults')
+       import :: kidmp_brightband_cfg
+       type(kidmp_brightband_cfg), intent(out) :: cfg
+     end subroutine kidmp_brightband_defaults
+     integer(c_int) function kidmp_bright_band_host(ctx, ncol, nz, t, p, qv, qr, nr, qs, qg, cfg, grids, out) &
+          bind(C, name='kidmp_bright_band_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr, kidmp_brightband_grids, kidmp_brightband_out
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qr, nr, qs, qg, cfg
+       type(kidmp_brightband_grids), intent(in) :: grids
+       type(kidmp_brightband_out), intent(in) :: out
+     end function kidmp_bright_band_host
+     integer(c_int) function kidmp32_bright_band_host(ctx, ncol, nz, t, p, qv, qr, nr, qs, qg, cfg, grids, out) &
+          bind(C, name='kidmp32_bright_band_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr, kidmp_brightband_grids, kidmp_brightband_out
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qr, nr, qs, qg, cfg
+       type(kidmp_brightband_grids), intent(in) :: grids
+       type(kidmp_brightband_out), intent(in) :: out
+     end function kidmp32_bright_band_host
   end interface
 
 contains
@@ -1074,6 +1112,80 @@ contains
       stop 1
     end subroutine bad
   end subroutine doppler_spectrum_batch
+
+  ! calc_refl10cm with melting snow and graupel below the melting level, over ncol columns of KiD's (nz, ncol) storage in
+  ! one call (include/kidmp_brightband.h): dbz and the per-species dbz_s, dbz_g (dBZ), the linear enhancements enh_s, enh_g
+  ! (exactly 1.0 where the species is dry), the melt fractions fmelt_s, fmelt_g, all (nz, ncol) in the array kind the
+  ! arithmetic stores, and the melting level k0(ncol) as the library counts it: 0-based, k0 + 1 is the Fortran level, -1 =
+  ! none.  Every output is optional; at least one must be present.  qs and qg left out mean zero.  topology: 0 = water is
+  ! the matrix (the default), 1 = the ice-air core is; the rest of the configuration keeps the library's defaults.  A
+  ! species is put on the diameter grid D_x(nb), dD_x(nb) (m, always REAL 8; 1 <= nb <= 256) when both are given, else on
+  ! the scheme's own 100 bins.  The inputs are not changed.  Default REAL 8 goes to kidmp_bright_band_host, REAL 4 to kidmp32_...
+  subroutine bright_band_batch(ncol, nz, t, p, qv, qr, nr, dbz, dbz_s, dbz_g, enh_s, enh_g, fmelt_s, fmelt_g, k0, qs, qg, &
+       topology, D_s, dD_s, D_g, dD_g)
+    integer, intent(in) :: ncol, nz
+    real, dimension(nz,ncol), intent(in), target :: t, p, qv, qr, nr
+    real, dimension(nz,ncol), intent(out), optional, target :: dbz, dbz_s, dbz_g, enh_s, enh_g, fmelt_s, fmelt_g
+    integer(c_int32_t), dimension(ncol), intent(out), optional, target :: k0
+    real, dimension(nz,ncol), intent(in), optional, target :: qs, qg
+    integer, intent(in), optional :: topology
+    real(c_double), dimension(:), intent(in), optional, target, contiguous :: D_s, dD_s, D_g, dD_g
+    type(kidmp_brightband_out) :: out
+    type(kidmp_brightband_grids) :: grids
+    type(kidmp_brightband_cfg), target :: cfg
+    type(c_ptr) :: pqs, pqg, pcfg
+    integer(c_int) :: rc
+    integer :: x
+    if (.not. c_associated(ctx)) call thompson_init
+    if (c_associated(mctx)) then
+       write(*,'(a)') ' module_mp_thompson09n: the bright band is not available with kidmp_ndevices > 1'
+       stop 1
+    end if
+    pqs = c_null_ptr;  pqg = c_null_ptr;  pcfg = c_null_ptr
+    if (present(qs)) pqs = c_loc(qs)
+    if (present(qg)) pqg = c_loc(qg)
+    if (present(topology)) then
+       call kidmp_brightband_defaults(cfg)
+       cfg%topology = int(topology, c_int32_t)
+       pcfg = c_loc(cfg)
+    end if
+    do x = 1, 2
+       grids%D(x) = c_null_ptr;  grids%dD(x) = c_null_ptr;  grids%nb(x) = 0_c_int32_t
+    end do
+    call grid(1, D_s, dD_s)
+    call grid(2, D_g, dD_g)
+    out = kidmp_brightband_out(c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr)
+    if (present(dbz)) out%dbz = c_loc(dbz)
+    if (present(dbz_s)) out%dbz_s = c_loc(dbz_s)
+    if (present(dbz_g)) out%dbz_g = c_loc(dbz_g)
+    if (present(enh_s)) out%enh_s = c_loc(enh_s)
+    if (present(enh_g)) out%enh_g = c_loc(enh_g)
+    if (present(fmelt_s)) out%fmelt_s = c_loc(fmelt_s)
+    if (present(fmelt_g)) out%fmelt_g = c_loc(fmelt_g)
+    if (present(k0)) out%k0 = c_loc(k0)
+    if (kind(t) == c_double) then
+       rc = kidmp_bright_band_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), c_loc(qr), &
+            c_loc(nr), pqs, pqg, pcfg, grids, out)
+    else
+       rc = kidmp32_bright_band_host(ctx, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), c_loc(qr), &
+            c_loc(nr), pqs, pqg, pcfg, grids, out)
+    end if
+    call stop_on_error(rc, 'bright_band_batch')
+  contains
+    subroutine grid(x, D, dD)
+      integer, intent(in) :: x
+      real(c_double), dimension(:), intent(in), optional, target, contiguous :: D, dD
+      if (present(D) .neqv. present(dD)) call bad('a grid needs both D and dD')
+      if (.not. present(D)) return
+      if (size(D) /= size(dD)) call bad('D and dD differ in the number of bins')
+      grids%D(x) = c_loc(D);  grids%dD(x) = c_loc(dD);  grids%nb(x) = int(size(D), c_int32_t)
+    end subroutine grid
+    subroutine bad(msg)
+      character(*), intent(in) :: msg
+      write(*,'(2a)') ' module_mp_thompson09n: bright_band_batch: ', msg
+      stop 1
+    end subroutine bad
+  end subroutine bright_band_batch
 
   ! A droplet number per column (kidmp_set_column_nc): column i of every following batched call uses Nt_c =
   ! set_nc_col(i)*1.e6 (M:381) in place of the namelist's set_Nc -- an Nd ensemble, or an aerosol gradient along x, in

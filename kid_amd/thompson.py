@@ -643,6 +643,17 @@ class ThompsonMP:
         from .dspectrum import doppler_spectrum_host
         return doppler_spectrum_host(self, st, v0, dv, nv, w, grids, want, out)
 
+    def bright_band(self, st, cfg=None, grids=None, want=("dbz",), out=None, stream=None):
+        """calc_refl10cm with melting snow and graupel below the melting level (include/kidmp_brightband.h):
+        kid_amd.brightband.bright_band on this context."""
+        from .brightband import bright_band
+        return bright_band(self, st, cfg, grids, want, out, stream)
+
+    def bright_band_host(self, st, cfg=None, grids=None, want=("dbz",), out=None):
+        """bright_band on numpy arrays: kid_amd.brightband.bright_band_host on this context."""
+        from .brightband import bright_band_host
+        return bright_band_host(self, st, cfg, grids, want, out)
+
     REFL_NAMES = ("t", "p", "qv", "qr", "nr", "qs", "qg")      # the inputs of calc_refl10cm that are read (qc1d is not)
 
     def reflectivity(self, st, out=None, stream=None):
