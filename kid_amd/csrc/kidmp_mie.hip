@@ -1,0 +1,340 @@
+// kidmp_mie.hip -- the entries of include/kidmp_mie.h: the Lorenz-Mie sphere and the per-bin rows on the host
+// (kidmp_mie_sphere.h), the table object that carries them to the device, and the cloud radar of device arrays in one
+// launch of k_mie_radar (thompson_reflectivity.hip) or of host arrays in chunks through the context's staging memory.
+#include <cmath>
+#include <cstddef>
+
+#include "kidmp_ctx.h"
+#include "kidmp_mie_sphere.h"
+#include "../../include/kidmp_mie.h"
+
+using namespace kidmp;
+
+static_assert(sizeof(kidmp_mie_out) == (MIE_NOUT + 1) * sizeof(double *) && sizeof(kidmp32_mie_out) == (MIE_NOUT + 1) * sizeof(float *)
+                  && MIE_NSPEC == KIDMP_MIE_NSPECIES && MIE_MAX_BINS == KIDMP_MIE_MAX_BINS && MIE_NROWS == KIDMP_MIE_NROWS
+                  && MIE_ROWS == KIDMP_MIE_NROWS && nbins <= KIDMP_MIE_MAX_BINS && sizeof(kidmp_mie_cfg) == 8 * sizeof(double)
+                  && MIE_RAIN == KIDMP_MIE_R && MIE_SNOW == KIDMP_MIE_S && MIE_GRAUPEL == KIDMP_MIE_G,
+              "include/kidmp_mie.h");
+
+// one device buffer: per species D[nb], dD[nb], rows[MIE_NROWS][nb]
+struct kidmp_mie_table {
+    kidmp_ctx *ctx;
+    int device;
+    kidmp_mie_cfg cfg;
+    int32_t nb[MIE_NSPEC];
+    size_t off[MIE_NSPEC];                                // the species' first double in the buffer
+    double *d_buf;
+    double kc;
+};
+
+namespace {
+constexpr int NIN = 8, NREQ = 5;                          // t, p, qv, qr, nr | qc, qs, qg
+const char *const IN_NAMES[NIN] = {"t", "p", "qv", "qr", "nr", "qc", "qs", "qg"};
+const char *const OUT_NAMES[MIE_NOUT] = {"dbz", "dbz_up", "dbz_down", "dbz_r", "dbz_s", "dbz_g", "mie_r", "mie_s", "mie_g", "ext",
+                                         "pia_up", "pia_down", "vd"};
+
+const double *bins_D(const Bins &b, int x) { return x == 0 ? b.Dr : x == 1 ? b.Ds : b.Dg; }
+const double *bins_dD(const Bins &b, int x) { return x == 0 ? b.dtr : x == 1 ? b.dts : b.dtg; }
+
+// nullptr where the configuration is good, else what is wrong with it
+const char *bad_cfg(const kidmp_mie_cfg &g)
+{
+    const double members[] = {g.wavelength, g.eps_w_re, g.eps_w_im, g.eps_i_re, g.eps_i_im, g.rho_w, g.rho_i, g.kw2};
+    for (double m : members)
+        if (!std::isfinite(m)) return "a member of the configuration is not finite";
+    if (!(g.wavelength > 0.) || !(g.rho_w > 0.) || !(g.rho_i > 0.) || !(g.kw2 > 0.)) return "wavelength, rho_w, rho_i and kw2 must be above 0";
+    if (g.eps_w_im < 0. || g.eps_i_im < 0.) return "Im(eps) must not be below 0";
+    if ((g.eps_w_im == 0. && !(g.eps_w_re > 0.)) || (g.eps_i_im == 0. && !(g.eps_i_re > 0.))) return "a real permittivity must be above 0";
+    return nullptr;
+}
+MieCfg model_cfg(const kidmp_mie_cfg &g) { return MieCfg{g.wavelength, {g.eps_w_re, g.eps_w_im}, {g.eps_i_re, g.eps_i_im}, g.rho_w, g.rho_i, g.kw2}; }
+
+template <class T> struct MieCall {
+    const T *in[NIN];
+    const T *dz, *w, *k_gas;
+    int64_t dz_col_stride, k_gas_col_stride;
+    T *out[MIE_NOUT];
+    T *pia_total;
+};
+template <class T, class O>
+MieCall<T> mie_call(const T *t, const T *p, const T *qv, const T *qc, const T *qr, const T *nr, const T *qs, const T *qg, const T *dz,
+                    int64_t dz_col_stride, const T *w, const T *k_gas, int64_t k_gas_col_stride, const O *out)
+{
+    MieCall<T> c{{t, p, qv, qr, nr, qc, qs, qg}, dz, w, k_gas, dz_col_stride, k_gas_col_stride, {}, nullptr};
+    if (out) {
+        T *const o[MIE_NOUT] = {out->dbz, out->dbz_up, out->dbz_down, out->dbz_r, out->dbz_s, out->dbz_g, out->mie_r, out->mie_s, out->mie_g,
+                                out->ext, out->pia_up, out->pia_down, out->vd};
+        for (int v = 0; v < MIE_NOUT; ++v) c.out[v] = o[v];
+        c.pia_total = out->pia_total;
+    }
+    return c;
+}
+template <class T> bool needs_path(const MieCall<T> &a)
+{ return a.out[MIE_DBZ_UP] || a.out[MIE_DBZ_DOWN] || a.out[MIE_PIA_UP] || a.out[MIE_PIA_DOWN] || a.pia_total; }
+
+// what the device and the host entries check alike, before anything is touched
+template <class T>
+int check_mie(kidmp_ctx *ctx, const char *who, const kidmp_mie_table *tab, int64_t ncol, int32_t nz, const MieCall<T> &a)
+{
+    const std::string w(who);
+    if (int rc = require_ready(ctx)) return rc;
+    if (!tab || tab->ctx != ctx) return fail(ctx, KIDMP_EINVAL, w + ": the table is NULL or belongs to another context");
+    if (ncol < 0) return fail(ctx, KIDMP_EINVAL, w + ": ncol < 0");
+    if (nz < 2 || nz > KIDMP_MAX_NZ) return fail(ctx, KIDMP_EINVAL, w + ": nz outside [2, KIDMP_MAX_NZ]");
+    if (a.dz_col_stride != 0 && a.dz_col_stride < nz) return fail(ctx, KIDMP_EINVAL, w + ": dz_col_stride must be 0 or >= nz");
+    if (a.k_gas_col_stride != 0 && a.k_gas_col_stride < nz) return fail(ctx, KIDMP_EINVAL, w + ": k_gas_col_stride must be 0 or >= nz");
+    if (ncol == 0) return KIDMP_OK;                       // an empty batch has nothing to point at
+    bool any = a.pia_total != nullptr;
+    for (int v = 0; v < MIE_NOUT; ++v) any = any || a.out[v];
+    if (!any) return fail(ctx, KIDMP_EINVAL, w + ": nothing requested: out is NULL or every member is");
+    for (int v = 0; v < NREQ; ++v)
+        if (!a.in[v]) return fail(ctx, KIDMP_EINVAL, w + ": null array argument");
+    if (needs_path(a) && !a.dz) return fail(ctx, KIDMP_EINVAL, w + ": path integrals need dz");
+    if (!doppler_consts_supported(ctx->hc) || !spectra_consts_supported(ctx->hc))
+        return fail(ctx, KIDMP_ESTATE, w + ": exponents differ from the kernel's");
+    return KIDMP_OK;
+}
+
+// one launch over device pointers; an iiwarm context reads no snow and no graupel
+template <class T>
+hipError_t enqueue_mie(kidmp_ctx *ctx, const kidmp_mie_table *tab, int64_t ncol, int nz, const MieCall<T> &a, hipStream_t s)
+{
+    const bool warm = ctx->cfg.iiwarm != 0;
+    const T *const *q = a.in;
+    MieArgs<T> args{};
+    args.t = q[0]; args.p = q[1]; args.qv = q[2]; args.qr = q[3]; args.nr = q[4]; args.qc = q[5];
+    args.qs = warm ? nullptr : q[6];
+    args.qg = warm ? nullptr : q[7];
+    args.dz = a.dz; args.w = a.w; args.k_gas = a.k_gas;
+    args.dz_col_stride = a.dz_col_stride; args.k_gas_col_stride = a.k_gas_col_stride;
+    for (int v = 0; v < MIE_NOUT; ++v) args.out[v] = a.out[v];
+    args.pia_total = a.pia_total;
+    for (int x = 0; x < MIE_NSPEC; ++x) {
+        const double *b = tab->d_buf + tab->off[x];
+        args.nb[x] = tab->nb[x];
+        args.D[x] = b;
+        args.dD[x] = b + tab->nb[x];
+        args.rows[x] = b + 2 * size_t(tab->nb[x]);
+    }
+    args.kc = tab->kc;
+    args.rho_w = tab->cfg.rho_w;
+    return launch_mie_radar<T>(refl_consts(ctx->hc), doppler_consts(ctx->hc), ncol, nz, args, s);
+}
+
+template <class T>
+int mie_device(kidmp_ctx *ctx, const char *who, const kidmp_mie_table *tab, int64_t ncol, int32_t nz, const MieCall<T> &a, void *stream)
+{
+    if (int rc = check_mie<T>(ctx, who, tab, ncol, nz, a)) return rc;
+    if (ncol == 0) return KIDMP_OK;
+    GUARD(ctx);
+    for (int v = 0; v < NIN; ++v)
+        if (int rc = check_device_array(ctx, who, a.in[v], IN_NAMES[v])) return rc;
+    if (int rc = check_device_array(ctx, who, a.dz, "dz")) return rc;
+    if (int rc = check_device_array(ctx, who, a.w, "w")) return rc;
+    if (int rc = check_device_array(ctx, who, a.k_gas, "k_gas")) return rc;
+    for (int v = 0; v < MIE_NOUT; ++v)
+        if (int rc = check_device_array(ctx, who, a.out[v], OUT_NAMES[v])) return rc;
+    if (int rc = check_device_array(ctx, who, a.pia_total, "pia_total")) return rc;
+    HIPTRY(ctx, enqueue_mie<T>(ctx, tab, ncol, nz, a, (hipStream_t)stream));
+    return KIDMP_OK;
+}
+
+// host arrays: chunks of columns through the context's staging memory on its compute stream, one after the other
+// (lidar_host of kidmp_lidar.hip).  A column's result does not depend on its batch, so any chunking gives the same bits.
+// Only the inputs given go up and only what was asked for comes down.
+template <class T>
+int mie_host(kidmp_ctx *ctx, const char *who, const kidmp_mie_table *tab, int64_t ncol, int32_t nz, const MieCall<T> &h)
+{
+    if (int rc = check_mie<T>(ctx, who, tab, ncol, nz, h)) return rc;
+    if (ncol == 0) return KIDMP_OK;
+    GUARD(ctx);
+    const bool warm = ctx->cfg.iiwarm != 0, path = needs_path(h);
+    const int64_t CH = pick_host_chunk(ctx, ncol);
+    const size_t b_prof = (size_t(CH) * size_t(nz) * sizeof(T) + 255) / 256 * 256, b_col = (size_t(CH) * sizeof(T) + 255) / 256 * 256;
+    bool up[NIN];
+    int slots = (path ? 1 : 0) + (h.w ? 1 : 0) + (h.k_gas ? 1 : 0);
+    for (int v = 0; v < NIN; ++v) {
+        up[v] = h.in[v] && !(warm && v >= 6);
+        slots += up[v];
+    }
+    for (int v = 0; v < MIE_NOUT; ++v) slots += h.out[v] != nullptr;
+    if (int rc = ensure_stage(ctx, size_t(slots) * b_prof + (h.pia_total ? b_col : 0))) return rc;
+    char *next = reinterpret_cast<char *>(ctx->d_stage);
+    auto slot = [&](bool wanted) { T *p = wanted ? reinterpret_cast<T *>(next) : nullptr; if (wanted) next += b_prof; return p; };
+    MieCall<T> d{};
+    for (int v = 0; v < NIN; ++v) d.in[v] = slot(up[v]);
+    T *const d_dz = slot(path), *const d_w = slot(h.w != nullptr), *const d_kg = slot(h.k_gas != nullptr);
+    d.dz = d_dz; d.w = d_w; d.k_gas = d_kg;
+    d.dz_col_stride = h.dz_col_stride ? nz : 0;           // staged rows are packed
+    d.k_gas_col_stride = h.k_gas_col_stride ? nz : 0;
+    for (int v = 0; v < MIE_NOUT; ++v) d.out[v] = slot(h.out[v] != nullptr);
+    d.pia_total = h.pia_total ? reinterpret_cast<T *>(next) : nullptr;
+    hipError_t e = hipSuccess;
+    const size_t row = size_t(nz) * sizeof(T);
+    if (path && !h.dz_col_stride) e = hipMemcpyAsync(d_dz, h.dz, row, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && h.k_gas && !h.k_gas_col_stride) e = hipMemcpyAsync(d_kg, h.k_gas, row, hipMemcpyHostToDevice, ctx->stream);
+    for (int64_t c0 = 0; c0 < ncol && e == hipSuccess; c0 += CH) {
+        const int64_t n = c0 + CH <= ncol ? CH : ncol - c0;
+        const size_t off = size_t(c0) * size_t(nz), cnt = size_t(n) * size_t(nz);
+        for (int v = 0; v < NIN && e == hipSuccess; ++v)
+            if (up[v]) e = hipMemcpyAsync(const_cast<T *>(d.in[v]), h.in[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess && h.w) e = hipMemcpyAsync(d_w, h.w + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess && path && h.dz_col_stride)
+            e = hipMemcpy2DAsync(d_dz, row, h.dz + size_t(c0) * size_t(h.dz_col_stride), size_t(h.dz_col_stride) * sizeof(T), row, size_t(n),
+                                 hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess && h.k_gas && h.k_gas_col_stride)
+            e = hipMemcpy2DAsync(d_kg, row, h.k_gas + size_t(c0) * size_t(h.k_gas_col_stride), size_t(h.k_gas_col_stride) * sizeof(T), row,
+                                 size_t(n), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = enqueue_mie<T>(ctx, tab, n, nz, d, ctx->stream);
+        for (int v = 0; v < MIE_NOUT && e == hipSuccess; ++v)
+            if (h.out[v]) e = hipMemcpyAsync(h.out[v] + off, d.out[v], cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && h.pia_total)
+            e = hipMemcpyAsync(h.pia_total + c0, d.pia_total, size_t(n) * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(ctx->stream);        // no copy may still be in flight towards the caller's arrays
+    HIPTRY(ctx, e);
+    HIPTRY(ctx, es);
+    return KIDMP_OK;
+}
+}  // namespace
+
+extern "C" {
+void kidmp_mie_defaults(kidmp_mie_cfg *cfg)
+{
+    if (!cfg) return;
+    const double k = std::sqrt(0.176);
+    *cfg = kidmp_mie_cfg{0.10, 79.5, 24.9, (1. + 2. * k) / (1. - k), 0., 1000., 900., 0.93};
+}
+
+int kidmp_mie_sphere(double x, double m_re, double m_im, double *qext, double *qback)
+{
+    if (!qext || !qback) return fail(nullptr, KIDMP_EINVAL, "kidmp_mie_sphere: null argument");
+    double qe, qb;
+    if (!mie_sphere(x, m_re, m_im, qe, qb))
+        return fail(nullptr, KIDMP_EINVAL, "kidmp_mie_sphere: x and Re(m) must be finite and above 0, Im(m) finite and not below 0, |m| x below 1e7");
+    *qext = qe;
+    *qback = qb;
+    return KIDMP_OK;
+}
+
+int kidmp_mie_bins(const kidmp_mie_cfg *cfg, int32_t species, int32_t nb, const double *D, double *rows)
+{
+    const std::string w("kidmp_mie_bins");
+    if (!cfg || !D || !rows) return fail(nullptr, KIDMP_EINVAL, w + ": null argument");
+    if (const char *bad = bad_cfg(*cfg)) return fail(nullptr, KIDMP_EINVAL, w + ": " + bad);
+    if (species < 0 || species >= MIE_NSPEC) return fail(nullptr, KIDMP_EINVAL, w + ": unknown species");
+    if (nb < 1) return fail(nullptr, KIDMP_EINVAL, w + ": nb < 1");
+    std::vector<double> r(size_t(MIE_ROWS) * size_t(nb));
+    if (!mie_bins(model_cfg(*cfg), species, nb, D, r.data()))
+        return fail(nullptr, KIDMP_EINVAL, w + ": a diameter is not finite or not above 0, or its sphere has more than 1e7 terms");
+    std::memcpy(rows, r.data(), r.size() * sizeof(double));
+    return KIDMP_OK;
+}
+
+int kidmp_mie_table_create(kidmp_ctx *ctx, const kidmp_mie_cfg *cfg, const kidmp_mie_grids *grids, kidmp_mie_table **table)
+{
+    const std::string w("kidmp_mie_table_create");
+    if (table) *table = nullptr;
+    if (int rc = require_ready(ctx)) return rc;
+    if (!table) return fail(ctx, KIDMP_EINVAL, w + ": null argument");
+    kidmp_mie_cfg g;
+    if (cfg) g = *cfg;
+    else kidmp_mie_defaults(&g);
+    if (const char *bad = bad_cfg(g)) return fail(ctx, KIDMP_EINVAL, w + ": " + bad);
+    int32_t nb[MIE_NSPEC];
+    size_t off[MIE_NSPEC], total = 0;
+    const double *D[MIE_NSPEC], *dD[MIE_NSPEC];
+    for (int x = 0; x < MIE_NSPEC; ++x) {
+        nb[x] = nbins;
+        D[x] = bins_D(ctx->hb, x);
+        dD[x] = bins_dD(ctx->hb, x);
+        if (grids && (grids->D[x] || grids->dD[x])) {
+            if (!grids->D[x] || !grids->dD[x]) return fail(ctx, KIDMP_EINVAL, w + ": a grid needs both D and dD");
+            if (grids->nb[x] < 1 || grids->nb[x] > KIDMP_MIE_MAX_BINS) return fail(ctx, KIDMP_EINVAL, w + ": nb outside [1, KIDMP_MIE_MAX_BINS]");
+            nb[x] = grids->nb[x]; D[x] = grids->D[x]; dD[x] = grids->dD[x];
+            for (int b = 0; b < nb[x]; ++b)
+                if (!std::isfinite(dD[x][b])) return fail(ctx, KIDMP_EINVAL, w + ": a dD is not finite");
+        }
+        off[x] = total;
+        total += size_t(2 + MIE_ROWS) * size_t(nb[x]);
+    }
+    std::vector<double> buf(total);
+    const MieCfg mc = model_cfg(g);
+    for (int x = 0; x < MIE_NSPEC; ++x) {
+        double *b = buf.data() + off[x];
+        std::memcpy(b, D[x], size_t(nb[x]) * sizeof(double));
+        std::memcpy(b + nb[x], dD[x], size_t(nb[x]) * sizeof(double));
+        if (!mie_bins(mc, x, nb[x], D[x], b + 2 * size_t(nb[x])))
+            return fail(ctx, KIDMP_EINVAL, w + ": a diameter is not finite or not above 0, or its sphere has more than 1e7 terms");
+    }
+    GUARD(ctx);
+    double *d_buf = nullptr;
+    HIPTRY(ctx, hipMalloc(reinterpret_cast<void **>(&d_buf), total * sizeof(double)));
+    const hipError_t e = hipMemcpy(d_buf, buf.data(), total * sizeof(double), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d_buf); return hipfail(ctx, e, "hipMemcpy of the Mie table"); }
+    kidmp_mie_table *t = new kidmp_mie_table{ctx, ctx->cfg.device, g, {nb[0], nb[1], nb[2]}, {off[0], off[1], off[2]}, d_buf, mie_cloud_absorption(mc)};
+    *table = t;
+    return KIDMP_OK;
+}
+
+void kidmp_mie_table_destroy(kidmp_mie_table *table)
+{
+    if (!table) return;
+    {
+        DeviceGuard guard(table->device);
+        if (table->d_buf) (void)hipFree(table->d_buf);
+    }
+    delete table;
+}
+
+int kidmp_mie_table_get(const kidmp_mie_table *table, int32_t species, int32_t *nb, double *D, double *dD, double *rows, kidmp_mie_cfg *cfg)
+{
+    const std::string w("kidmp_mie_table_get");
+    if (!table) return fail(nullptr, KIDMP_EINVAL, w + ": null table");
+    kidmp_ctx *ctx = table->ctx;
+    if (species < 0 || species >= MIE_NSPEC) return fail(ctx, KIDMP_EINVAL, w + ": unknown species");
+    const size_t n = size_t(table->nb[species]);
+    if (nb) *nb = table->nb[species];
+    if (cfg) *cfg = table->cfg;
+    DeviceGuard guard(table->device);
+    if (guard.err != hipSuccess) return hipfail(ctx, guard.err, "hipSetDevice");
+    const double *b = table->d_buf + table->off[species];
+    if (D) HIPTRY(ctx, hipMemcpy(D, b, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (dD) HIPTRY(ctx, hipMemcpy(dD, b + n, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (rows) HIPTRY(ctx, hipMemcpy(rows, b + 2 * n, size_t(MIE_ROWS) * n * sizeof(double), hipMemcpyDeviceToHost));
+    return KIDMP_OK;
+}
+
+int kidmp_mie_radar_device(kidmp_ctx *ctx, const kidmp_mie_table *table, int64_t ncol, int32_t nz, const double *t, const double *p,
+                           const double *qv, const double *qc, const double *qr, const double *nr, const double *qs, const double *qg,
+                           const double *dz, int64_t dz_col_stride, const double *w, const double *k_gas, int64_t k_gas_col_stride,
+                           const kidmp_mie_out *out, void *stream)
+{
+    return mie_device<double>(ctx, "kidmp_mie_radar_device", table, ncol, nz,
+                              mie_call<double>(t, p, qv, qc, qr, nr, qs, qg, dz, dz_col_stride, w, k_gas, k_gas_col_stride, out), stream);
+}
+int kidmp32_mie_radar_device(kidmp_ctx *ctx, const kidmp_mie_table *table, int64_t ncol, int32_t nz, const float *t, const float *p,
+                             const float *qv, const float *qc, const float *qr, const float *nr, const float *qs, const float *qg,
+                             const float *dz, int64_t dz_col_stride, const float *w, const float *k_gas, int64_t k_gas_col_stride,
+                             const kidmp32_mie_out *out, void *stream)
+{
+    return mie_device<float>(ctx, "kidmp32_mie_radar_device", table, ncol, nz,
+                             mie_call<float>(t, p, qv, qc, qr, nr, qs, qg, dz, dz_col_stride, w, k_gas, k_gas_col_stride, out), stream);
+}
+int kidmp_mie_radar_host(kidmp_ctx *ctx, const kidmp_mie_table *table, int64_t ncol, int32_t nz, const double *t, const double *p,
+                         const double *qv, const double *qc, const double *qr, const double *nr, const double *qs, const double *qg,
+                         const double *dz, int64_t dz_col_stride, const double *w, const double *k_gas, int64_t k_gas_col_stride,
+                         const kidmp_mie_out *out)
+{
+    return mie_host<double>(ctx, "kidmp_mie_radar_host", table, ncol, nz,
+                            mie_call<double>(t, p, qv, qc, qr, nr, qs, qg, dz, dz_col_stride, w, k_gas, k_gas_col_stride, out));
+}
+int kidmp32_mie_radar_host(kidmp_ctx *ctx, const kidmp_mie_table *table, int64_t ncol, int32_t nz, const float *t, const float *p,
+                           const float *qv, const float *qc, const float *qr, const float *nr, const float *qs, const float *qg,
+                           const float *dz, int64_t dz_col_stride, const float *w, const float *k_gas, int64_t k_gas_col_stride,
+                           const kidmp32_mie_out *out)
+{
+    return mie_host<float>(ctx, "kidmp32_mie_radar_host", table, ncol, nz,
+                           mie_call<float>(t, p, qv, qc, qr, nr, qs, qg, dz, dz_col_stride, w, k_gas, k_gas_col_stride, out));
+}
+}  // extern "C"

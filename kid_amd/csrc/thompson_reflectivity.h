@@ -161,4 +161,25 @@ template <class T>
 hipError_t launch_bright_band(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const BrightBandArgs<T> &a,
                               hipStream_t stream);
 
+// The cloud radar (include/kidmp_mie.h): Mie reflectivity, extinction, path-integrated attenuation and mean Doppler
+// velocity from k_doppler_moments' load and a table of five rows per diameter bin.  Null means: qc, qs, qg, w, k_gas --
+// zero; an output -- not wanted; dz -- not read when no path integral is wanted.  out in the order of kidmp_mie_out,
+// pia_total [ncol].  D, dD: device arrays of nb[x] doubles by species rain, snow, graupel; rows[x]: [MIE_NROWS][nb[x]]
+// (s_mie, s_ray, s_ext, mass, v0).  kc: (6 pi/lambda) Im(K(eps_w)); rho_w: the configuration's.  Cloud water enters through
+// its mass alone, where qc > R1.  One launch; lanes over levels, a loop over the bins.
+constexpr int MIE_NOUT = 13, MIE_NSPEC = 3, MIE_MAX_BINS = 256, MIE_NROWS = 5;
+constexpr int MIE_DBZ = 0, MIE_DBZ_UP = 1, MIE_DBZ_DOWN = 2, MIE_DBZ_X = 3, MIE_MIE_X = 6, MIE_EXT = 9, MIE_PIA_UP = 10, MIE_PIA_DOWN = 11, MIE_VD = 12;
+template <class T> struct MieArgs {
+    const T *t, *p, *qv, *qc, *qr, *nr, *qs, *qg, *dz, *w, *k_gas;
+    int64_t dz_col_stride, k_gas_col_stride;
+    T *out[MIE_NOUT];
+    T *pia_total;
+    const double *D[MIE_NSPEC], *dD[MIE_NSPEC], *rows[MIE_NSPEC];
+    int32_t nb[MIE_NSPEC];
+    double kc, rho_w;
+};
+template <class T>
+hipError_t launch_mie_radar(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const MieArgs<T> &a,
+                            hipStream_t stream);
+
 }  // namespace kidmp

@@ -971,7 +971,7 @@ k_lidar_profiles(const Consts *__restrict__ hc, LidarArgs<T> a, int64_t ncol, in
 // rs = qs*rho (R1 without snow, M:5019) are what the melting layer reads beside them.
 struct RadarLevel {
     bool L_qr, L_qs, L_qg;
-    double temp, rs, rhof, rg, n0_exp, ze_rain, ze_snow, lamr, N0_r;
+    double temp, rho, rs, rhof, rg, n0_exp, ze_rain, ze_snow, lamr, N0_r;
     lvl::SnowLevel sl;
 };
 template <class A>
@@ -987,6 +987,7 @@ __device__ __forceinline__ RadarLevel radar_level(const ReflConsts &c, const A &
     r.L_qr = qr > R1;
     r.L_qs = qs > R2;
     r.L_qg = qg > R2;
+    r.rho = rho;
     r.rhof = fm::sqrt_pos(rho_not / rho);
     r.ze_rain = r.ze_snow = 1.E-22;
     r.lamr = r.N0_r = 0.;
@@ -1429,6 +1430,208 @@ k_bright_band(ReflConsts c, DopplerConsts dc, BrightBandArgs<T> a, int64_t ncol,
     if (a.k0 && lane == 0) a.k0[col] = k0;
 }
 
+// ---- the cloud radar (include/kidmp_mie.h) ----
+constexpr double MIE_PIA = 20. / 2.302585092994045684;              // two-way dB per unit of one-way optical depth: 2*(10/ln 10)
+
+// The five sums of one species at every level of the lane: A = sum n s_mie, B = sum n s_ray, E = sum n s_ext,
+// M = sum n mass, V = sum (n s_mie) v0, over the bins ascending into accumulators that start at +0.0.  The lanes hold
+// levels; D, dD and the five rows are wave-uniform loads.  density(j, D, dD, Dmu) gives n of the lane's level of group j;
+// a level group none of whose levels holds the species is passed over.  SP == 1: Dmu = D**mu_s is formed once per bin,
+// 64 bins at a time and one per lane, and handed round with v_readlane (as store_bins does).
+template <int SP, int NJ, class T, class F>
+__device__ __forceinline__ void mie_sums(const MieArgs<T> &a, int lane, const bool (&has)[NJ], F &&density, double (&A)[NJ],
+                                         double (&B)[NJ], double (&E)[NJ], double (&M)[NJ], double (&V)[NJ])
+{
+    const double *__restrict__ D = a.D[SP], *__restrict__ dD = a.dD[SP], *__restrict__ rows = a.rows[SP];
+    const int nb = a.nb[SP];
+    bool live[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) { live[j] = __ballot(has[j]) != 0; A[j] = B[j] = E[j] = M[j] = V[j] = 0.; }
+    for (int bb = 0; bb < nb; bb += 64) {
+        double mine = 0.;
+        if (SP == 1 && bb + lane < nb) mine = fm::pow(D[bb + lane], mu_s);
+        const int be = bb + 64 < nb ? bb + 64 : nb;
+        for (int b = bb; b < be; ++b) {
+            const double Db = D[b], dDb = dD[b];
+            const double Dmu = SP == 1 ? readlane(mine, b - bb) : 0.;
+            const double s_mie = rows[b], s_ray = rows[nb + b], s_ext = rows[2 * nb + b], mass = rows[3 * nb + b], v0 = rows[4 * nb + b];
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                if (!live[j]) continue;                              // wave-uniform
+                const double n = has[j] ? density(j, Db, dDb, Dmu) : 0.;
+                const double ns = n * s_mie;
+                A[j] += ns;
+                B[j] += n * s_ray;
+                E[j] += n * s_ext;
+                M[j] += n * mass;
+                V[j] += ns * v0;
+            }
+        }
+    }
+}
+
+// One wavefront per column: the cloud radar of include/kidmp_mie.h.  The load and the scan are k_doppler_moments'
+// (radar_level, graupel_running_min), lanes over levels.  Then species by species -- rain, snow, graupel -- the five sums
+// over the table's bins (mie_sums), which leave behind only mie_x, the species' extinction and its share of the Doppler
+// sums.  Cloud water (present where qc > R1) and the caller's gas extinction close ext; the path integrals are
+// column_depths, the scans of k_lidar_profiles, and a request without them ends before.  No atomics, no scratch, nothing
+// but the fastmath tables in LDS.
+template <class T, int NJ>
+__global__ void __launch_bounds__(REFL_THREADS)
+k_mie_radar(ReflConsts c, DopplerConsts dc, MieArgs<T> a, int64_t ncol, int nz)
+{
+#if KFM_TABLES
+    fm::tab::load_tables(int(threadIdx.x), REFL_THREADS);
+    __syncthreads();
+#endif
+    const int lane = int(threadIdx.x) & 63;
+    const int64_t col = int64_t(blockIdx.x) * REFL_WAVES + (int(threadIdx.x) >> 6);
+    if (col >= ncol) return;                                         // whole wavefronts only: the scans need every lane
+    const int64_t base = col * int64_t(nz);
+    T *const *out = a.out;
+    const bool want_up = out[MIE_DBZ_UP] || out[MIE_PIA_UP], want_dn = out[MIE_DBZ_DOWN] || out[MIE_PIA_DOWN];
+    const bool path = want_up || want_dn || a.pia_total;
+    const bool want_ext = path || out[MIE_EXT];
+    const bool all = want_ext || out[MIE_DBZ] || out[MIE_VD];        // what takes every species
+    const auto wants = [&](int x) __attribute__((always_inline)) { return all || out[MIE_DBZ_X + x] || out[MIE_MIE_X + x]; };
+
+    double ze_r[NJ], ze_s[NJ], ze_g[NJ], rho[NJ], rhof[NJ], rs[NJ], rg[NJ], n0[NJ], N0_r[NJ], lamr[NJ];
+    lvl::SnowSpectrum ss[NJ];
+    bool lqr[NJ], lqs[NJ], lqg[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        ze_r[j] = ze_s[j] = ze_g[j] = 1.E-22;
+        rho[j] = 1.; rhof[j] = 0.;
+        rs[j] = rg[j] = R1;
+        N0_r[j] = lamr[j] = 0.;
+        ss[j] = lvl::SnowSpectrum{0., 0., 0., 0.};
+        lqr[j] = lqs[j] = lqg[j] = false;
+        n0[j] = double(__builtin_inf());                             // levels past kte do not enter the minimum
+        if (k >= nz) continue;
+        const RadarLevel r = radar_level(c, a, base + k);            // ---- load, M:4991-5028 ----
+        ze_r[j] = r.ze_rain;
+        ze_s[j] = r.ze_snow;
+        rho[j] = r.rho;
+        rhof[j] = r.rhof;
+        rs[j] = r.rs;
+        rg[j] = r.rg;
+        N0_r[j] = r.N0_r;
+        lamr[j] = r.lamr;
+        lqr[j] = r.L_qr; lqs[j] = r.L_qs; lqg[j] = r.L_qg;
+        if (r.L_qs) ss[j] = lvl::snow_spectrum(r.sl, lvl::snow_moment(c.sa, c.sb, dc.cse1, r.sl));
+        n0[j] = r.n0_exp;
+    }
+    graupel_running_min<NJ>(n0, lane);
+    double N0_g[NJ], lamg[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        N0_g[j] = lamg[j] = 0.;
+        if (!lqg[j]) continue;
+        double ilamg;
+        ze_g[j] = lvl::graupel_ze(c, n0[j], rg[j], ilamg, lamg[j], N0_g[j]);
+    }
+
+    // what the species leave behind: ze_x' in ze_x, ext = (ext_r + ext_s) + ext_g, and the Doppler sums over the species
+    // that are present with A above 0
+    double ext[NJ], zw[NJ], zv[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) ext[j] = zw[j] = zv[j] = 0.;
+    double A[NJ], B[NJ], E[NJ], M[NJ], V[NJ], mie[NJ], dbz_out[NJ];
+    const auto finish = [&](int x, const bool (&has)[NJ], double (&ze)[NJ], const double (&rq)[NJ]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            mie[j] = has[j] && B[j] > 0. ? A[j] / B[j] : 1.;
+            ze[j] = ze[j] * mie[j];
+            ext[j] = ext[j] + (has[j] && M[j] > 0. ? rq[j] * E[j] / M[j] : 0.);
+            if (has[j] && A[j] > 0.) { zw[j] = zw[j] + ze[j]; zv[j] = zv[j] + ze[j] * (V[j] / A[j]); }
+            dbz_out[j] = lvl::dbz_of(ze[j]);
+        }
+        store_profile<T, NJ>(out[MIE_MIE_X + x], base, nz, lane, mie);
+        store_profile<T, NJ>(out[MIE_DBZ_X + x], base, nz, lane, dbz_out);
+    };
+    if (wants(0)) {
+        double rr[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) rr[j] = lqr[j] ? double(a.qr[base + 64 * j + lane]) * rho[j] : 0.;
+        mie_sums<0, NJ, T>(a, lane, lqr, [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(N0_r[j], lamr[j], D, dD); },
+                           A, B, E, M, V);
+        finish(0, lqr, ze_r, rr);
+    }
+    if (wants(1)) {
+        mie_sums<1, NJ, T>(a, lane, lqs, [&](int j, double D, double dD, double Dmu) __attribute__((always_inline)) { return lvl::snow_bin(ss[j], D, Dmu, dD); },
+                           A, B, E, M, V);
+        finish(1, lqs, ze_s, rs);
+    }
+    if (wants(2)) {
+        mie_sums<2, NJ, T>(a, lane, lqg, [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(N0_g[j], lamg[j], D, dD); },
+                           A, B, E, M, V);
+        finish(2, lqg, ze_g, rg);
+    }
+    if (!all) return;                                                // wave-uniform: one species' own profiles alone
+
+    double dbz[NJ], vd[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        dbz[j] = lvl::dbz_of(ze_r[j] + ze_s[j] + ze_g[j]);           // M:5196
+        vd[j] = 0.;                                                  // no echo: +0.0, w is not applied
+        if (k < nz && zw[j] > 0.) vd[j] = rhof[j] * (zv[j] / zw[j]) - (a.w ? double(a.w[base + k]) : 0.);
+    }
+    store_profile<T, NJ>(out[MIE_DBZ], base, nz, lane, dbz);
+    store_profile<T, NJ>(out[MIE_VD], base, nz, lane, vd);
+    if (!want_ext) return;
+
+    // ---- ext = ((ext_r + ext_s) + ext_g) + ext_c + k_gas; levels past nz keep +0.0 ----
+    // cloud water enters through its mass alone, so of load_cloud only the presence test is taken (qc > R1, M:1395): its
+    // droplet number, nu_c and lamc would be formed and thrown away
+    if (a.qc) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            if (64 * j + lane >= nz) continue;
+            const double qc = double(a.qc[base + 64 * j + lane]);
+            if (qc > R1) ext[j] = ext[j] + a.kc * ((rho[j] * qc) / a.rho_w);
+        }
+    }
+    if (a.k_gas) {
+        const T *__restrict__ kg = a.k_gas + col * a.k_gas_col_stride;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+            if (64 * j + lane < nz) ext[j] = ext[j] + double(kg[64 * j + lane]);
+    }
+    store_profile<T, NJ>(out[MIE_EXT], base, nz, lane, ext);
+    if (!path) return;
+
+    // ---- the path: dtau = ext*dz, tau_up = (the levels below) + dtau/2, tau_down from the top ----
+    const T *__restrict__ dzc = a.dz + col * a.dz_col_stride;
+    double dt[NJ], tu[NJ], td[NJ], total = 0.;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        dt[j] = k < nz ? ext[j] * double(dzc[k]) : 0.;
+        total += dt[j];
+        tu[j] = td[j] = 0.;
+    }
+    if (a.pia_total) {
+        total = wave_sum(total);
+        if (lane == 0) a.pia_total[col] = T(MIE_PIA * total);
+    }
+    if (!(want_up || want_dn)) return;
+    column_depths<NJ>(dt, lane, want_up, want_dn, tu, td);
+    if (want_up) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { tu[j] = MIE_PIA * (tu[j] + 0.5 * dt[j]); dbz_out[j] = dbz[j] - tu[j]; }
+        store_profile<T, NJ>(out[MIE_PIA_UP], base, nz, lane, tu);
+        store_profile<T, NJ>(out[MIE_DBZ_UP], base, nz, lane, dbz_out);
+    }
+    if (want_dn) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { td[j] = MIE_PIA * (td[j] + 0.5 * dt[j]); dbz_out[j] = dbz[j] - td[j]; }
+        store_profile<T, NJ>(out[MIE_PIA_DOWN], base, nz, lane, td);
+        store_profile<T, NJ>(out[MIE_DBZ_DOWN], base, nz, lane, dbz_out);
+    }
+}
+
 // the reflectivity alone; the kernel name rocprofv3 lists is kidmp::k_reflectivity<T, NJ>
 template <class T, int NJ>
 __global__ void __launch_bounds__(REFL_THREADS)
@@ -1704,6 +1907,25 @@ hipError_t launch_bright_band(const ReflConsts &c, const DopplerConsts &dc, int6
 }
 template hipError_t launch_bright_band<double>(const ReflConsts &, const DopplerConsts &, int64_t, int, const BrightBandArgs<double> &, hipStream_t);
 template hipError_t launch_bright_band<float>(const ReflConsts &, const DopplerConsts &, int64_t, int, const BrightBandArgs<float> &, hipStream_t);
+
+template <class T>
+hipError_t launch_mie_radar(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const MieArgs<T> &a, hipStream_t s)
+{
+    if (ncol <= 0) return hipSuccess;
+    for (int x = 0; x < MIE_NSPEC; ++x)
+        if (a.nb[x] < 1 || a.nb[x] > MIE_MAX_BINS) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((ncol + REFL_WAVES - 1) / REFL_WAVES)), block(REFL_THREADS);
+    switch ((nz + 63) / 64) {
+    case 1: hipLaunchKernelGGL((k_mie_radar<T, 1>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 2: hipLaunchKernelGGL((k_mie_radar<T, 2>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 3: hipLaunchKernelGGL((k_mie_radar<T, 3>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 4: hipLaunchKernelGGL((k_mie_radar<T, 4>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+template hipError_t launch_mie_radar<double>(const ReflConsts &, const DopplerConsts &, int64_t, int, const MieArgs<double> &, hipStream_t);
+template hipError_t launch_mie_radar<float>(const ReflConsts &, const DopplerConsts &, int64_t, int, const MieArgs<float> &, hipStream_t);
 
 bool doppler_consts_supported(const Consts &hc)
 {

@@ -65,6 +65,7 @@ module module_mp_thompson09n
   public :: size_spectra_batch
   public :: doppler_spectrum_batch
   public :: bright_band_batch
+  public :: mie_radar_batch
   public :: lidar_profiles_batch
   public :: mp_thompson_kid_interface, mp_thompson_kid_staging
   logical, public :: is_aerosol_aware = .false.          ! M:28 (read at thompson_init)
@@ -138,6 +139,13 @@ module module_mp_thompson09n
      real(c_double) :: eps_w_re, eps_w_im, eps_i, rho_w, rho_i, kw2
      integer(c_int32_t) :: topology
   end type kidmp_brightband_cfg
+
+  type, bind(C) :: kidmp_mie_out                         ! kidmp_mie_out / kidmp32_mie_out: NULL = not wanted
+     type(c_ptr) :: dbz, dbz_up, dbz_down, dbz_r, dbz_s, dbz_g, mie_r, mie_s, mie_g, ext, pia_up, pia_down, vd, pia_total
+  end type kidmp_mie_out
+  type, bind(C) :: kidmp_mie_cfg                         ! kidmp_mie_cfg; kidmp_mie_defaults fills it
+     real(c_double) :: wavelength, eps_w_re, eps_w_im, eps_i_re, eps_i_im, rho_w, rho_i, kw2
+  end type kidmp_mie_cfg
 
   type, bind(C) :: kidmp_kid_fields                      ! kidmp_kid_fields / kidmp32_kid_fields: KiD's fields, [ncol][nz] each
      type(c_ptr) :: theta, qv, qc, qr, nr, qi, ni, qs, qg
@@ -455,6 +463,46 @@ module module_mp_thompson09n
        type(kidmp_brightband_grids), intent(in) :: grids
        type(kidmp_brightband_out), intent(in) :: out
      end function kidmp32_bright_band_host
+     ! the cloud radar (include/kidmp_mie.h): a table of Mie rows per wavelength, then the operator; qc, qs, qg, dz, w and
+     ! k_gas may be NULL
+     subroutine kidmp_mie_defaults(cfg) bind(C, name='kidmp_mie_defaults')
+       import :: kidmp_mie_cfg
+       type(kidmp_mie_cfg), intent(out) :: cfg
+     end subroutine kidmp_mie_defaults
+     integer(c_int) function kidmp_mie_table_create(ctx, cfg, grids, table) bind(C, name='kidmp_mie_table_create')
+       import :: c_int, c_ptr, kidmp_mie_cfg
+       type(c_ptr), value :: ctx, grids
+       type(kidmp_mie_cfg), intent(in) :: cfg
+       type(c_ptr), intent(out) :: table
+     end function kidmp_mie_table_create
+     subroutine kidmp_mie_table_destroy(table) bind(C, name='kidmp_mie_table_destroy')
+       import :: c_ptr
+       type(c_ptr), value :: table
+     end subroutine kidmp_mie_table_destroy
+     integer(c_int) function kidmp_mie_radar_host(ctx, table, ncol, nz, t, p, qv, qc, qr, nr, qs, qg, dz, dz_col_stride, w, &
+          k_gas, k_gas_col_stride, out) bind(C, name='kidmp_mie_radar_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr, kidmp_mie_out
+       type(c_ptr), value :: ctx, table
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qc, qr, nr, qs, qg, dz
+       integer(c_int64_t), value :: dz_col_stride
+       type(c_ptr), value :: w, k_gas
+       integer(c_int64_t), value :: k_gas_col_stride
+       type(kidmp_mie_out), intent(in) :: out
+     end function kidmp_mie_radar_host
+     integer(c_int) function kidmp32_mie_radar_host(ctx, table, ncol, nz, t, p, qv, qc, qr, nr, qs, qg, dz, dz_col_stride, w, &
+          k_gas, k_gas_col_stride, out) bind(C, name='kidmp32_mie_radar_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr, kidmp_mie_out
+       type(c_ptr), value :: ctx, table
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qc, qr, nr, qs, qg, dz
+       integer(c_int64_t), value :: dz_col_stride
+       type(c_ptr), value :: w, k_gas
+       integer(c_int64_t), value :: k_gas_col_stride
+       type(kidmp_mie_out), intent(in) :: out
+     end function kidmp32_mie_radar_host
   end interface
 
 contains
@@ -1186,6 +1234,79 @@ contains
       stop 1
     end subroutine bad
   end subroutine bright_band_batch
+
+  ! The cloud radar over ncol columns of KiD's (nz, ncol) storage in one call (include/kidmp_mie.h): Mie reflectivity, its
+  ! per-species parts and their ratios mie_x to the Rayleigh reflectivity, the one-way extinction ext (1/m), the two-way
+  ! path-integrated attenuation seen from the ground (pia_up) and from space (pia_down) with the attenuated dbz_up and
+  ! dbz_down, the mean Doppler velocity vd, all (nz, ncol) in the array kind the arithmetic stores, and pia_total(ncol).
+  ! Every output is optional; at least one must be present.  The configuration: wavelength (m) and the complex relative
+  ! permittivities of water and ice at that wavelength are the caller's; rho_w, rho_i and kw2 keep the library's defaults
+  ! when left out.  The table of Mie rows on the scheme's own bins is built for the call and freed after it: a caller of many
+  ! batches at one wavelength pays some 300 spheres per call.  qc, qs, qg, w (nz, ncol) and k_gas(nz) left out mean zero;
+  ! dz(nz) is needed for the path outputs.  The inputs are not changed.  Default REAL 8 goes to kidmp_mie_radar_host, REAL
+  ! 4 to kidmp32_...
+  subroutine mie_radar_batch(ncol, nz, wavelength, eps_w_re, eps_w_im, eps_i_re, eps_i_im, t, p, qv, qr, nr, dbz, dbz_up, &
+       dbz_down, dbz_r, dbz_s, dbz_g, mie_r, mie_s, mie_g, ext, pia_up, pia_down, vd, pia_total, qc, qs, qg, dz, w, k_gas, &
+       rho_w, rho_i, kw2)
+    integer, intent(in) :: ncol, nz
+    real(c_double), intent(in) :: wavelength, eps_w_re, eps_w_im, eps_i_re, eps_i_im
+    real, dimension(nz,ncol), intent(in), target :: t, p, qv, qr, nr
+    real, dimension(nz,ncol), intent(out), optional, target :: dbz, dbz_up, dbz_down, dbz_r, dbz_s, dbz_g, mie_r, mie_s, mie_g, &
+         ext, pia_up, pia_down, vd
+    real, dimension(ncol), intent(out), optional, target :: pia_total
+    real, dimension(nz,ncol), intent(in), optional, target :: qc, qs, qg, w
+    real, dimension(nz), intent(in), optional, target :: dz, k_gas
+    real(c_double), intent(in), optional :: rho_w, rho_i, kw2
+    type(kidmp_mie_out) :: out
+    type(kidmp_mie_cfg) :: cfg
+    type(c_ptr) :: table, pqc, pqs, pqg, pdz, pw, pkg
+    integer(c_int) :: rc
+    if (.not. c_associated(ctx)) call thompson_init
+    if (c_associated(mctx)) then
+       write(*,'(a)') ' module_mp_thompson09n: the cloud radar is not available with kidmp_ndevices > 1'
+       stop 1
+    end if
+    call kidmp_mie_defaults(cfg)
+    cfg%wavelength = wavelength
+    cfg%eps_w_re = eps_w_re;  cfg%eps_w_im = eps_w_im;  cfg%eps_i_re = eps_i_re;  cfg%eps_i_im = eps_i_im
+    if (present(rho_w)) cfg%rho_w = rho_w
+    if (present(rho_i)) cfg%rho_i = rho_i
+    if (present(kw2)) cfg%kw2 = kw2
+    pqc = c_null_ptr;  pqs = c_null_ptr;  pqg = c_null_ptr;  pdz = c_null_ptr;  pw = c_null_ptr;  pkg = c_null_ptr
+    if (present(qc)) pqc = c_loc(qc)
+    if (present(qs)) pqs = c_loc(qs)
+    if (present(qg)) pqg = c_loc(qg)
+    if (present(dz)) pdz = c_loc(dz)
+    if (present(w)) pw = c_loc(w)
+    if (present(k_gas)) pkg = c_loc(k_gas)
+    out = kidmp_mie_out(c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
+         c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr)
+    if (present(dbz)) out%dbz = c_loc(dbz)
+    if (present(dbz_up)) out%dbz_up = c_loc(dbz_up)
+    if (present(dbz_down)) out%dbz_down = c_loc(dbz_down)
+    if (present(dbz_r)) out%dbz_r = c_loc(dbz_r)
+    if (present(dbz_s)) out%dbz_s = c_loc(dbz_s)
+    if (present(dbz_g)) out%dbz_g = c_loc(dbz_g)
+    if (present(mie_r)) out%mie_r = c_loc(mie_r)
+    if (present(mie_s)) out%mie_s = c_loc(mie_s)
+    if (present(mie_g)) out%mie_g = c_loc(mie_g)
+    if (present(ext)) out%ext = c_loc(ext)
+    if (present(pia_up)) out%pia_up = c_loc(pia_up)
+    if (present(pia_down)) out%pia_down = c_loc(pia_down)
+    if (present(vd)) out%vd = c_loc(vd)
+    if (present(pia_total)) out%pia_total = c_loc(pia_total)
+    rc = kidmp_mie_table_create(ctx, cfg, c_null_ptr, table)
+    call stop_on_error(rc, 'mie_radar_batch (table)')
+    if (kind(t) == c_double) then
+       rc = kidmp_mie_radar_host(ctx, table, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), pqc, &
+            c_loc(qr), c_loc(nr), pqs, pqg, pdz, 0_c_int64_t, pw, pkg, 0_c_int64_t, out)
+    else
+       rc = kidmp32_mie_radar_host(ctx, table, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), pqc, &
+            c_loc(qr), c_loc(nr), pqs, pqg, pdz, 0_c_int64_t, pw, pkg, 0_c_int64_t, out)
+    end if
+    call kidmp_mie_table_destroy(table)
+    call stop_on_error(rc, 'mie_radar_batch')
+  end subroutine mie_radar_batch
 
   ! A droplet number per column (kidmp_set_column_nc): column i of every following batched call uses Nt_c =
   ! set_nc_col(i)*1.e6 (M:381) in place of the namelist's set_Nc -- an Nd ensemble, or an aerosol gradient along x, in

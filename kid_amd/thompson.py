@@ -654,6 +654,23 @@ class ThompsonMP:
         from .brightband import bright_band_host
         return bright_band_host(self, st, cfg, grids, want, out)
 
+    def mie_table(self, cfg=None, grids=None):
+        """The Mie rows of rain, snow and graupel for one wavelength on this context's device (include/kidmp_mie.h):
+        a kid_amd.mie.MieTable."""
+        from .mie import MieTable
+        return MieTable(self, cfg, grids)
+
+    def mie_radar(self, table, st, dz=None, w=None, k_gas=None, want=("dbz",), out=None, stream=None):
+        """Mie reflectivity, extinction, path-integrated attenuation and mean Doppler velocity at the table's wavelength:
+        kid_amd.mie.mie_radar on this context."""
+        from .mie import mie_radar
+        return mie_radar(self, table, st, dz, w, k_gas, want, out, stream)
+
+    def mie_radar_host(self, table, st, dz=None, w=None, k_gas=None, want=("dbz",), out=None):
+        """mie_radar on numpy arrays: kid_amd.mie.mie_radar_host on this context."""
+        from .mie import mie_radar_host
+        return mie_radar_host(self, table, st, dz, w, k_gas, want, out)
+
     REFL_NAMES = ("t", "p", "qv", "qr", "nr", "qs", "qg")      # the inputs of calc_refl10cm that are read (qc1d is not)
 
     def reflectivity(self, st, out=None, stream=None):
