@@ -13,6 +13,9 @@ from .lidar import LIDAR_INPUTS, LIDAR_NAMES, LIDAR_SUMMARY_NAMES, LidarCfg, lid
 from .fall import FALL_INPUTS, FALL_NAMES, fall_speeds, fall_speeds_host  # noqa: F401
 from .brightband import BRIGHTBAND_INPUTS, BRIGHTBAND_NAMES, BrightBandCfg, bright_band, bright_band_host  # noqa: F401
 from .mie import MIE_INPUTS, MIE_NAMES, MIE_ROWS, MIE_SPECIES, MieCfg, MieTable, mie_bins, mie_radar, mie_radar_host, mie_sphere  # noqa: F401
+# (the function radiometer.radiometer is not re-exported: the name is the submodule's; ThompsonMP.radiometer calls it)
+from .radiometer import (RADIOMETER_INPUTS, RADIOMETER_NAMES, RADIOMETER_ROWS, RADIOMETER_SUMMARY_NAMES, RadiometerCfg, RadiometerTable,  # noqa: F401
+                         radiometer_bins, radiometer_host, radiometer_sphere)
 from .dspectrum import DSPECTRUM_INPUTS, DSPECTRUM_NAMES, doppler_spectrum, doppler_spectrum_host, velocity_grid  # noqa: F401
 from .spectra import SPECTRA_INPUTS, SPECTRA_PARAMS, SPECTRA_SPECIES, default_grid, size_spectra, size_spectra_host  # noqa: F401
 from .kinematic import ADVECT_OUTPUTS, advect, run, update  # noqa: F401

@@ -4,9 +4,7 @@
 #include <cmath>
 #include <cstddef>
 
-#include "kidmp_ctx.h"
-#include "kidmp_mie_sphere.h"
-#include "../../include/kidmp_mie.h"
+#include "kidmp_mie_table.h"
 
 using namespace kidmp;
 
@@ -17,37 +15,13 @@ static_assert(sizeof(kidmp_mie_out) == (MIE_NOUT + 1) * sizeof(double *) && size
               "include/kidmp_mie.h");
 
 // one device buffer: per species D[nb], dD[nb], rows[MIE_NROWS][nb]
-struct kidmp_mie_table {
-    kidmp_ctx *ctx;
-    int device;
-    kidmp_mie_cfg cfg;
-    int32_t nb[MIE_NSPEC];
-    size_t off[MIE_NSPEC];                                // the species' first double in the buffer
-    double *d_buf;
-    double kc;
-};
+struct kidmp_mie_table : kidmp::MieTableData {};
 
 namespace {
 constexpr int NIN = 8, NREQ = 5;                          // t, p, qv, qr, nr | qc, qs, qg
 const char *const IN_NAMES[NIN] = {"t", "p", "qv", "qr", "nr", "qc", "qs", "qg"};
 const char *const OUT_NAMES[MIE_NOUT] = {"dbz", "dbz_up", "dbz_down", "dbz_r", "dbz_s", "dbz_g", "mie_r", "mie_s", "mie_g", "ext",
                                          "pia_up", "pia_down", "vd"};
-
-const double *bins_D(const Bins &b, int x) { return x == 0 ? b.Dr : x == 1 ? b.Ds : b.Dg; }
-const double *bins_dD(const Bins &b, int x) { return x == 0 ? b.dtr : x == 1 ? b.dts : b.dtg; }
-
-// nullptr where the configuration is good, else what is wrong with it
-const char *bad_cfg(const kidmp_mie_cfg &g)
-{
-    const double members[] = {g.wavelength, g.eps_w_re, g.eps_w_im, g.eps_i_re, g.eps_i_im, g.rho_w, g.rho_i, g.kw2};
-    for (double m : members)
-        if (!std::isfinite(m)) return "a member of the configuration is not finite";
-    if (!(g.wavelength > 0.) || !(g.rho_w > 0.) || !(g.rho_i > 0.) || !(g.kw2 > 0.)) return "wavelength, rho_w, rho_i and kw2 must be above 0";
-    if (g.eps_w_im < 0. || g.eps_i_im < 0.) return "Im(eps) must not be below 0";
-    if ((g.eps_w_im == 0. && !(g.eps_w_re > 0.)) || (g.eps_i_im == 0. && !(g.eps_i_re > 0.))) return "a real permittivity must be above 0";
-    return nullptr;
-}
-MieCfg model_cfg(const kidmp_mie_cfg &g) { return MieCfg{g.wavelength, {g.eps_w_re, g.eps_w_im}, {g.eps_i_re, g.eps_i_im}, g.rho_w, g.rho_i, g.kw2}; }
 
 template <class T> struct MieCall {
     const T *in[NIN];
@@ -221,11 +195,11 @@ int kidmp_mie_bins(const kidmp_mie_cfg *cfg, int32_t species, int32_t nb, const 
 {
     const std::string w("kidmp_mie_bins");
     if (!cfg || !D || !rows) return fail(nullptr, KIDMP_EINVAL, w + ": null argument");
-    if (const char *bad = bad_cfg(*cfg)) return fail(nullptr, KIDMP_EINVAL, w + ": " + bad);
+    if (const char *bad = mie_bad_cfg(*cfg)) return fail(nullptr, KIDMP_EINVAL, w + ": " + bad);
     if (species < 0 || species >= MIE_NSPEC) return fail(nullptr, KIDMP_EINVAL, w + ": unknown species");
     if (nb < 1) return fail(nullptr, KIDMP_EINVAL, w + ": nb < 1");
     std::vector<double> r(size_t(MIE_ROWS) * size_t(nb));
-    if (!mie_bins(model_cfg(*cfg), species, nb, D, r.data()))
+    if (!mie_bins(mie_model_cfg(*cfg), species, nb, D, r.data()))
         return fail(nullptr, KIDMP_EINVAL, w + ": a diameter is not finite or not above 0, or its sphere has more than 1e7 terms");
     std::memcpy(rows, r.data(), r.size() * sizeof(double));
     return KIDMP_OK;
@@ -237,42 +211,10 @@ int kidmp_mie_table_create(kidmp_ctx *ctx, const kidmp_mie_cfg *cfg, const kidmp
     if (table) *table = nullptr;
     if (int rc = require_ready(ctx)) return rc;
     if (!table) return fail(ctx, KIDMP_EINVAL, w + ": null argument");
-    kidmp_mie_cfg g;
-    if (cfg) g = *cfg;
-    else kidmp_mie_defaults(&g);
-    if (const char *bad = bad_cfg(g)) return fail(ctx, KIDMP_EINVAL, w + ": " + bad);
-    int32_t nb[MIE_NSPEC];
-    size_t off[MIE_NSPEC], total = 0;
-    const double *D[MIE_NSPEC], *dD[MIE_NSPEC];
-    for (int x = 0; x < MIE_NSPEC; ++x) {
-        nb[x] = nbins;
-        D[x] = bins_D(ctx->hb, x);
-        dD[x] = bins_dD(ctx->hb, x);
-        if (grids && (grids->D[x] || grids->dD[x])) {
-            if (!grids->D[x] || !grids->dD[x]) return fail(ctx, KIDMP_EINVAL, w + ": a grid needs both D and dD");
-            if (grids->nb[x] < 1 || grids->nb[x] > KIDMP_MIE_MAX_BINS) return fail(ctx, KIDMP_EINVAL, w + ": nb outside [1, KIDMP_MIE_MAX_BINS]");
-            nb[x] = grids->nb[x]; D[x] = grids->D[x]; dD[x] = grids->dD[x];
-            for (int b = 0; b < nb[x]; ++b)
-                if (!std::isfinite(dD[x][b])) return fail(ctx, KIDMP_EINVAL, w + ": a dD is not finite");
-        }
-        off[x] = total;
-        total += size_t(2 + MIE_ROWS) * size_t(nb[x]);
-    }
-    std::vector<double> buf(total);
-    const MieCfg mc = model_cfg(g);
-    for (int x = 0; x < MIE_NSPEC; ++x) {
-        double *b = buf.data() + off[x];
-        std::memcpy(b, D[x], size_t(nb[x]) * sizeof(double));
-        std::memcpy(b + nb[x], dD[x], size_t(nb[x]) * sizeof(double));
-        if (!mie_bins(mc, x, nb[x], D[x], b + 2 * size_t(nb[x])))
-            return fail(ctx, KIDMP_EINVAL, w + ": a diameter is not finite or not above 0, or its sphere has more than 1e7 terms");
-    }
-    GUARD(ctx);
-    double *d_buf = nullptr;
-    HIPTRY(ctx, hipMalloc(reinterpret_cast<void **>(&d_buf), total * sizeof(double)));
-    const hipError_t e = hipMemcpy(d_buf, buf.data(), total * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d_buf); return hipfail(ctx, e, "hipMemcpy of the Mie table"); }
-    kidmp_mie_table *t = new kidmp_mie_table{ctx, ctx->cfg.device, g, {nb[0], nb[1], nb[2]}, {off[0], off[1], off[2]}, d_buf, mie_cloud_absorption(mc)};
+    MieTableData d;
+    if (int rc = mie_table_build(ctx, w, cfg, grids, MIE_ROWS, mie_bins, &d)) return rc;
+    kidmp_mie_table *t = new kidmp_mie_table;
+    static_cast<MieTableData &>(*t) = d;
     *table = t;
     return KIDMP_OK;
 }
@@ -280,10 +222,7 @@ int kidmp_mie_table_create(kidmp_ctx *ctx, const kidmp_mie_cfg *cfg, const kidmp
 void kidmp_mie_table_destroy(kidmp_mie_table *table)
 {
     if (!table) return;
-    {
-        DeviceGuard guard(table->device);
-        if (table->d_buf) (void)hipFree(table->d_buf);
-    }
+    mie_table_free(table);
     delete table;
 }
 
@@ -291,18 +230,7 @@ int kidmp_mie_table_get(const kidmp_mie_table *table, int32_t species, int32_t *
 {
     const std::string w("kidmp_mie_table_get");
     if (!table) return fail(nullptr, KIDMP_EINVAL, w + ": null table");
-    kidmp_ctx *ctx = table->ctx;
-    if (species < 0 || species >= MIE_NSPEC) return fail(ctx, KIDMP_EINVAL, w + ": unknown species");
-    const size_t n = size_t(table->nb[species]);
-    if (nb) *nb = table->nb[species];
-    if (cfg) *cfg = table->cfg;
-    DeviceGuard guard(table->device);
-    if (guard.err != hipSuccess) return hipfail(ctx, guard.err, "hipSetDevice");
-    const double *b = table->d_buf + table->off[species];
-    if (D) HIPTRY(ctx, hipMemcpy(D, b, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (dD) HIPTRY(ctx, hipMemcpy(dD, b + n, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (rows) HIPTRY(ctx, hipMemcpy(rows, b + 2 * n, size_t(MIE_ROWS) * n * sizeof(double), hipMemcpyDeviceToHost));
-    return KIDMP_OK;
+    return mie_table_read(table, w, species, nb, D, dD, rows, cfg);
 }
 
 int kidmp_mie_radar_device(kidmp_ctx *ctx, const kidmp_mie_table *table, int64_t ncol, int32_t nz, const double *t, const double *p,

@@ -14,6 +14,8 @@
 //   b_n = ((m D_n + n/x) psi_n - psi_{n-1}) / ((m D_n + n/x) xi_n - xi_{n-1})
 //   Q_ext  = (2/x**2) sum (2n+1) Re(a_n + b_n);     Q_back = |sum (2n+1) (-1)**n (a_n - b_n)|**2 / x**2
 // Q_back is the radar backscatter efficiency sigma_back/(pi a**2); its Rayleigh limit is 4 x**4 |K(m**2)|**2.
+//   Q_sca  = (2/x**2) sum (2n+1) (|a_n|**2 + |b_n|**2)
+//   g Q_sca = (4/x**2) [sum (n(n+2)/(n+1)) Re(a_n conj(a_{n+1}) + b_n conj(b_{n+1})) + sum ((2n+1)/(n(n+1))) Re(a_n conj(b_n))]
 //
 // The particle models are the project's own convention, not a standard's and not any instrument simulator's:
 //   rain     a water sphere of diameter D: m = sqrt(eps_w), mass = (PI/6) rho_w D**3
@@ -65,9 +67,15 @@ inline BBComplex mie_sqrt(BBComplex e)
     return m;
 }
 
-// Q_ext and Q_back of a sphere of size parameter x and refractive index m.  False, nothing written: x or m not finite,
-// x not above 0, Re(m) not above 0, Im(m) below 0, or more than MIE_MAX_TERMS terms of D_n.
-inline bool mie_sphere(double x, double m_re, double m_im, double &qext, double &qback)
+// The sums of the series, for mie_sphere and for the radiometer's efficiencies (include/kidmp_radiometer.h): the a_n, b_n
+// loop exists once.  ext = sum (2n+1) Re(a_n + b_n); back = sum (2n+1)(-1)**n (a_n - b_n); sca = sum (2n+1)(|a_n|**2 +
+// |b_n|**2); adj = sum_{n<nstop} (n(n+2)/(n+1)) Re(a_n conj(a_{n+1}) + b_n conj(b_{n+1})); ab = sum ((2n+1)/(n(n+1)))
+// Re(a_n conj(b_n)).  Each sum ascends in n from +0.0.
+struct MieSeries { double ext, back_re, back_im, sca, adj, ab, x2; };
+
+// False, nothing written: x or m not finite, x not above 0, Re(m) not above 0, Im(m) below 0, or more than MIE_MAX_TERMS
+// terms of D_n.
+inline bool mie_series(double x, double m_re, double m_im, MieSeries &out)
 {
     if (!(std::isfinite(x) && std::isfinite(m_re) && std::isfinite(m_im)) || !(x > 0.) || !(m_re > 0.) || m_im < 0.) return false;
     const BBComplex m = {m_re, m_im};
@@ -92,6 +100,8 @@ inline bool mie_sphere(double x, double m_re, double m_im, double &qext, double 
     double psi0 = std::cos(x), psi1 = std::sin(x);
     double chi0 = -std::sin(x), chi1 = std::cos(x);
     double sum_ext = 0., back_re = 0., back_im = 0., sign = -1.;
+    double sum_sca = 0., sum_adj = 0., sum_ab = 0.;
+    BBComplex pa = {0., 0.}, pb = {0., 0.};                // a_{n-1}, b_{n-1}
     for (int n = 1; n <= nstop; ++n) {
         const double en = double(n), f = (2. * en - 1.) / x, nx = en / x;
         const double psi = f * psi1 - psi0;
@@ -109,13 +119,43 @@ inline bool mie_sphere(double x, double m_re, double m_im, double &qext, double 
         sum_ext = sum_ext + w * (an.re + bn.re);
         back_re = back_re + (w * sign) * (an.re - bn.re);
         back_im = back_im + (w * sign) * (an.im - bn.im);
+        sum_sca = sum_sca + w * ((an.re * an.re + an.im * an.im) + (bn.re * bn.re + bn.im * bn.im));
+        if (n > 1) {
+            const double e1 = en - 1.;                       // the pair (n-1, n)
+            sum_adj = sum_adj + ((e1 * (e1 + 2.)) / (e1 + 1.)) * ((pa.re * an.re + pa.im * an.im) + (pb.re * bn.re + pb.im * bn.im));
+        }
+        sum_ab = sum_ab + (w / (en * (en + 1.))) * (an.re * bn.re + an.im * bn.im);
+        pa = an; pb = bn;
         sign = -sign;
         psi0 = psi1; psi1 = psi;
         chi0 = chi1; chi1 = chi;
     }
-    const double x2 = x * x;
-    qext = (2. / x2) * sum_ext;
-    qback = (back_re * back_re + back_im * back_im) / x2;
+    out = MieSeries{sum_ext, back_re, back_im, sum_sca, sum_adj, sum_ab, x * x};
+    return true;
+}
+
+// Q_ext and Q_back of a sphere of size parameter x and refractive index m.  False, nothing written: as mie_series.
+inline bool mie_sphere(double x, double m_re, double m_im, double &qext, double &qback)
+{
+    MieSeries s;
+    if (!mie_series(x, m_re, m_im, s)) return false;
+    qext = (2. / s.x2) * s.ext;
+    qback = (s.back_re * s.back_re + s.back_im * s.back_im) / s.x2;
+    return true;
+}
+
+// The efficiencies a radiometer needs beside them: Q_sca = (2/x**2) sca, gQ = g*Q_sca = (4/x**2) (adj + ab), and the
+// asymmetry factor g = gQ/Q_sca (+0.0 where Q_sca is not above 0).  Q_ext and Q_back are mie_sphere's bit for bit.
+struct MieEff { double qext, qsca, qback, g, gq; };
+inline bool mie_efficiencies(double x, double m_re, double m_im, MieEff &e)
+{
+    MieSeries s;
+    if (!mie_series(x, m_re, m_im, s)) return false;
+    e.qext = (2. / s.x2) * s.ext;
+    e.qback = (s.back_re * s.back_re + s.back_im * s.back_im) / s.x2;
+    e.qsca = (2. / s.x2) * s.sca;
+    e.gq = (4. / s.x2) * (s.adj + s.ab);
+    e.g = e.qsca > 0. ? e.gq / e.qsca : 0.;
     return true;
 }
 
@@ -171,6 +211,32 @@ inline bool mie_bins(const MieCfg &c, int species, int nb, const double *D, doub
         rows[2 * nb + b] = qext * area;
         rows[3 * nb + b] = mass;
         rows[4 * nb + b] = v0;
+    }
+    return true;
+}
+
+// The radiometer's rows (include/kidmp_radiometer.h), rows[r*nb + b], r = s_abs, s_bsc, mass, with the particle models
+// above: s_abs = max(Q_ext - Q_sca, 0) (pi D**2/4), s_bsc = max(0.5 (Q_sca - gQ), 0) (pi D**2/4), the cross-section
+// scattered into the backward hemisphere.  A particle whose index is real does not absorb: with Im(m) = 0 s_abs is +0.0, not
+// the rounding residue of Q_ext - Q_sca (of either sign; the max would keep the positive half of it).  False as mie_bins.
+constexpr int RADIOMETER_ROWS = 3;
+inline bool radiometer_bins(const MieCfg &c, int species, int nb, const double *D, double *rows)
+{
+    if (species < MIE_RAIN || species > MIE_GRAUPEL) return false;
+    for (int b = 0; b < nb; ++b) {
+        const double d = D[b];
+        if (!std::isfinite(d) || !(d > 0.)) return false;
+        const double d2 = d * d, d3 = d2 * d;
+        const double mass = species == MIE_RAIN ? (PI / 6.0) * c.rho_w * d3 : species == MIE_SNOW ? am_s * d2 : am_g * d3;
+        const BBComplex m = mie_index(c, species, d, mass);
+        const double x = MIE_PI * d / c.wavelength;
+        MieEff e;
+        if (!mie_efficiencies(x, m.re, m.im, e)) return false;
+        const double area = 0.25 * MIE_PI * d2;
+        const double qa = m.im > 0. ? e.qext - e.qsca : 0., qb = 0.5 * (e.qsca - e.gq);
+        rows[0 * nb + b] = (qa > 0. ? qa : 0.) * area;
+        rows[1 * nb + b] = (qb > 0. ? qb : 0.) * area;
+        rows[2 * nb + b] = mass;
     }
     return true;
 }

@@ -182,4 +182,24 @@ template <class T>
 hipError_t launch_mie_radar(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const MieArgs<T> &a,
                             hipStream_t stream);
 
+// The microwave radiometer (include/kidmp_radiometer.h): absorption and back-hemisphere scattering coefficients from
+// k_mie_radar's load and a table of three rows per diameter bin (s_abs, s_bsc, mass), the two-stream layer of every level
+// and the adding of the layers by two wave scans.  Null means: qc, qs, qg, k_gas -- zero; t_sfc -- the column's t at level
+// 0; an output -- not wanted; dz -- not read when only k_abs and k_bsc are wanted.  out: k_abs, k_bsc, refl, trans, tb_up,
+// tb_down [ncol][nz]; tb_toa, tb_ground, tau_abs [ncol].  One launch; lanes over levels, a loop over the bins.
+constexpr int RAD_NOUT = 6, RAD_NROWS = 3;
+constexpr int RAD_K_ABS = 0, RAD_K_BSC = 1, RAD_REFL = 2, RAD_TRANS = 3, RAD_TB_UP = 4, RAD_TB_DOWN = 5;
+template <class T> struct RadiometerArgs {
+    const T *t, *p, *qv, *qc, *qr, *nr, *qs, *qg, *dz, *k_gas, *t_sfc;
+    int64_t dz_col_stride, k_gas_col_stride;
+    T *out[RAD_NOUT];
+    T *tb_toa, *tb_ground, *tau_abs;
+    const double *D[MIE_NSPEC], *dD[MIE_NSPEC], *rows[MIE_NSPEC];
+    int32_t nb[MIE_NSPEC];
+    double kc, rho_w, mu, emissivity, t_cosmic;
+};
+template <class T>
+hipError_t launch_radiometer(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const RadiometerArgs<T> &a,
+                             hipStream_t stream);
+
 }  // namespace kidmp

@@ -27,6 +27,7 @@
 
 #include "thompson_levels.h"
 #include "kidmp_dspectrum_slot.h"
+#include "kidmp_radiometer_layer.h"
 
 namespace kidmp {
 
@@ -1433,20 +1434,19 @@ k_bright_band(ReflConsts c, DopplerConsts dc, BrightBandArgs<T> a, int64_t ncol,
 // ---- the cloud radar (include/kidmp_mie.h) ----
 constexpr double MIE_PIA = 20. / 2.302585092994045684;              // two-way dB per unit of one-way optical depth: 2*(10/ln 10)
 
-// The five sums of one species at every level of the lane: A = sum n s_mie, B = sum n s_ray, E = sum n s_ext,
-// M = sum n mass, V = sum (n s_mie) v0, over the bins ascending into accumulators that start at +0.0.  The lanes hold
-// levels; D, dD and the five rows are wave-uniform loads.  density(j, D, dD, Dmu) gives n of the lane's level of group j;
-// a level group none of whose levels holds the species is passed over.  SP == 1: Dmu = D**mu_s is formed once per bin,
-// 64 bins at a time and one per lane, and handed round with v_readlane (as store_bins does).
-template <int SP, int NJ, class T, class F>
-__device__ __forceinline__ void mie_sums(const MieArgs<T> &a, int lane, const bool (&has)[NJ], F &&density, double (&A)[NJ],
-                                         double (&B)[NJ], double (&E)[NJ], double (&M)[NJ], double (&V)[NJ])
+// The loop over the bins of one species' table at every level of the lane, NR rows per bin.  The lanes hold levels; D, dD
+// and the rows are wave-uniform loads.  density(j, D, dD, Dmu) gives n of the lane's level of group j; add(j, n, r) folds
+// the bin's rows r[NR] into the caller's accumulators.  A level group none of whose levels holds the species is passed
+// over.  SP == 1: Dmu = D**mu_s is formed once per bin, 64 bins at a time and one per lane, and handed round with
+// v_readlane (as store_bins does).  A: MieArgs or RadiometerArgs.
+template <int SP, int NJ, int NR, class A, class F, class G>
+__device__ __forceinline__ void bin_loop(const A &a, int lane, const bool (&has)[NJ], F &&density, G &&add)
 {
     const double *__restrict__ D = a.D[SP], *__restrict__ dD = a.dD[SP], *__restrict__ rows = a.rows[SP];
     const int nb = a.nb[SP];
     bool live[NJ];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) { live[j] = __ballot(has[j]) != 0; A[j] = B[j] = E[j] = M[j] = V[j] = 0.; }
+    for (int j = 0; j < NJ; ++j) live[j] = __ballot(has[j]) != 0;
     for (int bb = 0; bb < nb; bb += 64) {
         double mine = 0.;
         if (SP == 1 && bb + lane < nb) mine = fm::pow(D[bb + lane], mu_s);
@@ -1454,20 +1454,35 @@ __device__ __forceinline__ void mie_sums(const MieArgs<T> &a, int lane, const bo
         for (int b = bb; b < be; ++b) {
             const double Db = D[b], dDb = dD[b];
             const double Dmu = SP == 1 ? readlane(mine, b - bb) : 0.;
-            const double s_mie = rows[b], s_ray = rows[nb + b], s_ext = rows[2 * nb + b], mass = rows[3 * nb + b], v0 = rows[4 * nb + b];
+            double r[NR];
+#pragma unroll
+            for (int i = 0; i < NR; ++i) r[i] = rows[i * nb + b];
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
                 if (!live[j]) continue;                              // wave-uniform
                 const double n = has[j] ? density(j, Db, dDb, Dmu) : 0.;
-                const double ns = n * s_mie;
-                A[j] += ns;
-                B[j] += n * s_ray;
-                E[j] += n * s_ext;
-                M[j] += n * mass;
-                V[j] += ns * v0;
+                add(j, n, r);
             }
         }
     }
+}
+
+// The five sums of one species at every level of the lane: A = sum n s_mie, B = sum n s_ray, E = sum n s_ext,
+// M = sum n mass, V = sum (n s_mie) v0, over the bins ascending into accumulators that start at +0.0.
+template <int SP, int NJ, class T, class F>
+__device__ __forceinline__ void mie_sums(const MieArgs<T> &a, int lane, const bool (&has)[NJ], F &&density, double (&A)[NJ],
+                                         double (&B)[NJ], double (&E)[NJ], double (&M)[NJ], double (&V)[NJ])
+{
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) A[j] = B[j] = E[j] = M[j] = V[j] = 0.;
+    bin_loop<SP, NJ, MIE_NROWS>(a, lane, has, density, [&](int j, double n, const double (&r)[MIE_NROWS]) __attribute__((always_inline)) {
+        const double ns = n * r[0];
+        A[j] += ns;
+        B[j] += n * r[1];
+        E[j] += n * r[2];
+        M[j] += n * r[3];
+        V[j] += ns * r[4];
+    });
 }
 
 // One wavefront per column: the cloud radar of include/kidmp_mie.h.  The load and the scan are k_doppler_moments'
@@ -1629,6 +1644,211 @@ k_mie_radar(ReflConsts c, DopplerConsts dc, MieArgs<T> a, int64_t ncol, int nz)
         for (int j = 0; j < NJ; ++j) { td[j] = MIE_PIA * (td[j] + 0.5 * dt[j]); dbz_out[j] = dbz[j] - td[j]; }
         store_profile<T, NJ>(out[MIE_PIA_DOWN], base, nz, lane, td);
         store_profile<T, NJ>(out[MIE_DBZ_DOWN], base, nz, lane, dbz_out);
+    }
+}
+
+// ---- the microwave radiometer (include/kidmp_radiometer.h) ----
+__device__ __forceinline__ RadState state_readlane(const RadState &v, int l)
+{ return RadState{readlane(v.Rt, l), readlane(v.Rb, l), readlane(v.T, l), readlane(v.Eu, l), readlane(v.Ed, l)}; }
+template <bool DOWN>
+__device__ __forceinline__ RadState state_shift(const RadState &v, int d)
+{
+    return DOWN ? RadState{__shfl_down(v.Rt, d, 64), __shfl_down(v.Rb, d, 64), __shfl_down(v.T, d, 64), __shfl_down(v.Eu, d, 64), __shfl_down(v.Ed, d, 64)}
+                : RadState{__shfl_up(v.Rt, d, 64), __shfl_up(v.Rb, d, 64), __shfl_up(v.T, d, 64), __shfl_up(v.Eu, d, 64), __shfl_up(v.Ed, d, 64)};
+}
+__device__ __forceinline__ RadState state_select(bool c, const RadState &a, const RadState &b)
+{ return RadState{c ? a.Rt : b.Rt, c ? a.Rb : b.Rb, c ? a.T : b.T, c ? a.Eu : b.Eu, c ? a.Ed : b.Ed}; }
+// Inclusive scan over the wave with the adding of layers in place of a sum: Kogge-Stone over __shfl_up, of the shape of
+// wave_prefix_sum.  The operator is associative but not commutative: the lower stack always comes first.  Lane l receives
+// the stack of the levels 0..l of its group, in an order that l alone fixes; DOWN is the mirror image over __shfl_down and
+// gives the levels l..63.  A lane without a partner keeps its value (what it computed from the shuffle's own-lane return
+// is thrown away).  Whole wavefronts only.
+template <bool DOWN>
+__device__ __forceinline__ RadState wave_adding_scan(RadState v, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const RadState o = state_shift<DOWN>(v, d);
+        const RadState c = DOWN ? rad_combine(v, o) : rad_combine(o, v);
+        v = state_select(DOWN ? lane + d < 64 : lane >= d, c, v);
+    }
+    return v;
+}
+
+// One wavefront per column: the radiometer of include/kidmp_radiometer.h.  The load is k_mie_radar's (radar_level,
+// graupel_running_min), lanes over levels.  Then species by species the three sums over the table's bins (bin_loop), which
+// leave behind only k_abs and k_bsc; cloud water and the caller's gas absorption close k_abs.  The layers follow per level
+// (kidmp_radiometer_layer.h).  The stacks above every level come from a suffix scan of the layers, the level groups
+// chained from the top through a wave-uniform carry state as column_depths chains its sums; the stacks below from the
+// prefix scan, group by group, each group's brightness temperatures stored before the next is scanned, so that only the
+// suffix states stay alive across groups.  A request without a brightness temperature ends before the scans, one without
+// refl, trans either before the exponentials.  No atomics, no scratch, nothing but the fastmath tables in LDS.
+template <class T, int NJ>
+__global__ void __launch_bounds__(REFL_THREADS)
+k_radiometer(ReflConsts c, DopplerConsts dc, RadiometerArgs<T> a, int64_t ncol, int nz)
+{
+#if KFM_TABLES
+    fm::tab::load_tables(int(threadIdx.x), REFL_THREADS);
+    __syncthreads();
+#endif
+    const int lane = int(threadIdx.x) & 63;
+    const int64_t col = int64_t(blockIdx.x) * REFL_WAVES + (int(threadIdx.x) >> 6);
+    if (col >= ncol) return;                                         // whole wavefronts only: the scans need every lane
+    const int64_t base = col * int64_t(nz);
+    T *const *out = a.out;
+    const bool want_tb = out[RAD_TB_UP] || out[RAD_TB_DOWN] || a.tb_toa || a.tb_ground;
+    const bool want_layer = want_tb || out[RAD_REFL] || out[RAD_TRANS];
+
+    double temp[NJ], rho[NJ], rs[NJ], rg[NJ], n0[NJ], N0_r[NJ], lamr[NJ];
+    lvl::SnowSpectrum ss[NJ];
+    bool lqr[NJ], lqs[NJ], lqg[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        temp[j] = 0.; rho[j] = 1.;
+        rs[j] = rg[j] = R1;
+        N0_r[j] = lamr[j] = 0.;
+        ss[j] = lvl::SnowSpectrum{0., 0., 0., 0.};
+        lqr[j] = lqs[j] = lqg[j] = false;
+        n0[j] = double(__builtin_inf());                             // levels past kte do not enter the minimum
+        if (k >= nz) continue;
+        const RadarLevel r = radar_level(c, a, base + k);            // ---- load, M:4991-5028 ----
+        temp[j] = r.temp;
+        rho[j] = r.rho;
+        rs[j] = r.rs;
+        rg[j] = r.rg;
+        N0_r[j] = r.N0_r;
+        lamr[j] = r.lamr;
+        lqr[j] = r.L_qr; lqs[j] = r.L_qs; lqg[j] = r.L_qg;
+        if (r.L_qs) ss[j] = lvl::snow_spectrum(r.sl, lvl::snow_moment(c.sa, c.sb, dc.cse1, r.sl));
+        n0[j] = r.n0_exp;
+    }
+    graupel_running_min<NJ>(n0, lane);
+    double N0_g[NJ], lamg[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        N0_g[j] = lamg[j] = 0.;
+        if (!lqg[j]) continue;
+        double ilamg;
+        (void)lvl::graupel_ze(c, n0[j], rg[j], ilamg, lamg[j], N0_g[j]);
+    }
+
+    // ---- k_abs = (((abs_r + abs_s) + abs_g) + abs_c) + k_gas, k_bsc = (bsc_r + bsc_s) + bsc_g; levels past nz keep +0.0 ----
+    double kabs[NJ], kbsc[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) kabs[j] = kbsc[j] = 0.;
+    {
+        double A[NJ], S[NJ], M[NJ];
+        const auto zero = [&]() __attribute__((always_inline)) {
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) A[j] = S[j] = M[j] = 0.;
+        };
+        const auto add = [&](int j, double n, const double (&r)[RAD_NROWS]) __attribute__((always_inline)) {
+            A[j] += n * r[0];
+            S[j] += n * r[1];
+            M[j] += n * r[2];
+        };
+        const auto finish = [&](const bool (&has)[NJ], const double (&rq)[NJ]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const bool ok = has[j] && M[j] > 0.;
+                kabs[j] = kabs[j] + (ok ? rq[j] * A[j] / M[j] : 0.);
+                kbsc[j] = kbsc[j] + (ok ? rq[j] * S[j] / M[j] : 0.);
+            }
+        };
+        double rr[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) rr[j] = lqr[j] ? double(a.qr[base + 64 * j + lane]) * rho[j] : 0.;
+        zero();
+        bin_loop<0, NJ, RAD_NROWS>(a, lane, lqr, [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(N0_r[j], lamr[j], D, dD); }, add);
+        finish(lqr, rr);
+        zero();
+        bin_loop<1, NJ, RAD_NROWS>(a, lane, lqs, [&](int j, double D, double dD, double Dmu) __attribute__((always_inline)) { return lvl::snow_bin(ss[j], D, Dmu, dD); }, add);
+        finish(lqs, rs);
+        zero();
+        bin_loop<2, NJ, RAD_NROWS>(a, lane, lqg, [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(N0_g[j], lamg[j], D, dD); }, add);
+        finish(lqg, rg);
+    }
+    if (a.qc) {                                                      // present where qc > R1, as in k_mie_radar
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            if (64 * j + lane >= nz) continue;
+            const double qc = double(a.qc[base + 64 * j + lane]);
+            if (qc > R1) kabs[j] = kabs[j] + a.kc * ((rho[j] * qc) / a.rho_w);
+        }
+    }
+    if (a.k_gas) {
+        const T *__restrict__ kg = a.k_gas + col * a.k_gas_col_stride;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+            if (64 * j + lane < nz) kabs[j] = kabs[j] + double(kg[64 * j + lane]);
+    }
+    store_profile<T, NJ>(out[RAD_K_ABS], base, nz, lane, kabs);
+    store_profile<T, NJ>(out[RAD_K_BSC], base, nz, lane, kbsc);
+    if (!(want_layer || a.tau_abs)) return;                          // wave-uniform: the optics alone
+
+    const T *__restrict__ dzc = a.dz + col * a.dz_col_stride;
+    double ta[NJ], bs[NJ], total = 0.;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        const double dz = k < nz ? double(dzc[k]) : 0.;
+        ta[j] = k < nz ? kabs[j] * dz : 0.;
+        bs[j] = k < nz ? kbsc[j] * dz : 0.;
+        total += ta[j];
+    }
+    if (a.tau_abs) {
+        total = wave_sum(total);
+        if (lane == 0) a.tau_abs[col] = T(total);
+    }
+    if (!want_layer) return;
+
+    // ---- the layer of every level; a level past nz is the identity ----
+    double lr[NJ], lt[NJ], le[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const double x = rad_layer_x(ta[j], bs[j]), y = x / a.mu;
+        const double e = lvl::exp_neg(y), f = y * lvl::layer_mean(y);
+        const RadLayer l = rad_layer(ta[j], bs[j], x, a.mu, e, f);
+        lr[j] = l.R; lt[j] = l.T; le[j] = l.a * temp[j];
+    }
+    store_profile<T, NJ>(out[RAD_REFL], base, nz, lane, lr);
+    store_profile<T, NJ>(out[RAD_TRANS], base, nz, lane, lt);
+    if (!want_tb) return;
+
+    // ---- the stack above every level: suffix scan, chained from the top ----
+    RadState above[NJ];
+    {
+        RadState carry = rad_identity();
+#pragma unroll
+        for (int j = NJ - 1; j >= 0; --j) {
+            const RadState inc = wave_adding_scan<true>(RadState{lr[j], lr[j], lt[j], le[j], le[j]}, lane);
+            const RadState first = state_readlane(inc, 0);
+            const RadState next = state_shift<true>(inc, 1);
+            above[j] = state_select(lane < 63, rad_combine(next, carry), carry);
+            carry = rad_combine(first, carry);
+        }
+    }
+    // ---- the stack below, group by group, and the closure at the level's two faces ----
+    const double ts = a.t_sfc ? double(a.t_sfc[col]) : double(a.t[base]);
+    const double rsfc = 1. - a.emissivity;
+    RadState carry = rad_identity();
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const RadState own{lr[j], lr[j], lt[j], le[j], le[j]};
+        const RadState inc = wave_adding_scan<false>(own, lane);
+        const RadState last = state_readlane(inc, 63);
+        const RadState prev = state_shift<false>(inc, 1);
+        const RadState below = state_select(lane > 0, rad_combine(carry, prev), carry);
+        carry = rad_combine(carry, last);
+        const int k = 64 * j + lane;
+        if (k >= nz) continue;
+        const double up = rad_face(rad_combine(below, own), above[j], a.emissivity, rsfc, ts, a.t_cosmic).up;
+        const double down = rad_face(below, rad_combine(own, above[j]), a.emissivity, rsfc, ts, a.t_cosmic).down;
+        if (out[RAD_TB_UP]) out[RAD_TB_UP][base + k] = T(up);
+        if (out[RAD_TB_DOWN]) out[RAD_TB_DOWN][base + k] = T(down);
+        if (a.tb_toa && k == nz - 1) a.tb_toa[col] = T(up);
+        if (a.tb_ground && k == 0) a.tb_ground[col] = T(down);
     }
 }
 
@@ -1926,6 +2146,25 @@ hipError_t launch_mie_radar(const ReflConsts &c, const DopplerConsts &dc, int64_
 }
 template hipError_t launch_mie_radar<double>(const ReflConsts &, const DopplerConsts &, int64_t, int, const MieArgs<double> &, hipStream_t);
 template hipError_t launch_mie_radar<float>(const ReflConsts &, const DopplerConsts &, int64_t, int, const MieArgs<float> &, hipStream_t);
+
+template <class T>
+hipError_t launch_radiometer(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const RadiometerArgs<T> &a, hipStream_t s)
+{
+    if (ncol <= 0) return hipSuccess;
+    for (int x = 0; x < MIE_NSPEC; ++x)
+        if (a.nb[x] < 1 || a.nb[x] > MIE_MAX_BINS) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((ncol + REFL_WAVES - 1) / REFL_WAVES)), block(REFL_THREADS);
+    switch ((nz + 63) / 64) {
+    case 1: hipLaunchKernelGGL((k_radiometer<T, 1>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 2: hipLaunchKernelGGL((k_radiometer<T, 2>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 3: hipLaunchKernelGGL((k_radiometer<T, 3>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 4: hipLaunchKernelGGL((k_radiometer<T, 4>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+template hipError_t launch_radiometer<double>(const ReflConsts &, const DopplerConsts &, int64_t, int, const RadiometerArgs<double> &, hipStream_t);
+template hipError_t launch_radiometer<float>(const ReflConsts &, const DopplerConsts &, int64_t, int, const RadiometerArgs<float> &, hipStream_t);
 
 bool doppler_consts_supported(const Consts &hc)
 {

@@ -66,6 +66,7 @@ module module_mp_thompson09n
   public :: doppler_spectrum_batch
   public :: bright_band_batch
   public :: mie_radar_batch
+  public :: radiometer_batch
   public :: lidar_profiles_batch
   public :: mp_thompson_kid_interface, mp_thompson_kid_staging
   logical, public :: is_aerosol_aware = .false.          ! M:28 (read at thompson_init)
@@ -146,6 +147,12 @@ module module_mp_thompson09n
   type, bind(C) :: kidmp_mie_cfg                         ! kidmp_mie_cfg; kidmp_mie_defaults fills it
      real(c_double) :: wavelength, eps_w_re, eps_w_im, eps_i_re, eps_i_im, rho_w, rho_i, kw2
   end type kidmp_mie_cfg
+  type, bind(C) :: kidmp_radiometer_out                  ! kidmp_radiometer_out / kidmp32_radiometer_out: NULL = not wanted
+     type(c_ptr) :: k_abs, k_bsc, refl, trans, tb_up, tb_down, tb_toa, tb_ground, tau_abs
+  end type kidmp_radiometer_out
+  type, bind(C) :: kidmp_radiometer_cfg                  ! kidmp_radiometer_cfg; kidmp_radiometer_defaults fills it
+     real(c_double) :: mu, emissivity, t_cosmic
+  end type kidmp_radiometer_cfg
 
   type, bind(C) :: kidmp_kid_fields                      ! kidmp_kid_fields / kidmp32_kid_fields: KiD's fields, [ncol][nz] each
      type(c_ptr) :: theta, qv, qc, qr, nr, qi, ni, qs, qg
@@ -503,6 +510,50 @@ module module_mp_thompson09n
        integer(c_int64_t), value :: k_gas_col_stride
        type(kidmp_mie_out), intent(in) :: out
      end function kidmp32_mie_radar_host
+     ! the radiometer (include/kidmp_radiometer.h): a table of three rows per bin and wavelength, then the operator; qc, qs,
+     ! qg, k_gas and t_sfc may be NULL
+     subroutine kidmp_radiometer_defaults(rcfg) bind(C, name='kidmp_radiometer_defaults')
+       import :: kidmp_radiometer_cfg
+       type(kidmp_radiometer_cfg), intent(out) :: rcfg
+     end subroutine kidmp_radiometer_defaults
+     integer(c_int) function kidmp_radiometer_table_create(ctx, cfg, grids, table) bind(C, name='kidmp_radiometer_table_create')
+       import :: c_int, c_ptr, kidmp_mie_cfg
+       type(c_ptr), value :: ctx, grids
+       type(kidmp_mie_cfg), intent(in) :: cfg
+       type(c_ptr), intent(out) :: table
+     end function kidmp_radiometer_table_create
+     subroutine kidmp_radiometer_table_destroy(table) bind(C, name='kidmp_radiometer_table_destroy')
+       import :: c_ptr
+       type(c_ptr), value :: table
+     end subroutine kidmp_radiometer_table_destroy
+     integer(c_int) function kidmp_radiometer_host(ctx, table, rcfg, ncol, nz, t, p, qv, qc, qr, nr, qs, qg, dz, dz_col_stride, k_gas, &
+          k_gas_col_stride, t_sfc, out) bind(C, name='kidmp_radiometer_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr, kidmp_radiometer_cfg, kidmp_radiometer_out
+       type(c_ptr), value :: ctx, table
+       type(kidmp_radiometer_cfg), intent(in) :: rcfg
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qc, qr, nr, qs, qg, dz
+       integer(c_int64_t), value :: dz_col_stride
+       type(c_ptr), value :: k_gas
+       integer(c_int64_t), value :: k_gas_col_stride
+       type(c_ptr), value :: t_sfc
+       type(kidmp_radiometer_out), intent(in) :: out
+     end function kidmp_radiometer_host
+     integer(c_int) function kidmp32_radiometer_host(ctx, table, rcfg, ncol, nz, t, p, qv, qc, qr, nr, qs, qg, dz, dz_col_stride, k_gas, &
+          k_gas_col_stride, t_sfc, out) bind(C, name='kidmp32_radiometer_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr, kidmp_radiometer_cfg, kidmp_radiometer_out
+       type(c_ptr), value :: ctx, table
+       type(kidmp_radiometer_cfg), intent(in) :: rcfg
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qc, qr, nr, qs, qg, dz
+       integer(c_int64_t), value :: dz_col_stride
+       type(c_ptr), value :: k_gas
+       integer(c_int64_t), value :: k_gas_col_stride
+       type(c_ptr), value :: t_sfc
+       type(kidmp_radiometer_out), intent(in) :: out
+     end function kidmp32_radiometer_host
   end interface
 
 contains
@@ -1307,6 +1358,78 @@ contains
     call kidmp_mie_table_destroy(table)
     call stop_on_error(rc, 'mie_radar_batch')
   end subroutine mie_radar_batch
+
+  ! The microwave radiometer over ncol columns of KiD's (nz, ncol) storage in one call (include/kidmp_radiometer.h): the
+  ! absorption and back-hemisphere scattering coefficients k_abs, k_bsc (1/m), the two-stream layer's refl and trans, the
+  ! brightness temperatures going up through the upper face (tb_up) and coming down through the lower face (tb_down) of
+  ! every level, all (nz, ncol) in the array kind the arithmetic stores, and per column tb_toa (what a satellite sees),
+  ! tb_ground (what a ground radiometer sees) and tau_abs.  Every output is optional; at least one must be present.  The
+  ! configuration is mie_radar_batch's (kw2 is not read); mu, emissivity and t_cosmic keep the library's 1, 1 and 2.725 K
+  ! when left out.  The table on the scheme's own bins is built for the call and freed after it.  qc, qs, qg (nz, ncol) and
+  ! k_gas(nz) left out mean zero; t_sfc(ncol) left out means the column's t at the lowest level; dz(nz) is needed for
+  ! everything but k_abs and k_bsc.  The inputs are not changed.  Default REAL 8 goes to kidmp_radiometer_host, REAL 4 to
+  ! kidmp32_...
+  subroutine radiometer_batch(ncol, nz, wavelength, eps_w_re, eps_w_im, eps_i_re, eps_i_im, t, p, qv, qr, nr, k_abs, k_bsc, &
+       refl, trans, tb_up, tb_down, tb_toa, tb_ground, tau_abs, qc, qs, qg, dz, k_gas, t_sfc, rho_w, rho_i, mu, emissivity, &
+       t_cosmic)
+    integer, intent(in) :: ncol, nz
+    real(c_double), intent(in) :: wavelength, eps_w_re, eps_w_im, eps_i_re, eps_i_im
+    real, dimension(nz,ncol), intent(in), target :: t, p, qv, qr, nr
+    real, dimension(nz,ncol), intent(out), optional, target :: k_abs, k_bsc, refl, trans, tb_up, tb_down
+    real, dimension(ncol), intent(out), optional, target :: tb_toa, tb_ground, tau_abs
+    real, dimension(nz,ncol), intent(in), optional, target :: qc, qs, qg
+    real, dimension(nz), intent(in), optional, target :: dz, k_gas
+    real, dimension(ncol), intent(in), optional, target :: t_sfc
+    real(c_double), intent(in), optional :: rho_w, rho_i, mu, emissivity, t_cosmic
+    type(kidmp_radiometer_out) :: out
+    type(kidmp_radiometer_cfg) :: rcfg
+    type(kidmp_mie_cfg) :: cfg
+    type(c_ptr) :: table, pqc, pqs, pqg, pdz, pkg, pts
+    integer(c_int) :: rc
+    if (.not. c_associated(ctx)) call thompson_init
+    if (c_associated(mctx)) then
+       write(*,'(a)') ' module_mp_thompson09n: the radiometer is not available with kidmp_ndevices > 1'
+       stop 1
+    end if
+    call kidmp_mie_defaults(cfg)
+    cfg%wavelength = wavelength
+    cfg%eps_w_re = eps_w_re;  cfg%eps_w_im = eps_w_im;  cfg%eps_i_re = eps_i_re;  cfg%eps_i_im = eps_i_im
+    if (present(rho_w)) cfg%rho_w = rho_w
+    if (present(rho_i)) cfg%rho_i = rho_i
+    call kidmp_radiometer_defaults(rcfg)
+    if (present(mu)) rcfg%mu = mu
+    if (present(emissivity)) rcfg%emissivity = emissivity
+    if (present(t_cosmic)) rcfg%t_cosmic = t_cosmic
+    pqc = c_null_ptr;  pqs = c_null_ptr;  pqg = c_null_ptr;  pdz = c_null_ptr;  pkg = c_null_ptr;  pts = c_null_ptr
+    if (present(qc)) pqc = c_loc(qc)
+    if (present(qs)) pqs = c_loc(qs)
+    if (present(qg)) pqg = c_loc(qg)
+    if (present(dz)) pdz = c_loc(dz)
+    if (present(k_gas)) pkg = c_loc(k_gas)
+    if (present(t_sfc)) pts = c_loc(t_sfc)
+    out = kidmp_radiometer_out(c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
+         c_null_ptr)
+    if (present(k_abs)) out%k_abs = c_loc(k_abs)
+    if (present(k_bsc)) out%k_bsc = c_loc(k_bsc)
+    if (present(refl)) out%refl = c_loc(refl)
+    if (present(trans)) out%trans = c_loc(trans)
+    if (present(tb_up)) out%tb_up = c_loc(tb_up)
+    if (present(tb_down)) out%tb_down = c_loc(tb_down)
+    if (present(tb_toa)) out%tb_toa = c_loc(tb_toa)
+    if (present(tb_ground)) out%tb_ground = c_loc(tb_ground)
+    if (present(tau_abs)) out%tau_abs = c_loc(tau_abs)
+    rc = kidmp_radiometer_table_create(ctx, cfg, c_null_ptr, table)
+    call stop_on_error(rc, 'radiometer_batch (table)')
+    if (kind(t) == c_double) then
+       rc = kidmp_radiometer_host(ctx, table, rcfg, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), pqc, &
+            c_loc(qr), c_loc(nr), pqs, pqg, pdz, 0_c_int64_t, pkg, 0_c_int64_t, pts, out)
+    else
+       rc = kidmp32_radiometer_host(ctx, table, rcfg, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), pqc, &
+            c_loc(qr), c_loc(nr), pqs, pqg, pdz, 0_c_int64_t, pkg, 0_c_int64_t, pts, out)
+    end if
+    call kidmp_radiometer_table_destroy(table)
+    call stop_on_error(rc, 'radiometer_batch')
+  end subroutine radiometer_batch
 
   ! A droplet number per column (kidmp_set_column_nc): column i of every following batched call uses Nt_c =
   ! set_nc_col(i)*1.e6 (M:381) in place of the namelist's set_Nc -- an Nd ensemble, or an aerosol gradient along x, in

@@ -671,6 +671,23 @@ class ThompsonMP:
         from .mie import mie_radar_host
         return mie_radar_host(self, table, st, dz, w, k_gas, want, out)
 
+    def radiometer_table(self, cfg=None, grids=None):
+        """The radiometer's rows of rain, snow and graupel for one wavelength on this context's device
+        (include/kidmp_radiometer.h): a kid_amd.radiometer.RadiometerTable."""
+        from .radiometer import RadiometerTable
+        return RadiometerTable(self, cfg, grids)
+
+    def radiometer(self, table, st, dz=None, k_gas=None, t_sfc=None, rcfg=None, want=("tb_toa",), out=None, stream=None):
+        """Two-stream brightness temperatures at the table's wavelength, seen from the ground and from orbit:
+        kid_amd.radiometer.radiometer on this context."""
+        from .radiometer import radiometer
+        return radiometer(self, table, st, dz, k_gas, t_sfc, rcfg, want, out, stream)
+
+    def radiometer_host(self, table, st, dz=None, k_gas=None, t_sfc=None, rcfg=None, want=("tb_toa",), out=None):
+        """radiometer on numpy arrays: kid_amd.radiometer.radiometer_host on this context."""
+        from .radiometer import radiometer_host
+        return radiometer_host(self, table, st, dz, k_gas, t_sfc, rcfg, want, out)
+
     REFL_NAMES = ("t", "p", "qv", "qr", "nr", "qs", "qg")      # the inputs of calc_refl10cm that are read (qc1d is not)
 
     def reflectivity(self, st, out=None, stream=None):

@@ -32,57 +32,66 @@ COL_CHUNK = 2048
 CFG = dict(wavelength=3.19e-3, eps_w=complex(7.7, 14.2), eps_i=complex(3.17, 0.01), rho_w=1000.0, rho_i=917.0, kw2=0.75)
 
 
+def torch_load(c, d):
+    """The load of tests/mie_radar_ref.py in torch on device tensors [ncol, nz] (tools/bench_radiometer.py shares it):
+    (rho, species -> (present, ze, rho*q), density(x, D, dD) -> [ncol, nz, bins])."""
+    import torch
+    import doppler_ref as r
+    import refl_oracle as ro
+    t, p = d["t"], d["p"]
+    qv = torch.clamp(d["qv"], min=1e-10)
+    rho = 0.622 * p / (ro.R * t * (qv + 0.622))
+    tiny = torch.full_like(t, 1.e-22)
+    pr, ps, pg = d["qr"] > ro.R1, d["qs"] > ro.R2, d["qg"] > ro.R2
+    rr = torch.where(pr, d["qr"] * rho, ro.R1)
+    nr = torch.where(pr, torch.clamp(d["nr"] * rho, min=ro.R2), ro.R1)
+    lamr = (ro.am_r * c["crg"][2] * c["org2"] * nr / rr) ** (1. / 3.)
+    N0_r = nr * c["org2"] * lamr
+    mvd_r = torch.where(pr, 3.672 / lamr, 50.E-6)
+    ze_r = torch.where(pr, N0_r * c["crg"][3] / lamr ** 7, tiny)
+    rs = torch.where(ps, d["qs"] * rho, ro.R1)
+    tc0 = torch.clamp(t - 273.15, max=-0.1)
+    fit = lambda a, x: (a[0] + a[1] * tc0 + a[2] * x + a[3] * tc0 * x + a[4] * tc0 * tc0 + a[5] * x * x + a[6] * tc0 * tc0 * x   # noqa: E731
+                        + a[7] * tc0 * x * x + a[8] * tc0 * tc0 * tc0 + a[9] * x * x * x)
+    smob = rs * c["oams"]
+    moment = lambda x: 10.0 ** fit(ro.sa, x) * smob ** fit(ro.sb, x)   # noqa: E731
+    ze_s = torch.where(ps, (0.176 / 0.93) * (6.0 / ro.PI) * (6.0 / ro.PI) * (ro.am_s / 900.0) * (ro.am_s / 900.0) * moment(c["cse"][2]), tiny)
+    rg = torch.where(pg, d["qg"] * rho, ro.R1)
+    slw = (t < 270.65) & pr & (mvd_r > 100.E-6)
+    xslw1 = torch.where(slw, 4.01 + torch.log10(mvd_r), 0.01)
+    ygra1 = 4.31 + torch.log10(torch.clamp(rg, min=5.E-5))
+    zans1 = 3.1 + (100. / (300. * xslw1 * ygra1 / (10. / xslw1 + 1. + 0.25 * ygra1) + 30. + 10. * ygra1))
+    n0 = torch.clamp(10. ** zans1, min=ro.gonv_min, max=ro.gonv_max)
+    n0 = torch.flip(torch.cummin(torch.flip(n0, [1]), 1).values, [1])
+    lam_exp = (n0 * ro.am_g * c["cgg"][0] / rg) ** 0.25
+    lamg = lam_exp * (c["cgg"][2] * c["ogg2"] * c["ogg1"]) ** c["obmg"]
+    N0_g = n0 / (c["cgg"][1] * lam_exp) * lamg
+    ze_g = torch.where(pg, (0.176 / 0.93) * (6.0 / ro.PI) * (6.0 / ro.PI) * (ro.am_g / 900.0) * (ro.am_g / 900.0)
+                       * N0_g * c["cgg"][3] * (1. / lamg) ** 7, tiny)
+    ratio = smob / moment(c["cse"][0])
+
+    def density(x, D, dD):
+        if x == "s":
+            q = ratio[..., None]
+            return (smob * ratio ** 3)[..., None] * (r.Kap0 * torch.exp(-q * r.Lam0 * D) + r.Kap1 * q ** r.mu_s * D ** r.mu_s * torch.exp(-q * r.Lam1 * D)) * dD
+        N0, lam = (N0_r, lamr) if x == "r" else (N0_g, lamg)
+        return N0[..., None] * torch.exp(-lam[..., None] * D) * dD
+
+    return rho, {"r": (pr, ze_r, rr), "s": (ps, ze_s, rs), "g": (pg, ze_g, rg)}, density
+
+
 def torch_composite(c, dev, table, kc, rho_w):
     """tests/mie_radar_ref.py in torch, on device tensors [ncol, nz]: mie_x, ext (no gas) and dbz."""
     import torch
-    import doppler_ref as r
     import refl_oracle as ro
     out = {n: torch.empty_like(dev["t"]) for n in ("mie_r", "mie_s", "mie_g", "ext", "dbz")}
     ncol = dev["t"].shape[0]
     for lo in range(0, ncol, COL_CHUNK):
         d = {k: v[lo:lo + COL_CHUNK] for k, v in dev.items()}
-        t, p = d["t"], d["p"]
-        qv = torch.clamp(d["qv"], min=1e-10)
-        rho = 0.622 * p / (ro.R * t * (qv + 0.622))
-        tiny = torch.full_like(t, 1.e-22)
-        pr, ps, pg = d["qr"] > ro.R1, d["qs"] > ro.R2, d["qg"] > ro.R2
-        rr = torch.where(pr, d["qr"] * rho, ro.R1)
-        nr = torch.where(pr, torch.clamp(d["nr"] * rho, min=ro.R2), ro.R1)
-        lamr = (ro.am_r * c["crg"][2] * c["org2"] * nr / rr) ** (1. / 3.)
-        N0_r = nr * c["org2"] * lamr
-        mvd_r = torch.where(pr, 3.672 / lamr, 50.E-6)
-        ze_r = torch.where(pr, N0_r * c["crg"][3] / lamr ** 7, tiny)
-        rs = torch.where(ps, d["qs"] * rho, ro.R1)
-        tc0 = torch.clamp(t - 273.15, max=-0.1)
-        fit = lambda a, x: (a[0] + a[1] * tc0 + a[2] * x + a[3] * tc0 * x + a[4] * tc0 * tc0 + a[5] * x * x + a[6] * tc0 * tc0 * x   # noqa: E731
-                            + a[7] * tc0 * x * x + a[8] * tc0 * tc0 * tc0 + a[9] * x * x * x)
-        smob = rs * c["oams"]
-        moment = lambda x: 10.0 ** fit(ro.sa, x) * smob ** fit(ro.sb, x)   # noqa: E731
-        ze_s = torch.where(ps, (0.176 / 0.93) * (6.0 / ro.PI) * (6.0 / ro.PI) * (ro.am_s / 900.0) * (ro.am_s / 900.0) * moment(c["cse"][2]), tiny)
-        rg = torch.where(pg, d["qg"] * rho, ro.R1)
-        slw = (t < 270.65) & pr & (mvd_r > 100.E-6)
-        xslw1 = torch.where(slw, 4.01 + torch.log10(mvd_r), 0.01)
-        ygra1 = 4.31 + torch.log10(torch.clamp(rg, min=5.E-5))
-        zans1 = 3.1 + (100. / (300. * xslw1 * ygra1 / (10. / xslw1 + 1. + 0.25 * ygra1) + 30. + 10. * ygra1))
-        n0 = torch.clamp(10. ** zans1, min=ro.gonv_min, max=ro.gonv_max)
-        n0 = torch.flip(torch.cummin(torch.flip(n0, [1]), 1).values, [1])
-        lam_exp = (n0 * ro.am_g * c["cgg"][0] / rg) ** 0.25
-        lamg = lam_exp * (c["cgg"][2] * c["ogg2"] * c["ogg1"]) ** c["obmg"]
-        N0_g = n0 / (c["cgg"][1] * lam_exp) * lamg
-        ze_g = torch.where(pg, (0.176 / 0.93) * (6.0 / ro.PI) * (6.0 / ro.PI) * (ro.am_g / 900.0) * (ro.am_g / 900.0)
-                           * N0_g * c["cgg"][3] * (1. / lamg) ** 7, tiny)
-        ratio = smob / moment(c["cse"][0])
-
-        def density(x, D, dD):
-            if x == "s":
-                q = ratio[..., None]
-                return (smob * ratio ** 3)[..., None] * (r.Kap0 * torch.exp(-q * r.Lam0 * D) + r.Kap1 * q ** r.mu_s * D ** r.mu_s * torch.exp(-q * r.Lam1 * D)) * dD
-            N0, lam = (N0_r, lamr) if x == "r" else (N0_g, lamg)
-            return N0[..., None] * torch.exp(-lam[..., None] * D) * dD
-
-        ext = torch.zeros_like(t)
+        rho, species, density = torch_load(c, d)
+        ext = torch.zeros_like(rho)
         zp = {}
-        for x, has, ze, rq in (("r", pr, ze_r, rr), ("s", ps, ze_s, rs), ("g", pg, ze_g, rg)):
+        for x, (has, ze, rq) in species.items():
             D, dD, rows = table[x]
             n = torch.where(has[..., None], density(x, D, dD), 0.0)
             A, B, E, M = ((n * rows[i]).sum(dim=2) for i in range(4))
