@@ -159,10 +159,11 @@ inline bool mie_efficiencies(double x, double m_re, double m_im, MieEff &e)
     return true;
 }
 
-// the refractive index of the species' particle of diameter D
-inline BBComplex mie_index(const MieCfg &c, int species, double D, double mass)
+// the permittivity of the species' particle of diameter D: water, or the soft particle's Maxwell-Garnett ice in air
+// (kidmp_spheroid.h takes it from here too)
+inline BBComplex mie_permittivity(const MieCfg &c, int species, double D, double mass)
 {
-    if (species == MIE_RAIN) return mie_sqrt(c.eps_w);
+    if (species == MIE_RAIN) return c.eps_w;
     const double PI_6 = PI / 6.0;
     const double sphere = PI_6 * D * D * D;
     const double vi = mass / c.rho_i;
@@ -170,8 +171,11 @@ inline BBComplex mie_index(const MieCfg &c, int species, double D, double mass)
     const BBComplex k = bb_K(c.eps_i);
     const BBComplex fk = {f * k.re, f * k.im};
     const BBComplex num = {1. + 2. * fk.re, 2. * fk.im}, den = {1. - fk.re, -fk.im};
-    return mie_sqrt(bb_div(num, den));
+    return bb_div(num, den);
 }
+// the refractive index of the species' particle of diameter D
+inline BBComplex mie_index(const MieCfg &c, int species, double D, double mass)
+{ return mie_sqrt(mie_permittivity(c, species, D, mass)); }
 
 // rows[r*nb + b], r = s_mie, s_ray, s_ext, mass, v0, of the nb diameters D.  False: an unknown species, a D that is not
 // finite or not above 0, or a sphere that mie_sphere refuses; the rows are then unspecified.

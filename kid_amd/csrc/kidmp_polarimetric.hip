@@ -1,0 +1,264 @@
+// kidmp_polarimetric.hip -- the entries of include/kidmp_polarimetric.h: the spheroid and the per-bin rows on the host
+// (kidmp_spheroid.h), the table object that carries them and the uniform species' scalars to the device, and the
+// polarimetric radar of device arrays in one launch of k_polarimetric (thompson_reflectivity.hip) or of host arrays in
+// chunks through the context's staging memory.
+#include <cmath>
+#include <cstddef>
+
+#include "kidmp_mie_table.h"
+#include "kidmp_spheroid.h"
+#include "../../include/kidmp_polarimetric.h"
+
+using namespace kidmp;
+
+static_assert(sizeof(kidmp_pol_out) == POL_NOUT * sizeof(double *) && sizeof(kidmp32_pol_out) == POL_NOUT * sizeof(float *)
+                  && POL_NROWS == KIDMP_POL_NROWS && POL_ROWS == KIDMP_POL_NROWS && POL_NSCAL == KIDMP_POL_NSCALARS
+                  && sizeof(kidmp_pol_cfg) == 12 * sizeof(double) && offsetof(kidmp_pol_cfg, force_quadrature) == 11 * sizeof(double),
+              "include/kidmp_polarimetric.h");
+
+// the Mie table's buffer with seven rows per bin, and per species the flag and the scalars of a uniform one
+struct kidmp_pol_table : kidmp::MieTableData {
+    kidmp_pol_cfg pol;
+    int32_t uniform[MIE_NSPEC];
+    double scal[MIE_NSPEC][POL_NSCAL];
+    double kfac;                                              // 90e3 pi/lambda: degrees per km
+};
+
+namespace {
+constexpr int NIN = 7, NREQ = 5;                              // t, p, qv, qr, nr | qs, qg
+const char *const IN_NAMES[NIN] = {"t", "p", "qv", "qr", "nr", "qs", "qg"};
+const char *const OUT_NAMES[POL_NOUT] = {"dbz_h", "zdr", "kdp", "rhohv", "dbz_h_r", "dbz_h_s", "dbz_h_g", "zdr_r", "zdr_s", "zdr_g",
+                                         "kdp_r", "kdp_s", "kdp_g"};
+
+PolCfg pol_model_cfg(const kidmp_pol_cfg &g)
+{
+    return PolCfg{{g.axis_r[0], g.axis_r[1], g.axis_r[2], g.axis_r[3], g.axis_r[4]}, g.axis_r_min, g.axis_s, g.axis_g,
+                  {g.sigma[0], g.sigma[1], g.sigma[2]}, g.force_quadrature};
+}
+
+template <class T> struct PolCall {
+    const T *in[NIN];
+    T *out[POL_NOUT];
+};
+template <class T, class O>
+PolCall<T> pol_call(const T *t, const T *p, const T *qv, const T *qr, const T *nr, const T *qs, const T *qg, const O *out)
+{
+    PolCall<T> c{{t, p, qv, qr, nr, qs, qg}, {}};
+    if (out) {
+        T *const o[POL_NOUT] = {out->dbz_h, out->zdr, out->kdp, out->rhohv, out->dbz_h_r, out->dbz_h_s, out->dbz_h_g, out->zdr_r, out->zdr_s,
+                                out->zdr_g, out->kdp_r, out->kdp_s, out->kdp_g};
+        for (int v = 0; v < POL_NOUT; ++v) c.out[v] = o[v];
+    }
+    return c;
+}
+
+// what the device and the host entries check alike, before anything is touched
+template <class T>
+int check_pol(kidmp_ctx *ctx, const char *who, const kidmp_pol_table *tab, int64_t ncol, int32_t nz, const PolCall<T> &a)
+{
+    const std::string w(who);
+    if (int rc = require_ready(ctx)) return rc;
+    if (!tab || tab->ctx != ctx) return fail(ctx, KIDMP_EINVAL, w + ": the table is NULL or belongs to another context");
+    if (ncol < 0) return fail(ctx, KIDMP_EINVAL, w + ": ncol < 0");
+    if (nz < 2 || nz > KIDMP_MAX_NZ) return fail(ctx, KIDMP_EINVAL, w + ": nz outside [2, KIDMP_MAX_NZ]");
+    if (ncol == 0) return KIDMP_OK;                       // an empty batch has nothing to point at
+    bool any = false;
+    for (int v = 0; v < POL_NOUT; ++v) any = any || a.out[v];
+    if (!any) return fail(ctx, KIDMP_EINVAL, w + ": nothing requested: out is NULL or every member is");
+    for (int v = 0; v < NREQ; ++v)
+        if (!a.in[v]) return fail(ctx, KIDMP_EINVAL, w + ": null array argument");
+    if (!doppler_consts_supported(ctx->hc) || !spectra_consts_supported(ctx->hc))
+        return fail(ctx, KIDMP_ESTATE, w + ": exponents differ from the kernel's");
+    return KIDMP_OK;
+}
+
+// one launch over device pointers; an iiwarm context reads no snow and no graupel
+template <class T>
+hipError_t enqueue_pol(kidmp_ctx *ctx, const kidmp_pol_table *tab, int64_t ncol, int nz, const PolCall<T> &a, hipStream_t s)
+{
+    const bool warm = ctx->cfg.iiwarm != 0;
+    const T *const *q = a.in;
+    PolArgs<T> args{};
+    args.t = q[0]; args.p = q[1]; args.qv = q[2]; args.qr = q[3]; args.nr = q[4];
+    args.qs = warm ? nullptr : q[5];
+    args.qg = warm ? nullptr : q[6];
+    for (int v = 0; v < POL_NOUT; ++v) args.out[v] = a.out[v];
+    for (int x = 0; x < MIE_NSPEC; ++x) {
+        const double *b = tab->d_buf + tab->off[x];
+        args.nb[x] = tab->nb[x];
+        args.D[x] = b;
+        args.dD[x] = b + tab->nb[x];
+        args.rows[x] = b + 2 * size_t(tab->nb[x]);
+        args.uniform[x] = tab->uniform[x];
+        for (int i = 0; i < POL_NSCAL; ++i) args.scal[x][i] = tab->scal[x][i];
+    }
+    args.kfac = tab->kfac;
+    return launch_polarimetric<T>(refl_consts(ctx->hc), doppler_consts(ctx->hc), ncol, nz, args, s);
+}
+
+template <class T>
+int pol_device(kidmp_ctx *ctx, const char *who, const kidmp_pol_table *tab, int64_t ncol, int32_t nz, const PolCall<T> &a, void *stream)
+{
+    if (int rc = check_pol<T>(ctx, who, tab, ncol, nz, a)) return rc;
+    if (ncol == 0) return KIDMP_OK;
+    GUARD(ctx);
+    for (int v = 0; v < NIN; ++v)
+        if (int rc = check_device_array(ctx, who, a.in[v], IN_NAMES[v])) return rc;
+    for (int v = 0; v < POL_NOUT; ++v)
+        if (int rc = check_device_array(ctx, who, a.out[v], OUT_NAMES[v])) return rc;
+    HIPTRY(ctx, enqueue_pol<T>(ctx, tab, ncol, nz, a, (hipStream_t)stream));
+    return KIDMP_OK;
+}
+
+// host arrays: chunks of columns through the context's staging memory on its compute stream, one after the other
+// (mie_host of kidmp_mie.hip).  A column's result does not depend on its batch, so any chunking gives the same bits.
+// Only the inputs given go up and only what was asked for comes down.
+template <class T>
+int pol_host(kidmp_ctx *ctx, const char *who, const kidmp_pol_table *tab, int64_t ncol, int32_t nz, const PolCall<T> &h)
+{
+    if (int rc = check_pol<T>(ctx, who, tab, ncol, nz, h)) return rc;
+    if (ncol == 0) return KIDMP_OK;
+    GUARD(ctx);
+    const bool warm = ctx->cfg.iiwarm != 0;
+    const int64_t CH = pick_host_chunk(ctx, ncol);
+    const size_t b_prof = (size_t(CH) * size_t(nz) * sizeof(T) + 255) / 256 * 256;
+    bool up[NIN];
+    int slots = 0;
+    for (int v = 0; v < NIN; ++v) {
+        up[v] = h.in[v] && !(warm && v >= NREQ);
+        slots += up[v];
+    }
+    for (int v = 0; v < POL_NOUT; ++v) slots += h.out[v] != nullptr;
+    if (int rc = ensure_stage(ctx, size_t(slots) * b_prof)) return rc;
+    char *next = reinterpret_cast<char *>(ctx->d_stage);
+    auto slot = [&](bool wanted) { T *p = wanted ? reinterpret_cast<T *>(next) : nullptr; if (wanted) next += b_prof; return p; };
+    PolCall<T> d{};
+    for (int v = 0; v < NIN; ++v) d.in[v] = slot(up[v]);
+    for (int v = 0; v < POL_NOUT; ++v) d.out[v] = slot(h.out[v] != nullptr);
+    hipError_t e = hipSuccess;
+    for (int64_t c0 = 0; c0 < ncol && e == hipSuccess; c0 += CH) {
+        const int64_t n = c0 + CH <= ncol ? CH : ncol - c0;
+        const size_t off = size_t(c0) * size_t(nz), cnt = size_t(n) * size_t(nz);
+        for (int v = 0; v < NIN && e == hipSuccess; ++v)
+            if (up[v]) e = hipMemcpyAsync(const_cast<T *>(d.in[v]), h.in[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = enqueue_pol<T>(ctx, tab, n, nz, d, ctx->stream);
+        for (int v = 0; v < POL_NOUT && e == hipSuccess; ++v)
+            if (h.out[v]) e = hipMemcpyAsync(h.out[v] + off, d.out[v], cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(ctx->stream);        // no copy may still be in flight towards the caller's arrays
+    HIPTRY(ctx, e);
+    HIPTRY(ctx, es);
+    return KIDMP_OK;
+}
+}  // namespace
+
+extern "C" {
+void kidmp_pol_defaults(kidmp_pol_cfg *cfg)
+{
+    if (!cfg) return;
+    const PolCfg p = pol_defaults();
+    *cfg = kidmp_pol_cfg{{p.axis_r[0], p.axis_r[1], p.axis_r[2], p.axis_r[3], p.axis_r[4]}, p.axis_r_min, p.axis_s, p.axis_g,
+                         {p.sigma[0], p.sigma[1], p.sigma[2]}, 0};
+}
+
+int kidmp_pol_spheroid(double eps_re, double eps_im, double ratio, double sigma, double *rows7_per_unit_D)
+{
+    const std::string w("kidmp_pol_spheroid");
+    if (!rows7_per_unit_D) return fail(nullptr, KIDMP_EINVAL, w + ": null argument");
+    if (!(std::isfinite(eps_re) && std::isfinite(eps_im) && std::isfinite(ratio) && std::isfinite(sigma)))
+        return fail(nullptr, KIDMP_EINVAL, w + ": an argument is not finite");
+    if (eps_im < 0. || (eps_im == 0. && !(eps_re > 0.))) return fail(nullptr, KIDMP_EINVAL, w + ": Im(eps) must not be below 0 and a real permittivity must be above 0");
+    if (!(ratio > 0. && ratio <= 1.)) return fail(nullptr, KIDMP_EINVAL, w + ": ratio outside (0, 1]");
+    if (sigma < 0.) return fail(nullptr, KIDMP_EINVAL, w + ": sigma must not be below 0");
+    double r[POL_ROWS];
+    pol_spheroid(BBComplex{eps_re, eps_im}, ratio, pol_moments(sigma), 1., r);
+    r[POL_ROWS - 1] = 0.;
+    std::memcpy(rows7_per_unit_D, r, sizeof(r));
+    return KIDMP_OK;
+}
+
+int kidmp_pol_bins(const kidmp_mie_cfg *mie_cfg, const kidmp_pol_cfg *pol_cfg, int32_t species, int32_t nb, const double *D, double *rows)
+{
+    const std::string w("kidmp_pol_bins");
+    if (!mie_cfg || !pol_cfg || !D || !rows) return fail(nullptr, KIDMP_EINVAL, w + ": null argument");
+    if (const char *bad = mie_bad_cfg(*mie_cfg)) return fail(nullptr, KIDMP_EINVAL, w + ": " + bad);
+    const PolCfg pc = pol_model_cfg(*pol_cfg);
+    if (const char *bad = pol_bad_cfg(pc)) return fail(nullptr, KIDMP_EINVAL, w + ": " + bad);
+    if (species < 0 || species >= MIE_NSPEC) return fail(nullptr, KIDMP_EINVAL, w + ": unknown species");
+    if (nb < 1) return fail(nullptr, KIDMP_EINVAL, w + ": nb < 1");
+    std::vector<double> r(size_t(POL_ROWS) * size_t(nb));
+    if (!pol_bins(mie_model_cfg(*mie_cfg), pc, species, nb, D, r.data()))
+        return fail(nullptr, KIDMP_EINVAL, w + ": a diameter is not finite or not above 0");
+    std::memcpy(rows, r.data(), r.size() * sizeof(double));
+    return KIDMP_OK;
+}
+
+int kidmp_pol_table_create(kidmp_ctx *ctx, const kidmp_mie_cfg *mie_cfg, const kidmp_pol_cfg *pol_cfg, const kidmp_mie_grids *grids,
+                           kidmp_pol_table **table)
+{
+    const std::string w("kidmp_pol_table_create");
+    if (table) *table = nullptr;
+    if (int rc = require_ready(ctx)) return rc;
+    if (!table) return fail(ctx, KIDMP_EINVAL, w + ": null argument");
+    kidmp_pol_cfg g;
+    if (pol_cfg) g = *pol_cfg;
+    else kidmp_pol_defaults(&g);
+    const PolCfg pc = pol_model_cfg(g);
+    if (const char *bad = pol_bad_cfg(pc)) return fail(ctx, KIDMP_EINVAL, w + ": " + bad);
+    MieTableData d;
+    const auto bins = [&](const MieCfg &mc, int x, int nb, const double *D, double *rows) { return pol_bins(mc, pc, x, nb, D, rows); };
+    if (int rc = mie_table_build(ctx, w, mie_cfg, grids, POL_ROWS, bins, &d)) return rc;
+    kidmp_pol_table *t = new kidmp_pol_table;
+    static_cast<MieTableData &>(*t) = d;
+    t->pol = g;
+    t->kfac = (90.e3 * MIE_PI) / d.cfg.wavelength;
+    // the scalars: the ratios of the rows of the species' first bin, formed as the table's own first bin was
+    const MieCfg mc = mie_model_cfg(d.cfg);
+    for (int x = 0; x < MIE_NSPEC; ++x) {
+        const double D0 = grids && grids->D[x] ? grids->D[x][0] : mie_bins_D(ctx->hb, x)[0];
+        double r[POL_ROWS];
+        (void)pol_bins(mc, pc, x, 1, &D0, r);
+        t->uniform[x] = !g.force_quadrature && pol_uniform(x) ? 1 : 0;
+        for (int i = 0; i < 4; ++i) t->scal[x][i] = r[i] / r[4];
+        t->scal[x][4] = r[5] / r[6];
+    }
+    *table = t;
+    return KIDMP_OK;
+}
+
+void kidmp_pol_table_destroy(kidmp_pol_table *table)
+{
+    if (!table) return;
+    mie_table_free(table);
+    delete table;
+}
+
+int kidmp_pol_table_get(const kidmp_pol_table *table, int32_t species, int32_t *nb, double *D, double *dD, double *rows,
+                        kidmp_mie_cfg *mie_cfg, kidmp_pol_cfg *pol_cfg, int32_t *uniform, double *scalars)
+{
+    const std::string w("kidmp_pol_table_get");
+    if (!table) return fail(nullptr, KIDMP_EINVAL, w + ": null table");
+    if (int rc = mie_table_read(table, w, species, nb, D, dD, rows, mie_cfg)) return rc;
+    if (pol_cfg) *pol_cfg = table->pol;
+    if (uniform) *uniform = table->uniform[species];
+    if (scalars) std::memcpy(scalars, table->scal[species], sizeof(table->scal[species]));
+    return KIDMP_OK;
+}
+
+int kidmp_polarimetric_device(kidmp_ctx *ctx, const kidmp_pol_table *table, int64_t ncol, int32_t nz, const double *t, const double *p,
+                              const double *qv, const double *qr, const double *nr, const double *qs, const double *qg,
+                              const kidmp_pol_out *out, void *stream)
+{ return pol_device<double>(ctx, "kidmp_polarimetric_device", table, ncol, nz, pol_call<double>(t, p, qv, qr, nr, qs, qg, out), stream); }
+int kidmp32_polarimetric_device(kidmp_ctx *ctx, const kidmp_pol_table *table, int64_t ncol, int32_t nz, const float *t, const float *p,
+                                const float *qv, const float *qr, const float *nr, const float *qs, const float *qg,
+                                const kidmp32_pol_out *out, void *stream)
+{ return pol_device<float>(ctx, "kidmp32_polarimetric_device", table, ncol, nz, pol_call<float>(t, p, qv, qr, nr, qs, qg, out), stream); }
+int kidmp_polarimetric_host(kidmp_ctx *ctx, const kidmp_pol_table *table, int64_t ncol, int32_t nz, const double *t, const double *p,
+                            const double *qv, const double *qr, const double *nr, const double *qs, const double *qg,
+                            const kidmp_pol_out *out)
+{ return pol_host<double>(ctx, "kidmp_polarimetric_host", table, ncol, nz, pol_call<double>(t, p, qv, qr, nr, qs, qg, out)); }
+int kidmp32_polarimetric_host(kidmp_ctx *ctx, const kidmp_pol_table *table, int64_t ncol, int32_t nz, const float *t, const float *p,
+                              const float *qv, const float *qr, const float *nr, const float *qs, const float *qg,
+                              const kidmp32_pol_out *out)
+{ return pol_host<float>(ctx, "kidmp32_polarimetric_host", table, ncol, nz, pol_call<float>(t, p, qv, qr, nr, qs, qg, out)); }
+}  // extern "C"

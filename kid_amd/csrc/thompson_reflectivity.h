@@ -202,4 +202,24 @@ template <class T>
 hipError_t launch_radiometer(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const RadiometerArgs<T> &a,
                              hipStream_t stream);
 
+// The polarimetric radar (include/kidmp_polarimetric.h): Z_DR, K_DP and rho_hv of oblate spheroids from k_mie_radar's load
+// and a table of seven rows per diameter bin (s_h, s_v, c_re, c_im, s_0, k, mass).  Null means: qs, qg -- zero; an output
+// -- not wanted.  out in the order of kidmp_pol_out.  uniform[x] != 0: the species walks no bins and takes scal[x] (s_h/s_0,
+// s_v/s_0, c_re/s_0, c_im/s_0, k/mass) in place of the ratios of its sums; its D, dD, rows and nb are not read.
+// kfac: 90e3 pi/lambda.  One launch; lanes over levels, a loop over the bins.
+constexpr int POL_NOUT = 13, POL_NROWS = 7, POL_NSCAL = 5;
+constexpr int POL_DBZ_H = 0, POL_ZDR = 1, POL_KDP = 2, POL_RHOHV = 3, POL_DBZ_H_X = 4, POL_ZDR_X = 7, POL_KDP_X = 10;
+template <class T> struct PolArgs {
+    const T *t, *p, *qv, *qr, *nr, *qs, *qg;
+    T *out[POL_NOUT];
+    const double *D[MIE_NSPEC], *dD[MIE_NSPEC], *rows[MIE_NSPEC];
+    int32_t nb[MIE_NSPEC];
+    int32_t uniform[MIE_NSPEC];
+    double scal[MIE_NSPEC][POL_NSCAL];
+    double kfac;
+};
+template <class T>
+hipError_t launch_polarimetric(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const PolArgs<T> &a,
+                               hipStream_t stream);
+
 }  // namespace kidmp

@@ -66,6 +66,7 @@ module module_mp_thompson09n
   public :: doppler_spectrum_batch
   public :: bright_band_batch
   public :: mie_radar_batch
+  public :: polarimetric_batch
   public :: radiometer_batch
   public :: lidar_profiles_batch
   public :: mp_thompson_kid_interface, mp_thompson_kid_staging
@@ -147,6 +148,13 @@ module module_mp_thompson09n
   type, bind(C) :: kidmp_mie_cfg                         ! kidmp_mie_cfg; kidmp_mie_defaults fills it
      real(c_double) :: wavelength, eps_w_re, eps_w_im, eps_i_re, eps_i_im, rho_w, rho_i, kw2
   end type kidmp_mie_cfg
+  type, bind(C) :: kidmp_pol_out                         ! kidmp_pol_out / kidmp32_pol_out: NULL = not wanted
+     type(c_ptr) :: dbz_h, zdr, kdp, rhohv, dbz_h_r, dbz_h_s, dbz_h_g, zdr_r, zdr_s, zdr_g, kdp_r, kdp_s, kdp_g
+  end type kidmp_pol_out
+  type, bind(C) :: kidmp_pol_cfg                         ! kidmp_pol_cfg; kidmp_pol_defaults fills it
+     real(c_double) :: axis_r(5), axis_r_min, axis_s, axis_g, sigma(3)
+     integer(c_int32_t) :: force_quadrature
+  end type kidmp_pol_cfg
   type, bind(C) :: kidmp_radiometer_out                  ! kidmp_radiometer_out / kidmp32_radiometer_out: NULL = not wanted
      type(c_ptr) :: k_abs, k_bsc, refl, trans, tb_up, tb_down, tb_toa, tb_ground, tau_abs
   end type kidmp_radiometer_out
@@ -554,6 +562,42 @@ module module_mp_thompson09n
        type(c_ptr), value :: t_sfc
        type(kidmp_radiometer_out), intent(in) :: out
      end function kidmp32_radiometer_host
+     ! the polarimetric radar (include/kidmp_polarimetric.h): a table of seven rows per bin, then the operator; qs and qg
+     ! may be NULL
+     subroutine kidmp_pol_defaults(pcfg) bind(C, name='kidmp_pol_defaults')
+       import :: kidmp_pol_cfg
+       type(kidmp_pol_cfg), intent(out) :: pcfg
+     end subroutine kidmp_pol_defaults
+     integer(c_int) function kidmp_pol_table_create(ctx, cfg, pcfg, grids, table) bind(C, name='kidmp_pol_table_create')
+       import :: c_int, c_ptr, kidmp_mie_cfg, kidmp_pol_cfg
+       type(c_ptr), value :: ctx
+       type(kidmp_mie_cfg), intent(in) :: cfg
+       type(kidmp_pol_cfg), intent(in) :: pcfg
+       type(c_ptr), value :: grids
+       type(c_ptr), intent(out) :: table
+     end function kidmp_pol_table_create
+     subroutine kidmp_pol_table_destroy(table) bind(C, name='kidmp_pol_table_destroy')
+       import :: c_ptr
+       type(c_ptr), value :: table
+     end subroutine kidmp_pol_table_destroy
+     integer(c_int) function kidmp_polarimetric_host(ctx, table, ncol, nz, t, p, qv, qr, nr, qs, qg, out) &
+          bind(C, name='kidmp_polarimetric_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr, kidmp_pol_out
+       type(c_ptr), value :: ctx, table
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qr, nr, qs, qg
+       type(kidmp_pol_out), intent(in) :: out
+     end function kidmp_polarimetric_host
+     integer(c_int) function kidmp32_polarimetric_host(ctx, table, ncol, nz, t, p, qv, qr, nr, qs, qg, out) &
+          bind(C, name='kidmp32_polarimetric_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr, kidmp_pol_out
+       type(c_ptr), value :: ctx, table
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qr, nr, qs, qg
+       type(kidmp_pol_out), intent(in) :: out
+     end function kidmp32_polarimetric_host
   end interface
 
 contains
@@ -1430,6 +1474,82 @@ contains
     call kidmp_radiometer_table_destroy(table)
     call stop_on_error(rc, 'radiometer_batch')
   end subroutine radiometer_batch
+
+  ! The polarimetric radar over ncol columns of KiD's (nz, ncol) storage in one call (include/kidmp_polarimetric.h): the
+  ! reflectivity at horizontal polarisation dbz_h (dBZ), the differential reflectivity zdr (dB), the specific differential
+  ! phase kdp (degrees per km) and the co-polar correlation rhohv of oblate spheroids in the Rayleigh-Gans approximation,
+  ! with the parts of rain, snow and graupel, all (nz, ncol) in the array kind the arithmetic stores.  Every output is
+  ! optional; at least one must be present.  The wavelength, the permittivities and the densities keep kidmp_mie_defaults'
+  ! 10 cm when left out; the axis ratios (axis_r(5) the coefficients of rain's law in mm, axis_r_min, axis_s, axis_g), the
+  ! canting widths sigma(3) in radians and force_quadrature keep kidmp_pol_defaults' illustrative values.  The table on the
+  ! scheme's own bins is built for the call and freed after it.  qs, qg (nz, ncol) left out mean zero.  The inputs are not
+  ! changed.  Default REAL 8 goes to kidmp_polarimetric_host, REAL 4 to kidmp32_...
+  subroutine polarimetric_batch(ncol, nz, t, p, qv, qr, nr, dbz_h, zdr, kdp, rhohv, dbz_h_r, dbz_h_s, dbz_h_g, zdr_r, zdr_s, &
+       zdr_g, kdp_r, kdp_s, kdp_g, qs, qg, wavelength, eps_w_re, eps_w_im, eps_i_re, eps_i_im, rho_w, rho_i, axis_r, &
+       axis_r_min, axis_s, axis_g, sigma, force_quadrature)
+    integer, intent(in) :: ncol, nz
+    real, dimension(nz,ncol), intent(in), target :: t, p, qv, qr, nr
+    real, dimension(nz,ncol), intent(out), optional, target :: dbz_h, zdr, kdp, rhohv, dbz_h_r, dbz_h_s, dbz_h_g, zdr_r, zdr_s, &
+         zdr_g, kdp_r, kdp_s, kdp_g
+    real, dimension(nz,ncol), intent(in), optional, target :: qs, qg
+    real(c_double), intent(in), optional :: wavelength, eps_w_re, eps_w_im, eps_i_re, eps_i_im, rho_w, rho_i
+    real(c_double), intent(in), optional :: axis_r(5), axis_r_min, axis_s, axis_g, sigma(3)
+    logical, intent(in), optional :: force_quadrature
+    type(kidmp_pol_out) :: out
+    type(kidmp_mie_cfg) :: cfg
+    type(kidmp_pol_cfg) :: pcfg
+    type(c_ptr) :: table, pqs, pqg
+    integer(c_int) :: rc
+    if (.not. c_associated(ctx)) call thompson_init
+    if (c_associated(mctx)) then
+       write(*,'(a)') ' module_mp_thompson09n: the polarimetric radar is not available with kidmp_ndevices > 1'
+       stop 1
+    end if
+    call kidmp_mie_defaults(cfg)
+    if (present(wavelength)) cfg%wavelength = wavelength
+    if (present(eps_w_re)) cfg%eps_w_re = eps_w_re
+    if (present(eps_w_im)) cfg%eps_w_im = eps_w_im
+    if (present(eps_i_re)) cfg%eps_i_re = eps_i_re
+    if (present(eps_i_im)) cfg%eps_i_im = eps_i_im
+    if (present(rho_w)) cfg%rho_w = rho_w
+    if (present(rho_i)) cfg%rho_i = rho_i
+    call kidmp_pol_defaults(pcfg)
+    if (present(axis_r)) pcfg%axis_r = axis_r
+    if (present(axis_r_min)) pcfg%axis_r_min = axis_r_min
+    if (present(axis_s)) pcfg%axis_s = axis_s
+    if (present(axis_g)) pcfg%axis_g = axis_g
+    if (present(sigma)) pcfg%sigma = sigma
+    if (present(force_quadrature)) pcfg%force_quadrature = merge(1_c_int32_t, 0_c_int32_t, force_quadrature)
+    pqs = c_null_ptr;  pqg = c_null_ptr
+    if (present(qs)) pqs = c_loc(qs)
+    if (present(qg)) pqg = c_loc(qg)
+    out = kidmp_pol_out(c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
+         c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr)
+    if (present(dbz_h)) out%dbz_h = c_loc(dbz_h)
+    if (present(zdr)) out%zdr = c_loc(zdr)
+    if (present(kdp)) out%kdp = c_loc(kdp)
+    if (present(rhohv)) out%rhohv = c_loc(rhohv)
+    if (present(dbz_h_r)) out%dbz_h_r = c_loc(dbz_h_r)
+    if (present(dbz_h_s)) out%dbz_h_s = c_loc(dbz_h_s)
+    if (present(dbz_h_g)) out%dbz_h_g = c_loc(dbz_h_g)
+    if (present(zdr_r)) out%zdr_r = c_loc(zdr_r)
+    if (present(zdr_s)) out%zdr_s = c_loc(zdr_s)
+    if (present(zdr_g)) out%zdr_g = c_loc(zdr_g)
+    if (present(kdp_r)) out%kdp_r = c_loc(kdp_r)
+    if (present(kdp_s)) out%kdp_s = c_loc(kdp_s)
+    if (present(kdp_g)) out%kdp_g = c_loc(kdp_g)
+    rc = kidmp_pol_table_create(ctx, cfg, pcfg, c_null_ptr, table)
+    call stop_on_error(rc, 'polarimetric_batch (table)')
+    if (kind(t) == c_double) then
+       rc = kidmp_polarimetric_host(ctx, table, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), &
+            c_loc(qr), c_loc(nr), pqs, pqg, out)
+    else
+       rc = kidmp32_polarimetric_host(ctx, table, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), c_loc(qv), &
+            c_loc(qr), c_loc(nr), pqs, pqg, out)
+    end if
+    call kidmp_pol_table_destroy(table)
+    call stop_on_error(rc, 'polarimetric_batch')
+  end subroutine polarimetric_batch
 
   ! A droplet number per column (kidmp_set_column_nc): column i of every following batched call uses Nt_c =
   ! set_nc_col(i)*1.e6 (M:381) in place of the namelist's set_Nc -- an Nd ensemble, or an aerosol gradient along x, in

@@ -671,6 +671,23 @@ class ThompsonMP:
         from .mie import mie_radar_host
         return mie_radar_host(self, table, st, dz, w, k_gas, want, out)
 
+    def pol_table(self, mie_cfg=None, pol_cfg=None, grids=None):
+        """The spheroid rows of rain, snow and graupel on this context's device (include/kidmp_polarimetric.h): a
+        kid_amd.polarimetric.PolTable."""
+        from .polarimetric import PolTable
+        return PolTable(self, mie_cfg, pol_cfg, grids)
+
+    def polarimetric(self, table, st, want=("dbz_h", "zdr", "kdp", "rhohv"), out=None, stream=None):
+        """Z_DR, K_DP, rho_hv and the reflectivity at horizontal polarisation of oblate spheroids:
+        kid_amd.polarimetric.polarimetric on this context."""
+        from .polarimetric import polarimetric
+        return polarimetric(self, table, st, want, out, stream)
+
+    def polarimetric_host(self, table, st, want=("dbz_h", "zdr", "kdp", "rhohv"), out=None):
+        """polarimetric on numpy arrays: kid_amd.polarimetric.polarimetric_host on this context."""
+        from .polarimetric import polarimetric_host
+        return polarimetric_host(self, table, st, want, out)
+
     def radiometer_table(self, cfg=None, grids=None):
         """The radiometer's rows of rain, snow and graupel for one wavelength on this context's device
         (include/kidmp_radiometer.h): a kid_amd.radiometer.RadiometerTable."""
