@@ -60,8 +60,8 @@
  *             were requested.
  *
  * Not modelled: the Planck function, polarisation and view angles beyond mu, cloud ice, melting particles,
- * temperature-dependent permittivities and any gas absorption model (the caller passes k_gas), several channels in one
- * launch.
+ * temperature-dependent permittivities and any gas absorption model (the caller passes k_gas).  Several channels in one
+ * launch: kidmp_multichannel.h.
  */
 #ifndef KIDMP_RADIOMETER_H
 #define KIDMP_RADIOMETER_H

@@ -16,6 +16,7 @@ from .mie import MIE_INPUTS, MIE_NAMES, MIE_ROWS, MIE_SPECIES, MieCfg, MieTable,
 # (the function radiometer.radiometer is not re-exported: the name is the submodule's; ThompsonMP.radiometer calls it)
 from .radiometer import (RADIOMETER_INPUTS, RADIOMETER_NAMES, RADIOMETER_ROWS, RADIOMETER_SUMMARY_NAMES, RadiometerCfg, RadiometerTable,  # noqa: F401
                          radiometer_bins, radiometer_host, radiometer_sphere)
+from .multichannel import MAX_CHANNELS, mie_radar_multi, mie_radar_multi_host, multichannel_tile, radiometer_multi, radiometer_multi_host  # noqa: F401
 # (the function polarimetric.polarimetric is not re-exported either: ThompsonMP.polarimetric calls it)
 from .polarimetric import POL_INPUTS, POL_NAMES, POL_ROWS, POL_SCALARS, PolCfg, PolTable, pol_bins, pol_spheroid, polarimetric_host  # noqa: F401
 from .dspectrum import DSPECTRUM_INPUTS, DSPECTRUM_NAMES, doppler_spectrum, doppler_spectrum_host, velocity_grid  # noqa: F401

@@ -4,7 +4,7 @@
 #include <cmath>
 #include <cstddef>
 
-#include "kidmp_mie_table.h"
+#include "kidmp_channel_call.h"
 
 using namespace kidmp;
 
@@ -14,61 +14,7 @@ static_assert(sizeof(kidmp_mie_out) == (MIE_NOUT + 1) * sizeof(double *) && size
                   && MIE_RAIN == KIDMP_MIE_R && MIE_SNOW == KIDMP_MIE_S && MIE_GRAUPEL == KIDMP_MIE_G,
               "include/kidmp_mie.h");
 
-// one device buffer: per species D[nb], dD[nb], rows[MIE_NROWS][nb]
-struct kidmp_mie_table : kidmp::MieTableData {};
-
 namespace {
-constexpr int NIN = 8, NREQ = 5;                          // t, p, qv, qr, nr | qc, qs, qg
-const char *const IN_NAMES[NIN] = {"t", "p", "qv", "qr", "nr", "qc", "qs", "qg"};
-const char *const OUT_NAMES[MIE_NOUT] = {"dbz", "dbz_up", "dbz_down", "dbz_r", "dbz_s", "dbz_g", "mie_r", "mie_s", "mie_g", "ext",
-                                         "pia_up", "pia_down", "vd"};
-
-template <class T> struct MieCall {
-    const T *in[NIN];
-    const T *dz, *w, *k_gas;
-    int64_t dz_col_stride, k_gas_col_stride;
-    T *out[MIE_NOUT];
-    T *pia_total;
-};
-template <class T, class O>
-MieCall<T> mie_call(const T *t, const T *p, const T *qv, const T *qc, const T *qr, const T *nr, const T *qs, const T *qg, const T *dz,
-                    int64_t dz_col_stride, const T *w, const T *k_gas, int64_t k_gas_col_stride, const O *out)
-{
-    MieCall<T> c{{t, p, qv, qr, nr, qc, qs, qg}, dz, w, k_gas, dz_col_stride, k_gas_col_stride, {}, nullptr};
-    if (out) {
-        T *const o[MIE_NOUT] = {out->dbz, out->dbz_up, out->dbz_down, out->dbz_r, out->dbz_s, out->dbz_g, out->mie_r, out->mie_s, out->mie_g,
-                                out->ext, out->pia_up, out->pia_down, out->vd};
-        for (int v = 0; v < MIE_NOUT; ++v) c.out[v] = o[v];
-        c.pia_total = out->pia_total;
-    }
-    return c;
-}
-template <class T> bool needs_path(const MieCall<T> &a)
-{ return a.out[MIE_DBZ_UP] || a.out[MIE_DBZ_DOWN] || a.out[MIE_PIA_UP] || a.out[MIE_PIA_DOWN] || a.pia_total; }
-
-// what the device and the host entries check alike, before anything is touched
-template <class T>
-int check_mie(kidmp_ctx *ctx, const char *who, const kidmp_mie_table *tab, int64_t ncol, int32_t nz, const MieCall<T> &a)
-{
-    const std::string w(who);
-    if (int rc = require_ready(ctx)) return rc;
-    if (!tab || tab->ctx != ctx) return fail(ctx, KIDMP_EINVAL, w + ": the table is NULL or belongs to another context");
-    if (ncol < 0) return fail(ctx, KIDMP_EINVAL, w + ": ncol < 0");
-    if (nz < 2 || nz > KIDMP_MAX_NZ) return fail(ctx, KIDMP_EINVAL, w + ": nz outside [2, KIDMP_MAX_NZ]");
-    if (a.dz_col_stride != 0 && a.dz_col_stride < nz) return fail(ctx, KIDMP_EINVAL, w + ": dz_col_stride must be 0 or >= nz");
-    if (a.k_gas_col_stride != 0 && a.k_gas_col_stride < nz) return fail(ctx, KIDMP_EINVAL, w + ": k_gas_col_stride must be 0 or >= nz");
-    if (ncol == 0) return KIDMP_OK;                       // an empty batch has nothing to point at
-    bool any = a.pia_total != nullptr;
-    for (int v = 0; v < MIE_NOUT; ++v) any = any || a.out[v];
-    if (!any) return fail(ctx, KIDMP_EINVAL, w + ": nothing requested: out is NULL or every member is");
-    for (int v = 0; v < NREQ; ++v)
-        if (!a.in[v]) return fail(ctx, KIDMP_EINVAL, w + ": null array argument");
-    if (needs_path(a) && !a.dz) return fail(ctx, KIDMP_EINVAL, w + ": path integrals need dz");
-    if (!doppler_consts_supported(ctx->hc) || !spectra_consts_supported(ctx->hc))
-        return fail(ctx, KIDMP_ESTATE, w + ": exponents differ from the kernel's");
-    return KIDMP_OK;
-}
-
 // one launch over device pointers; an iiwarm context reads no snow and no graupel
 template <class T>
 hipError_t enqueue_mie(kidmp_ctx *ctx, const kidmp_mie_table *tab, int64_t ncol, int nz, const MieCall<T> &a, hipStream_t s)
@@ -107,7 +53,7 @@ int mie_device(kidmp_ctx *ctx, const char *who, const kidmp_mie_table *tab, int6
     if (int rc = check_device_array(ctx, who, a.w, "w")) return rc;
     if (int rc = check_device_array(ctx, who, a.k_gas, "k_gas")) return rc;
     for (int v = 0; v < MIE_NOUT; ++v)
-        if (int rc = check_device_array(ctx, who, a.out[v], OUT_NAMES[v])) return rc;
+        if (int rc = check_device_array(ctx, who, a.out[v], MIE_OUT_NAMES[v])) return rc;
     if (int rc = check_device_array(ctx, who, a.pia_total, "pia_total")) return rc;
     HIPTRY(ctx, enqueue_mie<T>(ctx, tab, ncol, nz, a, (hipStream_t)stream));
     return KIDMP_OK;

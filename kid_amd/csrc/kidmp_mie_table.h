@@ -22,7 +22,16 @@ struct MieTableData {
     double *d_buf;
     double kc;
     int nrows;
+    double *h_buf;                                        // the host's copy of d_buf: what a channel set compares
 };
+
+}  // namespace kidmp
+
+// the handles of include/kidmp_mie.h and include/kidmp_radiometer.h: one device buffer, per species D[nb], dD[nb], rows[nrows][nb]
+struct kidmp_mie_table : kidmp::MieTableData {};
+struct kidmp_radiometer_table : kidmp::MieTableData {};
+
+namespace kidmp {
 
 inline const double *mie_bins_D(const Bins &b, int x) { return x == 0 ? b.Dr : x == 1 ? b.Ds : b.Dg; }
 inline const double *mie_bins_dD(const Bins &b, int x) { return x == 0 ? b.dtr : x == 1 ? b.dts : b.dtg; }
@@ -80,7 +89,9 @@ int mie_table_build(kidmp_ctx *ctx, const std::string &w, const kidmp_mie_cfg *c
     HIPTRY(ctx, hipMalloc(reinterpret_cast<void **>(&d_buf), total * sizeof(double)));
     const hipError_t e = hipMemcpy(d_buf, buf.data(), total * sizeof(double), hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(d_buf); return hipfail(ctx, e, "hipMemcpy of the table"); }
-    *out = MieTableData{ctx, ctx->cfg.device, g, {nb[0], nb[1], nb[2]}, {off[0], off[1], off[2]}, d_buf, mie_cloud_absorption(mc), nrows};
+    double *h_buf = new double[total];
+    std::memcpy(h_buf, buf.data(), total * sizeof(double));
+    *out = MieTableData{ctx, ctx->cfg.device, g, {nb[0], nb[1], nb[2]}, {off[0], off[1], off[2]}, d_buf, mie_cloud_absorption(mc), nrows, h_buf};
     return KIDMP_OK;
 }
 
@@ -88,6 +99,7 @@ inline void mie_table_free(MieTableData *t)
 {
     DeviceGuard guard(t->device);
     if (t->d_buf) (void)hipFree(t->d_buf);
+    delete[] t->h_buf;
 }
 
 inline int mie_table_read(const MieTableData *table, const std::string &w, int32_t species, int32_t *nb, double *D, double *dD, double *rows,

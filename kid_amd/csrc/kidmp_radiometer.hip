@@ -5,8 +5,7 @@
 #include <cmath>
 #include <cstddef>
 
-#include "kidmp_mie_table.h"
-#include "../../include/kidmp_radiometer.h"
+#include "kidmp_channel_call.h"
 
 using namespace kidmp;
 
@@ -15,76 +14,7 @@ static_assert(sizeof(kidmp_radiometer_out) == (RAD_NOUT + 3) * sizeof(double *) 
                   && sizeof(kidmp_radiometer_cfg) == 3 * sizeof(double),
               "include/kidmp_radiometer.h");
 
-struct kidmp_radiometer_table : kidmp::MieTableData {};
-
 namespace {
-constexpr int NIN = 8, NREQ = 5, NCOL_OUT = 3;            // t, p, qv, qr, nr | qc, qs, qg;  tb_toa, tb_ground, tau_abs
-const char *const IN_NAMES[NIN] = {"t", "p", "qv", "qr", "nr", "qc", "qs", "qg"};
-const char *const OUT_NAMES[RAD_NOUT] = {"k_abs", "k_bsc", "refl", "trans", "tb_up", "tb_down"};
-const char *const COL_NAMES[NCOL_OUT] = {"tb_toa", "tb_ground", "tau_abs"};
-
-template <class T> struct RadCall {
-    const T *in[NIN];
-    const T *dz, *k_gas, *t_sfc;
-    int64_t dz_col_stride, k_gas_col_stride;
-    T *out[RAD_NOUT];
-    T *col[NCOL_OUT];
-};
-template <class T, class O>
-RadCall<T> rad_call(const T *t, const T *p, const T *qv, const T *qc, const T *qr, const T *nr, const T *qs, const T *qg, const T *dz,
-                    int64_t dz_col_stride, const T *k_gas, int64_t k_gas_col_stride, const T *t_sfc, const O *out)
-{
-    RadCall<T> c{{t, p, qv, qr, nr, qc, qs, qg}, dz, k_gas, t_sfc, dz_col_stride, k_gas_col_stride, {}, {}};
-    if (out) {
-        T *const o[RAD_NOUT] = {out->k_abs, out->k_bsc, out->refl, out->trans, out->tb_up, out->tb_down};
-        for (int v = 0; v < RAD_NOUT; ++v) c.out[v] = o[v];
-        c.col[0] = out->tb_toa; c.col[1] = out->tb_ground; c.col[2] = out->tau_abs;
-    }
-    return c;
-}
-template <class T> bool needs_dz(const RadCall<T> &a)
-{
-    bool any = a.col[0] || a.col[1] || a.col[2];
-    for (int v = RAD_REFL; v < RAD_NOUT; ++v) any = any || a.out[v];
-    return any;
-}
-
-kidmp_radiometer_cfg resolve(const kidmp_radiometer_cfg *rcfg)
-{
-    kidmp_radiometer_cfg r;
-    if (rcfg) r = *rcfg;
-    else kidmp_radiometer_defaults(&r);
-    return r;
-}
-
-// what the device and the host entries check alike, before anything is touched
-template <class T>
-int check_rad(kidmp_ctx *ctx, const char *who, const kidmp_radiometer_table *tab, const kidmp_radiometer_cfg &r, int64_t ncol, int32_t nz,
-              const RadCall<T> &a)
-{
-    const std::string w(who);
-    if (int rc = require_ready(ctx)) return rc;
-    if (!tab || tab->ctx != ctx) return fail(ctx, KIDMP_EINVAL, w + ": the table is NULL or belongs to another context");
-    if (!(r.mu > 0. && r.mu <= 1.)) return fail(ctx, KIDMP_EINVAL, w + ": mu outside (0, 1]");
-    if (!(r.emissivity >= 0. && r.emissivity <= 1.)) return fail(ctx, KIDMP_EINVAL, w + ": emissivity outside [0, 1]");
-    if (!(std::isfinite(r.t_cosmic) && r.t_cosmic >= 0.)) return fail(ctx, KIDMP_EINVAL, w + ": t_cosmic must be finite and not below 0");
-    if (ncol < 0) return fail(ctx, KIDMP_EINVAL, w + ": ncol < 0");
-    if (nz < 2 || nz > KIDMP_MAX_NZ) return fail(ctx, KIDMP_EINVAL, w + ": nz outside [2, KIDMP_MAX_NZ]");
-    if (a.dz_col_stride != 0 && a.dz_col_stride < nz) return fail(ctx, KIDMP_EINVAL, w + ": dz_col_stride must be 0 or >= nz");
-    if (a.k_gas_col_stride != 0 && a.k_gas_col_stride < nz) return fail(ctx, KIDMP_EINVAL, w + ": k_gas_col_stride must be 0 or >= nz");
-    if (ncol == 0) return KIDMP_OK;                       // an empty batch has nothing to point at
-    bool any = false;
-    for (int v = 0; v < RAD_NOUT; ++v) any = any || a.out[v];
-    for (int v = 0; v < NCOL_OUT; ++v) any = any || a.col[v];
-    if (!any) return fail(ctx, KIDMP_EINVAL, w + ": nothing requested: out is NULL or every member is");
-    for (int v = 0; v < NREQ; ++v)
-        if (!a.in[v]) return fail(ctx, KIDMP_EINVAL, w + ": null array argument");
-    if (needs_dz(a) && !a.dz) return fail(ctx, KIDMP_EINVAL, w + ": everything but k_abs and k_bsc needs dz");
-    if (!doppler_consts_supported(ctx->hc) || !spectra_consts_supported(ctx->hc))
-        return fail(ctx, KIDMP_ESTATE, w + ": exponents differ from the kernel's");
-    return KIDMP_OK;
-}
-
 // one launch over device pointers; an iiwarm context reads no snow and no graupel
 template <class T>
 hipError_t enqueue_rad(kidmp_ctx *ctx, const kidmp_radiometer_table *tab, const kidmp_radiometer_cfg &r, int64_t ncol, int nz, const RadCall<T> &a,
@@ -127,9 +57,9 @@ int rad_device(kidmp_ctx *ctx, const char *who, const kidmp_radiometer_table *ta
     if (int rc = check_device_array(ctx, who, a.k_gas, "k_gas")) return rc;
     if (int rc = check_device_array(ctx, who, a.t_sfc, "t_sfc")) return rc;
     for (int v = 0; v < RAD_NOUT; ++v)
-        if (int rc = check_device_array(ctx, who, a.out[v], OUT_NAMES[v])) return rc;
+        if (int rc = check_device_array(ctx, who, a.out[v], RAD_OUT_NAMES[v])) return rc;
     for (int v = 0; v < NCOL_OUT; ++v)
-        if (int rc = check_device_array(ctx, who, a.col[v], COL_NAMES[v])) return rc;
+        if (int rc = check_device_array(ctx, who, a.col[v], RAD_COL_NAMES[v])) return rc;
     HIPTRY(ctx, enqueue_rad<T>(ctx, tab, r, ncol, nz, a, (hipStream_t)stream));
     return KIDMP_OK;
 }

@@ -202,6 +202,45 @@ template <class T>
 hipError_t launch_radiometer(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const RadiometerArgs<T> &a,
                              hipStream_t stream);
 
+// Several channels of the radiometer or of the cloud radar in one launch (include/kidmp_multichannel.h): the load and the
+// densities of the bin loop are formed once and shared by the channels, which are taken in tiles of
+// multichannel_tile(which, nz) inside the launch.  The state, dz, w and t_sfc are the single-channel kernels'; everything
+// else is per channel c < nch: rows[c][x] the species' rows of the channel's table (all tables on the grids D, dD, nb, the
+// rows that do not depend on the wavelength equal bit for bit), kc, rho_w and the radiometer's closure, k_gas at
+// k_gas + c*k_gas_ch_stride, and the slab of every output: a profile at out + c*prof_ch_stride, a per-column one at
+// + c*col_ch_stride.  Slab c holds the bits the single-channel kernel writes with channel c's table.
+constexpr int MC_MAX_CHANNELS = 16;
+template <class T> struct RadiometerMultiArgs {
+    const T *t, *p, *qv, *qc, *qr, *nr, *qs, *qg, *dz, *k_gas, *t_sfc;
+    int64_t dz_col_stride, k_gas_col_stride, k_gas_ch_stride, prof_ch_stride, col_ch_stride;
+    T *out[RAD_NOUT];
+    T *tb_toa, *tb_ground, *tau_abs;
+    const double *D[MIE_NSPEC], *dD[MIE_NSPEC];
+    int32_t nb[MIE_NSPEC];
+    int32_t nch;
+    const double *rows[MC_MAX_CHANNELS][MIE_NSPEC];
+    double kc[MC_MAX_CHANNELS], rho_w[MC_MAX_CHANNELS], mu[MC_MAX_CHANNELS], emissivity[MC_MAX_CHANNELS], t_cosmic[MC_MAX_CHANNELS];
+};
+template <class T> struct MieMultiArgs {
+    const T *t, *p, *qv, *qc, *qr, *nr, *qs, *qg, *dz, *w, *k_gas;
+    int64_t dz_col_stride, k_gas_col_stride, k_gas_ch_stride, prof_ch_stride, col_ch_stride;
+    T *out[MIE_NOUT];
+    T *pia_total;
+    const double *D[MIE_NSPEC], *dD[MIE_NSPEC];
+    int32_t nb[MIE_NSPEC];
+    int32_t nch;
+    const double *rows[MC_MAX_CHANNELS][MIE_NSPEC];
+    double kc[MC_MAX_CHANNELS], rho_w[MC_MAX_CHANNELS];
+};
+// how many channels one pass of the kernel carries at nz levels; which: 0 the radiometer, 1 the radar
+int multichannel_tile(int which, int nz);
+template <class T>
+hipError_t launch_radiometer_multi(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const RadiometerMultiArgs<T> &a,
+                                   hipStream_t stream);
+template <class T>
+hipError_t launch_mie_radar_multi(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const MieMultiArgs<T> &a,
+                                  hipStream_t stream);
+
 // The polarimetric radar (include/kidmp_polarimetric.h): Z_DR, K_DP and rho_hv of oblate spheroids from k_mie_radar's load
 // and a table of seven rows per diameter bin (s_h, s_v, c_re, c_im, s_0, k, mass).  Null means: qs, qg -- zero; an output
 // -- not wanted.  out in the order of kidmp_pol_out.  uniform[x] != 0: the species walks no bins and takes scal[x] (s_h/s_0,

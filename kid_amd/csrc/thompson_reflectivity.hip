@@ -1467,30 +1467,244 @@ __device__ __forceinline__ void bin_loop(const A &a, int lane, const bool (&has)
     }
 }
 
-// The five sums of one species at every level of the lane: A = sum n s_mie, B = sum n s_ray, E = sum n s_ext,
-// M = sum n mass, V = sum (n s_mie) v0, over the bins ascending into accumulators that start at +0.0.
-template <int SP, int NJ, class T, class F>
-__device__ __forceinline__ void mie_sums(const MieArgs<T> &a, int lane, const bool (&has)[NJ], F &&density, double (&A)[NJ],
-                                         double (&B)[NJ], double (&E)[NJ], double (&M)[NJ], double (&V)[NJ])
+// bin_loop for a tile of CT channels (include/kidmp_multichannel.h): the tables of the channels lie on the same grids, so
+// D, dD, Dmu and the density n are formed once per bin and level group and shared; rows[cc] is channel cc's [NR][nb], and
+// add(j, n, r) folds r[cc][NR] of every channel of the tile into the caller's accumulators.  The rows of a tile's unused
+// places (the caller points them at a channel in use) are loaded and not read.  With CT == 1 this is bin_loop.
+template <int SP, int NJ, int NR, int CT, class F, class G>
+__device__ __forceinline__ void bin_loop_multi(const double *__restrict__ D, const double *__restrict__ dD, int nb, const double *const (&rows)[CT],
+                                               int lane, const bool (&has)[NJ], F &&density, G &&add)
+{
+    bool live[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) live[j] = __ballot(has[j]) != 0;
+    for (int bb = 0; bb < nb; bb += 64) {
+        double mine = 0.;
+        if (SP == 1 && bb + lane < nb) mine = fm::pow(D[bb + lane], mu_s);
+        const int be = bb + 64 < nb ? bb + 64 : nb;
+        for (int b = bb; b < be; ++b) {
+            const double Db = D[b], dDb = dD[b];
+            const double Dmu = SP == 1 ? readlane(mine, b - bb) : 0.;
+            double r[CT][NR];
+#pragma unroll
+            for (int cc = 0; cc < CT; ++cc)
+#pragma unroll
+                for (int i = 0; i < NR; ++i) r[cc][i] = rows[cc][i * nb + b];
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                if (!live[j]) continue;                              // wave-uniform
+                const double n = has[j] ? density(j, Db, dDb, Dmu) : 0.;
+                add(j, n, r);
+            }
+        }
+    }
+}
+
+// What k_mie_radar, k_radiometer and their multi-channel kernels keep of a column's levels: the load (radar_level), the
+// running minimum of the graupel intercept and the parameters of the three size distributions.  Lanes over levels; a level
+// past nz holds no species.  What a kernel does not read is not formed.
+template <int NJ> struct ChannelLevels {
+    double temp[NJ], ze_r[NJ], ze_s[NJ], ze_g[NJ], rho[NJ], rhof[NJ], rs[NJ], rg[NJ], N0_r[NJ], lamr[NJ], N0_g[NJ], lamg[NJ];
+    lvl::SnowSpectrum ss[NJ];
+    bool lqr[NJ], lqs[NJ], lqg[NJ];
+};
+template <int NJ, class A>
+__device__ __forceinline__ void load_channel_levels(const ReflConsts &c, const DopplerConsts &dc, const A &a, int64_t base, int nz, int lane,
+                                                    ChannelLevels<NJ> &L)
+{
+    double n0[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        L.ze_r[j] = L.ze_s[j] = L.ze_g[j] = 1.E-22;
+        L.temp[j] = 0.;
+        L.rho[j] = 1.; L.rhof[j] = 0.;
+        L.rs[j] = L.rg[j] = R1;
+        L.N0_r[j] = L.lamr[j] = 0.;
+        L.ss[j] = lvl::SnowSpectrum{0., 0., 0., 0.};
+        L.lqr[j] = L.lqs[j] = L.lqg[j] = false;
+        n0[j] = double(__builtin_inf());                             // levels past kte do not enter the minimum
+        if (k >= nz) continue;
+        const RadarLevel r = radar_level(c, a, base + k);            // ---- load, M:4991-5028 ----
+        L.temp[j] = r.temp;
+        L.ze_r[j] = r.ze_rain;
+        L.ze_s[j] = r.ze_snow;
+        L.rho[j] = r.rho;
+        L.rhof[j] = r.rhof;
+        L.rs[j] = r.rs;
+        L.rg[j] = r.rg;
+        L.N0_r[j] = r.N0_r;
+        L.lamr[j] = r.lamr;
+        L.lqr[j] = r.L_qr; L.lqs[j] = r.L_qs; L.lqg[j] = r.L_qg;
+        if (r.L_qs) L.ss[j] = lvl::snow_spectrum(r.sl, lvl::snow_moment(c.sa, c.sb, dc.cse1, r.sl));
+        n0[j] = r.n0_exp;
+    }
+    graupel_running_min<NJ>(n0, lane);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        L.N0_g[j] = L.lamg[j] = 0.;
+        if (!L.lqg[j]) continue;
+        double ilamg;
+        L.ze_g[j] = lvl::graupel_ze(c, n0[j], L.rg[j], ilamg, L.lamg[j], L.N0_g[j]);
+    }
+}
+// rr = qr*rho where rain is present, what scales rain's sums
+template <int NJ, class A>
+__device__ __forceinline__ void rain_mass(const A &a, int64_t base, int lane, const ChannelLevels<NJ> &L, double (&rr)[NJ])
 {
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) A[j] = B[j] = E[j] = M[j] = V[j] = 0.;
-    bin_loop<SP, NJ, MIE_NROWS>(a, lane, has, density, [&](int j, double n, const double (&r)[MIE_NROWS]) __attribute__((always_inline)) {
-        const double ns = n * r[0];
-        A[j] += ns;
-        B[j] += n * r[1];
-        E[j] += n * r[2];
-        M[j] += n * r[3];
-        V[j] += ns * r[4];
+    for (int j = 0; j < NJ; ++j) rr[j] = L.lqr[j] ? double(a.qr[base + 64 * j + lane]) * L.rho[j] : 0.;
+}
+
+// ---- the cloud radar: what k_mie_radar and k_mie_radar_multi share ----
+// One channel's outputs and scalars: a profile of the channel is out[v] + slab where out[v] is not null; k_gas is the
+// column's row or null.
+template <class T> struct MieChannel {
+    T *const *out;
+    int64_t slab;
+    T *pia_total;
+    const T *k_gas;
+    double kc, rho_w;
+    __device__ __forceinline__ T *profile(int v) const { return out[v] ? out[v] + slab : nullptr; }
+};
+struct MieWants { bool up, dn, path, ext, all; };
+template <class T>
+__device__ __forceinline__ MieWants mie_wants(T *const *out, const T *pia_total)
+{
+    MieWants w;
+    w.up = out[MIE_DBZ_UP] || out[MIE_PIA_UP];
+    w.dn = out[MIE_DBZ_DOWN] || out[MIE_PIA_DOWN];
+    w.path = w.up || w.dn || pia_total;
+    w.ext = w.path || out[MIE_EXT];
+    w.all = w.ext || out[MIE_DBZ] || out[MIE_VD];                    // what takes every species
+    return w;
+}
+// What a species' five sums (A = sum n s_mie, B = sum n s_ray, E = sum n s_ext, M = sum n mass, V = sum (n s_mie) v0, over
+// the bins ascending into accumulators that start at +0.0) leave behind: ze_x' in ze, the species' share of ext and of the
+// Doppler sums (where it is present with A above 0), and its own two profiles.
+template <class T, int NJ>
+__device__ __forceinline__ void mie_species_finish(const bool (&has)[NJ], const double (&rq)[NJ], const double (&A)[NJ], const double (&B)[NJ],
+                                                   const double (&E)[NJ], const double (&M)[NJ], const double (&V)[NJ], double (&ze)[NJ],
+                                                   double (&ext)[NJ], double (&zw)[NJ], double (&zv)[NJ], T *out_mie, T *out_dbz,
+                                                   int64_t base, int nz, int lane)
+{
+    double mie[NJ], dbz_out[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        mie[j] = has[j] && B[j] > 0. ? A[j] / B[j] : 1.;
+        ze[j] = ze[j] * mie[j];
+        ext[j] = ext[j] + (has[j] && M[j] > 0. ? rq[j] * E[j] / M[j] : 0.);
+        if (has[j] && A[j] > 0.) { zw[j] = zw[j] + ze[j]; zv[j] = zv[j] + ze[j] * (V[j] / A[j]); }
+        dbz_out[j] = lvl::dbz_of(ze[j]);
+    }
+    store_profile<T, NJ>(out_mie, base, nz, lane, mie);
+    store_profile<T, NJ>(out_dbz, base, nz, lane, dbz_out);
+}
+// What follows the species, for one channel: dbz and vd, then ext = ((ext_r + ext_s) + ext_g) + ext_c + k_gas, then the
+// path integrals (column_depths); a request ends as early as its outputs allow.  A: MieArgs or MieMultiArgs (qc, w, dz).
+template <class T, int NJ, class A>
+__device__ __forceinline__ void mie_tail(const A &a, const MieChannel<T> &ch, const MieWants &want, int64_t col, int64_t base, int nz, int lane,
+                                         const ChannelLevels<NJ> &L, const double (&ze_r)[NJ], const double (&ze_s)[NJ],
+                                         const double (&ze_g)[NJ], double (&ext)[NJ], const double (&zw)[NJ], const double (&zv)[NJ])
+{
+    double dbz[NJ], vd[NJ], dbz_out[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        dbz[j] = lvl::dbz_of(ze_r[j] + ze_s[j] + ze_g[j]);           // M:5196
+        vd[j] = 0.;                                                  // no echo: +0.0, w is not applied
+        if (k < nz && zw[j] > 0.) vd[j] = L.rhof[j] * (zv[j] / zw[j]) - (a.w ? double(a.w[base + k]) : 0.);
+    }
+    store_profile<T, NJ>(ch.profile(MIE_DBZ), base, nz, lane, dbz);
+    store_profile<T, NJ>(ch.profile(MIE_VD), base, nz, lane, vd);
+    if (!want.ext) return;
+
+    // ---- ext = ((ext_r + ext_s) + ext_g) + ext_c + k_gas; levels past nz keep +0.0 ----
+    // cloud water enters through its mass alone, so of load_cloud only the presence test is taken (qc > R1, M:1395): its
+    // droplet number, nu_c and lamc would be formed and thrown away
+    if (a.qc) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            if (64 * j + lane >= nz) continue;
+            const double qc = double(a.qc[base + 64 * j + lane]);
+            if (qc > R1) ext[j] = ext[j] + ch.kc * ((L.rho[j] * qc) / ch.rho_w);
+        }
+    }
+    if (ch.k_gas) {
+        const T *__restrict__ kg = ch.k_gas;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+            if (64 * j + lane < nz) ext[j] = ext[j] + double(kg[64 * j + lane]);
+    }
+    store_profile<T, NJ>(ch.profile(MIE_EXT), base, nz, lane, ext);
+    if (!want.path) return;
+
+    // ---- the path: dtau = ext*dz, tau_up = (the levels below) + dtau/2, tau_down from the top ----
+    const T *__restrict__ dzc = a.dz + col * a.dz_col_stride;
+    double dt[NJ], tu[NJ], td[NJ], total = 0.;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        dt[j] = k < nz ? ext[j] * double(dzc[k]) : 0.;
+        total += dt[j];
+        tu[j] = td[j] = 0.;
+    }
+    if (ch.pia_total) {
+        total = wave_sum(total);
+        if (lane == 0) ch.pia_total[col] = T(MIE_PIA * total);
+    }
+    if (!(want.up || want.dn)) return;
+    column_depths<NJ>(dt, lane, want.up, want.dn, tu, td);
+    if (want.up) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { tu[j] = MIE_PIA * (tu[j] + 0.5 * dt[j]); dbz_out[j] = dbz[j] - tu[j]; }
+        store_profile<T, NJ>(ch.profile(MIE_PIA_UP), base, nz, lane, tu);
+        store_profile<T, NJ>(ch.profile(MIE_DBZ_UP), base, nz, lane, dbz_out);
+    }
+    if (want.dn) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { td[j] = MIE_PIA * (td[j] + 0.5 * dt[j]); dbz_out[j] = dbz[j] - td[j]; }
+        store_profile<T, NJ>(ch.profile(MIE_PIA_DOWN), base, nz, lane, td);
+        store_profile<T, NJ>(ch.profile(MIE_DBZ_DOWN), base, nz, lane, dbz_out);
+    }
+}
+
+// The five sums of one species for a tile of CT channels.  Per channel and bin the operations are those of one channel
+// alone, in their order: ns = n*s_mie; A += ns; B += n*s_ray; E += n*s_ext; M += n*mass; V += ns*v0.  s_ray, mass and v0
+// do not depend on the wavelength, so B and M are formed once, from the rows of the tile's first channel; `used` (wave-
+// uniform) is how many of the tile's places hold a channel.
+template <int SP, int NJ, int CT, class F>
+__device__ __forceinline__ void mie_sums(const double *D, const double *dD, int nb, const double *const (&rows)[CT], int used, int lane,
+                                         const bool (&has)[NJ], F &&density, double (&A)[CT][NJ], double (&B)[NJ], double (&E)[CT][NJ],
+                                         double (&M)[NJ], double (&V)[CT][NJ])
+{
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        B[j] = M[j] = 0.;
+#pragma unroll
+        for (int cc = 0; cc < CT; ++cc) A[cc][j] = E[cc][j] = V[cc][j] = 0.;
+    }
+    bin_loop_multi<SP, NJ, MIE_NROWS, CT>(D, dD, nb, rows, lane, has, density,
+                                          [&](int j, double n, const double (&r)[CT][MIE_NROWS]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int cc = 0; cc < CT; ++cc) {
+            if (cc >= used) continue;                                // wave-uniform
+            const double ns = n * r[cc][0];
+            A[cc][j] += ns;
+            if (cc == 0) B[j] += n * r[0][1];
+            E[cc][j] += n * r[cc][2];
+            if (cc == 0) M[j] += n * r[0][3];
+            V[cc][j] += ns * r[0][4];
+        }
     });
 }
 
 // One wavefront per column: the cloud radar of include/kidmp_mie.h.  The load and the scan are k_doppler_moments'
-// (radar_level, graupel_running_min), lanes over levels.  Then species by species -- rain, snow, graupel -- the five sums
-// over the table's bins (mie_sums), which leave behind only mie_x, the species' extinction and its share of the Doppler
-// sums.  Cloud water (present where qc > R1) and the caller's gas extinction close ext; the path integrals are
-// column_depths, the scans of k_lidar_profiles, and a request without them ends before.  No atomics, no scratch, nothing
-// but the fastmath tables in LDS.
+// (load_channel_levels), lanes over levels.  Then species by species -- rain, snow, graupel -- the five sums over the
+// table's bins (mie_sums), which leave behind only mie_x, the species' extinction and its share of the Doppler sums
+// (mie_species_finish).  Cloud water (present where qc > R1) and the caller's gas extinction close ext; the path integrals
+// are column_depths, the scans of k_lidar_profiles, and a request without them ends before (mie_tail).  No atomics, no
+// scratch, nothing but the fastmath tables in LDS.
 template <class T, int NJ>
 __global__ void __launch_bounds__(REFL_THREADS)
 k_mie_radar(ReflConsts c, DopplerConsts dc, MieArgs<T> a, int64_t ncol, int nz)
@@ -1504,146 +1718,135 @@ k_mie_radar(ReflConsts c, DopplerConsts dc, MieArgs<T> a, int64_t ncol, int nz)
     if (col >= ncol) return;                                         // whole wavefronts only: the scans need every lane
     const int64_t base = col * int64_t(nz);
     T *const *out = a.out;
-    const bool want_up = out[MIE_DBZ_UP] || out[MIE_PIA_UP], want_dn = out[MIE_DBZ_DOWN] || out[MIE_PIA_DOWN];
-    const bool path = want_up || want_dn || a.pia_total;
-    const bool want_ext = path || out[MIE_EXT];
-    const bool all = want_ext || out[MIE_DBZ] || out[MIE_VD];        // what takes every species
-    const auto wants = [&](int x) __attribute__((always_inline)) { return all || out[MIE_DBZ_X + x] || out[MIE_MIE_X + x]; };
+    const MieChannel<T> ch{out, 0, a.pia_total, a.k_gas ? a.k_gas + col * a.k_gas_col_stride : nullptr, a.kc, a.rho_w};
+    const MieWants want = mie_wants<T>(out, a.pia_total);
+    const auto wants = [&](int x) __attribute__((always_inline)) { return want.all || out[MIE_DBZ_X + x] || out[MIE_MIE_X + x]; };
 
-    double ze_r[NJ], ze_s[NJ], ze_g[NJ], rho[NJ], rhof[NJ], rs[NJ], rg[NJ], n0[NJ], N0_r[NJ], lamr[NJ];
-    lvl::SnowSpectrum ss[NJ];
-    bool lqr[NJ], lqs[NJ], lqg[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int k = 64 * j + lane;
-        ze_r[j] = ze_s[j] = ze_g[j] = 1.E-22;
-        rho[j] = 1.; rhof[j] = 0.;
-        rs[j] = rg[j] = R1;
-        N0_r[j] = lamr[j] = 0.;
-        ss[j] = lvl::SnowSpectrum{0., 0., 0., 0.};
-        lqr[j] = lqs[j] = lqg[j] = false;
-        n0[j] = double(__builtin_inf());                             // levels past kte do not enter the minimum
-        if (k >= nz) continue;
-        const RadarLevel r = radar_level(c, a, base + k);            // ---- load, M:4991-5028 ----
-        ze_r[j] = r.ze_rain;
-        ze_s[j] = r.ze_snow;
-        rho[j] = r.rho;
-        rhof[j] = r.rhof;
-        rs[j] = r.rs;
-        rg[j] = r.rg;
-        N0_r[j] = r.N0_r;
-        lamr[j] = r.lamr;
-        lqr[j] = r.L_qr; lqs[j] = r.L_qs; lqg[j] = r.L_qg;
-        if (r.L_qs) ss[j] = lvl::snow_spectrum(r.sl, lvl::snow_moment(c.sa, c.sb, dc.cse1, r.sl));
-        n0[j] = r.n0_exp;
-    }
-    graupel_running_min<NJ>(n0, lane);
-    double N0_g[NJ], lamg[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        N0_g[j] = lamg[j] = 0.;
-        if (!lqg[j]) continue;
-        double ilamg;
-        ze_g[j] = lvl::graupel_ze(c, n0[j], rg[j], ilamg, lamg[j], N0_g[j]);
-    }
+    ChannelLevels<NJ> L;
+    load_channel_levels<NJ>(c, dc, a, base, nz, lane, L);
 
     // what the species leave behind: ze_x' in ze_x, ext = (ext_r + ext_s) + ext_g, and the Doppler sums over the species
     // that are present with A above 0
     double ext[NJ], zw[NJ], zv[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) ext[j] = zw[j] = zv[j] = 0.;
-    double A[NJ], B[NJ], E[NJ], M[NJ], V[NJ], mie[NJ], dbz_out[NJ];
-    const auto finish = [&](int x, const bool (&has)[NJ], double (&ze)[NJ], const double (&rq)[NJ]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            mie[j] = has[j] && B[j] > 0. ? A[j] / B[j] : 1.;
-            ze[j] = ze[j] * mie[j];
-            ext[j] = ext[j] + (has[j] && M[j] > 0. ? rq[j] * E[j] / M[j] : 0.);
-            if (has[j] && A[j] > 0.) { zw[j] = zw[j] + ze[j]; zv[j] = zv[j] + ze[j] * (V[j] / A[j]); }
-            dbz_out[j] = lvl::dbz_of(ze[j]);
-        }
-        store_profile<T, NJ>(out[MIE_MIE_X + x], base, nz, lane, mie);
-        store_profile<T, NJ>(out[MIE_DBZ_X + x], base, nz, lane, dbz_out);
-    };
+    double A[1][NJ], B[NJ], E[1][NJ], M[NJ], V[1][NJ];
     if (wants(0)) {
         double rr[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) rr[j] = lqr[j] ? double(a.qr[base + 64 * j + lane]) * rho[j] : 0.;
-        mie_sums<0, NJ, T>(a, lane, lqr, [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(N0_r[j], lamr[j], D, dD); },
+        rain_mass<NJ>(a, base, lane, L, rr);
+        const double *const rows[1] = {a.rows[0]};
+        mie_sums<0, NJ, 1>(a.D[0], a.dD[0], a.nb[0], rows, 1, lane, L.lqr,
+                           [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(L.N0_r[j], L.lamr[j], D, dD); },
                            A, B, E, M, V);
-        finish(0, lqr, ze_r, rr);
+        mie_species_finish<T, NJ>(L.lqr, rr, A[0], B, E[0], M, V[0], L.ze_r, ext, zw, zv, out[MIE_MIE_X + 0], out[MIE_DBZ_X + 0], base, nz, lane);
     }
     if (wants(1)) {
-        mie_sums<1, NJ, T>(a, lane, lqs, [&](int j, double D, double dD, double Dmu) __attribute__((always_inline)) { return lvl::snow_bin(ss[j], D, Dmu, dD); },
+        const double *const rows[1] = {a.rows[1]};
+        mie_sums<1, NJ, 1>(a.D[1], a.dD[1], a.nb[1], rows, 1, lane, L.lqs,
+                           [&](int j, double D, double dD, double Dmu) __attribute__((always_inline)) { return lvl::snow_bin(L.ss[j], D, Dmu, dD); },
                            A, B, E, M, V);
-        finish(1, lqs, ze_s, rs);
+        mie_species_finish<T, NJ>(L.lqs, L.rs, A[0], B, E[0], M, V[0], L.ze_s, ext, zw, zv, out[MIE_MIE_X + 1], out[MIE_DBZ_X + 1], base, nz, lane);
     }
     if (wants(2)) {
-        mie_sums<2, NJ, T>(a, lane, lqg, [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(N0_g[j], lamg[j], D, dD); },
+        const double *const rows[1] = {a.rows[2]};
+        mie_sums<2, NJ, 1>(a.D[2], a.dD[2], a.nb[2], rows, 1, lane, L.lqg,
+                           [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(L.N0_g[j], L.lamg[j], D, dD); },
                            A, B, E, M, V);
-        finish(2, lqg, ze_g, rg);
+        mie_species_finish<T, NJ>(L.lqg, L.rg, A[0], B, E[0], M, V[0], L.ze_g, ext, zw, zv, out[MIE_MIE_X + 2], out[MIE_DBZ_X + 2], base, nz, lane);
     }
-    if (!all) return;                                                // wave-uniform: one species' own profiles alone
+    if (!want.all) return;                                           // wave-uniform: one species' own profiles alone
+    mie_tail<T, NJ>(a, ch, want, col, base, nz, lane, L, L.ze_r, L.ze_s, L.ze_g, ext, zw, zv);
+}
 
-    double dbz[NJ], vd[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int k = 64 * j + lane;
-        dbz[j] = lvl::dbz_of(ze_r[j] + ze_s[j] + ze_g[j]);           // M:5196
-        vd[j] = 0.;                                                  // no echo: +0.0, w is not applied
-        if (k < nz && zw[j] > 0.) vd[j] = rhof[j] * (zv[j] / zw[j]) - (a.w ? double(a.w[base + k]) : 0.);
-    }
-    store_profile<T, NJ>(out[MIE_DBZ], base, nz, lane, dbz);
-    store_profile<T, NJ>(out[MIE_VD], base, nz, lane, vd);
-    if (!want_ext) return;
+// One wavefront per column: nch channels of the cloud radar (include/kidmp_multichannel.h).  The load is formed once; the
+// channels are taken in tiles of CT, and per tile and species one walk over the bins forms every density once and folds
+// it into the sums of the tile's channels (mie_sums).  What stays alive per channel across the species is ze_r', ze_s',
+// ze_g', ext and the two Doppler sums; mie_species_finish and mie_tail then run per channel as in k_mie_radar, so slab c
+// of every output holds k_mie_radar's bits for channel c's table.  No atomics, no scratch.
+template <class T, int NJ, int CT>
+__global__ void __launch_bounds__(REFL_THREADS)
+k_mie_radar_multi(ReflConsts c, DopplerConsts dc, MieMultiArgs<T> a, int64_t ncol, int nz)
+{
+#if KFM_TABLES
+    fm::tab::load_tables(int(threadIdx.x), REFL_THREADS);
+    __syncthreads();
+#endif
+    const int lane = int(threadIdx.x) & 63;
+    const int64_t col = int64_t(blockIdx.x) * REFL_WAVES + (int(threadIdx.x) >> 6);
+    if (col >= ncol) return;                                         // whole wavefronts only: the scans need every lane
+    const int64_t base = col * int64_t(nz);
+    const MieWants want = mie_wants<T>(a.out, a.pia_total);
+    const auto wants = [&](int x) __attribute__((always_inline)) { return want.all || a.out[MIE_DBZ_X + x] || a.out[MIE_MIE_X + x]; };
 
-    // ---- ext = ((ext_r + ext_s) + ext_g) + ext_c + k_gas; levels past nz keep +0.0 ----
-    // cloud water enters through its mass alone, so of load_cloud only the presence test is taken (qc > R1, M:1395): its
-    // droplet number, nu_c and lamc would be formed and thrown away
-    if (a.qc) {
+    ChannelLevels<NJ> L;
+    load_channel_levels<NJ>(c, dc, a, base, nz, lane, L);
+    double rr[NJ];
+    rain_mass<NJ>(a, base, lane, L, rr);
+
+    for (int c0 = 0; c0 < a.nch; c0 += CT) {
+        const int used = a.nch - c0 < CT ? a.nch - c0 : CT;
+        double ze_r[CT][NJ], ze_s[CT][NJ], ze_g[CT][NJ], ext[CT][NJ], zw[CT][NJ], zv[CT][NJ];
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            if (64 * j + lane >= nz) continue;
-            const double qc = double(a.qc[base + 64 * j + lane]);
-            if (qc > R1) ext[j] = ext[j] + a.kc * ((rho[j] * qc) / a.rho_w);
+        for (int cc = 0; cc < CT; ++cc)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                ze_r[cc][j] = L.ze_r[j]; ze_s[cc][j] = L.ze_s[j]; ze_g[cc][j] = L.ze_g[j];
+                ext[cc][j] = zw[cc][j] = zv[cc][j] = 0.;
+            }
+        double A[CT][NJ], B[NJ], E[CT][NJ], M[NJ], V[CT][NJ];
+        const auto rows_of = [&](int x, const double *(&rows)[CT]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int cc = 0; cc < CT; ++cc) rows[cc] = a.rows[c0 + (cc < used ? cc : 0)][x];
+        };
+        const auto finish = [&](int x, const bool (&has)[NJ], const double (&rq)[NJ], double (&ze)[CT][NJ]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int cc = 0; cc < CT; ++cc) {
+                if (cc >= used) continue;                            // wave-uniform
+                const int64_t slab = int64_t(c0 + cc) * a.prof_ch_stride;
+                T *const om = a.out[MIE_MIE_X + x], *const od = a.out[MIE_DBZ_X + x];
+                mie_species_finish<T, NJ>(has, rq, A[cc], B, E[cc], M, V[cc], ze[cc], ext[cc], zw[cc], zv[cc], om ? om + slab : nullptr,
+                                          od ? od + slab : nullptr, base, nz, lane);
+            }
+        };
+        const double *rows[CT];
+        if (wants(0)) {
+            rows_of(0, rows);
+            mie_sums<0, NJ, CT>(a.D[0], a.dD[0], a.nb[0], rows, used, lane, L.lqr,
+                                [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(L.N0_r[j], L.lamr[j], D, dD); },
+                                A, B, E, M, V);
+            finish(0, L.lqr, rr, ze_r);
         }
-    }
-    if (a.k_gas) {
-        const T *__restrict__ kg = a.k_gas + col * a.k_gas_col_stride;
+        if (wants(1)) {
+            rows_of(1, rows);
+            mie_sums<1, NJ, CT>(a.D[1], a.dD[1], a.nb[1], rows, used, lane, L.lqs,
+                                [&](int j, double D, double dD, double Dmu) __attribute__((always_inline)) { return lvl::snow_bin(L.ss[j], D, Dmu, dD); },
+                                A, B, E, M, V);
+            finish(1, L.lqs, L.rs, ze_s);
+        }
+        if (wants(2)) {
+            rows_of(2, rows);
+            mie_sums<2, NJ, CT>(a.D[2], a.dD[2], a.nb[2], rows, used, lane, L.lqg,
+                                [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(L.N0_g[j], L.lamg[j], D, dD); },
+                                A, B, E, M, V);
+            finish(2, L.lqg, L.rg, ze_g);
+        }
+        if (!want.all) continue;                                     // wave-uniform: one species' own profiles alone
+        // the tail once in the code, channel after channel: the channel's registers are picked by wave-uniform selects
+#pragma unroll 1
+        for (int cc = 0; cc < used; ++cc) {
+            double zr[NJ], zs[NJ], zg[NJ], ex[NJ], w1[NJ], v1[NJ];
 #pragma unroll
-        for (int j = 0; j < NJ; ++j)
-            if (64 * j + lane < nz) ext[j] = ext[j] + double(kg[64 * j + lane]);
-    }
-    store_profile<T, NJ>(out[MIE_EXT], base, nz, lane, ext);
-    if (!path) return;
-
-    // ---- the path: dtau = ext*dz, tau_up = (the levels below) + dtau/2, tau_down from the top ----
-    const T *__restrict__ dzc = a.dz + col * a.dz_col_stride;
-    double dt[NJ], tu[NJ], td[NJ], total = 0.;
+            for (int j = 0; j < NJ; ++j) {
+                zr[j] = ze_r[0][j]; zs[j] = ze_s[0][j]; zg[j] = ze_g[0][j]; ex[j] = ext[0][j]; w1[j] = zw[0][j]; v1[j] = zv[0][j];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int k = 64 * j + lane;
-        dt[j] = k < nz ? ext[j] * double(dzc[k]) : 0.;
-        total += dt[j];
-        tu[j] = td[j] = 0.;
-    }
-    if (a.pia_total) {
-        total = wave_sum(total);
-        if (lane == 0) a.pia_total[col] = T(MIE_PIA * total);
-    }
-    if (!(want_up || want_dn)) return;
-    column_depths<NJ>(dt, lane, want_up, want_dn, tu, td);
-    if (want_up) {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) { tu[j] = MIE_PIA * (tu[j] + 0.5 * dt[j]); dbz_out[j] = dbz[j] - tu[j]; }
-        store_profile<T, NJ>(out[MIE_PIA_UP], base, nz, lane, tu);
-        store_profile<T, NJ>(out[MIE_DBZ_UP], base, nz, lane, dbz_out);
-    }
-    if (want_dn) {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) { td[j] = MIE_PIA * (td[j] + 0.5 * dt[j]); dbz_out[j] = dbz[j] - td[j]; }
-        store_profile<T, NJ>(out[MIE_PIA_DOWN], base, nz, lane, td);
-        store_profile<T, NJ>(out[MIE_DBZ_DOWN], base, nz, lane, dbz_out);
+                for (int u = 1; u < CT; ++u)
+                    if (u == cc) { zr[j] = ze_r[u][j]; zs[j] = ze_s[u][j]; zg[j] = ze_g[u][j]; ex[j] = ext[u][j]; w1[j] = zw[u][j]; v1[j] = zv[u][j]; }
+            }
+            const int ci = c0 + cc;
+            const MieChannel<T> ch{a.out, int64_t(ci) * a.prof_ch_stride, a.pia_total ? a.pia_total + int64_t(ci) * a.col_ch_stride : nullptr,
+                                   a.k_gas ? a.k_gas + int64_t(ci) * a.k_gas_ch_stride + col * a.k_gas_col_stride : nullptr, a.kc[ci], a.rho_w[ci]};
+            mie_tail<T, NJ>(a, ch, want, col, base, nz, lane, L, zr, zs, zg, ex, w1, v1);
+        }
     }
 }
 
@@ -1675,117 +1878,83 @@ __device__ __forceinline__ RadState wave_adding_scan(RadState v, int lane)
     return v;
 }
 
-// One wavefront per column: the radiometer of include/kidmp_radiometer.h.  The load is k_mie_radar's (radar_level,
-// graupel_running_min), lanes over levels.  Then species by species the three sums over the table's bins (bin_loop), which
-// leave behind only k_abs and k_bsc; cloud water and the caller's gas absorption close k_abs.  The layers follow per level
-// (kidmp_radiometer_layer.h).  The stacks above every level come from a suffix scan of the layers, the level groups
+// ---- what k_radiometer and k_radiometer_multi share ----
+// One channel's outputs and scalars: a profile of the channel is out[v] + slab where out[v] is not null; k_gas is the
+// column's row or null.
+template <class T> struct RadChannel {
+    T *const *out;
+    int64_t slab;
+    T *tb_toa, *tb_ground, *tau_abs;
+    const T *k_gas;
+    double kc, rho_w, mu, emissivity, t_cosmic;
+    __device__ __forceinline__ T *profile(int v) const { return out[v] ? out[v] + slab : nullptr; }
+};
+// The three sums of one species for a tile of CT channels.  Per channel and bin the operations are those of one channel
+// alone: A += n*s_abs; S += n*s_bsc; M += n*mass.  The mass row does not depend on the wavelength, so M is formed once,
+// from the rows of the tile's first channel; `used` (wave-uniform) is how many of the tile's places hold a channel.
+template <int SP, int NJ, int CT, class F>
+__device__ __forceinline__ void radiometer_sums(const double *D, const double *dD, int nb, const double *const (&rows)[CT], int used, int lane,
+                                                const bool (&has)[NJ], F &&density, double (&A)[CT][NJ], double (&S)[CT][NJ], double (&M)[NJ])
+{
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        M[j] = 0.;
+#pragma unroll
+        for (int cc = 0; cc < CT; ++cc) A[cc][j] = S[cc][j] = 0.;
+    }
+    bin_loop_multi<SP, NJ, RAD_NROWS, CT>(D, dD, nb, rows, lane, has, density,
+                                          [&](int j, double n, const double (&r)[CT][RAD_NROWS]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int cc = 0; cc < CT; ++cc) {
+            if (cc >= used) continue;                                // wave-uniform
+            A[cc][j] += n * r[cc][0];
+            S[cc][j] += n * r[cc][1];
+            if (cc == 0) M[j] += n * r[0][2];
+        }
+    });
+}
+// a species' carriers abs_x = (rho*q_x)*A/M and bsc_x = (rho*q_x)*S/M, added to k_abs and k_bsc
+template <int NJ>
+__device__ __forceinline__ void radiometer_species_finish(const bool (&has)[NJ], const double (&rq)[NJ], const double (&A)[NJ],
+                                                          const double (&S)[NJ], const double (&M)[NJ], double (&kabs)[NJ], double (&kbsc)[NJ])
+{
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const bool ok = has[j] && M[j] > 0.;
+        kabs[j] = kabs[j] + (ok ? rq[j] * A[j] / M[j] : 0.);
+        kbsc[j] = kbsc[j] + (ok ? rq[j] * S[j] / M[j] : 0.);
+    }
+}
+// What follows the species, for one channel: cloud water and the caller's gas absorption close k_abs; the layers follow per
+// level (kidmp_radiometer_layer.h).  The stacks above every level come from a suffix scan of the layers, the level groups
 // chained from the top through a wave-uniform carry state as column_depths chains its sums; the stacks below from the
 // prefix scan, group by group, each group's brightness temperatures stored before the next is scanned, so that only the
 // suffix states stay alive across groups.  A request without a brightness temperature ends before the scans, one without
-// refl, trans either before the exponentials.  No atomics, no scratch, nothing but the fastmath tables in LDS.
-template <class T, int NJ>
-__global__ void __launch_bounds__(REFL_THREADS)
-k_radiometer(ReflConsts c, DopplerConsts dc, RadiometerArgs<T> a, int64_t ncol, int nz)
+// refl, trans either before the exponentials.  A: RadiometerArgs or RadiometerMultiArgs (qc, dz, t_sfc, t).
+template <class T, int NJ, class A>
+__device__ __forceinline__ void radiometer_tail(const A &a, const RadChannel<T> &ch, int64_t col, int64_t base, int nz, int lane,
+                                                const ChannelLevels<NJ> &L, double (&kabs)[NJ], const double (&kbsc)[NJ])
 {
-#if KFM_TABLES
-    fm::tab::load_tables(int(threadIdx.x), REFL_THREADS);
-    __syncthreads();
-#endif
-    const int lane = int(threadIdx.x) & 63;
-    const int64_t col = int64_t(blockIdx.x) * REFL_WAVES + (int(threadIdx.x) >> 6);
-    if (col >= ncol) return;                                         // whole wavefronts only: the scans need every lane
-    const int64_t base = col * int64_t(nz);
-    T *const *out = a.out;
-    const bool want_tb = out[RAD_TB_UP] || out[RAD_TB_DOWN] || a.tb_toa || a.tb_ground;
-    const bool want_layer = want_tb || out[RAD_REFL] || out[RAD_TRANS];
-
-    double temp[NJ], rho[NJ], rs[NJ], rg[NJ], n0[NJ], N0_r[NJ], lamr[NJ];
-    lvl::SnowSpectrum ss[NJ];
-    bool lqr[NJ], lqs[NJ], lqg[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int k = 64 * j + lane;
-        temp[j] = 0.; rho[j] = 1.;
-        rs[j] = rg[j] = R1;
-        N0_r[j] = lamr[j] = 0.;
-        ss[j] = lvl::SnowSpectrum{0., 0., 0., 0.};
-        lqr[j] = lqs[j] = lqg[j] = false;
-        n0[j] = double(__builtin_inf());                             // levels past kte do not enter the minimum
-        if (k >= nz) continue;
-        const RadarLevel r = radar_level(c, a, base + k);            // ---- load, M:4991-5028 ----
-        temp[j] = r.temp;
-        rho[j] = r.rho;
-        rs[j] = r.rs;
-        rg[j] = r.rg;
-        N0_r[j] = r.N0_r;
-        lamr[j] = r.lamr;
-        lqr[j] = r.L_qr; lqs[j] = r.L_qs; lqg[j] = r.L_qg;
-        if (r.L_qs) ss[j] = lvl::snow_spectrum(r.sl, lvl::snow_moment(c.sa, c.sb, dc.cse1, r.sl));
-        n0[j] = r.n0_exp;
-    }
-    graupel_running_min<NJ>(n0, lane);
-    double N0_g[NJ], lamg[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        N0_g[j] = lamg[j] = 0.;
-        if (!lqg[j]) continue;
-        double ilamg;
-        (void)lvl::graupel_ze(c, n0[j], rg[j], ilamg, lamg[j], N0_g[j]);
-    }
-
-    // ---- k_abs = (((abs_r + abs_s) + abs_g) + abs_c) + k_gas, k_bsc = (bsc_r + bsc_s) + bsc_g; levels past nz keep +0.0 ----
-    double kabs[NJ], kbsc[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) kabs[j] = kbsc[j] = 0.;
-    {
-        double A[NJ], S[NJ], M[NJ];
-        const auto zero = [&]() __attribute__((always_inline)) {
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) A[j] = S[j] = M[j] = 0.;
-        };
-        const auto add = [&](int j, double n, const double (&r)[RAD_NROWS]) __attribute__((always_inline)) {
-            A[j] += n * r[0];
-            S[j] += n * r[1];
-            M[j] += n * r[2];
-        };
-        const auto finish = [&](const bool (&has)[NJ], const double (&rq)[NJ]) __attribute__((always_inline)) {
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const bool ok = has[j] && M[j] > 0.;
-                kabs[j] = kabs[j] + (ok ? rq[j] * A[j] / M[j] : 0.);
-                kbsc[j] = kbsc[j] + (ok ? rq[j] * S[j] / M[j] : 0.);
-            }
-        };
-        double rr[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) rr[j] = lqr[j] ? double(a.qr[base + 64 * j + lane]) * rho[j] : 0.;
-        zero();
-        bin_loop<0, NJ, RAD_NROWS>(a, lane, lqr, [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(N0_r[j], lamr[j], D, dD); }, add);
-        finish(lqr, rr);
-        zero();
-        bin_loop<1, NJ, RAD_NROWS>(a, lane, lqs, [&](int j, double D, double dD, double Dmu) __attribute__((always_inline)) { return lvl::snow_bin(ss[j], D, Dmu, dD); }, add);
-        finish(lqs, rs);
-        zero();
-        bin_loop<2, NJ, RAD_NROWS>(a, lane, lqg, [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(N0_g[j], lamg[j], D, dD); }, add);
-        finish(lqg, rg);
-    }
+    T *const tb_up = ch.profile(RAD_TB_UP), *const tb_down = ch.profile(RAD_TB_DOWN);
+    const bool want_tb = tb_up || tb_down || ch.tb_toa || ch.tb_ground;
+    const bool want_layer = want_tb || ch.profile(RAD_REFL) || ch.profile(RAD_TRANS);
     if (a.qc) {                                                      // present where qc > R1, as in k_mie_radar
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             if (64 * j + lane >= nz) continue;
             const double qc = double(a.qc[base + 64 * j + lane]);
-            if (qc > R1) kabs[j] = kabs[j] + a.kc * ((rho[j] * qc) / a.rho_w);
+            if (qc > R1) kabs[j] = kabs[j] + ch.kc * ((L.rho[j] * qc) / ch.rho_w);
         }
     }
-    if (a.k_gas) {
-        const T *__restrict__ kg = a.k_gas + col * a.k_gas_col_stride;
+    if (ch.k_gas) {
+        const T *__restrict__ kg = ch.k_gas;
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
             if (64 * j + lane < nz) kabs[j] = kabs[j] + double(kg[64 * j + lane]);
     }
-    store_profile<T, NJ>(out[RAD_K_ABS], base, nz, lane, kabs);
-    store_profile<T, NJ>(out[RAD_K_BSC], base, nz, lane, kbsc);
-    if (!(want_layer || a.tau_abs)) return;                          // wave-uniform: the optics alone
+    store_profile<T, NJ>(ch.profile(RAD_K_ABS), base, nz, lane, kabs);
+    store_profile<T, NJ>(ch.profile(RAD_K_BSC), base, nz, lane, kbsc);
+    if (!(want_layer || ch.tau_abs)) return;                         // wave-uniform: the optics alone
 
     const T *__restrict__ dzc = a.dz + col * a.dz_col_stride;
     double ta[NJ], bs[NJ], total = 0.;
@@ -1797,9 +1966,9 @@ k_radiometer(ReflConsts c, DopplerConsts dc, RadiometerArgs<T> a, int64_t ncol, 
         bs[j] = k < nz ? kbsc[j] * dz : 0.;
         total += ta[j];
     }
-    if (a.tau_abs) {
+    if (ch.tau_abs) {
         total = wave_sum(total);
-        if (lane == 0) a.tau_abs[col] = T(total);
+        if (lane == 0) ch.tau_abs[col] = T(total);
     }
     if (!want_layer) return;
 
@@ -1807,13 +1976,13 @@ k_radiometer(ReflConsts c, DopplerConsts dc, RadiometerArgs<T> a, int64_t ncol, 
     double lr[NJ], lt[NJ], le[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-        const double x = rad_layer_x(ta[j], bs[j]), y = x / a.mu;
+        const double x = rad_layer_x(ta[j], bs[j]), y = x / ch.mu;
         const double e = lvl::exp_neg(y), f = y * lvl::layer_mean(y);
-        const RadLayer l = rad_layer(ta[j], bs[j], x, a.mu, e, f);
-        lr[j] = l.R; lt[j] = l.T; le[j] = l.a * temp[j];
+        const RadLayer l = rad_layer(ta[j], bs[j], x, ch.mu, e, f);
+        lr[j] = l.R; lt[j] = l.T; le[j] = l.a * L.temp[j];
     }
-    store_profile<T, NJ>(out[RAD_REFL], base, nz, lane, lr);
-    store_profile<T, NJ>(out[RAD_TRANS], base, nz, lane, lt);
+    store_profile<T, NJ>(ch.profile(RAD_REFL), base, nz, lane, lr);
+    store_profile<T, NJ>(ch.profile(RAD_TRANS), base, nz, lane, lt);
     if (!want_tb) return;
 
     // ---- the stack above every level: suffix scan, chained from the top ----
@@ -1831,7 +2000,7 @@ k_radiometer(ReflConsts c, DopplerConsts dc, RadiometerArgs<T> a, int64_t ncol, 
     }
     // ---- the stack below, group by group, and the closure at the level's two faces ----
     const double ts = a.t_sfc ? double(a.t_sfc[col]) : double(a.t[base]);
-    const double rsfc = 1. - a.emissivity;
+    const double rsfc = 1. - ch.emissivity;
     RadState carry = rad_identity();
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -1843,12 +2012,131 @@ k_radiometer(ReflConsts c, DopplerConsts dc, RadiometerArgs<T> a, int64_t ncol, 
         carry = rad_combine(carry, last);
         const int k = 64 * j + lane;
         if (k >= nz) continue;
-        const double up = rad_face(rad_combine(below, own), above[j], a.emissivity, rsfc, ts, a.t_cosmic).up;
-        const double down = rad_face(below, rad_combine(own, above[j]), a.emissivity, rsfc, ts, a.t_cosmic).down;
-        if (out[RAD_TB_UP]) out[RAD_TB_UP][base + k] = T(up);
-        if (out[RAD_TB_DOWN]) out[RAD_TB_DOWN][base + k] = T(down);
-        if (a.tb_toa && k == nz - 1) a.tb_toa[col] = T(up);
-        if (a.tb_ground && k == 0) a.tb_ground[col] = T(down);
+        const double up = rad_face(rad_combine(below, own), above[j], ch.emissivity, rsfc, ts, ch.t_cosmic).up;
+        const double down = rad_face(below, rad_combine(own, above[j]), ch.emissivity, rsfc, ts, ch.t_cosmic).down;
+        if (tb_up) tb_up[base + k] = T(up);
+        if (tb_down) tb_down[base + k] = T(down);
+        if (ch.tb_toa && k == nz - 1) ch.tb_toa[col] = T(up);
+        if (ch.tb_ground && k == 0) ch.tb_ground[col] = T(down);
+    }
+}
+
+// One wavefront per column: the radiometer of include/kidmp_radiometer.h.  The load is k_mie_radar's (load_channel_levels),
+// lanes over levels.  Then species by species the three sums over the table's bins (radiometer_sums), which leave behind
+// only k_abs and k_bsc; the rest is radiometer_tail.  No atomics, no scratch, nothing but the fastmath tables in LDS.
+template <class T, int NJ>
+__global__ void __launch_bounds__(REFL_THREADS)
+k_radiometer(ReflConsts c, DopplerConsts dc, RadiometerArgs<T> a, int64_t ncol, int nz)
+{
+#if KFM_TABLES
+    fm::tab::load_tables(int(threadIdx.x), REFL_THREADS);
+    __syncthreads();
+#endif
+    const int lane = int(threadIdx.x) & 63;
+    const int64_t col = int64_t(blockIdx.x) * REFL_WAVES + (int(threadIdx.x) >> 6);
+    if (col >= ncol) return;                                         // whole wavefronts only: the scans need every lane
+    const int64_t base = col * int64_t(nz);
+    const RadChannel<T> ch{a.out, 0, a.tb_toa, a.tb_ground, a.tau_abs, a.k_gas ? a.k_gas + col * a.k_gas_col_stride : nullptr,
+                           a.kc, a.rho_w, a.mu, a.emissivity, a.t_cosmic};
+
+    ChannelLevels<NJ> L;
+    load_channel_levels<NJ>(c, dc, a, base, nz, lane, L);
+
+    // ---- k_abs = (((abs_r + abs_s) + abs_g) + abs_c) + k_gas, k_bsc = (bsc_r + bsc_s) + bsc_g; levels past nz keep +0.0 ----
+    double kabs[NJ], kbsc[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) kabs[j] = kbsc[j] = 0.;
+    {
+        double A[1][NJ], S[1][NJ], M[NJ], rr[NJ];
+        rain_mass<NJ>(a, base, lane, L, rr);
+        const double *const rows_r[1] = {a.rows[0]}, *const rows_s[1] = {a.rows[1]}, *const rows_g[1] = {a.rows[2]};
+        radiometer_sums<0, NJ, 1>(a.D[0], a.dD[0], a.nb[0], rows_r, 1, lane, L.lqr,
+                                  [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(L.N0_r[j], L.lamr[j], D, dD); }, A, S, M);
+        radiometer_species_finish<NJ>(L.lqr, rr, A[0], S[0], M, kabs, kbsc);
+        radiometer_sums<1, NJ, 1>(a.D[1], a.dD[1], a.nb[1], rows_s, 1, lane, L.lqs,
+                                  [&](int j, double D, double dD, double Dmu) __attribute__((always_inline)) { return lvl::snow_bin(L.ss[j], D, Dmu, dD); }, A, S, M);
+        radiometer_species_finish<NJ>(L.lqs, L.rs, A[0], S[0], M, kabs, kbsc);
+        radiometer_sums<2, NJ, 1>(a.D[2], a.dD[2], a.nb[2], rows_g, 1, lane, L.lqg,
+                                  [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(L.N0_g[j], L.lamg[j], D, dD); }, A, S, M);
+        radiometer_species_finish<NJ>(L.lqg, L.rg, A[0], S[0], M, kabs, kbsc);
+    }
+    radiometer_tail<T, NJ>(a, ch, col, base, nz, lane, L, kabs, kbsc);
+}
+
+// One wavefront per column: nch channels of the radiometer (include/kidmp_multichannel.h).  The load is formed once; the
+// channels are taken in tiles of CT, and per tile and species one walk over the bins forms every density once and folds
+// it into the sums of the tile's channels (radiometer_sums).  What stays alive per channel across the species is k_abs and
+// k_bsc; radiometer_tail then runs per channel as in k_radiometer, so slab c of every output holds k_radiometer's bits
+// for channel c's table, closure and k_gas.  No atomics, no scratch.
+template <class T, int NJ, int CT>
+__global__ void __launch_bounds__(REFL_THREADS)
+k_radiometer_multi(ReflConsts c, DopplerConsts dc, RadiometerMultiArgs<T> a, int64_t ncol, int nz)
+{
+#if KFM_TABLES
+    fm::tab::load_tables(int(threadIdx.x), REFL_THREADS);
+    __syncthreads();
+#endif
+    const int lane = int(threadIdx.x) & 63;
+    const int64_t col = int64_t(blockIdx.x) * REFL_WAVES + (int(threadIdx.x) >> 6);
+    if (col >= ncol) return;                                         // whole wavefronts only: the scans need every lane
+    const int64_t base = col * int64_t(nz);
+
+    ChannelLevels<NJ> L;
+    load_channel_levels<NJ>(c, dc, a, base, nz, lane, L);
+    double rr[NJ];
+    rain_mass<NJ>(a, base, lane, L, rr);
+
+    for (int c0 = 0; c0 < a.nch; c0 += CT) {
+        const int used = a.nch - c0 < CT ? a.nch - c0 : CT;
+        double kabs[CT][NJ], kbsc[CT][NJ];
+#pragma unroll
+        for (int cc = 0; cc < CT; ++cc)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) kabs[cc][j] = kbsc[cc][j] = 0.;
+        {
+            double A[CT][NJ], S[CT][NJ], M[NJ];
+            const double *rows[CT];
+            const auto rows_of = [&](int x) __attribute__((always_inline)) {
+#pragma unroll
+                for (int cc = 0; cc < CT; ++cc) rows[cc] = a.rows[c0 + (cc < used ? cc : 0)][x];
+            };
+            const auto finish = [&](const bool (&has)[NJ], const double (&rq)[NJ]) __attribute__((always_inline)) {
+#pragma unroll
+                for (int cc = 0; cc < CT; ++cc)
+                    if (cc < used) radiometer_species_finish<NJ>(has, rq, A[cc], S[cc], M, kabs[cc], kbsc[cc]);
+            };
+            rows_of(0);
+            radiometer_sums<0, NJ, CT>(a.D[0], a.dD[0], a.nb[0], rows, used, lane, L.lqr,
+                                       [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(L.N0_r[j], L.lamr[j], D, dD); }, A, S, M);
+            finish(L.lqr, rr);
+            rows_of(1);
+            radiometer_sums<1, NJ, CT>(a.D[1], a.dD[1], a.nb[1], rows, used, lane, L.lqs,
+                                       [&](int j, double D, double dD, double Dmu) __attribute__((always_inline)) { return lvl::snow_bin(L.ss[j], D, Dmu, dD); }, A, S, M);
+            finish(L.lqs, L.rs);
+            rows_of(2);
+            radiometer_sums<2, NJ, CT>(a.D[2], a.dD[2], a.nb[2], rows, used, lane, L.lqg,
+                                       [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(L.N0_g[j], L.lamg[j], D, dD); }, A, S, M);
+            finish(L.lqg, L.rg);
+        }
+        // the tail once in the code, channel after channel: the channel's registers are picked by wave-uniform selects
+#pragma unroll 1
+        for (int cc = 0; cc < used; ++cc) {
+            double ka[NJ], kb[NJ];
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                ka[j] = kabs[0][j]; kb[j] = kbsc[0][j];
+#pragma unroll
+                for (int u = 1; u < CT; ++u)
+                    if (u == cc) { ka[j] = kabs[u][j]; kb[j] = kbsc[u][j]; }
+            }
+            const int ci = c0 + cc;
+            const int64_t cslab = int64_t(ci) * a.col_ch_stride;
+            const RadChannel<T> ch{a.out, int64_t(ci) * a.prof_ch_stride, a.tb_toa ? a.tb_toa + cslab : nullptr,
+                                   a.tb_ground ? a.tb_ground + cslab : nullptr, a.tau_abs ? a.tau_abs + cslab : nullptr,
+                                   a.k_gas ? a.k_gas + int64_t(ci) * a.k_gas_ch_stride + col * a.k_gas_col_stride : nullptr,
+                                   a.kc[ci], a.rho_w[ci], a.mu[ci], a.emissivity[ci], a.t_cosmic[ci]};
+            radiometer_tail<T, NJ>(a, ch, col, base, nz, lane, L, ka, kb);
+        }
     }
 }
 
@@ -2307,6 +2595,60 @@ hipError_t launch_radiometer(const ReflConsts &c, const DopplerConsts &dc, int64
 }
 template hipError_t launch_radiometer<double>(const ReflConsts &, const DopplerConsts &, int64_t, int, const RadiometerArgs<double> &, hipStream_t);
 template hipError_t launch_radiometer<float>(const ReflConsts &, const DopplerConsts &, int64_t, int, const RadiometerArgs<float> &, hipStream_t);
+
+// The channels one pass carries, by the number of level groups.  Every channel place of a tile costs about half a
+// single-channel launch whether a channel fills it or not, and registers beyond 256 cost the second wave per SIMD, so the
+// tile is not the widest that fits: at two level groups 4 (radiometer) and 3 (radar) were the fastest of the candidates
+// measured, the other counts follow the compiler's report.  No instantiation has scratch; the
+// radar's NJ = 3 takes 2 because 3 needs 64 AGPRs, NJ = 4 takes 3 because 2 is the one candidate the compiler spilled.
+constexpr int rad_tile(int) { return 4; }
+constexpr int mie_tile(int nj) { return nj == 3 ? 2 : 3; }
+int multichannel_tile(int which, int nz)
+{
+    const int nj = (nz + 63) / 64;
+    if (nj < 1 || nj > 4 || (which != 0 && which != 1)) return 0;
+    return which == 0 ? rad_tile(nj) : mie_tile(nj);
+}
+
+template <class T>
+hipError_t launch_radiometer_multi(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const RadiometerMultiArgs<T> &a, hipStream_t s)
+{
+    if (ncol <= 0) return hipSuccess;
+    if (a.nch < 1 || a.nch > MC_MAX_CHANNELS) return hipErrorInvalidValue;
+    for (int x = 0; x < MIE_NSPEC; ++x)
+        if (a.nb[x] < 1 || a.nb[x] > MIE_MAX_BINS) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((ncol + REFL_WAVES - 1) / REFL_WAVES)), block(REFL_THREADS);
+    switch ((nz + 63) / 64) {
+    case 1: hipLaunchKernelGGL((k_radiometer_multi<T, 1, rad_tile(1)>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 2: hipLaunchKernelGGL((k_radiometer_multi<T, 2, rad_tile(2)>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 3: hipLaunchKernelGGL((k_radiometer_multi<T, 3, rad_tile(3)>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 4: hipLaunchKernelGGL((k_radiometer_multi<T, 4, rad_tile(4)>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+template hipError_t launch_radiometer_multi<double>(const ReflConsts &, const DopplerConsts &, int64_t, int, const RadiometerMultiArgs<double> &, hipStream_t);
+template hipError_t launch_radiometer_multi<float>(const ReflConsts &, const DopplerConsts &, int64_t, int, const RadiometerMultiArgs<float> &, hipStream_t);
+
+template <class T>
+hipError_t launch_mie_radar_multi(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const MieMultiArgs<T> &a, hipStream_t s)
+{
+    if (ncol <= 0) return hipSuccess;
+    if (a.nch < 1 || a.nch > MC_MAX_CHANNELS) return hipErrorInvalidValue;
+    for (int x = 0; x < MIE_NSPEC; ++x)
+        if (a.nb[x] < 1 || a.nb[x] > MIE_MAX_BINS) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((ncol + REFL_WAVES - 1) / REFL_WAVES)), block(REFL_THREADS);
+    switch ((nz + 63) / 64) {
+    case 1: hipLaunchKernelGGL((k_mie_radar_multi<T, 1, mie_tile(1)>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 2: hipLaunchKernelGGL((k_mie_radar_multi<T, 2, mie_tile(2)>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 3: hipLaunchKernelGGL((k_mie_radar_multi<T, 3, mie_tile(3)>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    case 4: hipLaunchKernelGGL((k_mie_radar_multi<T, 4, mie_tile(4)>), grid, block, 0, s, c, dc, a, ncol, nz); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+template hipError_t launch_mie_radar_multi<double>(const ReflConsts &, const DopplerConsts &, int64_t, int, const MieMultiArgs<double> &, hipStream_t);
+template hipError_t launch_mie_radar_multi<float>(const ReflConsts &, const DopplerConsts &, int64_t, int, const MieMultiArgs<float> &, hipStream_t);
 
 template <class T>
 hipError_t launch_polarimetric(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const PolArgs<T> &a, hipStream_t s)

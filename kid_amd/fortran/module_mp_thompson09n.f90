@@ -68,6 +68,7 @@ module module_mp_thompson09n
   public :: mie_radar_batch
   public :: polarimetric_batch
   public :: radiometer_batch
+  public :: radiometer_multi_batch, mie_radar_multi_batch
   public :: lidar_profiles_batch
   public :: mp_thompson_kid_interface, mp_thompson_kid_staging
   logical, public :: is_aerosol_aware = .false.          ! M:28 (read at thompson_init)
@@ -562,6 +563,68 @@ module module_mp_thompson09n
        type(c_ptr), value :: t_sfc
        type(kidmp_radiometer_out), intent(in) :: out
      end function kidmp32_radiometer_host
+     ! several channels in one launch (include/kidmp_multichannel.h): tables is an array of nch handles, rcfg one of nch
+     ! closures, the outputs carry a leading (in C) channel dimension
+     integer(c_int) function kidmp_radiometer_multi_host(ctx, tables, nch, rcfg, ncol, nz, t, p, qv, qc, qr, nr, qs, qg, dz, &
+          dz_col_stride, k_gas, k_gas_col_stride, k_gas_ch_stride, t_sfc, out) bind(C, name='kidmp_radiometer_multi_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr, kidmp_radiometer_cfg, kidmp_radiometer_out
+       type(c_ptr), value :: ctx
+       type(c_ptr), intent(in) :: tables(*)
+       integer(c_int32_t), value :: nch
+       type(kidmp_radiometer_cfg), intent(in) :: rcfg(*)
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qc, qr, nr, qs, qg, dz
+       integer(c_int64_t), value :: dz_col_stride
+       type(c_ptr), value :: k_gas
+       integer(c_int64_t), value :: k_gas_col_stride, k_gas_ch_stride
+       type(c_ptr), value :: t_sfc
+       type(kidmp_radiometer_out), intent(in) :: out
+     end function kidmp_radiometer_multi_host
+     integer(c_int) function kidmp32_radiometer_multi_host(ctx, tables, nch, rcfg, ncol, nz, t, p, qv, qc, qr, nr, qs, qg, dz, &
+          dz_col_stride, k_gas, k_gas_col_stride, k_gas_ch_stride, t_sfc, out) bind(C, name='kidmp32_radiometer_multi_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr, kidmp_radiometer_cfg, kidmp_radiometer_out
+       type(c_ptr), value :: ctx
+       type(c_ptr), intent(in) :: tables(*)
+       integer(c_int32_t), value :: nch
+       type(kidmp_radiometer_cfg), intent(in) :: rcfg(*)
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qc, qr, nr, qs, qg, dz
+       integer(c_int64_t), value :: dz_col_stride
+       type(c_ptr), value :: k_gas
+       integer(c_int64_t), value :: k_gas_col_stride, k_gas_ch_stride
+       type(c_ptr), value :: t_sfc
+       type(kidmp_radiometer_out), intent(in) :: out
+     end function kidmp32_radiometer_multi_host
+     integer(c_int) function kidmp_mie_radar_multi_host(ctx, tables, nch, ncol, nz, t, p, qv, qc, qr, nr, qs, qg, dz, dz_col_stride, &
+          w, k_gas, k_gas_col_stride, k_gas_ch_stride, out) bind(C, name='kidmp_mie_radar_multi_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr, kidmp_mie_out
+       type(c_ptr), value :: ctx
+       type(c_ptr), intent(in) :: tables(*)
+       integer(c_int32_t), value :: nch
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qc, qr, nr, qs, qg, dz
+       integer(c_int64_t), value :: dz_col_stride
+       type(c_ptr), value :: w, k_gas
+       integer(c_int64_t), value :: k_gas_col_stride, k_gas_ch_stride
+       type(kidmp_mie_out), intent(in) :: out
+     end function kidmp_mie_radar_multi_host
+     integer(c_int) function kidmp32_mie_radar_multi_host(ctx, tables, nch, ncol, nz, t, p, qv, qc, qr, nr, qs, qg, dz, dz_col_stride, &
+          w, k_gas, k_gas_col_stride, k_gas_ch_stride, out) bind(C, name='kidmp32_mie_radar_multi_host')
+       import :: c_int, c_int32_t, c_int64_t, c_ptr, kidmp_mie_out
+       type(c_ptr), value :: ctx
+       type(c_ptr), intent(in) :: tables(*)
+       integer(c_int32_t), value :: nch
+       integer(c_int64_t), value :: ncol
+       integer(c_int32_t), value :: nz
+       type(c_ptr), value :: t, p, qv, qc, qr, nr, qs, qg, dz
+       integer(c_int64_t), value :: dz_col_stride
+       type(c_ptr), value :: w, k_gas
+       integer(c_int64_t), value :: k_gas_col_stride, k_gas_ch_stride
+       type(kidmp_mie_out), intent(in) :: out
+     end function kidmp32_mie_radar_multi_host
      ! the polarimetric radar (include/kidmp_polarimetric.h): a table of seven rows per bin, then the operator; qs and qg
      ! may be NULL
      subroutine kidmp_pol_defaults(pcfg) bind(C, name='kidmp_pol_defaults')
@@ -1474,6 +1537,185 @@ contains
     call kidmp_radiometer_table_destroy(table)
     call stop_on_error(rc, 'radiometer_batch')
   end subroutine radiometer_batch
+
+  ! radiometer_batch at nch channels in one launch per chunk of columns (include/kidmp_multichannel.h): the configuration is
+  ! an array of nch wavelengths and permittivities, the outputs are (nz, ncol, nch) and (ncol, nch), and channel c holds the
+  ! bits radiometer_batch gives with the c-th configuration.  k_gas is (nz) for all channels or, as k_gas_ch(nz, nch), one
+  ! profile per channel; mu, emissivity and t_cosmic are one value per channel and keep the library's defaults when left
+  ! out; rho_w and rho_i are shared.  The nch tables are built for the call and freed after it.  1 <= nch <= 16.
+  subroutine radiometer_multi_batch(nch, ncol, nz, wavelength, eps_w_re, eps_w_im, eps_i_re, eps_i_im, t, p, qv, qr, nr, k_abs, &
+       k_bsc, refl, trans, tb_up, tb_down, tb_toa, tb_ground, tau_abs, qc, qs, qg, dz, k_gas, k_gas_ch, t_sfc, rho_w, rho_i, mu, &
+       emissivity, t_cosmic)
+    integer, intent(in) :: nch, ncol, nz
+    real(c_double), dimension(nch), intent(in) :: wavelength, eps_w_re, eps_w_im, eps_i_re, eps_i_im
+    real, dimension(nz,ncol), intent(in), target :: t, p, qv, qr, nr
+    real, dimension(nz,ncol,nch), intent(out), optional, target :: k_abs, k_bsc, refl, trans, tb_up, tb_down
+    real, dimension(ncol,nch), intent(out), optional, target :: tb_toa, tb_ground, tau_abs
+    real, dimension(nz,ncol), intent(in), optional, target :: qc, qs, qg
+    real, dimension(nz), intent(in), optional, target :: dz, k_gas
+    real, dimension(nz,nch), intent(in), optional, target :: k_gas_ch
+    real, dimension(ncol), intent(in), optional, target :: t_sfc
+    real(c_double), intent(in), optional :: rho_w, rho_i
+    real(c_double), dimension(nch), intent(in), optional :: mu, emissivity, t_cosmic
+    type(kidmp_radiometer_out) :: out
+    type(kidmp_radiometer_cfg) :: rcfg(nch)
+    type(kidmp_mie_cfg) :: cfg
+    type(c_ptr) :: tables(nch), pqc, pqs, pqg, pdz, pkg, pts
+    integer(c_int64_t) :: kg_ch
+    integer(c_int) :: rc
+    integer :: c, made
+    if (.not. c_associated(ctx)) call thompson_init
+    if (c_associated(mctx)) then
+       write(*,'(a)') ' module_mp_thompson09n: the radiometer is not available with kidmp_ndevices > 1'
+       stop 1
+    end if
+    if (nch < 1 .or. nch > 16 .or. (present(k_gas) .and. present(k_gas_ch))) then
+       write(*,'(a)') ' module_mp_thompson09n: radiometer_multi_batch: nch outside [1, 16], or both k_gas and k_gas_ch'
+       stop 1
+    end if
+    do c = 1, nch
+       call kidmp_radiometer_defaults(rcfg(c))
+       if (present(mu)) rcfg(c)%mu = mu(c)
+       if (present(emissivity)) rcfg(c)%emissivity = emissivity(c)
+       if (present(t_cosmic)) rcfg(c)%t_cosmic = t_cosmic(c)
+    end do
+    pqc = c_null_ptr;  pqs = c_null_ptr;  pqg = c_null_ptr;  pdz = c_null_ptr;  pkg = c_null_ptr;  pts = c_null_ptr
+    kg_ch = 0
+    if (present(qc)) pqc = c_loc(qc)
+    if (present(qs)) pqs = c_loc(qs)
+    if (present(qg)) pqg = c_loc(qg)
+    if (present(dz)) pdz = c_loc(dz)
+    if (present(k_gas)) pkg = c_loc(k_gas)
+    if (present(k_gas_ch)) then
+       pkg = c_loc(k_gas_ch)
+       kg_ch = nz
+    end if
+    if (present(t_sfc)) pts = c_loc(t_sfc)
+    out = kidmp_radiometer_out(c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
+         c_null_ptr)
+    if (present(k_abs)) out%k_abs = c_loc(k_abs)
+    if (present(k_bsc)) out%k_bsc = c_loc(k_bsc)
+    if (present(refl)) out%refl = c_loc(refl)
+    if (present(trans)) out%trans = c_loc(trans)
+    if (present(tb_up)) out%tb_up = c_loc(tb_up)
+    if (present(tb_down)) out%tb_down = c_loc(tb_down)
+    if (present(tb_toa)) out%tb_toa = c_loc(tb_toa)
+    if (present(tb_ground)) out%tb_ground = c_loc(tb_ground)
+    if (present(tau_abs)) out%tau_abs = c_loc(tau_abs)
+    rc = 0
+    made = 0
+    do c = 1, nch
+       call kidmp_mie_defaults(cfg)
+       cfg%wavelength = wavelength(c)
+       cfg%eps_w_re = eps_w_re(c);  cfg%eps_w_im = eps_w_im(c);  cfg%eps_i_re = eps_i_re(c);  cfg%eps_i_im = eps_i_im(c)
+       if (present(rho_w)) cfg%rho_w = rho_w
+       if (present(rho_i)) cfg%rho_i = rho_i
+       rc = kidmp_radiometer_table_create(ctx, cfg, c_null_ptr, tables(c))
+       if (rc < 0) exit
+       made = c
+    end do
+    if (rc >= 0) then
+       if (kind(t) == c_double) then
+          rc = kidmp_radiometer_multi_host(ctx, tables, int(nch, c_int32_t), rcfg, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), &
+               c_loc(p), c_loc(qv), pqc, c_loc(qr), c_loc(nr), pqs, pqg, pdz, 0_c_int64_t, pkg, 0_c_int64_t, kg_ch, pts, out)
+       else
+          rc = kidmp32_radiometer_multi_host(ctx, tables, int(nch, c_int32_t), rcfg, int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), &
+               c_loc(p), c_loc(qv), pqc, c_loc(qr), c_loc(nr), pqs, pqg, pdz, 0_c_int64_t, pkg, 0_c_int64_t, kg_ch, pts, out)
+       end if
+    end if
+    do c = 1, made
+       call kidmp_radiometer_table_destroy(tables(c))
+    end do
+    call stop_on_error(rc, 'radiometer_multi_batch')
+  end subroutine radiometer_multi_batch
+
+  ! mie_radar_batch at nch channels in one launch per chunk of columns (include/kidmp_multichannel.h), shaped as
+  ! radiometer_multi_batch: profiles (nz, ncol, nch), pia_total (ncol, nch), kw2 one value per channel.  A dual-wavelength
+  ! ratio is dbz(:,:,i) - dbz(:,:,j) on the result.
+  subroutine mie_radar_multi_batch(nch, ncol, nz, wavelength, eps_w_re, eps_w_im, eps_i_re, eps_i_im, t, p, qv, qr, nr, dbz, &
+       dbz_up, dbz_down, dbz_r, dbz_s, dbz_g, mie_r, mie_s, mie_g, ext, pia_up, pia_down, vd, pia_total, qc, qs, qg, dz, w, k_gas, &
+       k_gas_ch, rho_w, rho_i, kw2)
+    integer, intent(in) :: nch, ncol, nz
+    real(c_double), dimension(nch), intent(in) :: wavelength, eps_w_re, eps_w_im, eps_i_re, eps_i_im
+    real, dimension(nz,ncol), intent(in), target :: t, p, qv, qr, nr
+    real, dimension(nz,ncol,nch), intent(out), optional, target :: dbz, dbz_up, dbz_down, dbz_r, dbz_s, dbz_g, mie_r, mie_s, &
+         mie_g, ext, pia_up, pia_down, vd
+    real, dimension(ncol,nch), intent(out), optional, target :: pia_total
+    real, dimension(nz,ncol), intent(in), optional, target :: qc, qs, qg, w
+    real, dimension(nz), intent(in), optional, target :: dz, k_gas
+    real, dimension(nz,nch), intent(in), optional, target :: k_gas_ch
+    real(c_double), intent(in), optional :: rho_w, rho_i
+    real(c_double), dimension(nch), intent(in), optional :: kw2
+    type(kidmp_mie_out) :: out
+    type(kidmp_mie_cfg) :: cfg
+    type(c_ptr) :: tables(nch), pqc, pqs, pqg, pdz, pw, pkg
+    integer(c_int64_t) :: kg_ch
+    integer(c_int) :: rc
+    integer :: c, made
+    if (.not. c_associated(ctx)) call thompson_init
+    if (c_associated(mctx)) then
+       write(*,'(a)') ' module_mp_thompson09n: the cloud radar is not available with kidmp_ndevices > 1'
+       stop 1
+    end if
+    if (nch < 1 .or. nch > 16 .or. (present(k_gas) .and. present(k_gas_ch))) then
+       write(*,'(a)') ' module_mp_thompson09n: mie_radar_multi_batch: nch outside [1, 16], or both k_gas and k_gas_ch'
+       stop 1
+    end if
+    pqc = c_null_ptr;  pqs = c_null_ptr;  pqg = c_null_ptr;  pdz = c_null_ptr;  pw = c_null_ptr;  pkg = c_null_ptr
+    kg_ch = 0
+    if (present(qc)) pqc = c_loc(qc)
+    if (present(qs)) pqs = c_loc(qs)
+    if (present(qg)) pqg = c_loc(qg)
+    if (present(dz)) pdz = c_loc(dz)
+    if (present(w)) pw = c_loc(w)
+    if (present(k_gas)) pkg = c_loc(k_gas)
+    if (present(k_gas_ch)) then
+       pkg = c_loc(k_gas_ch)
+       kg_ch = nz
+    end if
+    out = kidmp_mie_out(c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, &
+         c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr)
+    if (present(dbz)) out%dbz = c_loc(dbz)
+    if (present(dbz_up)) out%dbz_up = c_loc(dbz_up)
+    if (present(dbz_down)) out%dbz_down = c_loc(dbz_down)
+    if (present(dbz_r)) out%dbz_r = c_loc(dbz_r)
+    if (present(dbz_s)) out%dbz_s = c_loc(dbz_s)
+    if (present(dbz_g)) out%dbz_g = c_loc(dbz_g)
+    if (present(mie_r)) out%mie_r = c_loc(mie_r)
+    if (present(mie_s)) out%mie_s = c_loc(mie_s)
+    if (present(mie_g)) out%mie_g = c_loc(mie_g)
+    if (present(ext)) out%ext = c_loc(ext)
+    if (present(pia_up)) out%pia_up = c_loc(pia_up)
+    if (present(pia_down)) out%pia_down = c_loc(pia_down)
+    if (present(vd)) out%vd = c_loc(vd)
+    if (present(pia_total)) out%pia_total = c_loc(pia_total)
+    rc = 0
+    made = 0
+    do c = 1, nch
+       call kidmp_mie_defaults(cfg)
+       cfg%wavelength = wavelength(c)
+       cfg%eps_w_re = eps_w_re(c);  cfg%eps_w_im = eps_w_im(c);  cfg%eps_i_re = eps_i_re(c);  cfg%eps_i_im = eps_i_im(c)
+       if (present(rho_w)) cfg%rho_w = rho_w
+       if (present(rho_i)) cfg%rho_i = rho_i
+       if (present(kw2)) cfg%kw2 = kw2(c)
+       rc = kidmp_mie_table_create(ctx, cfg, c_null_ptr, tables(c))
+       if (rc < 0) exit
+       made = c
+    end do
+    if (rc >= 0) then
+       if (kind(t) == c_double) then
+          rc = kidmp_mie_radar_multi_host(ctx, tables, int(nch, c_int32_t), int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), &
+               c_loc(qv), pqc, c_loc(qr), c_loc(nr), pqs, pqg, pdz, 0_c_int64_t, pw, pkg, 0_c_int64_t, kg_ch, out)
+       else
+          rc = kidmp32_mie_radar_multi_host(ctx, tables, int(nch, c_int32_t), int(ncol, c_int64_t), int(nz, c_int32_t), c_loc(t), c_loc(p), &
+               c_loc(qv), pqc, c_loc(qr), c_loc(nr), pqs, pqg, pdz, 0_c_int64_t, pw, pkg, 0_c_int64_t, kg_ch, out)
+       end if
+    end if
+    do c = 1, made
+       call kidmp_mie_table_destroy(tables(c))
+    end do
+    call stop_on_error(rc, 'mie_radar_multi_batch')
+  end subroutine mie_radar_multi_batch
 
   ! The polarimetric radar over ncol columns of KiD's (nz, ncol) storage in one call (include/kidmp_polarimetric.h): the
   ! reflectivity at horizontal polarisation dbz_h (dBZ), the differential reflectivity zdr (dB), the specific differential

@@ -705,6 +705,28 @@ class ThompsonMP:
         from .radiometer import radiometer_host
         return radiometer_host(self, table, st, dz, k_gas, t_sfc, rcfg, want, out)
 
+    def radiometer_multi(self, tables, st, dz=None, k_gas=None, t_sfc=None, rcfgs=None, want=("tb_toa",), out=None, stream=None):
+        """The radiometer at len(tables) channels in one launch (include/kidmp_multichannel.h):
+        kid_amd.multichannel.radiometer_multi on this context."""
+        from .multichannel import radiometer_multi
+        return radiometer_multi(self, tables, st, dz, k_gas, t_sfc, rcfgs, want, out, stream)
+
+    def radiometer_multi_host(self, tables, st, dz=None, k_gas=None, t_sfc=None, rcfgs=None, want=("tb_toa",), out=None):
+        """radiometer_multi on numpy arrays: kid_amd.multichannel.radiometer_multi_host on this context."""
+        from .multichannel import radiometer_multi_host
+        return radiometer_multi_host(self, tables, st, dz, k_gas, t_sfc, rcfgs, want, out)
+
+    def mie_radar_multi(self, tables, st, dz=None, w=None, k_gas=None, want=("dbz",), out=None, stream=None):
+        """The cloud radar at len(tables) channels in one launch (include/kidmp_multichannel.h):
+        kid_amd.multichannel.mie_radar_multi on this context."""
+        from .multichannel import mie_radar_multi
+        return mie_radar_multi(self, tables, st, dz, w, k_gas, want, out, stream)
+
+    def mie_radar_multi_host(self, tables, st, dz=None, w=None, k_gas=None, want=("dbz",), out=None):
+        """mie_radar_multi on numpy arrays: kid_amd.multichannel.mie_radar_multi_host on this context."""
+        from .multichannel import mie_radar_multi_host
+        return mie_radar_multi_host(self, tables, st, dz, w, k_gas, want, out)
+
     REFL_NAMES = ("t", "p", "qv", "qr", "nr", "qs", "qg")      # the inputs of calc_refl10cm that are read (qc1d is not)
 
     def reflectivity(self, st, out=None, stream=None):
