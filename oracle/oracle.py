@@ -28,7 +28,7 @@ _dp = C.POINTER(C.c_double)
 def build(force=False):
     """Compile oracle/libthompson_oracle.so with gcc (building the checker)."""
     srcs = [os.path.join(_HERE, f) for f in (
-        "thompson_oracle_init.c", "thompson_oracle_column.c", "thompson_oracle_p32n.c",
+        "thompson_oracle_init.c", "thompson_oracle_column.c", "thompson_oracle_p32n.c", "thompson_oracle_p32probe.c",
         "thompson_oracle.h", "thompson_oracle_internal.h", "Makefile")]
     if (not force and os.path.exists(_LIB)
             and all(os.path.getmtime(_LIB) >= os.path.getmtime(s) for s in srcs)):
@@ -62,12 +62,15 @@ def lib():
         L.th_oracle_batch_force.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_double] + [_dp] * 16 + [
             C.c_int, C.POINTER(C.c_int), C.c_int]
         _fp = C.POINTER(C.c_float)
-        L.th_oracle_batch_force_p32n.restype = C.c_int
-        L.th_oracle_batch_force_p32n.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_float] + [_fp] * 16 + [
-            C.c_int, C.POINTER(C.c_int), C.c_int]
-        L.th_oracle_mp_thompson_force_p32n.restype = C.c_int
-        L.th_oracle_mp_thompson_force_p32n.argtypes = [C.c_void_p] + [_fp] * 16 + [
-            C.c_int, C.c_float, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
+        for sfx in ("_p32n", "_p32probe"):        # the P32n build and its probe build (thompson_oracle_p32probe.c)
+            f = getattr(L, "th_oracle_batch_force" + sfx)
+            f.restype = C.c_int
+            f.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_float] + [_fp] * 16 + [C.c_int, C.POINTER(C.c_int), C.c_int]
+            f = getattr(L, "th_oracle_mp_thompson_force" + sfx)
+            f.restype = C.c_int
+            f.argtypes = [C.c_void_p] + [_fp] * 16 + [C.c_int, C.c_float, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
+        L.th_oracle_probe_set.restype = None
+        L.th_oracle_probe_set.argtypes = [C.c_int, C.c_int, C.c_int]
         L.th_oracle_kid_interface_p32n.restype = C.c_int
         L.th_oracle_kid_interface_p32n.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float] + [_fp] * 15
         for f in ("th_oracle_view_const", "th_oracle_view_const_p32n"):
@@ -166,20 +169,28 @@ class Oracle:
         return (ppt, flags) if want_illcond else ppt
 
     # -- P32n: the reference's native arithmetic (REAL = binary32) ------------
-    def batch_step_p32n(self, st, dt, nthreads=None):
-        """In-place step of float32 [ncol, nz] arrays in the reference's native arithmetic; returns ppt float32 [ncol, 4]."""
+    def batch_step_p32n(self, st, dt, nthreads=None, want_illcond=False, force=0, probe=None):
+        """In-place step of float32 [ncol, nz] arrays in the reference's native arithmetic; returns ppt float32 [ncol, 4]
+        (and, if asked, the int32 [ncol, nz] flags), with `force` as in batch_step.  probe = (shift, pattern, narrow)
+        steps through the probe build instead (probe_set; thompson_oracle_p32probe.c)."""
         ncol, nz = st["qv"].shape
         fp = C.POINTER(C.c_float)
         for k in STATE + FORCING:
             assert st[k].dtype == np.float32 and st[k].flags.c_contiguous and st[k].shape == (ncol, nz), k
         ppt = np.zeros((ncol, 4), dtype=np.float32)
-        lib().th_oracle_batch_force_p32n(self._h, ncol, nz, float(dt), *[st[k].ctypes.data_as(fp) for k in STATE],
-                                         *[st[k].ctypes.data_as(fp) for k in FORCING], ppt.ctypes.data_as(fp),
-                                         nthreads or self.nthreads, None, 0)
-        return ppt
+        flags = np.zeros((ncol, nz), dtype=np.int32) if want_illcond else None
+        entry = lib().th_oracle_batch_force_p32n
+        if probe is not None:
+            probe_set(*probe)
+            entry = lib().th_oracle_batch_force_p32probe
+        entry(self._h, ncol, nz, float(dt), *[st[k].ctypes.data_as(fp) for k in STATE],
+              *[st[k].ctypes.data_as(fp) for k in FORCING], ppt.ctypes.data_as(fp), nthreads or self.nthreads,
+              flags.ctypes.data_as(C.POINTER(C.c_int)) if want_illcond else None, int(force))
+        return (ppt, flags) if want_illcond else ppt
 
-    def column_step_p32n(self, st, dt, want_rates=False):
-        """One float32 column in place; returns (ppt[4] float32, rates float64 [36, nz] or None, nstep[4], no_micro)."""
+    def column_step_p32n(self, st, dt, want_rates=False, probe=None):
+        """One float32 column in place; returns (ppt[4] float32, rates float64 [36, nz] or None, nstep[4], no_micro).
+        probe: as in batch_step_p32n."""
         nz = st["qv"].shape[0]
         fp = C.POINTER(C.c_float)
         for k in STATE + FORCING:
@@ -187,7 +198,11 @@ class Oracle:
         ppt = np.zeros(4, dtype=np.float32)
         rates = np.zeros((NRATES, nz)) if want_rates else None
         nstep = (C.c_int * 4)()
-        rc = lib().th_oracle_mp_thompson_force_p32n(
+        entry = lib().th_oracle_mp_thompson_force_p32n
+        if probe is not None:
+            probe_set(*probe)
+            entry = lib().th_oracle_mp_thompson_force_p32probe
+        rc = entry(
             self._h, *[st[k].ctypes.data_as(fp) for k in STATE], *[st[k].ctypes.data_as(fp) for k in FORCING],
             ppt.ctypes.data_as(fp), nz, float(dt), _p(rates) if want_rates else None, nstep, None, 0)
         if rc < 0:
@@ -264,6 +279,16 @@ class Oracle:
 
     def integer(self, name):
         return lib().th_oracle_int(self._h, name.encode())
+
+
+PROBE_UP, PROBE_DOWN, PROBE_ALTERNATING = 0, 1, 2
+
+
+def probe_set(shift=0, pattern=PROBE_UP, narrow=False):
+    """The probe build's setting, process-wide; between batches only.  `shift` ulp (signed) on every REAL-argument exp,
+    log, log10, cbrt and pow, every REAL reciprocal of mp_thompson and its rate-limiting quotients, in the given pattern;
+    `narrow`: the DOUBLE-argument special functions rounded to binary32."""
+    lib().th_oracle_probe_set(int(shift), int(pattern), int(bool(narrow)))
 
 
 def u4_count(p32n=False):

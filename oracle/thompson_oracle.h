@@ -140,6 +140,23 @@ int th_oracle_kid_interface_p32n(const th_oracle *o, int nz, int nx, float dt, f
                                  const float *dqv_div, const float *hydro, const float *dhydro_adv,
                                  const float *dhydro_div, float *dtheta_mphys, float *dqv_mphys,
                                  float *dhydro_mphys, float *ppt);
+/* ---- the probe build of P32n (thompson_oracle_p32probe.c): the same two entries with the special functions, the REAL
+ * reciprocals of mp_thompson (RCP) and its rate-limiting quotients (RDIV) routed through helpers.  th_oracle_probe_set is
+ * process-wide and is called between batches only: each of those results is evaluated in binary64, rounded once and
+ * moved by `shift` ulp (signed); pattern 0 = every call by +shift, 1 = every call by -shift, 2 = alternating by call
+ * (+shift first in every column); narrow != 0 rounds the results of the DOUBLE-argument special functions to binary32.
+ * (0, 0, 0) is the P32n arithmetic with correctly rounded special functions. */
+void th_oracle_probe_set(int shift, int pattern, int narrow);
+int th_oracle_mp_thompson_force_p32probe(const th_oracle *o,
+                                         float *qv1d, float *qc1d, float *qi1d, float *qr1d, float *qs1d, float *qg1d,
+                                         float *ni1d, float *nr1d, float *nc1d, float *nwfa1d, float *nifa1d, float *t1d,
+                                         const float *p1d, const float *w1d, const float *dzq, float ppt[4],
+                                         int nz, float dt, double *rates, int *nstep_out, int *illcond, int force);
+int th_oracle_batch_force_p32probe(const th_oracle *o, long ncol, int nz, float dt,
+                                   float *qv, float *qc, float *qi, float *qr, float *qs, float *qg, float *ni, float *nr,
+                                   float *nc, float *nwfa, float *nifa, float *t,
+                                   const float *p, const float *w, const float *dz,
+                                   float *ppt, int nthreads, int *illcond, int force);
 /* the constants mp_thompson reads in each arithmetic, by name (tests): -1e30 if unknown */
 double th_oracle_view_const(const th_oracle *o, const char *name, int idx);
 double th_oracle_view_const_p32n(const th_oracle *o, const char *name, int idx);

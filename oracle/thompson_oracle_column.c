@@ -28,6 +28,9 @@
  *         arithmetic conversions then reproduce Fortran's mixed-mode rules (REAL op DOUBLE -> DOUBLE);
  *         <tgmath.h> picks expf/powf/logf... for REAL arguments exactly where the Fortran generic intrinsics
  *         do.  Entry points carry the suffix _p32n and take float arrays.
+ * A third compilation, the PROBE build of P32n (thompson_oracle_p32probe.c, suffix _p32probe), routes the special
+ * functions and the reciprocals written RCP(x) below through helpers that move their last bits; test infrastructure of
+ * tests/parity32.py.  In the other two builds RCP(x) is the text `1. / (x)` it replaced.
  */
 #include "thompson_oracle_internal.h"
 #include <pthread.h>
@@ -36,10 +39,33 @@
 #ifdef TH_P32N
 #include <tgmath.h>
 typedef float real;
+#ifdef TH_PROBE                      /* the probe build (thompson_oracle_p32probe.c): a second P32n build in the same library */
+#define P(name) name##_p32probe
+#else
 #define P(name) name##_p32n
+#endif
+#define VIEW view_p32n               /* both P32n builds read the view that the unmodified one made */
+#define RESIDUE_REL 1e-6             /* a cancellation residue of REAL terms: a few ulps of binary32 (block Q's flags) */
 #else
 typedef double real;
 #define P(name) name
+#define VIEW view
+#define RESIDUE_REL 1e-9
+#endif
+#ifndef TH_PROBE_COLUMN_START
+#define TH_PROBE_COLUMN_START() ((void)0)
+#endif
+/* the reciprocals of mp_thompson (odt, orho, ocp, otemp, ilamr ...): `1. / x` in every build but the probe build, which
+ * moves the REAL ones like its special functions (a device forms them with a reciprocal unit, not a correctly rounded
+ * division) */
+#ifndef RCP
+#define RCP(x) (1. / (x))
+#endif
+/* the six quotients rate_max / sump of block I, which scale a species' sinks so that they remove exactly what is there:
+ * the division itself in every build but the probe build, which moves it like a reciprocal (a device divides with its
+ * reciprocal unit and a product) */
+#ifndef RDIV
+#define RDIV(a, b) ((a) / (b))
 #endif
 
 /* real**integer for a REAL base (compiler-rt __powisf2 in P32n, __powidf2 in P64), e.g. 10.**nn at M:1766 */
@@ -378,7 +404,7 @@ void *P(th_oracle_make_view)(const th_oracle *c)
 /* the view's constants by name, for tests (P64: must equal the context's; P32n: the fp32 values) */
 double P(th_oracle_view_const)(const th_oracle *c, const char *name, int idx)
 {
-    const th_view *o = (const th_view *)c->P(view);
+    const th_view *o = (const th_view *)c->VIEW;
 #define VC(n) if (!strcmp(name, #n)) return (double)o->n
 #define VA(n) if (!strcmp(name, #n)) return (double)o->n[idx]
     VC(Nt_c); VC(Sc3); VC(D0i); VC(xm0s); VC(xm0g); VC(oig1); VC(oig2); VC(org1); VC(org2); VC(org3); VC(oams);
@@ -445,13 +471,14 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
                                 const real *dzq, real ppt[4],
                                 int nz, real dt, double *rates, int *nstep_out, int *illcond, int force)
 {
-    const th_view *o = (const th_view *)ctx->P(view);
+    const th_view *o = (const th_view *)ctx->VIEW;
+    TH_PROBE_COLUMN_START();                                   /* probe build only: the alternating pattern restarts with every column */
     const int aero = o->is_aerosol_aware;                      /* M:28; .false. in KiD, settable here */
     const int kts = 0, kte = nz - 1;
     const size_t NA = 100, ND = 80;
     real *ws = (real *)calloc(NA * (size_t)(nz + 2), sizeof(real));          /* REAL work arrays */
     double *wd = (double *)calloc(ND * (size_t)(nz + 2), sizeof(double));    /* DOUBLE PRECISION work arrays */
-    int *Lws = (int *)calloc(5 * (size_t)nz, sizeof(int));
+    int *Lws = (int *)calloc(7 * (size_t)nz, sizeof(int));
     if (!ws || !wd || !Lws) { free(ws); free(wd); free(Lws); return -1; }
     size_t wi = 0, di = 0;
 #define A(name) real *name = ws + (wi++) * (size_t)(nz + 2)
@@ -486,6 +513,10 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
 #undef A
 #undef AD
     int *L_qc = Lws, *L_qi = Lws + nz, *L_qr = Lws + 2 * nz, *L_qs = Lws + 3 * nz, *L_qg = Lws + 4 * nz;
+    /* P32n builds, force = 2 only: a residue-decided test of block Q taken as false means that the residue is not
+     * positive in that rounding, so the species is gone.  In binary64 the residue (1e-20) is below R1 and block R zeroes
+     * it anyway; one ulp of a binary32 mixing ratio (1e-11) is above R1 and would survive with a number of its own. */
+    int *gone_c = Lws + 5 * nz, *gone_i = Lws + 6 * nz;
 
     const real *cce2 = o->cce[2], *ccg1 = o->ccg[1], *ccg2 = o->ccg[2], *ccg3 = o->ccg[3];
     const real *ocg1 = o->ocg1, *ocg2 = o->ocg2;
@@ -526,8 +557,8 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
 
     no_micro = 1;                                           /* M:1276-1280 */
     dtsave = dt;
-    odt = 1. / dt;
-    odts = 1. / dtsave;
+    odt = RCP(dt);
+    odts = RCP(dtsave);
     /* M:1282-1381: all arrays are zero from calloc */
     if (rates) memset(rates, 0, sizeof(double) * TH_ORACLE_NRATES * (size_t)nz);
     if (nstep_out) { nstep_out[0] = nstep_out[1] = nstep_out[2] = nstep_out[3] = 0; }
@@ -574,7 +605,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
             }
             L_qi[k] = 1;
             lami = pow(am_i * cig[2] * oig1 * ni[k] / ri[k], obmi);
-            ilami = 1. / lami;
+            ilami = RCP(lami);
             xDi = (bm_i + mu_i + 1.) * ilami;
             if (xDi < 5.E-6) {
                 lami = cie[2] / 5.E-6;
@@ -662,7 +693,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
             visco[k] = (1.718 + 0.0049 * tempc) * 1.0E-5;
         else
             visco[k] = (1.718 + 0.0049 * tempc - 1.2E-5 * tempc * tempc) * 1.0E-5;
-        ocp[k] = 1. / (Cp * (1. + 0.887 * qv[k]));
+        ocp[k] = RCP((Cp * (1. + 0.887 * qv[k])));
         vsc2[k] = sqrt(rho[k] / visco[k]);
         lvap[k] = lvap0 + (2106.0 - 4218.0) * tempc;
         tcond[k] = (5.69 + 0.0168 * tempc) * 1.0E-5 * 418.936;
@@ -731,7 +762,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
             N0_exp = N0_min;
             lam_exp = pow(N0_exp * am_g * cgg[1] / rg[k], oge1);
             lamg = lam_exp * pow(cgg[3] * ogg2 * ogg1, obmg);
-            ilamg[k] = 1. / lamg;
+            ilamg[k] = RCP(lamg);
             N0_g[k] = N0_exp / (cgg[2] * lam_exp) * pow(lamg, cge[2]);
         }
     }
@@ -739,7 +770,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
     /* ---- F: rain slope/intercept, M:1661-1666 ---- */
     for (k = kte; k >= kts; k--) {
         lamr = pow(am_r * crg[3] * org2 * nr[k] / rr[k], obmr);
-        ilamr[k] = 1. / lamr;
+        ilamr[k] = RCP(lamr);
         mvd_r[k] = (3.0 + mu_r + 0.672) / lamr;
         N0_r[k] = nr[k] * org2 * pow(lamr, cre[2]);
     }
@@ -773,7 +804,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
         }
 
         if (L_qr[k] && mvd_r[k] > D0r && mvd_c[k] > D0c) {
-            lamr = 1. / ilamr[k];
+            lamr = RCP(ilamr[k]);
             idx = 1 + (int)(nbr * log(mvd_r[k] / o->Dr[1]) / log(o->Dr[nbr] / o->Dr[1]));
             idx = idx < nbr ? idx : nbr;
             if (idx < 1) idx = 1;
@@ -786,7 +817,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
 
         if (L_qr[k] && mvd_r[k] > D0r) {                    /* dead outputs, M:1729-1740 */
             Ef_ra = Eff_aero(mvd_r[k], 0.04E-6, visco[k], rho[k], temp[k], 'r');
-            lamr = 1. / ilamr[k];
+            lamr = RCP(ilamr[k]);
             pna_rca[k] = rhof[k] * o->t1_qr_qc * Ef_ra * nwfa[k] * N0_r[k] * pow(lamr + fv_r, -cre[9]);
             pna_rca[k] = MIND(nwfa[k] * odts, pna_rca[k]);
             Ef_ra = Eff_aero(mvd_r[k], 0.8E-6, visco[k], rho[k], temp[k], 'r');
@@ -824,7 +855,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
 
             if (rr[k] > o->r_r[1]) {
                 idx_r = decade_index(rr[k], NINT(log10(rr[k])), o->nir2, ntb_r);
-                lamr = 1. / ilamr[k];
+                lamr = RCP(ilamr[k]);
                 lam_exp = lamr * pow(crg[3] * org2 * org1, bm_r);
                 N0_exp = org1 * rr[k] / am_r * pow(lam_exp, cre[1]);
                 idx_r1 = decade_index_d(N0_exp, NINT(log10(N0_exp)), o->nir3, ntb_r1);
@@ -840,7 +871,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
 
             if (rg[k] > o->r_g[1]) {
                 idx_g = decade_index(rg[k], NINT(log10(rg[k])), o->nig2, ntb_g);
-                lamg = 1. / ilamg[k];
+                lamg = RCP(ilamg[k]);
                 lam_exp = lamg * pow(cgg[3] * ogg2 * ogg1, bm_g);
                 N0_exp = ogg1 * rg[k] / am_g * pow(lam_exp, cge[1]);
                 idx_g1 = decade_index_d(N0_exp, NINT(log10(N0_exp)), o->nig3, ntb_g1);
@@ -850,7 +881,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
             }
 
             /* S&C prefactor M:1884-1900 */
-            otemp = 1. / temp[k];
+            otemp = RCP(temp[k]);
             rvs = rho[k] * qvsi[k];
             rvs_p = rvs * otemp * (lsub * otemp * oRv - 1.);
             rvs_pp = rvs * (otemp * (lsub * otemp * oRv - 1.)
@@ -1008,10 +1039,10 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
                 /* ice deposition/sublimation M:2116-2149 */
                 if (L_qi[k]) {
                     lami = pow(am_i * cig[2] * oig1 * ni[k] / ri[k], obmi);
-                    ilami = 1. / lami;
+                    ilami = RCP(lami);
                     xDi = MAXD(D0i, (bm_i + mu_i + 1.) * ilami);
                     xmi = am_i * pow(xDi, bm_i);
-                    oxmi = 1. / xmi;
+                    oxmi = RCP(xmi);
                     pri_ide[k] = C_cube * t1_subl * diffu[k] * ssati[k] * rvs * oig1 * cig[5] * ni[k] * ilami;
 
                     if (pri_ide[k] < 0.0) {
@@ -1063,16 +1094,16 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
                 /* snow/rain collecting ice M:2178-2202 */
                 if (L_qi[k]) {
                     lami = pow(am_i * cig[2] * oig1 * ni[k] / ri[k], obmi);
-                    ilami = 1. / lami;
+                    ilami = RCP(lami);
                     xDi = MAXD(D0i, (bm_i + mu_i + 1.) * ilami);
                     xmi = am_i * pow(xDi, bm_i);
-                    oxmi = 1. / xmi;
+                    oxmi = RCP(xmi);
                     if (rs[k] >= o->r_s[1]) {
                         prs_sci[k] = o->t1_qs_qi * rhof[k] * Ef_si * ri[k] * smoe[k];
                         pni_sci[k] = prs_sci[k] * oxmi;
                     }
                     if (rr[k] >= o->r_r[1] && mvd_r[k] > 4. * xDi) {
-                        lamr = 1. / ilamr[k];
+                        lamr = RCP(ilamr[k]);
                         pri_rci[k] = rhof[k] * o->t1_qr_qi * Ef_ri * ri[k] * N0_r[k] * pow(lamr + fv_r, -cre[9]);
                         pnr_rci[k] = rhof[k] * o->t1_qr_qi * Ef_ri * ni[k] * N0_r[k] * pow(lamr + fv_r, -cre[9]);
                         pni_rci[k] = pri_rci[k] * oxmi;
@@ -1147,7 +1178,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
         sump = pri_inu[k] + pri_ide[k] + prs_ide[k] + prs_sde[k] + prg_gde[k] + pri_iha[k];
         rate_max = (qv[k] - qvsi[k]) * odts * 0.999;
         if ((sump > eps && sump > rate_max) || (sump < -eps && sump < rate_max)) {
-            ratio = rate_max / sump;
+            ratio = RDIV(rate_max, sump);
             pri_inu[k] = pri_inu[k] * ratio;
             pri_ide[k] = pri_ide[k] * ratio;
             pni_ide[k] = pni_ide[k] * ratio;
@@ -1160,7 +1191,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
         sump = -prr_wau[k] - pri_wfz[k] - prr_rcw[k] - prs_scw[k] - prg_scw[k] - prg_gcw[k];
         rate_max = -rc[k] * odts;
         if (sump < rate_max && L_qc[k]) {
-            ratio = rate_max / sump;
+            ratio = RDIV(rate_max, sump);
             prr_wau[k] = prr_wau[k] * ratio;
             pri_wfz[k] = pri_wfz[k] * ratio;
             prr_rcw[k] = prr_rcw[k] * ratio;
@@ -1172,7 +1203,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
         sump = pri_ide[k] - prs_iau[k] - prs_sci[k] - pri_rci[k];
         rate_max = -ri[k] * odts;
         if (sump < rate_max && L_qi[k]) {
-            ratio = rate_max / sump;
+            ratio = RDIV(rate_max, sump);
             pri_ide[k] = pri_ide[k] * ratio;
             prs_iau[k] = prs_iau[k] * ratio;
             prs_sci[k] = prs_sci[k] * ratio;
@@ -1182,7 +1213,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
         sump = -prg_rfz[k] - pri_rfz[k] - prr_rci[k] + prr_rcs[k] + prr_rcg[k];
         rate_max = -rr[k] * odts;
         if (sump < rate_max && L_qr[k]) {
-            ratio = rate_max / sump;
+            ratio = RDIV(rate_max, sump);
             prg_rfz[k] = prg_rfz[k] * ratio;
             pri_rfz[k] = pri_rfz[k] * ratio;
             prr_rci[k] = prr_rci[k] * ratio;
@@ -1193,7 +1224,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
         sump = prs_sde[k] - prs_ihm[k] - prr_sml[k] + prs_rcs[k];
         rate_max = -rs[k] * odts;
         if (sump < rate_max && L_qs[k]) {
-            ratio = rate_max / sump;
+            ratio = RDIV(rate_max, sump);
             prs_sde[k] = prs_sde[k] * ratio;
             prs_ihm[k] = prs_ihm[k] * ratio;
             prr_sml[k] = prr_sml[k] * ratio;
@@ -1203,7 +1234,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
         sump = prg_gde[k] - prg_ihm[k] - prr_gml[k] + prg_rcg[k];
         rate_max = -rg[k] * odts;
         if (sump < rate_max && L_qg[k]) {
-            ratio = rate_max / sump;
+            ratio = RDIV(rate_max, sump);
             prg_gde[k] = prg_gde[k] * ratio;
             prg_ihm[k] = prg_ihm[k] * ratio;
             prr_gml[k] = prr_gml[k] * ratio;
@@ -1223,7 +1254,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
 
     /* ---- J: tendencies + number re-balance, M:2393-2569 ---- */
     for (k = kts; k <= kte; k++) {
-        orho = 1. / rho[k];
+        orho = RCP(rho[k]);
         lfus2 = lsub - lvap[k];
 
         if (aero) {                                          /* M:2397-2408 (dustyIce = .true.) */
@@ -1270,7 +1301,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
         xni = MAXD(R2, (ni1d[k] + niten[k] * dtsave) * rho[k]);
         if (xri > R1) {
             lami = pow(am_i * cig[2] * oig1 * xni / xri, obmi);
-            ilami = 1. / lami;
+            ilami = RCP(lami);
             xDi = (bm_i + mu_i + 1.) * ilami;
             if (xDi < 5.E-6) {
                 lami = cie[2] / 5.E-6;
@@ -1338,7 +1369,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
     /* ---- K: update for TAU+1 before condensation & sedimentation, M:2574-2656 ---- */
     for (k = kts; k <= kte; k++) {
         temp[k] = t1d[k] + DT * tten[k];
-        otemp = 1. / temp[k];
+        otemp = RCP(temp[k]);
         tempc = temp[k] - 273.15;
         qv[k] = MAXD(1.E-10, qv1d[k] + DT * qvten[k]);
         rho[k] = 0.622 * pres[k] / (R_gas * temp[k] * (qv[k] + 0.622));
@@ -1355,7 +1386,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
         vsc2[k] = sqrt(rho[k] / visco[k]);
         lvap[k] = lvap0 + (2106.0 - 4218.0) * tempc;
         tcond[k] = (5.69 + 0.0168 * tempc) * 1.0E-5 * 418.936;
-        ocp[k] = 1. / (Cp * (1. + 0.887 * qv[k]));
+        ocp[k] = RCP((Cp * (1. + 0.887 * qv[k])));
         lvt2[k] = lvap[k] * lvap[k] * ocp[k] * oRv * otemp * otemp;
 
         nwfa[k] = MAXD(11.1E6, (nwfa1d[k] + nwfaten[k] * DT) * rho[k]);
@@ -1460,21 +1491,21 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
             N0_exp = N0_min;
             lam_exp = pow(N0_exp * am_g * cgg[1] / rg[k], oge1);
             lamg = lam_exp * pow(cgg[3] * ogg2 * ogg1, obmg);
-            ilamg[k] = 1. / lamg;
+            ilamg[k] = RCP(lamg);
             N0_g[k] = N0_exp / (cgg[2] * lam_exp) * pow(lamg, cge[2]);
         }
     }
 
     for (k = kte; k >= kts; k--) {                           /* M:2745-2750 */
         lamr = pow(am_r * crg[3] * org2 * nr[k] / rr[k], obmr);
-        ilamr[k] = 1. / lamr;
+        ilamr[k] = RCP(lamr);
         mvd_r[k] = (3.0 + mu_r + 0.672) / lamr;
         N0_r[k] = nr[k] * org2 * pow(lamr, cre[2]);
     }
 
     /* ---- M: cloud water condensation/evaporation, M:2780-2874 ---- */
     for (k = kts; k <= kte; k++) {
-        orho = 1. / rho[k];
+        orho = RCP(rho[k]);
         if ((ssatw[k] > eps) || (ssatw[k] < -eps && L_qc[k])) {
             clap = (qv[k] - qvs[k]) / (1. + lvt2[k] * qvs[k]);
             for (n = 1; n <= 3; n++) {
@@ -1492,7 +1523,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
                     pnc_wcd[k] = 0.5 * (xnc - nc[k] + fabs(xnc - nc[k])) * odts * orho;
                 } else if (clap < -eps && ssatw[k] < -1.E-6 && aero) {      /* droplet evaporation, M:2804-2852 */
                     tempc = temp[k] - 273.15;
-                    otemp = 1. / temp[k];
+                    otemp = RCP(temp[k]);
                     rvs = rho[k] * qvs[k];
                     rvs_p = rvs * otemp * (lvap[k] * otemp * oRv - 1.);
                     rvs_pp = rvs * (otemp * (lvap[k] * otemp * oRv - 1.) * otemp * (lvap[k] * otemp * oRv - 1.)
@@ -1539,8 +1570,8 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
     for (k = kts; k <= kte; k++) {
         if ((ssatw[k] < -eps) && L_qr[k] && (!(prw_vcd[k] > 0.))) {
             tempc = temp[k] - 273.15;
-            otemp = 1. / temp[k];
-            orho = 1. / rho[k];
+            otemp = RCP(temp[k]);
+            orho = RCP(rho[k]);
             rhof[k] = sqrt(rho_not * orho);
             rhof2[k] = sqrt(rhof[k]);
             diffu[k] = 2.11E-5 * pow(temp[k] / 273.15, 1.94) * (101325. / pres[k]);
@@ -1551,7 +1582,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
             vsc2[k] = sqrt(rho[k] / visco[k]);
             lvap[k] = lvap0 + (2106.0 - 4218.0) * tempc;
             tcond[k] = (5.69 + 0.0168 * tempc) * 1.0E-5 * 418.936;
-            ocp[k] = 1. / (Cp * (1. + 0.887 * qv[k]));
+            ocp[k] = RCP((Cp * (1. + 0.887 * qv[k])));
 
             rvs = rho[k] * qvs[k];
             rvs_p = rvs * otemp * (lvap[k] * otemp * oRv - 1.);
@@ -1568,7 +1599,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
                                - 5. * alphsc * alphsc * alphsc * xsat * xsat * xsat)
                     / (1. + gamsc);
 
-            lamr = 1. / ilamr[k];
+            lamr = RCP(ilamr[k]);
 
             if (qv[k] / qvs[k] < 0.95 && rr[k] * orho <= 1.E-8) {
                 prv_rev[k] = rr[k] * orho * odts;
@@ -1639,7 +1670,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
         }
     }
     if (ksed1[1] == kte) ksed1[1] = kte - 1;
-    if (nstep > 0) onstep[1] = 1. / (real)nstep;
+    if (nstep > 0) onstep[1] = RCP((real)nstep);
 
     if (!iiwarm) {
         nstep = 0;
@@ -1647,7 +1678,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
             vti = 0.;
             if (ri[k] > R1) {
                 lami = pow(am_i * cig[2] * oig1 * ni[k] / ri[k], obmi);
-                ilami = 1. / lami;
+                ilami = RCP(lami);
                 vti = rhof[k] * av_i * cig[3] * oig2 * pow(ilami, bv_i);
                 vtik[k] = vti;
                 vti = rhof[k] * av_i * cig[6] / cig[7] * pow(ilami, bv_i);
@@ -1664,20 +1695,20 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
             }
         }
         if (ksed1[2] == kte) ksed1[2] = kte - 1;
-        if (nstep > 0) onstep[2] = 1. / (real)nstep;
+        if (nstep > 0) onstep[2] = RCP((real)nstep);
 
         nstep = 0;
         for (k = kte; k >= kts; k--) {
             vts = 0.;
             if (rs[k] > R1) {
                 xDs = smoc[k] / smob[k];
-                Mrat = 1. / xDs;
-                ils1 = 1. / (Mrat * Lam0 + fv_s);
-                ils2 = 1. / (Mrat * Lam1 + fv_s);
+                Mrat = RCP(xDs);
+                ils1 = RCP((Mrat * Lam0 + fv_s));
+                ils2 = RCP((Mrat * Lam1 + fv_s));
                 t1_vts = Kap0 * csg[4] * pow(ils1, cse[4]);
                 t2_vts = Kap1 * pow(Mrat, mu_s) * csg[10] * pow(ils2, cse[10]);
-                ils1 = 1. / (Mrat * Lam0);
-                ils2 = 1. / (Mrat * Lam1);
+                ils1 = RCP((Mrat * Lam0));
+                ils2 = RCP((Mrat * Lam1));
                 t3_vts = Kap0 * csg[1] * pow(ils1, cse[1]);
                 t4_vts = Kap1 * pow(Mrat, mu_s) * csg[7] * pow(ils2, cse[7]);
                 vts = rhof[k] * av_s * (t1_vts + t2_vts) / (t3_vts + t4_vts);
@@ -1696,7 +1727,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
             }
         }
         if (ksed1[3] == kte) ksed1[3] = kte - 1;
-        if (nstep > 0) onstep[3] = 1. / (real)nstep;
+        if (nstep > 0) onstep[3] = RCP((real)nstep);
 
         nstep = 0;
         for (k = kte; k >= kts; k--) {
@@ -1718,7 +1749,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
             }
         }
         if (ksed1[4] == kte) ksed1[4] = kte - 1;
-        if (nstep > 0) onstep[4] = 1. / (real)nstep;
+        if (nstep > 0) onstep[4] = RCP((real)nstep);
     } else {
         for (k = kte; k >= kts; k--) { vtik[k] = 0.; vtnik[k] = 0.; vtsk[k] = 0.; vtgk[k] = 0.; }
     }
@@ -1732,15 +1763,15 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
             sed_n[k] = vtnrk[k] * nr[k];
         }
         k = kte;
-        odzq = 1. / dzq[k];
-        orho = 1. / rho[k];
+        odzq = RCP(dzq[k]);
+        orho = RCP(rho[k]);
         qrten[k] = qrten[k] - sed_r[k] * odzq * onstep[1] * orho;
         nrten[k] = nrten[k] - sed_n[k] * odzq * onstep[1] * orho;
         rr[k] = MAXD(R1, rr[k] - sed_r[k] * odzq * DT * onstep[1]);
         nr[k] = MAXD(R2, nr[k] - sed_n[k] * odzq * DT * onstep[1]);
         for (k = ksed1[1]; k >= kts; k--) {
-            odzq = 1. / dzq[k];
-            orho = 1. / rho[k];
+            odzq = RCP(dzq[k]);
+            orho = RCP(rho[k]);
             qrten[k] = qrten[k] + (sed_r[k + 1] - sed_r[k]) * odzq * onstep[1] * orho;
             nrten[k] = nrten[k] + (sed_n[k + 1] - sed_n[k]) * odzq * onstep[1] * orho;
             rr[k] = MAXD(R1, rr[k] + (sed_r[k + 1] - sed_r[k]) * odzq * DT * onstep[1]);
@@ -1764,15 +1795,15 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
             for (k = kts; k <= kte; k++) { sed_i[k] = 0.; sed_n[k] = 0.; }
         }
         k = kte;
-        odzq = 1. / dzq[k];
-        orho = 1. / rho[k];
+        odzq = RCP(dzq[k]);
+        orho = RCP(rho[k]);
         qiten[k] = qiten[k] - sed_i[k] * odzq * onstep[2] * orho;
         niten[k] = niten[k] - sed_n[k] * odzq * onstep[2] * orho;
         ri[k] = MAXD(R1, ri[k] - sed_i[k] * odzq * DT * onstep[2]);
         ni[k] = MAXD(R2, ni[k] - sed_n[k] * odzq * DT * onstep[2]);
         for (k = ksed1[2]; k >= kts; k--) {
-            odzq = 1. / dzq[k];
-            orho = 1. / rho[k];
+            odzq = RCP(dzq[k]);
+            orho = RCP(rho[k]);
             qiten[k] = qiten[k] + (sed_i[k + 1] - sed_i[k]) * odzq * onstep[2] * orho;
             niten[k] = niten[k] + (sed_n[k + 1] - sed_n[k]) * odzq * onstep[2] * orho;
             ri[k] = MAXD(R1, ri[k] + (sed_i[k + 1] - sed_i[k]) * odzq * DT * onstep[2]);
@@ -1791,13 +1822,13 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
             for (k = kts; k <= kte; k++) sed_s[k] = 0.;
         }
         k = kte;
-        odzq = 1. / dzq[k];
-        orho = 1. / rho[k];
+        odzq = RCP(dzq[k]);
+        orho = RCP(rho[k]);
         qsten[k] = qsten[k] - sed_s[k] * odzq * onstep[3] * orho;
         rs[k] = MAXD(R1, rs[k] - sed_s[k] * odzq * DT * onstep[3]);
         for (k = ksed1[3]; k >= kts; k--) {
-            odzq = 1. / dzq[k];
-            orho = 1. / rho[k];
+            odzq = RCP(dzq[k]);
+            orho = RCP(rho[k]);
             qsten[k] = qsten[k] + (sed_s[k + 1] - sed_s[k]) * odzq * onstep[3] * orho;
             rs[k] = MAXD(R1, rs[k] + (sed_s[k + 1] - sed_s[k]) * odzq * DT * onstep[3]);
         }
@@ -1814,13 +1845,13 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
             for (k = kts; k <= kte; k++) sed_g[k] = 0.;
         }
         k = kte;
-        odzq = 1. / dzq[k];
-        orho = 1. / rho[k];
+        odzq = RCP(dzq[k]);
+        orho = RCP(rho[k]);
         qgten[k] = qgten[k] - sed_g[k] * odzq * onstep[4] * orho;
         rg[k] = MAXD(R1, rg[k] - sed_g[k] * odzq * DT * onstep[4]);
         for (k = ksed1[4]; k >= kts; k--) {
-            odzq = 1. / dzq[k];
-            orho = 1. / rho[k];
+            odzq = RCP(dzq[k]);
+            orho = RCP(rho[k]);
             qgten[k] = qgten[k] + (sed_g[k + 1] - sed_g[k]) * odzq * onstep[4] * orho;
             rg[k] = MAXD(R1, rg[k] + (sed_g[k + 1] - sed_g[k]) * odzq * DT * onstep[4]);
         }
@@ -1840,12 +1871,15 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
             int res_ri = 0, res_rc = 0;
             {
                 double sc = MAXD(fabs(qi1d[k]), fabs(qiten[k] * DT));
-                if (temp[k] > T_0 && sc > 0. && fabs(qi1d[k] + qiten[k] * DT) <= 1e-9 * sc) res_ri = 1;
+                if (temp[k] > T_0 && sc > 0. && fabs(qi1d[k] + qiten[k] * DT) <= RESIDUE_REL * sc) res_ri = 1;
                 sc = MAXD(fabs(qc1d[k]), fabs(qcten[k] * DT));
                 /* xrc is re-evaluated after the melt branch; T > T_0 and T < HGFR exclude each other, so qcten
                  * is still the value this test will see */
-                if (temp[k] < HGFR && sc > 0. && fabs(qc1d[k] + qcten[k] * DT) <= 1e-9 * sc) res_rc = 1;
+                if (temp[k] < HGFR && sc > 0. && fabs(qc1d[k] + qcten[k] * DT) <= RESIDUE_REL * sc) res_rc = 1;
                 if (illcond) illcond[k] |= res_ri | (res_rc << 1);
+#ifdef TH_P32N
+                if (force == 2) { gone_i[k] = res_ri; gone_c[k] = res_rc; }
+#endif
             }
             const int take_ri = (force && res_ri) ? (force == 1) : (xri > 0.0);
             if ((temp[k] > T_0) && take_ri) {
@@ -1879,7 +1913,7 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
         nwfa1d[k] = MAXD(11.1E6 / rho[k], MIND(9999.E6 / rho[k], (nwfa1d[k] + nwfaten[k] * DT)));
         nifa1d[k] = MAXD(naIN1 * 0.01, MIND(9999.E6 / rho[k], (nifa1d[k] + nifaten[k] * DT)));
 
-        if (qc1d[k] <= R1) {
+        if (qc1d[k] <= R1 || gone_c[k]) {
             qc1d[k] = 0.0;
             nc1d[k] = 0.0;
         } else {
@@ -1895,12 +1929,12 @@ int P(th_oracle_mp_thompson_force)(const th_oracle *ctx,
 
         qi1d[k] = qi1d[k] + qiten[k] * DT;
         ni1d[k] = MAXD(R2 / rho[k], ni1d[k] + niten[k] * DT);
-        if (qi1d[k] <= R1) {
+        if (qi1d[k] <= R1 || gone_i[k]) {
             qi1d[k] = 0.0;
             ni1d[k] = 0.0;
         } else {
             lami = pow(am_i * cig[2] * oig1 * ni1d[k] / qi1d[k], obmi);
-            ilami = 1. / lami;
+            ilami = RCP(lami);
             xDi = (bm_i + mu_i + 1.) * ilami;
             if (xDi < 5.E-6)
                 lami = cie[2] / 5.E-6;
@@ -1943,7 +1977,7 @@ void P(th_oracle_calc_effectRad)(const th_oracle *ctx, int nz,
                                  const real *nc1d, const real *qi1d, const real *ni1d, const real *qs1d,
                                  real *re_qc1d, real *re_qi1d, real *re_qs1d)
 {
-    const th_view *o = (const th_view *)ctx->P(view);
+    const th_view *o = (const th_view *)ctx->VIEW;
     static const real g_ratio[16] = { 0, 24, 60, 120, 210, 336, 504, 720, 990, 1320, 1716, 2184, 2730, 3360, 4080, 4896 };
     const real *cse = o->cse;
     for (int k = 0; k < nz; k++) {
@@ -1985,7 +2019,7 @@ void P(th_oracle_default_aerosols)(const th_oracle *ctx, int nz,
                                 const real *p1d, real *nc1d,
                                 real *nwfa1d, real *nifa1d)
 {
-    const th_view *o = (const th_view *)ctx->P(view);
+    const th_view *o = (const th_view *)ctx->VIEW;
     for (int k = 0; k < nz; k++) {
         real rho = 0.622 * p1d[k] / (R_gas * t1d[k] * (qv1d[k] + 0.622));
         nc1d[k] = o->Nt_c / rho;

@@ -99,7 +99,7 @@ def native_inputs(b64):
     out = {}
     for name, (iiwarm, aero, st) in b64.items():
         out[name] = (iiwarm, aero, {k: np.ascontiguousarray(v.astype(f32)) for k, v in st.items()})
-    a_w, a_m, b = kc.kat_a_native(False), kc.kat_a_native(True), kc.kat_b_native()
+    a_w, a_m, b = kc.kat_a_native_formed(False), kc.kat_a_native_formed(True), kc.kat_b_native_formed()
     g = np.load(os.path.join(HERE, "kat_native_inputs.npz"))
     for k in ("t", "p", "qv", "nc"):
         assert np.array_equal(a_m[k], g["a_" + k]), "this host's powf / expf do not form the committed native inputs"

@@ -115,8 +115,55 @@ def _f32map(fn, *arrs):
     return np.array([f32(fn(*[float(a[i]) for a in arrs])) for i in range(len(arrs[0]))], dtype=f32)
 
 
+def _native_fixture():
+    """tests/golden/kat_native_inputs.npz: every profile below that needs powf / expf, as the image the native digits were
+    matched on (glibc 2.35) forms it (written by tests/golden/make_kat_native_inputs.py from the *_formed functions)."""
+    import os
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kat_native_inputs.npz"))
+
+
 def kat_b_native():
-    """KAT-B inputs in binary32 arithmetic (see above); same keys as kat_b(), arrays binary32."""
+    """KAT-B inputs in binary32 arithmetic (see above); same keys as kat_b() plus "p" (= p0*exner**(1./r_on_cp), W:61), arrays
+    binary32.  The profiles that need the binary32 libm are the COMMITTED ones, so the native-digit tests do not depend on
+    the host's libm; test_oracle_p32n.test_native_inputs_are_the_committed_ones alone compares it with the fixture."""
+    f32 = np.float32
+    g = _native_fixture()
+    nz = NZ
+    z = ((np.arange(1, nz + 1).astype(f32) - f32(0.5)) * f32(25.0)).astype(f32)
+    hydro = np.zeros((2, 5, 1, nz), dtype=f32)
+    mk = (z > 800) & (z < 2000)
+    hydro[0, 0, 0, mk] = f32(8e-4)
+    hydro[0, 1, 0, mk] = f32(3e-4)
+    hydro[1, 1, 0, mk] = f32(2e4)
+    return dict(nz=nz, nx=1, dt=10.0, p0=float(f32(1e5)), r_on_cp=float(g["b_r_on_cp"]), theta=g["b_theta"].copy(),
+                exner=g["b_exner"].copy(), dz=np.full(nz, 25.0, dtype=f32), qv=g["b_qv"].copy(), hydro=hydro, p=g["b_p"].copy())
+
+
+def kat_a_native(mixed=True):
+    """KAT-A (mixed) inputs in binary32 arithmetic; same keys as kat_a(), arrays binary32; t, p, qv, nc are the committed
+    profiles (see kat_b_native), the rest needs no libm."""
+    if not mixed:
+        raise ValueError("only the mixed column is committed; kat_a_native_formed(False) forms the warm one with the host's libm")
+    f32 = np.float32
+    g = _native_fixture()
+    z = ((np.arange(1, NZ + 1).astype(f32) - f32(0.5)) * f32(125.0)).astype(f32)
+    st = {k: np.zeros(NZ, dtype=f32) for k in ("qc", "qi", "qr", "qs", "qg", "ni", "nr")}
+    T, p, qv = g["a_t"].copy(), g["a_p"].copy(), g["a_qv"].copy()
+    st["t"], st["p"], st["qv"], st["nc"] = T, p, qv, g["a_nc"].copy()
+    mk = (z > 1000) & (z < 4000)
+    st["qc"][mk] = f32(1e-3); st["qr"][mk] = f32(5e-4); st["nr"][mk] = f32(5e3)
+    mk = (z > 4000) & (z < 11000)
+    st["qc"][mk] = f32(2e-4); st["qi"][mk] = f32(1e-4); st["ni"][mk] = f32(1e5)
+    st["qs"][mk] = f32(1e-3); st["qg"][mk] = f32(2e-3); st["qr"][mk] = f32(1e-4); st["nr"][mk] = f32(1e3)
+    rho = (f32(0.622) * p / (f32(287.04) * T * (qv + f32(0.622)).astype(f32)).astype(f32)).astype(f32)
+    st["nwfa"] = (f32(11.1e6) / rho).astype(f32); st["nifa"] = (f32(5e3) / rho).astype(f32)
+    st["w"] = np.zeros(NZ, dtype=f32)
+    st["dz"] = np.full(NZ, 125.0, dtype=f32)
+    return {k: np.ascontiguousarray(v, dtype=f32) for k, v in st.items()}
+
+
+def kat_b_native_formed():
+    """kat_b_native with every profile formed here, powf of THIS host's libm included (fixture writer, libm comparison)."""
     f32 = np.float32
     m = _libm32()
     nz = NZ
@@ -134,11 +181,13 @@ def kat_b_native():
     hydro[0, 0, 0, mk] = f32(8e-4)
     hydro[0, 1, 0, mk] = f32(3e-4)
     hydro[1, 1, 0, mk] = f32(2e4)
-    return dict(nz=nz, nx=1, dt=10.0, p0=float(f32(1e5)), r_on_cp=float(r_on_cp), theta=theta, exner=exner, dz=dz, qv=qv, hydro=hydro)
+    p1d = (f32(1e5) * _f32map(lambda e: m.powf(e, float(f32(1.0) / r_on_cp)), exner)).astype(f32)      # W:61: REAL**REAL = powf
+    return dict(nz=nz, nx=1, dt=10.0, p0=float(f32(1e5)), r_on_cp=float(r_on_cp), theta=theta, exner=exner, dz=dz, qv=qv, hydro=hydro,
+                p=p1d)
 
 
-def kat_a_native(mixed):
-    """KAT-A inputs in binary32 arithmetic; same keys as kat_a(), arrays binary32."""
+def kat_a_native_formed(mixed):
+    """kat_a_native with every profile formed here, powf / expf of THIS host's libm included; the warm column too."""
     f32 = np.float32
     m = _libm32()
     dz = np.full(NZ, 125.0, dtype=f32)

@@ -5,7 +5,12 @@ Oracle: the same split compiled into the CPU oracle (oracle/thompson_oracle_p32n
 known answers of the survey (tests/test_oracle_p32n.py).  Two binary32 implementations agree only to binary32
 rounding amplified by the scheme (their libm differs: glibc powf/expf vs the fp32 special-function units), so the
 bounds are statistical: medians at a few binary32 ulps, high percentiles at 1e-4, with the same floors as the P64
-metric.  P32n-vs-P64 and f32-vs-P64 differences are reported by tools/precision_sweep.py (BASELINE config 5)."""
+metric.  P32n-vs-P64 and f32-vs-P64 differences are reported by tools/precision_sweep.py (BASELINE config 5).
+
+What pins the binary32 builds level by level is tests/test_gpu_precision32_levels.py (tests/parity32.py): every level
+of the held columns within max(1e-4, 10 x the P32n oracle's own spread under 3-ulp moves of its special functions,
+reciprocals and rate limiters), on sets re-drawn by the oracle alone to at most 3 % undecidable levels (all warm columns,
+57 ... 61 of 64 mixed ones; the mixed fuzz seeds and the nz = 200 mixed set are not held yet)."""
 import numpy as np
 import pytest
 
@@ -73,14 +78,12 @@ def test_kat_b_native_through_the_p32n_kernel(gpu_warm):
     """the reference AS SHIPPED ends KAT-B (360 warm steps through the adapter) at sum(qc) 2.218541e-2,
     sum(qr) 2.693803e-3, sum(nr) 1.060634e6; its P64 build at 2.218719e-2, 2.694135e-3, 1.060568e6.  The p32n kernel,
     driven like the adapter drives it (state + dt*tendency in binary32), lands near the native numbers, not the P64 ones."""
-    c = kc.kat_b_native()                      # inputs formed in binary32, as the survey's native probe forms them
+    c = kc.kat_b_native()                      # inputs formed in binary32, as the survey's native probe forms them: the committed ones
     nz, dt = c["nz"], f32(c["dt"])
     theta, qv = c["theta"].copy(), c["qv"].copy()
     qc, qr, nr = (c["hydro"][0, 0, 0].copy(), c["hydro"][0, 1, 0].copy(), c["hydro"][1, 1, 0].copy())
     exner, dz = c["exner"], c["dz"]
-    m = kc._libm32()                           # p1d = p0*exner**(1./r_on_cp), W:61: REAL**REAL = powf
-    ex = float(f32(1.0) / f32(c["r_on_cp"]))
-    p = (f32(c["p0"]) * np.array([m.powf(float(e), ex) for e in exner], dtype=f32)).astype(f32)
+    p = c["p"]                                 # p1d = p0*exner**(1./r_on_cp), W:61: REAL**REAL = powf, from the fixture too
     z = np.zeros(nz, dtype=f32)
     for _ in range(360):
         t = (theta * exner).astype(f32)

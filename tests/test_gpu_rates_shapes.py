@@ -19,8 +19,10 @@ import pytest
 
 import rates_cases as rc
 from parity import OUT, assert_parity
+from parity32 import assert_rates32
 from rates_parity import NRATES, assert_rates, oracle_rates, rates_metric
 from test_gpu_column_nc import CYCLE, _own_defaults
+from test_gpu_precision32_levels import RATES_HELD          # (kind, nz) where every p32n rate element is held
 
 pytestmark = pytest.mark.gpu
 DT = rc.DT
@@ -413,6 +415,10 @@ def _hold32(what, kind, nz, rates, ref, bounds):
 def test_p32n_rates_against_the_p32n_oracle(request, kind, nz):
     m, o = _pair(request, kind)
     st, _, _, rates = _stepped32(kind, nz, m, "p32n")
+    if (kind, nz) in RATES_HELD:
+        # EVERY element (the maximum is only printed below): within max(the q99 bound, 10 x the spread of that rate under
+        # 3-ulp moves of the P32n oracle's binary32 special functions, reciprocals and rate limiters), parity32.assert_rates32
+        assert_rates32(o, st, DT, rates, P32N_BOUNDS[kind][1], what="%s nz %d" % (kind, nz))
     _hold32("p32n kernel against the p32n oracle", kind, nz, rates, oracle_rates(o.column_step_p32n, st, DT)[0], P32N_BOUNDS)
 
 

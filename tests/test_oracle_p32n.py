@@ -65,16 +65,27 @@ def test_kat_b_native_360_steps_through_the_adapter(oracle_warm):
 
 
 def test_native_inputs_are_the_committed_ones():
-    """kat_b_native / kat_a_native call this host's powf / expf: the binary32 profiles they form are frozen in
-    tests/golden/kat_native_inputs.npz (written on the image the native digits were matched on, glibc 2.35), so a libm
-    whose binary32 functions round differently shows up here and not as a shifted seventh digit above."""
+    """The binary32 profiles that need powf / expf are frozen in tests/golden/kat_native_inputs.npz (written on the image
+    the native digits were matched on, glibc 2.35) and every native-digit test reads them from there (kat_b_native,
+    kat_a_native).  This is the ONE test that forms them with this host's libm: a libm whose binary32 functions round
+    differently shows up here and nowhere else, and says so."""
     g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kat_native_inputs.npz"))
-    b, a = kc.kat_b_native(), kc.kat_a_native(True)
-    for k in ("theta", "exner", "qv"):
-        assert np.array_equal(b[k], g["b_" + k]), k
-    assert f32(b["r_on_cp"]) == g["b_r_on_cp"]
+    b, a = kc.kat_b_native_formed(), kc.kat_a_native_formed(True)
+    why = ("this host's libm (powf / expf) rounds differently from the one tests/golden/kat_native_inputs.npz was written with: "
+           "the libm differs, not the arithmetic under test -- ")
+    for k in ("theta", "exner", "qv", "p"):
+        assert np.array_equal(b[k], g["b_" + k]), why + "KAT-B " + k
+    assert f32(b["r_on_cp"]) == g["b_r_on_cp"], why + "r_on_cp"
     for k in ("t", "p", "qv", "nc"):
-        assert np.array_equal(a[k], g["a_" + k]), k
+        assert np.array_equal(a[k], g["a_" + k]), why + "KAT-A " + k
+    # what the tests consume is the committed data, completed without any libm call
+    used_b, used_a = kc.kat_b_native(), kc.kat_a_native(True)
+    for k in ("theta", "exner", "qv", "p", "dz", "hydro"):
+        assert np.array_equal(used_b[k], b[k]), why + "KAT-B " + k
+    assert used_b["r_on_cp"] == b["r_on_cp"] and used_b["p0"] == b["p0"] and set(used_b) == set(b)
+    assert set(used_a) == set(a)
+    for k in a:
+        assert np.array_equal(used_a[k], a[k]), why + "KAT-A " + k
 
 
 def test_kat_b_inputs_formed_in_binary64_miss_the_native_digits(oracle_warm):
