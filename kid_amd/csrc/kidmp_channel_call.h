@@ -63,8 +63,37 @@ int check_mie(kidmp_ctx *ctx, const char *who, const kidmp_mie_table *tab, int64
     return KIDMP_OK;
 }
 
+// The arrays of a host entry (kidmp_stage_plan.h), of one channel (nch = 1, k_gas_ch_stride = 0) or of a set: every output
+// has nch slabs, k_gas one per channel where the channels have profiles of their own.  Only what the kernel reads goes up.
+constexpr int MIE_A_DZ = NIN, MIE_A_W = NIN + 1, MIE_A_KGAS = NIN + 2, MIE_A_OUT = NIN + 3, MIE_A_PIA = MIE_A_OUT + MIE_NOUT,
+              MIE_NARRAYS = MIE_A_PIA + 1;
+template <class T>
+void mie_stage_list(const kidmp_ctx *ctx, StageArray (&a)[MIE_NARRAYS], int64_t ncol, int32_t nz, const MieCall<T> &h, int32_t nch,
+                    int64_t k_gas_ch_stride)
+{
+    const bool warm = ctx->cfg.iiwarm != 0;
+    for (int v = 0; v < NIN; ++v) a[v] = stage_array(warm && v >= 6 ? nullptr : h.in[v], nz, STAGE_UP);
+    a[MIE_A_DZ] = stage_rows(needs_path(h) ? h.dz : nullptr, nz, h.dz_col_stride);
+    a[MIE_A_W] = stage_array(h.w, nz, STAGE_UP);
+    a[MIE_A_KGAS] = stage_slabs(stage_rows(h.k_gas, nz, h.k_gas_col_stride), k_gas_ch_stride ? nch : 1, k_gas_ch_stride);
+    for (int v = 0; v < MIE_NOUT; ++v) a[MIE_A_OUT + v] = stage_slabs(stage_array(h.out[v], nz, STAGE_DOWN), nch, ncol * nz);
+    a[MIE_A_PIA] = stage_slabs(stage_array(h.pia_total, 1, STAGE_DOWN), nch, ncol);
+}
+// the call over the slots, once stage_open has made them
+template <class T> MieCall<T> mie_staged(const StageArray (&a)[MIE_NARRAYS], int32_t nz, const MieCall<T> &h)
+{
+    MieCall<T> d{};
+    for (int v = 0; v < NIN; ++v) d.in[v] = staged<T>(a[v]);
+    d.dz = staged<T>(a[MIE_A_DZ]); d.w = staged<T>(a[MIE_A_W]); d.k_gas = staged<T>(a[MIE_A_KGAS]);
+    d.dz_col_stride = h.dz_col_stride ? nz : 0;           // staged rows are packed
+    d.k_gas_col_stride = h.k_gas_col_stride ? nz : 0;
+    for (int v = 0; v < MIE_NOUT; ++v) d.out[v] = staged<T>(a[MIE_A_OUT + v]);
+    d.pia_total = staged<T>(a[MIE_A_PIA]);
+    return d;
+}
+
 // ---- the radiometer ----
-constexpr int NCOL_OUT = 3;                               // tb_toa, tb_ground, tau_abs
+constexpr int NCOL_OUT = 3;                              // tb_toa, tb_ground, tau_abs
 inline constexpr const char *RAD_OUT_NAMES[RAD_NOUT] = {"k_abs", "k_bsc", "refl", "trans", "tb_up", "tb_down"};
 inline constexpr const char *RAD_COL_NAMES[NCOL_OUT] = {"tb_toa", "tb_ground", "tau_abs"};
 
@@ -128,6 +157,33 @@ int check_rad(kidmp_ctx *ctx, const char *who, const kidmp_radiometer_table *tab
     if (!doppler_consts_supported(ctx->hc) || !spectra_consts_supported(ctx->hc))
         return fail(ctx, KIDMP_ESTATE, w + ": exponents differ from the kernel's");
     return KIDMP_OK;
+}
+
+// the arrays of a host entry, as mie_stage_list
+constexpr int RAD_A_DZ = NIN, RAD_A_KGAS = NIN + 1, RAD_A_OUT = NIN + 2, RAD_A_TSFC = RAD_A_OUT + RAD_NOUT, RAD_A_COL = RAD_A_TSFC + 1,
+              RAD_NARRAYS = RAD_A_COL + NCOL_OUT;
+template <class T>
+void rad_stage_list(const kidmp_ctx *ctx, StageArray (&a)[RAD_NARRAYS], int64_t ncol, int32_t nz, const RadCall<T> &h, int32_t nch,
+                    int64_t k_gas_ch_stride)
+{
+    const bool warm = ctx->cfg.iiwarm != 0;
+    for (int v = 0; v < NIN; ++v) a[v] = stage_array(warm && v >= 6 ? nullptr : h.in[v], nz, STAGE_UP);
+    a[RAD_A_DZ] = stage_rows(needs_dz(h) ? h.dz : nullptr, nz, h.dz_col_stride);
+    a[RAD_A_KGAS] = stage_slabs(stage_rows(h.k_gas, nz, h.k_gas_col_stride), k_gas_ch_stride ? nch : 1, k_gas_ch_stride);
+    for (int v = 0; v < RAD_NOUT; ++v) a[RAD_A_OUT + v] = stage_slabs(stage_array(h.out[v], nz, STAGE_DOWN), nch, ncol * nz);
+    a[RAD_A_TSFC] = stage_array(h.t_sfc, 1, STAGE_UP);
+    for (int v = 0; v < NCOL_OUT; ++v) a[RAD_A_COL + v] = stage_slabs(stage_array(h.col[v], 1, STAGE_DOWN), nch, ncol);
+}
+template <class T> RadCall<T> rad_staged(const StageArray (&a)[RAD_NARRAYS], int32_t nz, const RadCall<T> &h)
+{
+    RadCall<T> d{};
+    for (int v = 0; v < NIN; ++v) d.in[v] = staged<T>(a[v]);
+    d.dz = staged<T>(a[RAD_A_DZ]); d.k_gas = staged<T>(a[RAD_A_KGAS]); d.t_sfc = staged<T>(a[RAD_A_TSFC]);
+    d.dz_col_stride = h.dz_col_stride ? nz : 0;           // staged rows are packed
+    d.k_gas_col_stride = h.k_gas_col_stride ? nz : 0;
+    for (int v = 0; v < RAD_NOUT; ++v) d.out[v] = staged<T>(a[RAD_A_OUT + v]);
+    for (int v = 0; v < NCOL_OUT; ++v) d.col[v] = staged<T>(a[RAD_A_COL + v]);
+    return d;
 }
 
 }  // namespace kidmp

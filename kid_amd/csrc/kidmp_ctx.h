@@ -1,9 +1,11 @@
 // kidmp_ctx.h -- internal to the units behind include/kidmp.h (not installed): the context, the error and device-guard
-// helpers of every entry point, and what the units kidmp_{capi,diag,host,tables,multi,adapter,stats,summary,fall,doppler,kinematic,slab,spectra,aerosol,mathprobe}.hip offer one another.
+// helpers of every entry point, and what the units kidmp_{capi,diag,host,tables,multi,adapter,stats,summary,fall,doppler,kinematic,slab,
+// spectra,dspectrum,aerosol,lidar,brightband,mie,radiometer,multichannel,polarimetric,mathprobe}.hip offer one another.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -11,6 +13,7 @@
 #include "thompson_column.h"
 #include "thompson_reflectivity.h"
 #include "thompson_tables.h"
+#include "kidmp_stage_plan.h"
 
 namespace kidmp {
 constexpr int HOST_NBUF = 3;                         // staging sets of the host pipeline
@@ -189,6 +192,10 @@ hipError_t launch_radii_keep(kidmp_ctx *ctx, int64_t n, const T *t, const T *p, 
 // kidmp_host.hip: the columns per chunk of a host-array entry, and the context's staging memory (it only grows)
 int64_t pick_host_chunk(const kidmp_ctx *ctx, int64_t ncol);
 int ensure_stage(kidmp_ctx *ctx, size_t need);
+// kidmp_host.hip: the one body of the diagnostics' host-array entries (kidmp_stage_plan.h).  stage_open makes the plan's
+// staging memory and hands every present array its slot (StageArray::dev); stage_run moves the chunks through it.
+int stage_open(kidmp_ctx *ctx, const StagePlan &plan);
+int stage_run(kidmp_ctx *ctx, const StagePlan &plan, const std::function<hipError_t(int64_t c0, int64_t n)> &enqueue);
 // kidmp_host.hip.  What an entry may ask of the pipeline beyond the step: the exact precipitation sums and the sanity
 // scan (left in ctx->d_acc / d_sanity), and the column outputs (host arrays) of every chunk's post-step state.
 template <class T> struct PipelineExtras { bool exact_sums = false, scan_sanity = false; ColumnOutputs<T> out{}; };

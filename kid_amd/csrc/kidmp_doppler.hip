@@ -70,40 +70,22 @@ int doppler_device(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, co
     return KIDMP_OK;
 }
 
-// host arrays: chunks of columns through the context's staging memory on its compute stream, one after the other
-// (fall_host of kidmp_fall.hip).  A column's result does not depend on its batch, so any chunking gives the same bits.
-// Only the inputs given go up and only what was asked for comes down.
+// host arrays: stage_run of kidmp_host.hip.  Only the inputs given go up and only what was asked for comes down.
 template <class T>
 int doppler_host(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, const DopplerCall<T> &h)
 {
     if (int rc = check_doppler<T>(ctx, who, ncol, nz, h)) return rc;
     if (ncol == 0) return KIDMP_OK;
     GUARD(ctx);
-    const int64_t CH = pick_host_chunk(ctx, ncol);
-    const size_t b_prof = (size_t(CH) * size_t(nz) * sizeof(T) + 255) / 256 * 256;
-    int slots = 0;
-    for (int v = 0; v < NIN; ++v) slots += h.in[v] != nullptr;
-    for (int v = 0; v < DOPPLER_NOUT; ++v) slots += h.out[v] != nullptr;
-    if (int rc = ensure_stage(ctx, size_t(slots) * b_prof)) return rc;
-    char *next = reinterpret_cast<char *>(ctx->d_stage);
-    auto slot = [&](bool wanted) { T *p = wanted ? reinterpret_cast<T *>(next) : nullptr; if (wanted) next += b_prof; return p; };
+    StageArray a[NIN + DOPPLER_NOUT];
+    for (int v = 0; v < NIN; ++v) a[v] = stage_array(h.in[v], nz, STAGE_UP);
+    for (int v = 0; v < DOPPLER_NOUT; ++v) a[NIN + v] = stage_array(h.out[v], nz, STAGE_DOWN);
+    const StagePlan plan = stage_plan(a, ncol, pick_host_chunk(ctx, ncol));
+    if (int rc = stage_open(ctx, plan)) return rc;
     DopplerCall<T> d{};
-    for (int v = 0; v < NIN; ++v) d.in[v] = slot(h.in[v] != nullptr);
-    for (int v = 0; v < DOPPLER_NOUT; ++v) d.out[v] = slot(h.out[v] != nullptr);
-    hipError_t e = hipSuccess;
-    for (int64_t c0 = 0; c0 < ncol && e == hipSuccess; c0 += CH) {
-        const int64_t n = c0 + CH <= ncol ? CH : ncol - c0;
-        const size_t off = size_t(c0) * size_t(nz), cnt = size_t(n) * size_t(nz);
-        for (int v = 0; v < NIN && e == hipSuccess; ++v)
-            if (h.in[v]) e = hipMemcpyAsync(const_cast<T *>(d.in[v]), h.in[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = enqueue_doppler<T>(ctx, n, nz, d, ctx->stream);
-        for (int v = 0; v < DOPPLER_NOUT && e == hipSuccess; ++v)
-            if (h.out[v]) e = hipMemcpyAsync(h.out[v] + off, d.out[v], cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
-    }
-    const hipError_t es = hipStreamSynchronize(ctx->stream);        // no copy may still be in flight towards the caller's arrays
-    HIPTRY(ctx, e);
-    HIPTRY(ctx, es);
-    return KIDMP_OK;
+    for (int v = 0; v < NIN; ++v) d.in[v] = staged<T>(a[v]);
+    for (int v = 0; v < DOPPLER_NOUT; ++v) d.out[v] = staged<T>(a[NIN + v]);
+    return stage_run(ctx, plan, [&](int64_t, int64_t n) { return enqueue_doppler<T>(ctx, n, nz, d, ctx->stream); });
 }
 }  // namespace
 

@@ -105,61 +105,35 @@ int dspectrum_device(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, 
     return KIDMP_OK;
 }
 
-// host arrays: chunks of columns through the context's staging memory on its compute stream, one after the other
-// (spectra_host of kidmp_spectra.hip).  A column's result does not depend on its batch, so any chunking gives the same
-// bits.  The caller's grids go up once, only the inputs given go up per chunk and only what was asked for comes down.
+// host arrays: stage_run of kidmp_host.hip, the chunk narrowed to stay below MAX_STAGE.  The caller's grids go up once,
+// only the inputs given go up per chunk and only what was asked for comes down.
 template <class T>
 int dspectrum_host(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, const DSpectrumCall<T> &h)
 {
     if (int rc = check_dspectrum<T>(ctx, who, ncol, nz, h)) return rc;
     if (ncol == 0) return KIDMP_OK;
     GUARD(ctx);
-    auto up256 = [](size_t b) { return (b + 255) / 256 * 256; };
-    auto rows = [&](int v) { return v < NSPECTRA ? size_t(h.nv) : size_t(1); };   // profiles of nz values per column of output v
-    size_t per_col = 0, b_grids = 0;                      // bytes of staging per column, and for the caller's grids
-    for (int v = 0; v < NIN; ++v) per_col += h.in[v] ? size_t(nz) * sizeof(T) : 0;
-    for (int v = 0; v < DSPECTRUM_NOUT; ++v) per_col += h.out[v] ? rows(v) * size_t(nz) * sizeof(T) : 0;
-    for (int x = 0; x < DSPECTRUM_NSPEC; ++x)
-        if (h.D[x]) b_grids += 2 * up256(size_t(h.nb[x]) * sizeof(double));
-    int64_t CH = pick_host_chunk(ctx, ncol);
-    const int64_t fit = int64_t((MAX_STAGE - b_grids - 256 * size_t(NIN + DSPECTRUM_NOUT)) / per_col);
-    if (CH > fit) CH = fit > 0 ? fit : 1;
-    const size_t b_prof = up256(size_t(CH) * size_t(nz) * sizeof(T));
-    size_t need = b_grids;
-    for (int v = 0; v < NIN; ++v) need += h.in[v] ? b_prof : 0;
-    for (int v = 0; v < DSPECTRUM_NOUT; ++v) need += h.out[v] ? up256(size_t(CH) * rows(v) * size_t(nz) * sizeof(T)) : 0;
-    if (int rc = ensure_stage(ctx, need)) return rc;
-    char *next = reinterpret_cast<char *>(ctx->d_stage);
-    auto take = [&](size_t bytes) { char *p = next; next += bytes; return p; };
+    constexpr int A_D = 0, A_DD = DSPECTRUM_NSPEC, A_IN = 2 * DSPECTRUM_NSPEC, A_OUT = A_IN + NIN;
+    StageArray a[A_OUT + DSPECTRUM_NOUT];
+    for (int x = 0; x < DSPECTRUM_NSPEC; ++x) {
+        a[A_D + x] = stage_once(h.D[x], h.nb[x]);
+        a[A_DD + x] = stage_once(h.dD[x], h.nb[x]);
+    }
+    for (int v = 0; v < NIN; ++v) a[A_IN + v] = stage_array(h.in[v], nz, STAGE_UP);
+    for (int v = 0; v < DSPECTRUM_NOUT; ++v)                  // the spectra have nv profiles of nz values per column
+        a[A_OUT + v] = stage_array(h.out[v], int64_t(v < NSPECTRA ? h.nv : 1) * nz, STAGE_DOWN);
+    const StagePlan plan = stage_plan(a, ncol, pick_host_chunk(ctx, ncol), MAX_STAGE);
+    if (int rc = stage_open(ctx, plan)) return rc;
     DSpectrumCall<T> d{};
     d.v0 = h.v0; d.dv = h.dv; d.nv = h.nv;
-    hipError_t e = hipSuccess;
     for (int x = 0; x < DSPECTRUM_NSPEC; ++x) {
         d.nb[x] = h.nb[x];
-        if (!h.D[x]) continue;
-        const size_t b = size_t(h.nb[x]) * sizeof(double);
-        double *dD_ = reinterpret_cast<double *>(take(up256(b))), *ddD_ = reinterpret_cast<double *>(take(up256(b)));
-        if (e == hipSuccess) e = hipMemcpyAsync(dD_, h.D[x], b, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(ddD_, h.dD[x], b, hipMemcpyHostToDevice, ctx->stream);
-        d.D[x] = dD_;
-        d.dD[x] = ddD_;
+        d.D[x] = staged<double>(a[A_D + x]);
+        d.dD[x] = staged<double>(a[A_DD + x]);
     }
-    for (int v = 0; v < NIN; ++v) d.in[v] = h.in[v] ? reinterpret_cast<T *>(take(b_prof)) : nullptr;
-    for (int v = 0; v < DSPECTRUM_NOUT; ++v)
-        d.out[v] = h.out[v] ? reinterpret_cast<T *>(take(up256(size_t(CH) * rows(v) * size_t(nz) * sizeof(T)))) : nullptr;
-    for (int64_t c0 = 0; c0 < ncol && e == hipSuccess; c0 += CH) {
-        const int64_t n = c0 + CH <= ncol ? CH : ncol - c0;
-        const size_t off = size_t(c0) * size_t(nz), cnt = size_t(n) * size_t(nz);
-        for (int v = 0; v < NIN && e == hipSuccess; ++v)
-            if (h.in[v]) e = hipMemcpyAsync(const_cast<T *>(d.in[v]), h.in[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = enqueue_dspectrum<T>(ctx, n, nz, d, ctx->stream);
-        for (int v = 0; v < DSPECTRUM_NOUT && e == hipSuccess; ++v)
-            if (h.out[v]) e = hipMemcpyAsync(h.out[v] + off * rows(v), d.out[v], cnt * rows(v) * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
-    }
-    const hipError_t es = hipStreamSynchronize(ctx->stream);        // no copy may still be in flight towards the caller's arrays
-    HIPTRY(ctx, e);
-    HIPTRY(ctx, es);
-    return KIDMP_OK;
+    for (int v = 0; v < NIN; ++v) d.in[v] = staged<T>(a[A_IN + v]);
+    for (int v = 0; v < DSPECTRUM_NOUT; ++v) d.out[v] = staged<T>(a[A_OUT + v]);
+    return stage_run(ctx, plan, [&](int64_t, int64_t n) { return enqueue_dspectrum<T>(ctx, n, nz, d, ctx->stream); });
 }
 }  // namespace
 

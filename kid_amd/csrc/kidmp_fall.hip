@@ -93,9 +93,8 @@ int fall_device(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, const
     return KIDMP_OK;
 }
 
-// host arrays: chunks of columns through the context's staging memory on its compute stream, one after the other
-// (summary_host of kidmp_summary.hip).  A column's result does not depend on its batch, so any chunking gives the same
-// bits.  Only what the kernel reads goes up and only what was asked for comes down.
+// host arrays: stage_run of kidmp_host.hip.  Only what the kernel reads goes up (dz with nstep alone) and only what was
+// asked for comes down.
 template <class T>
 int fall_host(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, const FallCall<T> &h)
 {
@@ -103,46 +102,22 @@ int fall_host(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, const F
     if (ncol == 0) return KIDMP_OK;
     GUARD(ctx);
     const bool warm = ctx->cfg.iiwarm != 0;
-    const int64_t CH = pick_host_chunk(ctx, ncol);
-    const size_t b_prof = (size_t(CH) * size_t(nz) * sizeof(T) + 255) / 256 * 256;
-    const size_t b_nstep = (size_t(CH) * 4 * sizeof(int32_t) + 255) / 256 * 256;
-    // one staging slot per array that travels: the inputs the kernel reads, dz, the outputs asked for, nstep
-    bool up[NIN];
-    int slots = 0;
-    for (int v = 0; v < NIN; ++v) slots += (up[v] = h.in[v] && !(warm && v >= 5));
-    for (int v = 0; v < FALL_NOUT; ++v) slots += h.out[v] != nullptr;
-    slots += h.nstep != nullptr;                          // dz
-    if (int rc = ensure_stage(ctx, size_t(slots) * b_prof + (h.nstep ? b_nstep : 0))) return rc;
-    char *next = reinterpret_cast<char *>(ctx->d_stage);
-    auto slot = [&](bool wanted) { T *p = wanted ? reinterpret_cast<T *>(next) : nullptr; if (wanted) next += b_prof; return p; };
+    constexpr int A_DZ = NIN, A_OUT = NIN + 1, A_NSTEP = A_OUT + FALL_NOUT;
+    StageArray a[A_NSTEP + 1];
+    for (int v = 0; v < NIN; ++v) a[v] = stage_array(warm && v >= 5 ? nullptr : h.in[v], nz, STAGE_UP);
+    a[A_DZ] = stage_rows(h.nstep ? h.dz : nullptr, nz, h.dz_col_stride);
+    for (int v = 0; v < FALL_NOUT; ++v) a[A_OUT + v] = stage_array(h.out[v], nz, STAGE_DOWN);
+    a[A_NSTEP] = stage_array(h.nstep, 4, STAGE_DOWN);
+    const StagePlan plan = stage_plan(a, ncol, pick_host_chunk(ctx, ncol));
+    if (int rc = stage_open(ctx, plan)) return rc;
     FallCall<T> d{};
-    for (int v = 0; v < NIN; ++v) d.in[v] = slot(up[v]);
-    d.dz = slot(h.nstep != nullptr);
-    for (int v = 0; v < FALL_NOUT; ++v) d.out[v] = slot(h.out[v] != nullptr);
-    d.nstep = h.nstep ? reinterpret_cast<int32_t *>(next) : nullptr;
+    for (int v = 0; v < NIN; ++v) d.in[v] = staged<T>(a[v]);
+    d.dz = staged<T>(a[A_DZ]);
     d.dz_col_stride = h.dz_col_stride ? nz : 0;           // staged rows are packed
     d.dt = h.dt;
-    T *const d_dz = const_cast<T *>(d.dz);
-    hipError_t e = hipSuccess;
-    if (h.nstep && !h.dz_col_stride) e = hipMemcpyAsync(d_dz, h.dz, size_t(nz) * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-    for (int64_t c0 = 0; c0 < ncol && e == hipSuccess; c0 += CH) {
-        const int64_t n = c0 + CH <= ncol ? CH : ncol - c0;
-        const size_t off = size_t(c0) * size_t(nz), cnt = size_t(n) * size_t(nz);
-        for (int v = 0; v < NIN && e == hipSuccess; ++v)
-            if (up[v]) e = hipMemcpyAsync(const_cast<T *>(d.in[v]), h.in[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && h.nstep && h.dz_col_stride)
-            e = hipMemcpy2DAsync(d_dz, size_t(nz) * sizeof(T), h.dz + size_t(c0) * size_t(h.dz_col_stride),
-                                 size_t(h.dz_col_stride) * sizeof(T), size_t(nz) * sizeof(T), size_t(n), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = enqueue_fall<T>(ctx, n, nz, d, ctx->stream);
-        for (int v = 0; v < FALL_NOUT && e == hipSuccess; ++v)
-            if (h.out[v]) e = hipMemcpyAsync(h.out[v] + off, d.out[v], cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && h.nstep)
-            e = hipMemcpyAsync(h.nstep + size_t(c0) * 4, d.nstep, size_t(n) * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
-    }
-    const hipError_t es = hipStreamSynchronize(ctx->stream);        // no copy may still be in flight towards the caller's arrays
-    HIPTRY(ctx, e);
-    HIPTRY(ctx, es);
-    return KIDMP_OK;
+    for (int v = 0; v < FALL_NOUT; ++v) d.out[v] = staged<T>(a[A_OUT + v]);
+    d.nstep = staged<int32_t>(a[A_NSTEP]);
+    return stage_run(ctx, plan, [&](int64_t, int64_t n) { return enqueue_fall<T>(ctx, n, nz, d, ctx->stream); });
 }
 }  // namespace
 

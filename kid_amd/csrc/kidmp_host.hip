@@ -11,14 +11,7 @@ using namespace kidmp;
 // engines asynchronously; pageable arrays still work, but the runtime stages them through its own bounce buffer and
 // the calling thread waits for each copy.  Per column-step the boundary moves 14 (15 with w) profiles in and 12 out
 // (+36 for the rate diagnostics): about 25 KB in binary64.
-int64_t kidmp::pick_host_chunk(const kidmp_ctx *ctx, int64_t ncol)
-{
-    if (ctx->host_chunk > 0) return ctx->host_chunk < ncol ? ctx->host_chunk : ncol;
-    if (ncol <= 2048) return ncol;                            // one chunk: nothing to overlap with
-    int64_t ch = (ncol + 3) / 4;                              // at least four chunks ...
-    ch = (ch + 255) / 256 * 256;
-    return ch > 8192 ? 8192 : ch;                             // ... of at most 8 192 columns (7.9 MB per profile slice; measured optimum)
-}
+int64_t kidmp::pick_host_chunk(const kidmp_ctx *ctx, int64_t ncol) { return stage_pick_chunk(ctx->host_chunk, ncol); }
 
 // the context's staging memory only grows
 int kidmp::ensure_stage(kidmp_ctx *ctx, size_t need)
@@ -29,6 +22,61 @@ int kidmp::ensure_stage(kidmp_ctx *ctx, size_t need)
     ctx->stage_bytes = 0;
     HIPTRY(ctx, hipMalloc((void **)&ctx->d_stage, need));
     ctx->stage_bytes = need;
+    return KIDMP_OK;
+}
+
+// ---- the host-array entries of the diagnostics (reflectivity, radii, summary, fall speeds, Doppler moments and spectra,
+// size spectra, lidar, bright band, cloud radar, radiometer, polarimetric and multichannel): ONE body ----
+// The entry describes its arrays (kidmp_stage_plan.h); the batch goes through the context's staging memory in chunks of
+// plan.chunk columns, strictly one after the other on the context's compute stream: the shared profiles and the caller's
+// grids go up once, then per chunk what the kernel reads goes up, enqueue(c0, n) launches over the slots and what was asked
+// for comes down.  A column's result does not depend on its batch, so any chunking gives the same bits.  Page-locked host
+// arrays are moved asynchronously; the one synchronise at the end holds in every case, so that no copy is still in flight
+// towards the caller's arrays when the entry returns, and the first error is the one reported.
+int kidmp::stage_open(kidmp_ctx *ctx, const StagePlan &plan)
+{
+    if (int rc = ensure_stage(ctx, plan.total)) return rc;
+    for (int i = 0; i < plan.na; ++i)
+        if (plan.a[i].host) plan.a[i].dev = reinterpret_cast<char *>(ctx->d_stage) + plan.a[i].offset;
+    return KIDMP_OK;
+}
+
+namespace {
+// every slab of one array, up or down: the columns [c0, c0 + n)
+hipError_t stage_move(kidmp_ctx *ctx, const StageArray &a, bool down, int64_t c0, int64_t n)
+{
+    hipError_t e = hipSuccess;
+    for (int s = 0; s < a.nslab && e == hipSuccess; ++s) {
+        const StageCopy c = stage_copy(a, s, c0, n);
+        char *const host = const_cast<char *>(static_cast<const char *>(a.host)) + c.host_off;
+        char *const dev = reinterpret_cast<char *>(ctx->d_stage) + c.stage_off;
+        const hipMemcpyKind kind = down ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice;
+        if (c.rows == 1) e = down ? hipMemcpyAsync(host, dev, c.row_bytes, kind, ctx->stream) : hipMemcpyAsync(dev, host, c.row_bytes, kind, ctx->stream);
+        else e = down ? hipMemcpy2DAsync(host, c.host_pitch, dev, c.row_bytes, c.row_bytes, c.rows, kind, ctx->stream)
+                      : hipMemcpy2DAsync(dev, c.row_bytes, host, c.host_pitch, c.row_bytes, c.rows, kind, ctx->stream);
+    }
+    return e;
+}
+}  // namespace
+
+int kidmp::stage_run(kidmp_ctx *ctx, const StagePlan &plan, const std::function<hipError_t(int64_t, int64_t)> &enqueue)
+{
+    const StageArray *const a = plan.a;
+    hipError_t e = hipSuccess;
+    auto move = [&](bool down, bool before, int64_t c0, int64_t n) {
+        for (int i = 0; i < plan.na && e == hipSuccess; ++i)
+            if (a[i].host && (a[i].dir & (down ? STAGE_DOWN : STAGE_UP)) && stage_before_loop(a[i]) == before) e = stage_move(ctx, a[i], down, c0, n);
+    };
+    move(false, true, 0, 0);
+    for (int64_t c0 = 0; c0 < plan.ncol && e == hipSuccess; c0 += plan.chunk) {
+        const int64_t n = stage_chunk_cols(plan, c0);
+        move(false, false, c0, n);
+        if (e == hipSuccess) e = enqueue(c0, n);
+        move(true, false, c0, n);
+    }
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    HIPTRY(ctx, e);
+    HIPTRY(ctx, es);
     return KIDMP_OK;
 }
 
@@ -46,7 +94,7 @@ struct PipelineDrain {
     }
 };
 
-// host arrays: chunks of columns through the context's staging memory on its compute stream, one after the other
+// calc_refl10cm on host arrays: stage_run above
 template <class T>
 int refl_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const T *t, const T *p, const T *qv, const T *qr, const T *nr,
               const T *qs, const T *qg, T *dbz)
@@ -55,34 +103,23 @@ int refl_host(kidmp_ctx *ctx, int64_t ncol, int32_t nz, const T *t, const T *p, 
     if (int rc = check_refl_args(ctx, ncol, nz, req, 6, qs, qg)) return rc;
     if (ncol == 0) return KIDMP_OK;
     GUARD(ctx);
-    const int64_t CH = pick_host_chunk(ctx, ncol);
-    const size_t b_prof = (size_t(CH) * size_t(nz) * sizeof(T) + 255) / 256 * 256;
-    if (int rc = ensure_stage(ctx, 8 * b_prof)) return rc;
-    char *const base = reinterpret_cast<char *>(ctx->d_stage);
-    T *d[8];
-    for (int v = 0; v < 8; ++v) d[v] = reinterpret_cast<T *>(base + size_t(v) * b_prof);
     const T *h[7] = {t, p, qv, qr, nr, qs, qg};
+    StageArray a[8];                                          // every array keeps its slot
+    for (int v = 0; v < 7; ++v) a[v] = stage_keep(stage_array(h[v], nz, STAGE_UP));
+    a[7] = stage_array(dbz, nz, STAGE_DOWN);
+    const StagePlan plan = stage_plan(a, ncol, pick_host_chunk(ctx, ncol));
+    if (int rc = stage_open(ctx, plan)) return rc;
+    T *d[8];
+    for (int v = 0; v < 8; ++v) d[v] = staged<T>(a[v]);
     const ReflConsts c = refl_consts(ctx->hc);
-    hipError_t e = hipSuccess;
-    for (int64_t c0 = 0; c0 < ncol && e == hipSuccess; c0 += CH) {
-        const int64_t n = c0 + CH <= ncol ? CH : ncol - c0;
-        const size_t off = size_t(c0) * size_t(nz), cnt = size_t(n) * size_t(nz);
-        for (int v = 0; v < 7 && e == hipSuccess; ++v)
-            if (h[v]) e = hipMemcpyAsync(d[v], h[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess)
-            e = launch_reflectivity<T>(c, n, nz, d[0], d[1], d[2], d[3], d[4], qs ? d[5] : nullptr, qg ? d[6] : nullptr,
-                                       d[7], ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dbz + off, d[7], cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
-    }
-    const hipError_t es = hipStreamSynchronize(ctx->stream);        // no copy may still be in flight towards the caller's arrays
-    HIPTRY(ctx, e);
-    HIPTRY(ctx, es);
-    return KIDMP_OK;
+    return stage_run(ctx, plan, [&](int64_t, int64_t n) {
+        return launch_reflectivity<T>(c, n, nz, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], ctx->stream);
+    });
 }
 
-// calc_effectRad (M:4834-4935) on host arrays of n elements, INOUT: chunks through the staging memory on the compute stream
-// like refl_host; re_* go up as well as down.  The entry has no nz, so a chunk is the context's chunk size in columns of a
-// nominal 128 levels.
+// calc_effectRad (M:4834-4935) on host arrays of n elements, INOUT (stage_run): re_* go up as well as down.  The entry has
+// no nz, so its n elements are columns of one element and a chunk is the context's chunk size in columns of a nominal 128
+// levels.
 template <class T>
 int radii_host(kidmp_ctx *ctx, const char *who, int64_t n, const T *t, const T *p, const T *qv, const T *qc, const T *nc,
                const T *qi, const T *ni, const T *qs, T *re_qc, T *re_qi, T *re_qs)
@@ -92,30 +129,17 @@ int radii_host(kidmp_ctx *ctx, const char *who, int64_t n, const T *t, const T *
     int64_t nz_col = 0;
     if (int rc = nc_levels_of(ctx, who, n, nz_col)) return rc;
     GUARD(ctx);
-    const int64_t want = (ctx->host_chunk > 0 ? ctx->host_chunk : 8192) * 128, CH = want < n ? want : n;
-    const size_t b_prof = (size_t(CH) * sizeof(T) + 255) / 256 * 256;
-    if (int rc = ensure_stage(ctx, 11 * b_prof)) return rc;
-    char *const base = reinterpret_cast<char *>(ctx->d_stage);
-    T *d[11];
-    for (int v = 0; v < 11; ++v) d[v] = reinterpret_cast<T *>(base + size_t(v) * b_prof);
+    const int64_t want = (ctx->host_chunk > 0 ? ctx->host_chunk : 8192) * 128;
     const T *h[11] = {t, p, qv, qc, nc, qi, ni, qs, re_qc, re_qi, re_qs};
-    T *const hout[3] = {re_qc, re_qi, re_qs};
-    auto dev = [&](int v) { return h[v] ? d[v] : nullptr; };
-    hipError_t e = hipSuccess;
-    for (int64_t off = 0; off < n && e == hipSuccess; off += CH) {
-        const size_t cnt = size_t(off + CH <= n ? CH : n - off);
-        for (int v = 0; v < 11 && e == hipSuccess; ++v)
-            if (h[v]) e = hipMemcpyAsync(d[v], h[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess)
-            e = launch_radii_keep<T>(ctx, int64_t(cnt), d[0], d[1], d[2], d[3], dev(4), dev(5), dev(6), dev(7), d[8], dev(9),
-                                     dev(10), ctx->stream, nz_col, off);
-        for (int v = 0; v < 3 && e == hipSuccess; ++v)
-            if (hout[v]) e = hipMemcpyAsync(hout[v] + off, d[8 + v], cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
-    }
-    const hipError_t es = hipStreamSynchronize(ctx->stream);        // no copy may still be in flight towards the caller's arrays
-    HIPTRY(ctx, e);
-    HIPTRY(ctx, es);
-    return KIDMP_OK;
+    StageArray a[11];                                         // every array keeps its slot
+    for (int v = 0; v < 11; ++v) a[v] = stage_keep(stage_array(h[v], 1, v < 8 ? STAGE_UP : STAGE_BOTH));
+    const StagePlan plan = stage_plan(a, n, want < n ? want : n);
+    if (int rc = stage_open(ctx, plan)) return rc;
+    T *d[11];
+    for (int v = 0; v < 11; ++v) d[v] = staged<T>(a[v]);
+    return stage_run(ctx, plan, [&](int64_t off, int64_t cnt) {
+        return launch_radii_keep<T>(ctx, cnt, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10], ctx->stream, nz_col, off);
+    });
 }
 }  // namespace
 

@@ -117,9 +117,7 @@ int lidar_device(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, cons
     return KIDMP_OK;
 }
 
-// host arrays: chunks of columns through the context's staging memory on its compute stream, one after the other
-// (summary_host of kidmp_summary.hip).  A column's result does not depend on its batch, so any chunking gives the same
-// bits.  Only what the kernel reads goes up and only what was asked for comes down.
+// host arrays: stage_run of kidmp_host.hip.  Only what the kernel reads goes up and only what was asked for comes down.
 template <class T>
 int lidar_host(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, const LidarCall<T> &h, const kidmp_lidar_cfg *cfg)
 {
@@ -127,48 +125,22 @@ int lidar_host(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, const 
     if (int rc = check_lidar<T>(ctx, who, ncol, nz, h, cfg, g)) return rc;
     if (ncol == 0) return KIDMP_OK;
     GUARD(ctx);
-    const bool warm = ctx->cfg.iiwarm != 0, aero = ctx->cfg.is_aerosol_aware != 0, depth = needs_depth(h);
-    const int64_t CH = pick_host_chunk(ctx, ncol);
-    const size_t b_prof = (size_t(CH) * size_t(nz) * sizeof(T) + 255) / 256 * 256;
-    const size_t b_sum = (size_t(CH) * KIDMP_LIDAR_SUMMARY_N * sizeof(double) + 255) / 256 * 256;
-    bool up[NIN];
-    int slots = depth ? 1 : 0;
-    for (int v = 0; v < NIN; ++v) {
-        up[v] = h.in[v] && !(warm && FROZEN_IN[v]) && !(v == 4 && !aero);
-        slots += up[v];
-    }
-    for (int v = 0; v < LIDAR_NOUT; ++v) slots += h.out[v] != nullptr;
-    if (int rc = ensure_stage(ctx, size_t(slots) * b_prof + (h.summary ? b_sum : 0))) return rc;
-    char *next = reinterpret_cast<char *>(ctx->d_stage);
-    auto slot = [&](bool wanted) { T *p = wanted ? reinterpret_cast<T *>(next) : nullptr; if (wanted) next += b_prof; return p; };
+    const bool warm = ctx->cfg.iiwarm != 0, aero = ctx->cfg.is_aerosol_aware != 0;
+    constexpr int A_DZ = NIN, A_OUT = NIN + 1, A_SUM = A_OUT + LIDAR_NOUT;
+    StageArray a[A_SUM + 1];
+    for (int v = 0; v < NIN; ++v) a[v] = stage_array((warm && FROZEN_IN[v]) || (v == 4 && !aero) ? nullptr : h.in[v], nz, STAGE_UP);
+    a[A_DZ] = stage_rows(needs_depth(h) ? h.dz : nullptr, nz, h.dz_col_stride);
+    for (int v = 0; v < LIDAR_NOUT; ++v) a[A_OUT + v] = stage_array(h.out[v], nz, STAGE_DOWN);
+    a[A_SUM] = stage_array(h.summary, KIDMP_LIDAR_SUMMARY_N, STAGE_DOWN);
+    const StagePlan plan = stage_plan(a, ncol, pick_host_chunk(ctx, ncol));
+    if (int rc = stage_open(ctx, plan)) return rc;
     LidarCall<T> d{};
-    for (int v = 0; v < NIN; ++v) d.in[v] = slot(up[v]);
-    T *const d_dz = slot(depth);
-    d.dz = d_dz;
+    for (int v = 0; v < NIN; ++v) d.in[v] = staged<T>(a[v]);
+    d.dz = staged<T>(a[A_DZ]);
     d.dz_col_stride = h.dz_col_stride ? nz : 0;           // staged rows are packed
-    for (int v = 0; v < LIDAR_NOUT; ++v) d.out[v] = slot(h.out[v] != nullptr);
-    d.summary = h.summary ? reinterpret_cast<double *>(next) : nullptr;
-    hipError_t e = hipSuccess;
-    if (depth && !h.dz_col_stride) e = hipMemcpyAsync(d_dz, h.dz, size_t(nz) * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-    for (int64_t c0 = 0; c0 < ncol && e == hipSuccess; c0 += CH) {
-        const int64_t n = c0 + CH <= ncol ? CH : ncol - c0;
-        const size_t off = size_t(c0) * size_t(nz), cnt = size_t(n) * size_t(nz);
-        for (int v = 0; v < NIN && e == hipSuccess; ++v)
-            if (up[v]) e = hipMemcpyAsync(const_cast<T *>(d.in[v]), h.in[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && depth && h.dz_col_stride)
-            e = hipMemcpy2DAsync(d_dz, size_t(nz) * sizeof(T), h.dz + size_t(c0) * size_t(h.dz_col_stride),
-                                 size_t(h.dz_col_stride) * sizeof(T), size_t(nz) * sizeof(T), size_t(n), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = enqueue_lidar<T>(ctx, n, nz, d, g, c0, ctx->stream);
-        for (int v = 0; v < LIDAR_NOUT && e == hipSuccess; ++v)
-            if (h.out[v]) e = hipMemcpyAsync(h.out[v] + off, d.out[v], cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && h.summary)
-            e = hipMemcpyAsync(h.summary + size_t(c0) * KIDMP_LIDAR_SUMMARY_N, d.summary, size_t(n) * KIDMP_LIDAR_SUMMARY_N * sizeof(double),
-                               hipMemcpyDeviceToHost, ctx->stream);
-    }
-    const hipError_t es = hipStreamSynchronize(ctx->stream);        // no copy may still be in flight towards the caller's arrays
-    HIPTRY(ctx, e);
-    HIPTRY(ctx, es);
-    return KIDMP_OK;
+    for (int v = 0; v < LIDAR_NOUT; ++v) d.out[v] = staged<T>(a[A_OUT + v]);
+    d.summary = staged<double>(a[A_SUM]);
+    return stage_run(ctx, plan, [&](int64_t c0, int64_t n) { return enqueue_lidar<T>(ctx, n, nz, d, g, c0, ctx->stream); });
 }
 }  // namespace
 

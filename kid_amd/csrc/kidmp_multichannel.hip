@@ -13,7 +13,7 @@ using namespace kidmp;
 static_assert(MC_MAX_CHANNELS == KIDMP_MAX_CHANNELS, "include/kidmp_multichannel.h");
 
 namespace {
-constexpr size_t STAGE_LIMIT = size_t(1) << 30;          // a host entry narrows its chunk until nch slabs stay below this
+constexpr size_t STAGE_LIMIT = size_t(1) << 30;          // the host entries' staging: chunks are sized to stay below it
 
 // the rows of a table that do not depend on the wavelength, by the table's kind
 constexpr int RAD_SHARED[] = {2}, MIE_SHARED[] = {1, 3, 4};
@@ -135,52 +135,12 @@ int rad_multi_device(kidmp_ctx *ctx, const char *who, const kidmp_radiometer_tab
     return KIDMP_OK;
 }
 
-// What the two host entries share: the staging memory cut into slots, a chunk narrowed until everything fits below
-// STAGE_LIMIT, and the copies of k_gas and of the slabs.  Staged rows are packed; a channel's slab of a staged array is
-// one slot (b_prof or b_col bytes).
-template <class T> struct Stager {
-    int64_t CH;
-    size_t b_prof, b_col;
-    char *next;
-    // profs, cols: how many slots of either size the call needs
-    int open(kidmp_ctx *ctx, int64_t ncol, int nz, size_t profs, size_t cols)
-    {
-        CH = pick_host_chunk(ctx, ncol);
-        for (;;) {
-            b_prof = (size_t(CH) * size_t(nz) * sizeof(T) + 255) / 256 * 256;
-            b_col = (size_t(CH) * sizeof(T) + 255) / 256 * 256;
-            if (profs * b_prof + cols * b_col <= STAGE_LIMIT || CH == 1) break;
-            CH = (CH + 1) / 2;
-        }
-        if (int rc = ensure_stage(ctx, profs * b_prof + cols * b_col)) return rc;
-        next = reinterpret_cast<char *>(ctx->d_stage);
-        return KIDMP_OK;
-    }
-    T *slot(bool wanted, size_t bytes, size_t n = 1)
-    {
-        T *p = wanted ? reinterpret_cast<T *>(next) : nullptr;
-        if (wanted) next += n * bytes;
-        return p;
-    }
-};
-
-// k_gas of the host into its staged slots: the profiles shared by the columns once (first = true), those per column chunk
-// by chunk.  nk: the channels that have profiles of their own (1 with a channel stride of 0).
-template <class T>
-hipError_t stage_k_gas(kidmp_ctx *ctx, const Stager<T> &st, T *d_kg, const T *k_gas, int64_t col_stride, int64_t ch_stride, int nk, int nz,
-                       bool first, int64_t c0, int64_t n)
+// host arrays: stage_run of kidmp_host.hip over the arrays of kidmp_channel_call.h with nch slabs, the chunk narrowed to stay
+// below STAGE_LIMIT.  Staged rows are packed; a channel's slab of a staged array is one 256-byte aligned piece of its slot.
+template <class T> ChStrides staged_strides(const StagePlan &plan, int nz, const StageArray &k_gas)
 {
-    hipError_t e = hipSuccess;
-    if (!k_gas || first != (col_stride == 0)) return e;
-    const size_t row = size_t(nz) * sizeof(T);
-    for (int c = 0; c < nk && e == hipSuccess; ++c) {
-        T *dst = reinterpret_cast<T *>(reinterpret_cast<char *>(d_kg) + size_t(c) * st.b_prof);
-        const T *src = k_gas + size_t(c) * size_t(ch_stride);
-        if (first) e = hipMemcpyAsync(dst, src, row, hipMemcpyHostToDevice, ctx->stream);
-        else e = hipMemcpy2DAsync(dst, row, src + size_t(c0) * size_t(col_stride), size_t(col_stride) * sizeof(T), row, size_t(n),
-                                  hipMemcpyHostToDevice, ctx->stream);
-    }
-    return e;
+    const int64_t prof = int64_t(stage_slab_bytes(plan.chunk, nz, sizeof(T)) / sizeof(T)), col = int64_t(stage_slab_bytes(plan.chunk, 1, sizeof(T)) / sizeof(T));
+    return ChStrides{k_gas.host && k_gas.nslab > 1 ? prof : 0, prof, col};
 }
 
 template <class T>
@@ -191,60 +151,13 @@ int rad_multi_host(kidmp_ctx *ctx, const char *who, const kidmp_radiometer_table
     if (int rc = check_rad_multi<T>(ctx, who, set, rcfg, ncol, nz, h, k_gas_ch_stride)) return rc;
     if (ncol == 0) return KIDMP_OK;
     GUARD(ctx);
-    const bool warm = ctx->cfg.iiwarm != 0, with_dz = needs_dz(h);
-    const int nk = h.k_gas ? (k_gas_ch_stride ? nch : 1) : 0;
-    bool up[NIN];
-    size_t profs = (with_dz ? 1 : 0) + size_t(nk), cols = h.t_sfc ? 1 : 0;
-    for (int v = 0; v < NIN; ++v) {
-        up[v] = h.in[v] && !(warm && v >= 6);
-        profs += up[v];
-    }
-    for (int v = 0; v < RAD_NOUT; ++v) profs += h.out[v] ? size_t(nch) : 0;
-    for (int v = 0; v < NCOL_OUT; ++v) cols += h.col[v] ? size_t(nch) : 0;
-    Stager<T> st;
-    if (int rc = st.open(ctx, ncol, nz, profs, cols)) return rc;
-    const int64_t CH = st.CH;
-    RadCall<T> d{};
-    for (int v = 0; v < NIN; ++v) d.in[v] = st.slot(up[v], st.b_prof);
-    T *const d_dz = st.slot(with_dz, st.b_prof), *const d_kg = st.slot(nk > 0, st.b_prof, size_t(nk));
-    d.dz = d_dz; d.k_gas = d_kg;
-    d.dz_col_stride = h.dz_col_stride ? nz : 0;           // staged rows are packed
-    d.k_gas_col_stride = h.k_gas_col_stride ? nz : 0;
-    for (int v = 0; v < RAD_NOUT; ++v) d.out[v] = st.slot(h.out[v] != nullptr, st.b_prof, size_t(nch));
-    T *const d_ts = st.slot(h.t_sfc != nullptr, st.b_col);
-    d.t_sfc = d_ts;
-    for (int v = 0; v < NCOL_OUT; ++v) d.col[v] = st.slot(h.col[v] != nullptr, st.b_col, size_t(nch));
-    const ChStrides cs{nk > 1 ? int64_t(st.b_prof / sizeof(T)) : 0, int64_t(st.b_prof / sizeof(T)), int64_t(st.b_col / sizeof(T))};
-    hipError_t e = hipSuccess;
-    const size_t row = size_t(nz) * sizeof(T), slab = size_t(ncol) * size_t(nz);
-    if (with_dz && !h.dz_col_stride) e = hipMemcpyAsync(d_dz, h.dz, row, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = stage_k_gas<T>(ctx, st, d_kg, h.k_gas, h.k_gas_col_stride, k_gas_ch_stride, nk, nz, true, 0, 0);
-    for (int64_t c0 = 0; c0 < ncol && e == hipSuccess; c0 += CH) {
-        const int64_t n = c0 + CH <= ncol ? CH : ncol - c0;
-        const size_t off = size_t(c0) * size_t(nz), cnt = size_t(n) * size_t(nz);
-        for (int v = 0; v < NIN && e == hipSuccess; ++v)
-            if (up[v]) e = hipMemcpyAsync(const_cast<T *>(d.in[v]), h.in[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && h.t_sfc) e = hipMemcpyAsync(d_ts, h.t_sfc + c0, size_t(n) * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && with_dz && h.dz_col_stride)
-            e = hipMemcpy2DAsync(d_dz, row, h.dz + size_t(c0) * size_t(h.dz_col_stride), size_t(h.dz_col_stride) * sizeof(T), row, size_t(n),
-                                 hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = stage_k_gas<T>(ctx, st, d_kg, h.k_gas, h.k_gas_col_stride, k_gas_ch_stride, nk, nz, false, c0, n);
-        if (e == hipSuccess) e = enqueue_rad_multi<T>(ctx, set, n, nz, d, cs, ctx->stream);
-        for (int c = 0; c < nch; ++c) {
-            for (int v = 0; v < RAD_NOUT && e == hipSuccess; ++v)
-                if (h.out[v])
-                    e = hipMemcpyAsync(h.out[v] + size_t(c) * slab + off, d.out[v] + size_t(c) * size_t(cs.prof), cnt * sizeof(T), hipMemcpyDeviceToHost,
-                                       ctx->stream);
-            for (int v = 0; v < NCOL_OUT && e == hipSuccess; ++v)
-                if (h.col[v])
-                    e = hipMemcpyAsync(h.col[v] + size_t(c) * size_t(ncol) + c0, d.col[v] + size_t(c) * size_t(cs.col), size_t(n) * sizeof(T),
-                                       hipMemcpyDeviceToHost, ctx->stream);
-        }
-    }
-    const hipError_t es = hipStreamSynchronize(ctx->stream);        // no copy may still be in flight towards the caller's arrays
-    HIPTRY(ctx, e);
-    HIPTRY(ctx, es);
-    return KIDMP_OK;
+    StageArray a[RAD_NARRAYS];
+    rad_stage_list(ctx, a, ncol, nz, h, nch, k_gas_ch_stride);
+    const StagePlan plan = stage_plan(a, ncol, pick_host_chunk(ctx, ncol), STAGE_LIMIT);
+    if (int rc = stage_open(ctx, plan)) return rc;
+    const RadCall<T> d = rad_staged(a, nz, h);
+    const ChStrides cs = staged_strides<T>(plan, nz, a[RAD_A_KGAS]);
+    return stage_run(ctx, plan, [&](int64_t, int64_t n) { return enqueue_rad_multi<T>(ctx, set, n, nz, d, cs, ctx->stream); });
 }
 
 // ---- the cloud radar ----
@@ -310,56 +223,13 @@ int mie_multi_host(kidmp_ctx *ctx, const char *who, const kidmp_mie_table *const
     if (int rc = check_mie_multi<T>(ctx, who, set, ncol, nz, h, k_gas_ch_stride)) return rc;
     if (ncol == 0) return KIDMP_OK;
     GUARD(ctx);
-    const bool warm = ctx->cfg.iiwarm != 0, path = needs_path(h);
-    const int nk = h.k_gas ? (k_gas_ch_stride ? nch : 1) : 0;
-    bool up[NIN];
-    size_t profs = (path ? 1 : 0) + (h.w ? 1 : 0) + size_t(nk);
-    for (int v = 0; v < NIN; ++v) {
-        up[v] = h.in[v] && !(warm && v >= 6);
-        profs += up[v];
-    }
-    for (int v = 0; v < MIE_NOUT; ++v) profs += h.out[v] ? size_t(nch) : 0;
-    Stager<T> st;
-    if (int rc = st.open(ctx, ncol, nz, profs, h.pia_total ? size_t(nch) : 0)) return rc;
-    const int64_t CH = st.CH;
-    MieCall<T> d{};
-    for (int v = 0; v < NIN; ++v) d.in[v] = st.slot(up[v], st.b_prof);
-    T *const d_dz = st.slot(path, st.b_prof), *const d_w = st.slot(h.w != nullptr, st.b_prof), *const d_kg = st.slot(nk > 0, st.b_prof, size_t(nk));
-    d.dz = d_dz; d.w = d_w; d.k_gas = d_kg;
-    d.dz_col_stride = h.dz_col_stride ? nz : 0;           // staged rows are packed
-    d.k_gas_col_stride = h.k_gas_col_stride ? nz : 0;
-    for (int v = 0; v < MIE_NOUT; ++v) d.out[v] = st.slot(h.out[v] != nullptr, st.b_prof, size_t(nch));
-    d.pia_total = st.slot(h.pia_total != nullptr, st.b_col, size_t(nch));
-    const ChStrides cs{nk > 1 ? int64_t(st.b_prof / sizeof(T)) : 0, int64_t(st.b_prof / sizeof(T)), int64_t(st.b_col / sizeof(T))};
-    hipError_t e = hipSuccess;
-    const size_t row = size_t(nz) * sizeof(T), slab = size_t(ncol) * size_t(nz);
-    if (path && !h.dz_col_stride) e = hipMemcpyAsync(d_dz, h.dz, row, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = stage_k_gas<T>(ctx, st, d_kg, h.k_gas, h.k_gas_col_stride, k_gas_ch_stride, nk, nz, true, 0, 0);
-    for (int64_t c0 = 0; c0 < ncol && e == hipSuccess; c0 += CH) {
-        const int64_t n = c0 + CH <= ncol ? CH : ncol - c0;
-        const size_t off = size_t(c0) * size_t(nz), cnt = size_t(n) * size_t(nz);
-        for (int v = 0; v < NIN && e == hipSuccess; ++v)
-            if (up[v]) e = hipMemcpyAsync(const_cast<T *>(d.in[v]), h.in[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && h.w) e = hipMemcpyAsync(d_w, h.w + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && path && h.dz_col_stride)
-            e = hipMemcpy2DAsync(d_dz, row, h.dz + size_t(c0) * size_t(h.dz_col_stride), size_t(h.dz_col_stride) * sizeof(T), row, size_t(n),
-                                 hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = stage_k_gas<T>(ctx, st, d_kg, h.k_gas, h.k_gas_col_stride, k_gas_ch_stride, nk, nz, false, c0, n);
-        if (e == hipSuccess) e = enqueue_mie_multi<T>(ctx, set, n, nz, d, cs, ctx->stream);
-        for (int c = 0; c < nch; ++c) {
-            for (int v = 0; v < MIE_NOUT && e == hipSuccess; ++v)
-                if (h.out[v])
-                    e = hipMemcpyAsync(h.out[v] + size_t(c) * slab + off, d.out[v] + size_t(c) * size_t(cs.prof), cnt * sizeof(T), hipMemcpyDeviceToHost,
-                                       ctx->stream);
-            if (e == hipSuccess && h.pia_total)
-                e = hipMemcpyAsync(h.pia_total + size_t(c) * size_t(ncol) + c0, d.pia_total + size_t(c) * size_t(cs.col), size_t(n) * sizeof(T),
-                                   hipMemcpyDeviceToHost, ctx->stream);
-        }
-    }
-    const hipError_t es = hipStreamSynchronize(ctx->stream);        // no copy may still be in flight towards the caller's arrays
-    HIPTRY(ctx, e);
-    HIPTRY(ctx, es);
-    return KIDMP_OK;
+    StageArray a[MIE_NARRAYS];
+    mie_stage_list(ctx, a, ncol, nz, h, nch, k_gas_ch_stride);
+    const StagePlan plan = stage_plan(a, ncol, pick_host_chunk(ctx, ncol), STAGE_LIMIT);
+    if (int rc = stage_open(ctx, plan)) return rc;
+    const MieCall<T> d = mie_staged(a, nz, h);
+    const ChStrides cs = staged_strides<T>(plan, nz, a[MIE_A_KGAS]);
+    return stage_run(ctx, plan, [&](int64_t, int64_t n) { return enqueue_mie_multi<T>(ctx, set, n, nz, d, cs, ctx->stream); });
 }
 }  // namespace
 

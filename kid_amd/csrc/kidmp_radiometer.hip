@@ -64,9 +64,7 @@ int rad_device(kidmp_ctx *ctx, const char *who, const kidmp_radiometer_table *ta
     return KIDMP_OK;
 }
 
-// host arrays: chunks of columns through the context's staging memory on its compute stream, one after the other
-// (mie_host of kidmp_mie.hip).  A column's result does not depend on its batch, so any chunking gives the same bits.
-// Only the inputs given go up and only what was asked for comes down.
+// host arrays: stage_run of kidmp_host.hip.  Only the inputs the kernel reads go up and only what was asked for comes down.
 template <class T>
 int rad_host(kidmp_ctx *ctx, const char *who, const kidmp_radiometer_table *tab, const kidmp_radiometer_cfg *rcfg, int64_t ncol, int32_t nz,
              const RadCall<T> &h)
@@ -75,56 +73,12 @@ int rad_host(kidmp_ctx *ctx, const char *who, const kidmp_radiometer_table *tab,
     if (int rc = check_rad<T>(ctx, who, tab, r, ncol, nz, h)) return rc;
     if (ncol == 0) return KIDMP_OK;
     GUARD(ctx);
-    const bool warm = ctx->cfg.iiwarm != 0, with_dz = needs_dz(h);
-    const int64_t CH = pick_host_chunk(ctx, ncol);
-    const size_t b_prof = (size_t(CH) * size_t(nz) * sizeof(T) + 255) / 256 * 256, b_col = (size_t(CH) * sizeof(T) + 255) / 256 * 256;
-    bool up[NIN];
-    int slots = (with_dz ? 1 : 0) + (h.k_gas ? 1 : 0), cols = h.t_sfc ? 1 : 0;
-    for (int v = 0; v < NIN; ++v) {
-        up[v] = h.in[v] && !(warm && v >= 6);
-        slots += up[v];
-    }
-    for (int v = 0; v < RAD_NOUT; ++v) slots += h.out[v] != nullptr;
-    for (int v = 0; v < NCOL_OUT; ++v) cols += h.col[v] != nullptr;
-    if (int rc = ensure_stage(ctx, size_t(slots) * b_prof + size_t(cols) * b_col)) return rc;
-    char *next = reinterpret_cast<char *>(ctx->d_stage);
-    auto slot = [&](bool wanted, size_t bytes) { T *p = wanted ? reinterpret_cast<T *>(next) : nullptr; if (wanted) next += bytes; return p; };
-    RadCall<T> d{};
-    for (int v = 0; v < NIN; ++v) d.in[v] = slot(up[v], b_prof);
-    T *const d_dz = slot(with_dz, b_prof), *const d_kg = slot(h.k_gas != nullptr, b_prof);
-    d.dz = d_dz; d.k_gas = d_kg;
-    d.dz_col_stride = h.dz_col_stride ? nz : 0;           // staged rows are packed
-    d.k_gas_col_stride = h.k_gas_col_stride ? nz : 0;
-    for (int v = 0; v < RAD_NOUT; ++v) d.out[v] = slot(h.out[v] != nullptr, b_prof);
-    T *const d_ts = slot(h.t_sfc != nullptr, b_col);
-    d.t_sfc = d_ts;
-    for (int v = 0; v < NCOL_OUT; ++v) d.col[v] = slot(h.col[v] != nullptr, b_col);
-    hipError_t e = hipSuccess;
-    const size_t row = size_t(nz) * sizeof(T);
-    if (with_dz && !h.dz_col_stride) e = hipMemcpyAsync(d_dz, h.dz, row, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && h.k_gas && !h.k_gas_col_stride) e = hipMemcpyAsync(d_kg, h.k_gas, row, hipMemcpyHostToDevice, ctx->stream);
-    for (int64_t c0 = 0; c0 < ncol && e == hipSuccess; c0 += CH) {
-        const int64_t n = c0 + CH <= ncol ? CH : ncol - c0;
-        const size_t off = size_t(c0) * size_t(nz), cnt = size_t(n) * size_t(nz);
-        for (int v = 0; v < NIN && e == hipSuccess; ++v)
-            if (up[v]) e = hipMemcpyAsync(const_cast<T *>(d.in[v]), h.in[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && h.t_sfc) e = hipMemcpyAsync(d_ts, h.t_sfc + c0, size_t(n) * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && with_dz && h.dz_col_stride)
-            e = hipMemcpy2DAsync(d_dz, row, h.dz + size_t(c0) * size_t(h.dz_col_stride), size_t(h.dz_col_stride) * sizeof(T), row, size_t(n),
-                                 hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && h.k_gas && h.k_gas_col_stride)
-            e = hipMemcpy2DAsync(d_kg, row, h.k_gas + size_t(c0) * size_t(h.k_gas_col_stride), size_t(h.k_gas_col_stride) * sizeof(T), row,
-                                 size_t(n), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = enqueue_rad<T>(ctx, tab, r, n, nz, d, ctx->stream);
-        for (int v = 0; v < RAD_NOUT && e == hipSuccess; ++v)
-            if (h.out[v]) e = hipMemcpyAsync(h.out[v] + off, d.out[v], cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
-        for (int v = 0; v < NCOL_OUT && e == hipSuccess; ++v)
-            if (h.col[v]) e = hipMemcpyAsync(h.col[v] + c0, d.col[v], size_t(n) * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
-    }
-    const hipError_t es = hipStreamSynchronize(ctx->stream);        // no copy may still be in flight towards the caller's arrays
-    HIPTRY(ctx, e);
-    HIPTRY(ctx, es);
-    return KIDMP_OK;
+    StageArray a[RAD_NARRAYS];
+    rad_stage_list(ctx, a, ncol, nz, h, 1, 0);
+    const StagePlan plan = stage_plan(a, ncol, pick_host_chunk(ctx, ncol));
+    if (int rc = stage_open(ctx, plan)) return rc;
+    const RadCall<T> d = rad_staged(a, nz, h);
+    return stage_run(ctx, plan, [&](int64_t, int64_t n) { return enqueue_rad<T>(ctx, tab, r, n, nz, d, ctx->stream); });
 }
 }  // namespace
 

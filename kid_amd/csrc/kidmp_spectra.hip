@@ -128,9 +128,8 @@ int spectra_device(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, co
     return KIDMP_OK;
 }
 
-// host arrays: chunks of columns through the context's staging memory on its compute stream, one after the other
-// (fall_host of kidmp_fall.hip).  A column's result does not depend on its batch, so any chunking gives the same bits.
-// The caller's grids go up once, only what the kernel reads goes up per chunk and only what was asked for comes down.
+// host arrays: stage_run of kidmp_host.hip, the chunk narrowed to stay below MAX_STAGE.  The caller's grids go up once,
+// only what the kernel reads goes up per chunk and only what was asked for comes down.
 template <class T>
 int spectra_host(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, const SpectraCall<T> &h)
 {
@@ -138,62 +137,27 @@ int spectra_host(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, cons
     if (ncol == 0) return KIDMP_OK;
     GUARD(ctx);
     const bool warm = ctx->cfg.iiwarm != 0, aero = ctx->cfg.is_aerosol_aware != 0;
-    auto up256 = [](size_t b) { return (b + 255) / 256 * 256; };
-    bool up[NIN];
-    size_t per_col = 0, b_grids = 0;                      // bytes of staging per column, and for the caller's grids
-    for (int v = 0; v < NIN; ++v) {
-        up[v] = h.in[v] && !(warm && FROZEN_IN[v]) && !(v == 4 && !aero);
-        per_col += up[v] ? size_t(nz) * sizeof(T) : 0;
+    constexpr int A_D = 0, A_DD = SPECTRA_NSPEC, A_IN = 2 * SPECTRA_NSPEC, A_PAR = A_IN + NIN, A_SPEC = A_PAR + SPECTRA_NPAR;
+    StageArray a[A_SPEC + SPECTRA_NSPEC];
+    for (int x = 0; x < SPECTRA_NSPEC; ++x) {                 // a grid travels with its spectrum alone
+        a[A_D + x] = stage_once(h.spec[x] ? h.D[x] : nullptr, h.nb[x]);
+        a[A_DD + x] = stage_once(h.spec[x] ? h.dD[x] : nullptr, h.nb[x]);
+        a[A_SPEC + x] = stage_array(h.spec[x], int64_t(h.nb[x]) * nz, STAGE_DOWN);
     }
-    for (int v = 0; v < SPECTRA_NPAR; ++v) per_col += h.par[v] ? size_t(nz) * sizeof(T) : 0;
-    for (int x = 0; x < SPECTRA_NSPEC; ++x) {
-        if (!h.spec[x]) continue;
-        per_col += size_t(h.nb[x]) * size_t(nz) * sizeof(T);
-        if (h.D[x]) b_grids += 2 * up256(size_t(h.nb[x]) * sizeof(double));
-    }
-    int64_t CH = pick_host_chunk(ctx, ncol);
-    const int64_t fit = int64_t(MAX_STAGE / per_col);
-    if (CH > fit) CH = fit > 0 ? fit : 1;
-    const size_t b_prof = up256(size_t(CH) * size_t(nz) * sizeof(T));
-    size_t need = b_grids;
-    for (int v = 0; v < NIN; ++v) need += up[v] ? b_prof : 0;
-    for (int v = 0; v < SPECTRA_NPAR; ++v) need += h.par[v] ? b_prof : 0;
-    for (int x = 0; x < SPECTRA_NSPEC; ++x) need += h.spec[x] ? up256(size_t(CH) * size_t(h.nb[x]) * size_t(nz) * sizeof(T)) : 0;
-    if (int rc = ensure_stage(ctx, need)) return rc;
-    char *next = reinterpret_cast<char *>(ctx->d_stage);
-    auto take = [&](size_t bytes) { char *p = next; next += bytes; return p; };
+    for (int v = 0; v < NIN; ++v) a[A_IN + v] = stage_array((warm && FROZEN_IN[v]) || (v == 4 && !aero) ? nullptr : h.in[v], nz, STAGE_UP);
+    for (int v = 0; v < SPECTRA_NPAR; ++v) a[A_PAR + v] = stage_array(h.par[v], nz, STAGE_DOWN);
+    const StagePlan plan = stage_plan(a, ncol, pick_host_chunk(ctx, ncol), MAX_STAGE);
+    if (int rc = stage_open(ctx, plan)) return rc;
     SpectraCall<T> d{};
-    hipError_t e = hipSuccess;
     for (int x = 0; x < SPECTRA_NSPEC; ++x) {
         d.nb[x] = h.nb[x];
-        if (!h.spec[x] || !h.D[x]) continue;
-        const size_t b = size_t(h.nb[x]) * sizeof(double);
-        double *dD_ = reinterpret_cast<double *>(take(up256(b))), *ddD_ = reinterpret_cast<double *>(take(up256(b)));
-        if (e == hipSuccess) e = hipMemcpyAsync(dD_, h.D[x], b, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(ddD_, h.dD[x], b, hipMemcpyHostToDevice, ctx->stream);
-        d.D[x] = dD_;
-        d.dD[x] = ddD_;
+        d.D[x] = staged<double>(a[A_D + x]);
+        d.dD[x] = staged<double>(a[A_DD + x]);
+        d.spec[x] = staged<T>(a[A_SPEC + x]);
     }
-    for (int v = 0; v < NIN; ++v) d.in[v] = up[v] ? reinterpret_cast<T *>(take(b_prof)) : nullptr;
-    for (int v = 0; v < SPECTRA_NPAR; ++v) d.par[v] = h.par[v] ? reinterpret_cast<T *>(take(b_prof)) : nullptr;
-    for (int x = 0; x < SPECTRA_NSPEC; ++x)
-        d.spec[x] = h.spec[x] ? reinterpret_cast<T *>(take(up256(size_t(CH) * size_t(h.nb[x]) * size_t(nz) * sizeof(T)))) : nullptr;
-    for (int64_t c0 = 0; c0 < ncol && e == hipSuccess; c0 += CH) {
-        const int64_t n = c0 + CH <= ncol ? CH : ncol - c0;
-        const size_t off = size_t(c0) * size_t(nz), cnt = size_t(n) * size_t(nz);
-        for (int v = 0; v < NIN && e == hipSuccess; ++v)
-            if (up[v]) e = hipMemcpyAsync(const_cast<T *>(d.in[v]), h.in[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = enqueue_spectra<T>(ctx, n, nz, d, c0, ctx->stream);
-        for (int v = 0; v < SPECTRA_NPAR && e == hipSuccess; ++v)
-            if (h.par[v]) e = hipMemcpyAsync(h.par[v] + off, d.par[v], cnt * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
-        for (int x = 0; x < SPECTRA_NSPEC && e == hipSuccess; ++x)
-            if (h.spec[x])
-                e = hipMemcpyAsync(h.spec[x] + off * size_t(h.nb[x]), d.spec[x], cnt * size_t(h.nb[x]) * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
-    }
-    const hipError_t es = hipStreamSynchronize(ctx->stream);        // no copy may still be in flight towards the caller's arrays
-    HIPTRY(ctx, e);
-    HIPTRY(ctx, es);
-    return KIDMP_OK;
+    for (int v = 0; v < NIN; ++v) d.in[v] = staged<T>(a[A_IN + v]);
+    for (int v = 0; v < SPECTRA_NPAR; ++v) d.par[v] = staged<T>(a[A_PAR + v]);
+    return stage_run(ctx, plan, [&](int64_t c0, int64_t n) { return enqueue_spectra<T>(ctx, n, nz, d, c0, ctx->stream); });
 }
 }  // namespace
 

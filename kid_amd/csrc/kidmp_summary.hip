@@ -77,8 +77,7 @@ int summary_device(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, co
     return KIDMP_OK;
 }
 
-// host arrays: chunks of columns through the context's staging memory on its compute stream, one after the other
-// (refl_host of kidmp_host.hip).  A column's result does not depend on its batch, so any chunking gives the same bits.
+// host arrays: stage_run of kidmp_host.hip; every profile keeps its slot
 template <class T>
 int summary_host(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, const SummaryCall<T> &h, const kidmp_summary_cfg *cfg)
 {
@@ -86,36 +85,19 @@ int summary_host(kidmp_ctx *ctx, const char *who, int64_t ncol, int32_t nz, cons
     if (int rc = check_summary<T>(ctx, who, ncol, nz, h, cfg, thr)) return rc;
     if (ncol == 0) return KIDMP_OK;
     GUARD(ctx);
-    const int64_t CH = pick_host_chunk(ctx, ncol);
-    const size_t b_prof = (size_t(CH) * size_t(nz) * sizeof(T) + 255) / 256 * 256;
-    const size_t b_sum = (size_t(CH) * KIDMP_SUMMARY_N * sizeof(double) + 255) / 256 * 256;
-    if (int rc = ensure_stage(ctx, (NPROF + 1) * b_prof + b_sum)) return rc;
-    char *const base = reinterpret_cast<char *>(ctx->d_stage);
+    constexpr int A_DZ = NPROF, A_SUM = NPROF + 1;
+    StageArray a[A_SUM + 1];
+    for (int v = 0; v < NPROF; ++v) a[v] = stage_keep(stage_array(h.prof[v], nz, STAGE_UP));
+    a[A_DZ] = stage_rows(h.dz, nz, h.dz_col_stride);
+    a[A_SUM] = stage_array(h.summary, KIDMP_SUMMARY_N, STAGE_DOWN);
+    const StagePlan plan = stage_plan(a, ncol, pick_host_chunk(ctx, ncol));
+    if (int rc = stage_open(ctx, plan)) return rc;
     SummaryCall<T> d{};
-    for (int v = 0; v < NPROF; ++v) d.prof[v] = h.prof[v] ? reinterpret_cast<T *>(base + size_t(v) * b_prof) : nullptr;
-    T *const d_dz = reinterpret_cast<T *>(base + size_t(NPROF) * b_prof);
-    d.dz = d_dz;
+    for (int v = 0; v < NPROF; ++v) d.prof[v] = staged<T>(a[v]);
+    d.dz = staged<T>(a[A_DZ]);
     d.dz_col_stride = h.dz_col_stride ? nz : 0;           // staged rows are packed
-    d.summary = reinterpret_cast<double *>(base + size_t(NPROF + 1) * b_prof);
-    hipError_t e = hipSuccess;
-    if (!h.dz_col_stride) e = hipMemcpyAsync(d_dz, h.dz, size_t(nz) * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-    for (int64_t c0 = 0; c0 < ncol && e == hipSuccess; c0 += CH) {
-        const int64_t n = c0 + CH <= ncol ? CH : ncol - c0;
-        const size_t off = size_t(c0) * size_t(nz), cnt = size_t(n) * size_t(nz);
-        for (int v = 0; v < NPROF && e == hipSuccess; ++v)
-            if (h.prof[v]) e = hipMemcpyAsync(const_cast<T *>(d.prof[v]), h.prof[v] + off, cnt * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess && h.dz_col_stride)
-            e = hipMemcpy2DAsync(d_dz, size_t(nz) * sizeof(T), h.dz + size_t(c0) * size_t(h.dz_col_stride),
-                                 size_t(h.dz_col_stride) * sizeof(T), size_t(nz) * sizeof(T), size_t(n), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = enqueue_summary<T>(ctx, n, nz, d, thr, ctx->stream, c0);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(h.summary + size_t(c0) * KIDMP_SUMMARY_N, d.summary, size_t(n) * KIDMP_SUMMARY_N * sizeof(double),
-                               hipMemcpyDeviceToHost, ctx->stream);
-    }
-    const hipError_t es = hipStreamSynchronize(ctx->stream);        // no copy may still be in flight towards the caller's arrays
-    HIPTRY(ctx, e);
-    HIPTRY(ctx, es);
-    return KIDMP_OK;
+    d.summary = staged<double>(a[A_SUM]);
+    return stage_run(ctx, plan, [&](int64_t c0, int64_t n) { return enqueue_summary<T>(ctx, n, nz, d, thr, ctx->stream, c0); });
 }
 }  // namespace
 

@@ -286,6 +286,9 @@ def test_host_entries_equal_the_device_entry(gpu_mixed, own_grids, main_set, dty
         part = m.bright_band_host(st, want=some)
         assert sorted(part) == sorted(some) and all(_same(part[n], want[n]) for n in some), chunk
         assert _same_all(m.bright_band_host(st, _cfg(cfg), grids, ref.NAMES), want_g), chunk
+    m.set_host_chunk(1)                                       # seven columns, one per chunk
+    st7 = _take(st, np.arange(7))
+    assert _same_all(m.bright_band_host(st7, _cfg(cfg), grids, ref.NAMES), _bb(m, st7, cfg, grids))
 
 
 def test_hip_graph_replay_of_one_captured_launch(gpu_mixed, main_set):

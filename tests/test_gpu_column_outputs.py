@@ -156,6 +156,13 @@ def test_keep_mode_host_entry(gpu_mixed, oracle_mixed):
                     assert _same(h, w.astype(np.float32))
             for h, g in zip(host, device):
                 assert h.dtype == dtype and _same(h, g)
+            # seven columns, a chunk setting of 1: 455 elements in chunks of 128, the last one of 71
+            gpu_mixed.set_host_chunk(1)
+            s7 = {k: np.ascontiguousarray(v[:7]) for k, v in s.items()}
+            host7 = gpu_mixed.effective_radii_host(s7, preset=SENTINELS)
+            for h, g in zip(host7, device):
+                assert h.dtype == dtype and h.shape == (7, 65) and _same(h, g[:7])
+            gpu_mixed.set_host_chunk(16)
     finally:
         gpu_mixed.set_host_chunk(0)
 

@@ -354,6 +354,9 @@ def test_host_entries_equal_the_device_entry(gpu_mixed, dtype):
         fn = library().kidmp_column_summary_host if dtype == np.float64 else library().kidmp32_column_summary_host
         assert fn(m._h, 100, 120, *[hst[k].ctypes.data for k in ref.INPUTS], wide.ctypes.data, 125, None, out.ctypes.data) == 0
         assert _same(out, want), ("stride", chunk)
+    m.set_host_chunk(1)                                       # seven columns, one per chunk
+    st7 = {k: np.ascontiguousarray(v[:7]) for k, v in st.items()}
+    assert _same(m.column_summary_host({k: st7[k] for k in ref.INPUTS}, st7["dz"]), _summary(m, st7))
 
 
 # ---- 10. KiD workspace ----

@@ -259,7 +259,9 @@ def test_nstep_cap(gpu_mixed):
 
 # ---- 6. host entry ----
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
-def test_host_entries_equal_the_device_entry(gpu_mixed, sets, dtype):
+def test_host_entries_equal_the_device_entry(gpu_mixed, sets, dtype, monkeypatch):
+    from padded_rows import with_padded
+    from kid_amd.fall import library
     m = gpu_mixed
     st = {k: np.ascontiguousarray(v.astype(dtype)) for k, v in sets["random65_265"][0].items()}
     ncol = st["t"].shape[0]
@@ -275,6 +277,13 @@ def test_host_entries_equal_the_device_entry(gpu_mixed, sets, dtype):
     m.set_host_chunk(7)
     only_flux = m.fall_speeds_host(st, want=("flux_total",))
     assert sorted(only_flux) == ["flux_total"] and _same(only_flux["flux_total"], _fall(m, st)["flux_total"])
+    # seven columns in chunks of 3, 3 and 1, the rows of dz nz + 5 apart (dz_col_stride)
+    st7 = {k: np.ascontiguousarray(v[:7]) for k, v in st.items()}
+    dz7, boost7 = np.ascontiguousarray(dz[:7]), np.ascontiguousarray(boost[:7])
+    want7 = _fall(m, st7, boost=boost7, dz=dz7, dt=10.0)
+    m.set_host_chunk(3)
+    seen = with_padded(monkeypatch, library(), "kidmp_fall_speeds_host" if dtype == np.float64 else "kidmp32_fall_speeds_host", {13: dz7})
+    assert _same_all(m.fall_speeds_host(st7, boost7, dz7, 10.0), want7) and seen == [(13, 70)]
 
 
 # ---- 7. graph capture ----

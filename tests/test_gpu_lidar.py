@@ -310,7 +310,9 @@ def test_binary32_entries_round_once(gpu_mixed, gpu_warm, sets):
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
-def test_host_entries_equal_the_device_entry(gpu_mixed, sets, dtype):
+def test_host_entries_equal_the_device_entry(gpu_mixed, sets, dtype, monkeypatch):
+    from padded_rows import with_padded
+    from kid_amd.lidar import library
     m = gpu_mixed
     st0, _, dz0 = sets["config5"]                                                # dz per column
     st = {k: np.ascontiguousarray(v.astype(dtype)) for k, v in st0.items()}
@@ -329,6 +331,13 @@ def test_host_entries_equal_the_device_entry(gpu_mixed, sets, dtype):
         assert _same(got["att_up"], shared["att_up"]) and (_bits(got["summary"]) == _bits(shared["summary"])).all(), chunk
         only = m.lidar_profiles_host(st, None, CFG, ("ext", "bsc_mol"))
         assert _same(only["ext"], want["ext"]) and _same(only["bsc_mol"], want["bsc_mol"]), chunk
+    # seven columns in chunks of 3, 3 and 1, the rows of dz nz + 5 apart (dz_col_stride)
+    st7, dz7 = _take(st, np.arange(7)), np.ascontiguousarray(dz[:7])
+    want7 = _lidar(m, st7, dz7)
+    m.set_host_chunk(3)
+    seen = with_padded(monkeypatch, library(), "kidmp_lidar_profiles_host" if dtype == np.float64 else "kidmp32_lidar_profiles_host", {14: dz7})
+    got = m.lidar_profiles_host(st7, dz7, CFG, ref.NAMES, True)
+    assert sorted(got) == sorted(want7) and all((_bits(got[n]) == _bits(want7[n])).all() for n in want7) and seen == [(14, 125)]
 
 
 def test_hip_graph_replay_of_one_captured_launch(gpu_mixed, sets):

@@ -286,7 +286,9 @@ def test_binary32_entries_round_once(gpu_mixed, tables, main_set):
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
-def test_host_entry_in_chunks_equals_the_device_entry(gpu_mixed, tables, main_set, dtype):
+def test_host_entry_in_chunks_equals_the_device_entry(gpu_mixed, tables, main_set, dtype, monkeypatch):
+    from padded_rows import with_padded
+    from kid_amd.mie import library
     m, table = gpu_mixed, tables["ka"][0]
     st, dz, w, k_gas, _ = main_set
     st5 = {k: np.ascontiguousarray(v[:5].astype(dtype)) for k, v in st.items()}
@@ -299,6 +301,18 @@ def test_host_entry_in_chunks_equals_the_device_entry(gpu_mixed, tables, main_se
     assert sorted(part) == sorted(some) and all(_same(part[n], want[n]) for n in some)
     per_col = m.mie_radar_host(table, st5, np.ascontiguousarray(np.tile(dz_, (5, 1))), w_, np.ascontiguousarray(np.tile(kg_, (5, 1))), want=ref.NAMES)
     assert _same_all(per_col, want)
+    # seven columns with a dz and a k_gas of their own: one per chunk, then in chunks of 3, 3 and 1 with the rows of dz and
+    # k_gas nz + 5 apart (dz_col_stride, k_gas_col_stride)
+    idx = np.arange(7) % st["t"].shape[0]
+    st7 = {k: np.ascontiguousarray(v[idx].astype(dtype)) for k, v in st.items()}
+    scale = np.linspace(0.5, 2.0, 7)[:, None]
+    dz7, w7, kg7 = np.ascontiguousarray((dz * scale).astype(dtype)), np.ascontiguousarray(w[idx].astype(dtype)), np.ascontiguousarray((k_gas / scale).astype(dtype))
+    want7 = _run(m, table, st7, dz7, w7, kg7)
+    m.set_host_chunk(1)
+    assert _same_all(m.mie_radar_host(table, st7, dz7, w7, kg7, want=ref.NAMES), want7)
+    m.set_host_chunk(3)
+    seen = with_padded(monkeypatch, library(), "kidmp_mie_radar_host" if dtype == np.float64 else "kidmp32_mie_radar_host", {12: dz7, 15: kg7})
+    assert _same_all(m.mie_radar_host(table, st7, dz7, w7, kg7, want=ref.NAMES), want7) and seen == [(12, 125), (15, 125)]
 
 
 def test_hip_graph_replay_of_one_captured_launch(gpu_mixed, tables, main_set):

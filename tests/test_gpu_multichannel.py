@@ -308,8 +308,11 @@ def test_binary32_entries(gpu_mixed, tables):
 
 # ---- 6. the host entries ----
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
-def test_host_entries_in_chunks_equal_the_device_entries(gpu_mixed, tables, dtype):
+def test_host_entries_in_chunks_equal_the_device_entries(gpu_mixed, tables, dtype, monkeypatch):
+    from padded_rows import with_padded
     from kid_amd import multichannel_tile
+    from kid_amd.multichannel import library
+    entry = lambda what: "%s_%s_multi_host" % ("kidmp" if dtype == np.float64 else "kidmp32", what)   # noqa: E731
     m, nz = gpu_mixed, 129
     f = lambda a: None if a is None else np.ascontiguousarray(a.astype(dtype))   # noqa: E731
     (st, dz, kgs, t_sfc), _ = rad_reference(m, tables, "scheme", nz)
@@ -318,11 +321,15 @@ def test_host_entries_in_chunks_equal_the_device_entries(gpu_mixed, tables, dtyp
     st_ = {k: f(v) for k, v in st.items()}
     want = rad_multi(m, tabs, st, dz, kgs[:nch], t_sfc, r, dtype=dtype)
     full_gas = np.ascontiguousarray(np.repeat(kgs[:nch, None, :], 7, axis=1))
-    for chunk in (0, 2, 3):
+    for chunk in (0, 1, 2, 3):
         m.set_host_chunk(chunk)
         assert _same_all(m.radiometer_multi_host(tabs, st_, f(dz), f(kgs[:nch]), f(t_sfc), r, RAD_NAMES), want), chunk
         per_col = m.radiometer_multi_host(tabs, st_, f(np.tile(dz, (7, 1))), f(full_gas), f(t_sfc), r, RAD_NAMES)
         assert _same_all(per_col, want), chunk
+    with monkeypatch.context() as mp:                                                  # chunks of 3, 3 and 1, the rows of dz nz + 5 apart
+        dz7 = f(np.tile(dz, (7, 1)))
+        seen = with_padded(mp, library(), entry("radiometer"), {14: dz7})
+        assert _same_all(m.radiometer_multi_host(tabs, st_, dz7, f(full_gas), f(t_sfc), r, RAD_NAMES), want) and seen == [(14, nz + 5)]
     some = ("tb_ground", "k_bsc", "tau_abs")
     part = m.radiometer_multi_host(tabs, st_, f(dz), f(kgs[:nch]), f(t_sfc), r, some)
     assert sorted(part) == sorted(some) and all(_same(part[n], want[n]) for n in some)
@@ -335,10 +342,14 @@ def test_host_entries_in_chunks_equal_the_device_entries(gpu_mixed, tables, dtyp
     st_ = {k: f(v) for k, v in st.items()}
     want = mie_multi(m, tabs, st, dz, w, kgs[:nch], dtype=dtype)
     full_gas = np.ascontiguousarray(np.repeat(kgs[:nch, None, :], 7, axis=1))
-    for chunk in (0, 2, 3):
+    for chunk in (0, 1, 2, 3):
         m.set_host_chunk(chunk)
         assert _same_all(m.mie_radar_multi_host(tabs, st_, f(dz), f(w), f(kgs[:nch]), MIE_NAMES), want), chunk
         assert _same_all(m.mie_radar_multi_host(tabs, st_, f(np.tile(dz, (7, 1))), f(w), f(full_gas), MIE_NAMES), want), chunk
+    with monkeypatch.context() as mp:
+        dz7 = f(np.tile(dz, (7, 1)))
+        seen = with_padded(mp, library(), entry("mie_radar"), {13: dz7})
+        assert _same_all(m.mie_radar_multi_host(tabs, st_, dz7, f(w), f(full_gas), MIE_NAMES), want) and seen == [(13, nz + 5)]
     part = m.mie_radar_multi_host(tabs, st_, f(dz), None, f(kgs[1]), ("pia_total", "dbz_s"))
     dev = mie_multi(m, tabs, st, dz, None, kgs[1], want=("pia_total", "dbz_s"), dtype=dtype)
     assert _same_all(part, dev)

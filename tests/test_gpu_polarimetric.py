@@ -376,6 +376,9 @@ def test_host_entry_in_chunks_equals_the_device_entry(gpu_mixed, tables, main_se
     part = m.polarimetric_host(table, {k: v for k, v in st17.items() if k != "qg"}, want=some)
     no_g = _run(m, table, {k: v for k, v in st17.items() if k != "qg"}, want=some)
     assert sorted(part) == sorted(some) and _same_all(part, no_g)
+    m.set_host_chunk(1)                                       # seven columns, one per chunk
+    st7 = _take(st, np.arange(7) % ncol)
+    assert _same_all(m.polarimetric_host(table, st7, want=ref.NAMES), _run(m, table, st7))
 
 
 def test_hip_graph_replay_of_one_captured_launch(gpu_mixed, tables, main_set):

@@ -339,7 +339,9 @@ def test_binary32_entries_round_once(gpu_mixed, tables, main_set):
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
-def test_host_entry_in_chunks_equals_the_device_entry(gpu_mixed, tables, main_set, dtype):
+def test_host_entry_in_chunks_equals_the_device_entry(gpu_mixed, tables, main_set, dtype, monkeypatch):
+    from padded_rows import with_padded
+    from kid_amd.radiometer import library
     from kid_amd import RadiometerCfg
     m, table = gpu_mixed, tables["default"][0]
     st, dz, k_gas, t_sfc, _ = main_set
@@ -357,6 +359,18 @@ def test_host_entry_in_chunks_equals_the_device_entry(gpu_mixed, tables, main_se
     assert _same_all(per_col, want)
     bare = m.radiometer_host(table, st5, dz_, None, None, None, want=("tb_toa",))      # no gas, t_sfc and rcfg left out
     assert _same(bare["tb_toa"], _run(m, table, st5, dz_, None, None, None, want=("tb_toa",))["tb_toa"])
+    # seven columns with a dz and a k_gas of their own: one per chunk, then in chunks of 3, 3 and 1 with the rows of dz and
+    # k_gas nz + 5 apart (dz_col_stride, k_gas_col_stride)
+    idx = np.arange(7) % st["t"].shape[0]
+    st7 = {k: np.ascontiguousarray(v[idx].astype(dtype)) for k, v in st.items()}
+    scale = np.linspace(0.5, 2.0, 7)[:, None]
+    dz7, kg7, ts7 = np.ascontiguousarray((dz * scale).astype(dtype)), np.ascontiguousarray((k_gas / scale).astype(dtype)), np.ascontiguousarray(t_sfc[idx].astype(dtype))
+    want7 = _run(m, table, st7, dz7, kg7, ts7)
+    m.set_host_chunk(1)
+    assert _same_all(m.radiometer_host(table, st7, dz7, kg7, ts7, r, want=ref.NAMES), want7)
+    m.set_host_chunk(3)
+    seen = with_padded(monkeypatch, library(), "kidmp_radiometer_host" if dtype == np.float64 else "kidmp32_radiometer_host", {13: dz7, 15: kg7})
+    assert _same_all(m.radiometer_host(table, st7, dz7, kg7, ts7, r, want=ref.NAMES), want7) and seen == [(13, 134), (15, 134)]
 
 
 def test_hip_graph_replay_of_one_captured_launch(gpu_mixed, tables, main_set):

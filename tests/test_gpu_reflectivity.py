@@ -159,13 +159,14 @@ def test_float32_entry_is_fp64_kernel_on_widened_inputs(gpu_mixed):
 
 
 def test_host_entry_equals_device_entry(gpu_mixed):
-    gpu_mixed.set_host_chunk(16)                 # several chunks through the staging memory
     try:
-        for dtype, view in ((np.float64, np.uint64), (np.float32, np.uint32)):
-            st = {k: v.astype(dtype) for k, v in _random_state(65, 50, 11).items()}
-            h = gpu_mixed.reflectivity_host(st)
-            d = _gpu_dbz(gpu_mixed, st)
-            assert h.dtype == dtype and np.array_equal(h.view(view), d.view(view))
+        for chunk, ncol in ((16, 50), (1, 7)):   # several chunks through the staging memory: 16 + 16 + 16 + 2 columns; seven of one
+            gpu_mixed.set_host_chunk(chunk)
+            for dtype, view in ((np.float64, np.uint64), (np.float32, np.uint32)):
+                st = {k: np.ascontiguousarray(v[:ncol].astype(dtype)) for k, v in _random_state(65, 50, 11).items()}
+                h = gpu_mixed.reflectivity_host(st)
+                d = _gpu_dbz(gpu_mixed, st)
+                assert h.dtype == dtype and h.shape == (ncol, 65) and np.array_equal(h.view(view), d.view(view))
     finally:
         gpu_mixed.set_host_chunk(0)
 
