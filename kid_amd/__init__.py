@@ -19,6 +19,9 @@ from .radiometer import (RADIOMETER_INPUTS, RADIOMETER_NAMES, RADIOMETER_ROWS, R
 from .multichannel import MAX_CHANNELS, mie_radar_multi, mie_radar_multi_host, multichannel_tile, radiometer_multi, radiometer_multi_host  # noqa: F401
 # (the function polarimetric.polarimetric is not re-exported either: ThompsonMP.polarimetric calls it)
 from .polarimetric import POL_INPUTS, POL_NAMES, POL_ROWS, POL_SCALARS, PolCfg, PolTable, pol_bins, pol_spheroid, polarimetric_host  # noqa: F401
+# (the function scan.scan IS re-exported, so the attribute kid_amd.scan is the function: reach the submodule with
+# `from kid_amd.scan import ...` or importlib.import_module("kid_amd.scan"))
+from .scan import SCAN_NAMES, ScanCfg, rhi_rays, scan  # noqa: F401
 from .dspectrum import DSPECTRUM_INPUTS, DSPECTRUM_NAMES, doppler_spectrum, doppler_spectrum_host, velocity_grid  # noqa: F401
 from .spectra import SPECTRA_INPUTS, SPECTRA_PARAMS, SPECTRA_SPECIES, default_grid, size_spectra, size_spectra_host  # noqa: F401
 from .kinematic import ADVECT_OUTPUTS, advect, run, update  # noqa: F401

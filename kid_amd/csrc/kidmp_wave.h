@@ -1,5 +1,7 @@
-// kidmp_wave.h -- internal to kidmp_kinematic.hip and kidmp_slab.hip (not installed): a column held by one wavefront, level
-// k = 64 j + lane, and the moves between neighbouring levels that both advection kernels are built from.
+// kidmp_wave.h -- internal to kidmp_kinematic.hip, kidmp_slab.hip, thompson_reflectivity.hip and kidmp_scan.hip (not
+// installed): a column (or a ray) held by one wavefront, level (gate) k = 64 j + lane, the moves between neighbouring levels
+// that both advection kernels are built from, and the sum scan that the path integrals of the column diagnostics and of
+// the scan share.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,6 +39,20 @@ __device__ inline void level_above(const double (&v)[NJ], double (&out)[NJ])
 {
 #pragma unroll
     for (int j = 0; j < NJ; ++j) out[j] = wave_shift<DPP_WAVE_SHL1>(j + 1 < NJ ? readlane(v[j + 1], 0) : 0., v[j]);
+}
+// inclusive sum scan over the wave, Kogge-Stone over __shfl_up: lane l receives v[0] + ... + v[l], in an order that l alone
+// fixes.  DOWN is its mirror image over __shfl_down: lane l receives v[l] + ... + v[63].  `total` receives the sum of the
+// whole wave as the last (DOWN: the first) lane holds it, wave-uniform.  Whole wavefronts only.
+template <bool DOWN>
+__device__ inline double wave_prefix_sum(double v, int lane, double &total)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double o = DOWN ? __shfl_down(v, d, 64) : __shfl_up(v, d, 64);
+        if (DOWN ? lane + d < 64 : lane >= d) v += o;
+    }
+    total = readlane(v, DOWN ? 0 : 63);
+    return v;
 }
 __device__ inline double wave_max(double v)
 {

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "thompson_levels.h"
+#include "kidmp_wave.h"
 #include "kidmp_dspectrum_slot.h"
 #include "kidmp_radiometer_layer.h"
 
@@ -45,6 +46,8 @@ namespace {
 
 constexpr int REFL_WAVES = 4;                        // columns (wavefronts) per workgroup
 constexpr int REFL_THREADS = 64 * REFL_WAVES;
+using wave::readlane;                                // kidmp_wave.h
+using wave::wave_prefix_sum;
 
 // 64-bit DPP move: lane l receives lane l + D of its row of 16 (row_shl:D); lanes whose source lies past the row end get
 // garbage that the caller masks off
@@ -56,14 +59,6 @@ __device__ inline double row_shl(double v)
     const int hi = __builtin_amdgcn_update_dpp(0, int(b >> 32), 0x100 + D, 0xf, 0xf, false);
     return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned int>(lo));
 }
-__device__ inline double readlane(double v, int lane)
-{
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane(int(b & 0xffffffffll), lane);
-    const int hi = __builtin_amdgcn_readlane(int(b >> 32), lane);
-    return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned int>(lo));
-}
-
 // suffix minimum over the wave: lane l receives min(v[l], v[l+1], ..., v[63]); `tail` receives the minimum of the whole
 // wave (lane 0's result), wave-uniform
 __device__ inline double wave_suffix_min(double v, int lane, double &tail)
@@ -83,20 +78,6 @@ __device__ inline double wave_suffix_min(double v, int lane, double &tail)
     return v;
 }
 
-// inclusive sum scan over the wave, Kogge-Stone over __shfl_up: lane l receives v[0] + ... + v[l], in an order that l alone
-// fixes.  DOWN is its mirror image over __shfl_down: lane l receives v[l] + ... + v[63].  `total` receives the sum of the
-// whole wave as the last (DOWN: the first) lane holds it, wave-uniform.  Whole wavefronts only.
-template <bool DOWN>
-__device__ inline double wave_prefix_sum(double v, int lane, double &total)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const double o = DOWN ? __shfl_down(v, d, 64) : __shfl_up(v, d, 64);
-        if (DOWN ? lane + d < 64 : lane >= d) v += o;
-    }
-    total = readlane(v, DOWN ? 0 : 63);
-    return v;
-}
 // The exclusive sums of a column: up[j] = the sum of v over the levels below the lane's level of group j, dn[j] = over the
 // levels above it.  The level groups are chained through a wave-uniform carry, upward for up and from the top for dn (a
 // reversed scan, not total minus prefix: nothing cancels, dn is exact +0.0 at the top level and never negative).  Levels

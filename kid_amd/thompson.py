@@ -671,6 +671,12 @@ class ThompsonMP:
         from .mie import mie_radar_host
         return mie_radar_host(self, table, st, dz, w, k_gas, want, out)
 
+    def scan(self, fields, zf, rays, dx, nx, cfg, want=("dbz_att",), out=None, stream=None):
+        """A range-height radar scan of an x-z slab (slant beams, path attenuation, beam broadening, radial velocity):
+        kid_amd.scan.scan on this context."""
+        from .scan import scan
+        return scan(self, fields, zf, rays, dx, nx, cfg, want, out, stream)
+
     def pol_table(self, mie_cfg=None, pol_cfg=None, grids=None):
         """The spheroid rows of rain, snow and graupel on this context's device (include/kidmp_polarimetric.h): a
         kid_amd.polarimetric.PolTable."""
