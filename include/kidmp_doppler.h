@@ -34,7 +34,8 @@
  *             A level with no species at all has vd = sw = +0.0: w is NOT applied there (there is no echo to move).
  *
  * Not modelled: echoes of cloud ice and cloud droplets, Mie scattering and attenuation, the melting layer's wet
- * particles, turbulent and beam broadening of sw, full spectra.  A column gives the same bits alone, at any position
+ * particles, turbulent and beam broadening of sw, full spectra (kidmp_spectrum_process_device of kidmp_specproc.h
+ * broadens a spectrum of kidmp_dspectrum.h and takes its moments, noise floor included).  A column gives the same bits alone, at any position
  * in any batch and on a repeated call.  Inputs are assumed finite and physical; a NaN input is memory-safe and gives
  * unspecified values.
  */

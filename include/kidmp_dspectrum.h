@@ -50,6 +50,7 @@
  *             arithmetic gives (NaN or inf included); every index formed stays inside the nv + 2 slots.
  *
  * Turbulent and beam broadening are a one-dimensional convolution along the bin axis, which the caller applies.
+ * kidmp_spectrum_process_device (kidmp_specproc.h) applies it on the device, with a noise floor, detection and moments.
  * Not modelled: echoes of cloud ice and cloud droplets, Mie scattering, attenuation, the melting layer, noise floors,
  * non-uniform velocity grids, entries over several devices.
  */

@@ -23,6 +23,7 @@ from .polarimetric import POL_INPUTS, POL_NAMES, POL_ROWS, POL_SCALARS, PolCfg, 
 # `from kid_amd.scan import ...` or importlib.import_module("kid_amd.scan"))
 from .scan import SCAN_NAMES, ScanCfg, rhi_rays, scan  # noqa: F401
 from .dspectrum import DSPECTRUM_INPUTS, DSPECTRUM_NAMES, doppler_spectrum, doppler_spectrum_host, velocity_grid  # noqa: F401
+from .specproc import SPECPROC_NAMES, SpecCfg, spectrum_process  # noqa: F401
 from .spectra import SPECTRA_INPUTS, SPECTRA_PARAMS, SPECTRA_SPECIES, default_grid, size_spectra, size_spectra_host  # noqa: F401
 from .kinematic import ADVECT_OUTPUTS, advect, run, update  # noqa: F401
 from .advection import SCHEMES as ADVECTION_SCHEMES  # noqa: F401

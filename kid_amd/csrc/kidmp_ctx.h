@@ -1,6 +1,6 @@
 // kidmp_ctx.h -- internal to the units behind include/kidmp.h (not installed): the context, the error and device-guard
 // helpers of every entry point, and what the units kidmp_{capi,diag,host,tables,multi,adapter,stats,summary,fall,doppler,kinematic,slab,
-// spectra,dspectrum,aerosol,lidar,brightband,mie,radiometer,multichannel,polarimetric,scan,mathprobe}.hip offer one another.
+// spectra,dspectrum,aerosol,lidar,brightband,mie,radiometer,multichannel,polarimetric,scan,specproc,mathprobe}.hip offer one another.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

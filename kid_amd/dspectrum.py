@@ -3,7 +3,8 @@ reflectivity of rain, snow and graupel as a function of radial velocity, on a un
 size distributions and the fall-speed laws of doppler_moments -- one launch per call.
 
 Turbulent or beam broadening is a one-dimensional convolution along the bin axis (axis 1 of a spectrum), which the
-caller applies; the spectra here are the quiet-air ones shifted by the vertical air velocity.
+caller applies; the spectra here are the quiet-air ones shifted by the vertical air velocity.  kid_amd.specproc's
+spectrum_process applies it on the device, with a noise floor, detection and the moments, in one launch.
 
 The four entries of kidmp_dspectrum.h are declared here, on the object load_library() returned, the first time one of
 them is needed: include/kidmp.h and its mirror in thompson.py stay what they are.  There is no fallback: without the
@@ -172,7 +173,8 @@ def doppler_spectrum(model, st, v0, dv, nv, w=None, grids=None, want=("total",),
             bin (10*log10(1e18 * sum over bins) is dBZ); "below" and "above" [ncol, nz] hold what `total` puts outside
             the grid.  What is not named costs nothing.
     out     None, or a dict name -> tensor of the result's shape and dtype to write into instead of a fresh one
-    Turbulent or beam broadening is a 1-D convolution along the bin axis (axis 1), which the caller applies.
+    Turbulent or beam broadening is a 1-D convolution along the bin axis (axis 1), which the caller applies
+    (spectrum_process does it on the device).
     Returns a dict name -> tensor of the state's dtype.  Asynchronous on `stream` (default: torch's current stream)."""
     import torch
     who = "doppler_spectrum"

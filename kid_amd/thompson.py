@@ -638,6 +638,13 @@ class ThompsonMP:
         from .dspectrum import doppler_spectrum
         return doppler_spectrum(self, st, v0, dv, nv, w, grids, want, out, stream)
 
+    def spectrum_process(self, spec, v0, dv, sigma=None, noise=None, cfg=None,
+                         want=("dbz", "vm", "sw", "skew", "kurt", "v_lo", "v_hi", "nbins"), out=None, stream=None):
+        """Broadening, noise floor, detection and moments of spectra [ncol, nv, nz] (include/kidmp_specproc.h):
+        kid_amd.specproc.spectrum_process on this context."""
+        from .specproc import spectrum_process
+        return spectrum_process(self, spec, v0, dv, sigma, noise, cfg, want, out, stream)
+
     def doppler_spectrum_host(self, st, v0, dv, nv, w=None, grids=None, want=("total",), out=None):
         """doppler_spectrum on numpy arrays: kid_amd.dspectrum.doppler_spectrum_host on this context."""
         from .dspectrum import doppler_spectrum_host
