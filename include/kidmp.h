@@ -496,6 +496,13 @@ int kidmp_math_probe(kidmp_ctx *ctx, int32_t fn, int64_t n, const double *x, con
 #define KIDMP_MATH_PLAIN_RCP 13        /* 1 / y likewise                                                          */
 #define KIDMP_MATH_POW_DF    14        /* pow(double x, float y): DOUBLE**REAL, evaluated in binary64             */
 #define KIDMP_MATH_POW_FD    15        /* pow(float x, double y): REAL**DOUBLE, evaluated in binary64             */
+/* A size-limit test of the scheme decided both ways (kid_amd/csrc/limit_bracket.h), binary64 only: x = num, y = den,
+ * z = the site (0: ice, 1: rain, 2 .. 15: cloud droplets with nu = z).  out = b + 4 * o + 16 * i, where b is the bracket's
+ * answer (0 below, 1 inside, 2 above, 3 ambiguous), o the decision of the column kernel's original expression
+ * c / root3(num / den) against the two limits (0, 1 or 2) and i the one-sided form the kernel votes on
+ * (1: certainly inside).  Not a function of fastmath.h: the codes from 32 on are decisions of the kernel;
+ * 16 .. 31 stay unassigned (KIDMP_EINVAL). */
+#define KIDMP_MATH_LIMIT_BRACKET 32
 int kidmp_math_probe_ex(kidmp_ctx *ctx, int32_t fn, int32_t binary32, int64_t n, const double *x, const double *y,
                         const double *z, double *out);
 

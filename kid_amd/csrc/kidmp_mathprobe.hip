@@ -5,6 +5,7 @@
 // frcp<float> of thompson_column.hip).  kidmp_math_probe (kidmp_diag.hip, plain HIPFLAGS) stays as the reference point.
 #include "kidmp_ctx.h"
 #include "fastmath.h"
+#include "limit_bracket.h"
 
 using namespace kidmp;
 
@@ -46,6 +47,33 @@ template <class T> __device__ inline T eval(int fn, T x, T y, T z)
     return T(0);
 }
 
+// one size-limit test by limit_bracket.h and by the column kernel's original expression (the ice test multiplies by the
+// kernel's reciprocal, the other two divide): decide() + 4 * original + 16 * certainly_inside() (what the kernel votes on)
+__device__ inline double limit_both_ways(double num, double den, int site)
+{
+    const double lam = fm::cbrt_pos(fm::div(num, den));
+    int b, o;
+    bool in;
+    if (site == 0) {
+        b = lb::decide(num, den, lb::F_ICE);
+        in = lb::certainly_inside(num, den, lb::F_ICE);
+        const double xD = lb::SITE_ICE.c * fm::rcp(lam);
+        o = xD < lb::SITE_ICE.D_lo ? lb::BELOW : xD > lb::SITE_ICE.D_hi ? lb::ABOVE : lb::INSIDE;
+    } else if (site == 1) {
+        b = lb::decide(num, den, lb::F_RAIN);
+        in = lb::certainly_inside(num, den, lb::F_RAIN);
+        const double xD = fm::div(lb::SITE_RAIN.c, lam);
+        o = xD > lb::SITE_RAIN.D_hi ? lb::ABOVE : xD < lb::SITE_RAIN.D_lo ? lb::BELOW : lb::INSIDE;
+    } else {
+        const double c = lb::cloud_c(site);
+        b = lb::decide_scaled(num, den, c * c * c, lb::F_CLOUD);
+        in = lb::certainly_inside_scaled(num, den, c * c * c, lb::F_CLOUD);
+        const double xD = fm::div(c, lam);
+        o = xD < lb::SITE_CLOUD.D_lo ? lb::BELOW : xD > lb::SITE_CLOUD.D_hi ? lb::ABOVE : lb::INSIDE;
+    }
+    return double(b + 4 * o + 16 * int(in));
+}
+
 __global__ void k_math_probe_ex(int fn, int binary32, int64_t n, const double *x, const double *y, const double *z, double *out)
 {
     const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -61,6 +89,7 @@ __global__ void k_math_probe_ex(int fn, int binary32, int64_t n, const double *x
     case KIDMP_MATH_IEEE_DIV: r = ieee_div(x[i], y[i]); break;
     case KIDMP_MATH_POW_DF: r = fm::pow(x[i], float(y[i])); break;                 // DOUBLE**REAL
     case KIDMP_MATH_POW_FD: r = fm::pow(float(x[i]), y[i]); break;                 // REAL**DOUBLE
+    case KIDMP_MATH_LIMIT_BRACKET: r = limit_both_ways(x[i], y[i], int(z[i])); break;
     default:
         r = binary32 ? double(eval<float>(fn, float(x[i]), float(y[i]), float(z[i]))) : eval<double>(fn, x[i], y[i], z[i]);
     }
@@ -72,11 +101,16 @@ int kidmp_math_probe_ex(kidmp_ctx *ctx, int32_t fn, int32_t binary32, int64_t n,
                         double *out)
 {
     if (int rc = require_ready(ctx)) return rc;
-    if (n < 0 || !x || !y || !z || !out || fn < 0 || fn > KIDMP_MATH_POW_FD)
+    if (n < 0 || !x || !y || !z || !out || fn < 0 || (fn > KIDMP_MATH_POW_FD && fn != KIDMP_MATH_LIMIT_BRACKET))
         return fail(ctx, KIDMP_EINVAL, "kidmp_math_probe_ex: bad argument");
-    const bool only64 = fn == KIDMP_MATH_DIV || fn == KIDMP_MATH_IEEE_DIV || fn == KIDMP_MATH_RCP || fn == KIDMP_MATH_POW_DF || fn == KIDMP_MATH_POW_FD;
+    const bool only64 = fn == KIDMP_MATH_DIV || fn == KIDMP_MATH_IEEE_DIV || fn == KIDMP_MATH_RCP || fn == KIDMP_MATH_POW_DF ||
+                        fn == KIDMP_MATH_POW_FD || fn == KIDMP_MATH_LIMIT_BRACKET;
     if (binary32 && only64)
-        return fail(ctx, KIDMP_EINVAL, "kidmp_math_probe_ex: the three fp64 divisions and the mixed-type powers have no binary32 form");
+        return fail(ctx, KIDMP_EINVAL, "kidmp_math_probe_ex: the three fp64 divisions, the mixed-type powers and the limit bracket have no binary32 form");
+    if (fn == KIDMP_MATH_LIMIT_BRACKET)
+        for (int64_t i = 0; i < n; ++i)
+            if (!(z[i] >= 0. && z[i] <= 15.) || z[i] != double(int(z[i])))
+                return fail(ctx, KIDMP_EINVAL, "kidmp_math_probe_ex: the limit bracket's site is an integer 0 .. 15");
     if (n == 0) return KIDMP_OK;
     GUARD(ctx);
     double *d = nullptr;

@@ -1055,11 +1055,15 @@ class ThompsonMP:
         return out
 
     MATH_FUNCS_EX = MATH_FUNCS + ("pow10_times_pow", "plain_div", "plain_rcp", "pow_df", "pow_fd")
+    MATH_DECISIONS = {"limit_bracket": 32}       # KIDMP_MATH_LIMIT_BRACKET: not a function of fastmath.h, a code range of its own
 
     def math_probe_ex(self, fn, x, y=None, z=None, binary32=False):
         """math_probe on up to three operands, in binary64 or (binary32=True) through the float overloads, from a unit
         built with the column kernel's flags: "plain_div" / "plain_rcp" are the kernel's binary32 x / y and 1 / y.
         "pow10_times_pow": 10**x * y**z.  "pow_df" / "pow_fd": pow(double x, float y) / pow(float x, double y).
+        "limit_bracket": a size-limit test decided by csrc/limit_bracket.h (b) and by the kernel's original expression (o)
+        for x = num, y = den, z = site (0 ice, 1 rain, 2 .. 15 cloud droplets with nu = z), returned as b + 4 o + 16 i
+        (i: lb::certainly_inside, what the kernel votes on).
         Operands that the device narrows to float must be binary32-representable."""
         x = np.ascontiguousarray(x, dtype=np.float64)
         y = np.ascontiguousarray(x if y is None else y, dtype=np.float64)
@@ -1072,7 +1076,8 @@ class ThompsonMP:
                 if not np.array_equal(a.astype(np.float32).astype(np.float64), a):
                     raise ValueError("math_probe_ex: an operand the device narrows to binary32 is not binary32-representable")
         out = np.empty_like(x)
-        self._check(load_library().kidmp_math_probe_ex(self._h, self.MATH_FUNCS_EX.index(fn), int(bool(binary32)), x.size,
+        code = self.MATH_DECISIONS[fn] if fn in self.MATH_DECISIONS else self.MATH_FUNCS_EX.index(fn)
+        self._check(load_library().kidmp_math_probe_ex(self._h, code, int(bool(binary32)), x.size,
                                                        _np_ptr(x), _np_ptr(y), _np_ptr(z), _np_ptr(out)))
         return out
 
