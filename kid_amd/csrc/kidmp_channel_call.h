@@ -6,6 +6,7 @@
 #include <cmath>
 #include <string>
 
+#include "kidmp_column.h"
 #include "kidmp_mie_table.h"
 #include "../../include/kidmp_radiometer.h"
 
@@ -14,6 +15,9 @@ constexpr int NIN = 8, NREQ = 5;                          // t, p, qv, qr, nr | 
 inline constexpr const char *IN_NAMES[NIN] = {"t", "p", "qv", "qr", "nr", "qc", "qs", "qg"};
 
 // ---- the cloud radar ----
+// out in the order of kidmp_mie_out; a table has MIE_NROWS rows per diameter bin
+constexpr int MIE_NOUT = 13, MIE_NROWS = 5;
+constexpr int MIE_DBZ = 0, MIE_DBZ_UP = 1, MIE_DBZ_DOWN = 2, MIE_DBZ_X = 3, MIE_MIE_X = 6, MIE_EXT = 9, MIE_PIA_UP = 10, MIE_PIA_DOWN = 11, MIE_VD = 12;
 inline constexpr const char *MIE_OUT_NAMES[MIE_NOUT] = {"dbz", "dbz_up", "dbz_down", "dbz_r", "dbz_s", "dbz_g", "mie_r", "mie_s", "mie_g", "ext",
                                          "pia_up", "pia_down", "vd"};
 
@@ -93,6 +97,8 @@ template <class T> MieCall<T> mie_staged(const StageArray (&a)[MIE_NARRAYS], int
 }
 
 // ---- the radiometer ----
+constexpr int RAD_NOUT = 6, RAD_NROWS = 3;
+constexpr int RAD_K_ABS = 0, RAD_K_BSC = 1, RAD_REFL = 2, RAD_TRANS = 3, RAD_TB_UP = 4, RAD_TB_DOWN = 5;
 constexpr int NCOL_OUT = 3;                              // tb_toa, tb_ground, tau_abs
 inline constexpr const char *RAD_OUT_NAMES[RAD_NOUT] = {"k_abs", "k_bsc", "refl", "trans", "tb_up", "tb_down"};
 inline constexpr const char *RAD_COL_NAMES[NCOL_OUT] = {"tb_toa", "tb_ground", "tau_abs"};

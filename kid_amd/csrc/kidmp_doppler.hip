@@ -1,8 +1,109 @@
 // kidmp_doppler.hip -- the entries of include/kidmp_doppler.h: reflectivity, mean Doppler velocity and spectrum width of
-// device arrays in one launch of k_doppler_moments (thompson_reflectivity.hip), and of host arrays in chunks through the
+// device arrays in one launch of k_doppler_moments (below), and of host arrays in chunks through the
 // context's staging memory.
 #include "kidmp_ctx.h"
 #include "../../include/kidmp_doppler.h"
+
+#include "kidmp_column.h"
+
+namespace kidmp {
+
+// The Doppler moments of a vertically pointing radar (include/kidmp_doppler.h): reflectivity, mean Doppler velocity and
+// spectrum width of every level, from calc_refl10cm's load and size distributions.  Null means: qs, qg -- zero; w -- zero;
+// an output -- not wanted.  out: dbz, vd, sw, vz_r, vz_s, vz_g, dbz_r, dbz_s, dbz_g.
+constexpr int DOPPLER_NOUT = 9;
+template <class T> struct DopplerArgs {
+    const T *t, *p, *qv, *qr, *nr, *qs, *qg, *w;
+    T *out[DOPPLER_NOUT];
+};
+
+// One wavefront per column: the three radar moments of every level (include/kidmp_doppler.h).  The load, the ze_* and the
+// order of their sum are column_dbz's, through the same lvl:: functions; beside them the reflectivity-weighted first and
+// second moments of each species' fall speed.  Rain and snow are finished before the graupel scan and leave only their
+// sums behind; graupel follows the running minimum of its intercept.  Nothing but the fastmath tables is in LDS.
+template <class T, int NJ>
+__global__ void __launch_bounds__(REFL_THREADS)
+k_doppler_moments(ReflConsts c, DopplerConsts dc, DopplerArgs<T> a, int64_t ncol, int nz)
+{
+    int lane;
+    const int64_t col = enter_column(lane);
+    if (col >= ncol) return;                                         // whole wavefronts only: the scans need every lane
+    const int64_t base = col * int64_t(nz);
+
+    // of rain and snow together: ze with the 1.E-22 of an absent species (dbz), ze of the present ones, ze*vz, ze*v2
+    double ze_rs[NJ], wt[NJ], m1[NJ], m2[NJ], rhof[NJ], rg[NJ], n0[NJ];
+    bool lqg[NJ], any[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        ze_rs[j] = wt[j] = m1[j] = m2[j] = rhof[j] = 0.;
+        rg[j] = R1;
+        lqg[j] = any[j] = false;
+        n0[j] = double(__builtin_inf());                             // levels past kte do not enter the minimum
+        if (k >= nz) continue;
+        const int64_t i = base + k;
+        const RadarLevel r = radar_level(c, a, i);                   // ---- load, M:4991-5028 ----
+        const bool L_qr = r.L_qr, L_qs = r.L_qs;
+        const double ze_rain = r.ze_rain, ze_snow = r.ze_snow;
+        lqg[j] = r.L_qg;
+        any[j] = L_qr || L_qs || lqg[j];
+        rhof[j] = r.rhof;
+        rg[j] = r.rg;
+        double vz_r = 0., v2_r = 0., vz_s = 0., v2_s = 0.;
+        if (L_qr) lvl::rain_doppler(dc, rhof[j], r.lamr, vz_r, v2_r);
+        if (L_qs) lvl::snow_doppler(c, dc, rhof[j], r.sl, vz_s, v2_s);
+        ze_rs[j] = ze_rain + ze_snow;
+        wt[j] = (L_qr ? ze_rain : 0.) + (L_qs ? ze_snow : 0.);
+        m1[j] = ze_rain * vz_r + ze_snow * vz_s;                     // an absent species has vz = v2 = +0.0
+        m2[j] = ze_rain * v2_r + ze_snow * v2_s;
+        n0[j] = r.n0_exp;
+        if (a.out[3]) a.out[3][i] = T(vz_r);
+        if (a.out[4]) a.out[4][i] = T(vz_s);
+        if (a.out[6]) a.out[6][i] = T(lvl::dbz_of(ze_rain));
+        if (a.out[7]) a.out[7][i] = T(lvl::dbz_of(ze_snow));
+    }
+
+    graupel_running_min<NJ>(n0, lane);
+
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        if (k >= nz) continue;
+        const int64_t i = base + k;
+        double ze_graupel = 1.E-22, vz_g = 0., v2_g = 0.;
+        if (lqg[j]) {
+            double ilamg;
+            ze_graupel = lvl::graupel_ze(c, n0[j], rg[j], ilamg);
+            lvl::graupel_doppler(dc, rhof[j], ilamg, vz_g, v2_g);
+        }
+        if (a.out[0]) a.out[0][i] = T(lvl::dbz_of(ze_rs[j] + ze_graupel));          // M:5196
+        if (a.out[5]) a.out[5][i] = T(vz_g);
+        if (a.out[8]) a.out[8][i] = T(lvl::dbz_of(ze_graupel));
+        double vd = 0., sw = 0.;                                     // a level with no species: +0.0, w is not applied
+        if (any[j]) {
+            const double W = wt[j] + (lqg[j] ? ze_graupel : 0.);
+            const double V = (m1[j] + ze_graupel * vz_g) / W;
+            const double var = (m2[j] + ze_graupel * v2_g) / W - V * V;
+            vd = V - (a.w ? double(a.w[i]) : 0.);
+            sw = var > 0. ? fm::sqrt_pos(var) : 0.;
+        }
+        if (a.out[1]) a.out[1][i] = T(vd);
+        if (a.out[2]) a.out[2][i] = T(sw);
+    }
+}
+
+namespace {
+template <class T>
+hipError_t launch_doppler_moments(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const DopplerArgs<T> &a, hipStream_t s)
+{
+    return launch_level_groups(ncol, nz, [&](auto nj) {
+        constexpr int NJ = decltype(nj)::value;
+        hipLaunchKernelGGL((k_doppler_moments<T, NJ>), column_grid(ncol), dim3(REFL_THREADS), 0, s, c, dc, a, ncol, nz);
+    });
+}
+}  // namespace
+
+}  // namespace kidmp
 
 using namespace kidmp;
 

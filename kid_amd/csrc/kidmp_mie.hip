@@ -1,10 +1,99 @@
 // kidmp_mie.hip -- the entries of include/kidmp_mie.h: the Lorenz-Mie sphere and the per-bin rows on the host
 // (kidmp_mie_sphere.h), the table object that carries them to the device, and the cloud radar of device arrays in one
-// launch of k_mie_radar (thompson_reflectivity.hip) or of host arrays in chunks through the context's staging memory.
+// launch of k_mie_radar (below) or of host arrays in chunks through the context's staging memory.
 #include <cmath>
 #include <cstddef>
 
-#include "kidmp_channel_call.h"
+#include "kidmp_mie_channel.h"
+
+namespace kidmp {
+
+// The cloud radar (include/kidmp_mie.h): Mie reflectivity, extinction, path-integrated attenuation and mean Doppler
+// velocity from k_doppler_moments' load and a table of five rows per diameter bin.  Null means: qc, qs, qg, w, k_gas --
+// zero; an output -- not wanted; dz -- not read when no path integral is wanted.  out in the order of kidmp_mie_out,
+// pia_total [ncol].  D, dD: device arrays of nb[x] doubles by species rain, snow, graupel; rows[x]: [MIE_NROWS][nb[x]]
+// (s_mie, s_ray, s_ext, mass, v0).  kc: (6 pi/lambda) Im(K(eps_w)); rho_w: the configuration's.  Cloud water enters through
+// its mass alone, where qc > R1.  One launch; lanes over levels, a loop over the bins.
+template <class T> struct MieArgs {
+    const T *t, *p, *qv, *qc, *qr, *nr, *qs, *qg, *dz, *w, *k_gas;
+    int64_t dz_col_stride, k_gas_col_stride;
+    T *out[MIE_NOUT];
+    T *pia_total;
+    const double *D[MIE_NSPEC], *dD[MIE_NSPEC], *rows[MIE_NSPEC];
+    int32_t nb[MIE_NSPEC];
+    double kc, rho_w;
+};
+
+// One wavefront per column: the cloud radar of include/kidmp_mie.h.  The load and the scan are k_doppler_moments'
+// (load_channel_levels), lanes over levels.  Then species by species -- rain, snow, graupel -- the five sums over the
+// table's bins (mie_sums), which leave behind only mie_x, the species' extinction and its share of the Doppler sums
+// (mie_species_finish).  Cloud water (present where qc > R1) and the caller's gas extinction close ext; the path integrals
+// are column_depths, the scans of k_lidar_profiles, and a request without them ends before (mie_tail).  No atomics, no
+// scratch, nothing but the fastmath tables in LDS.
+template <class T, int NJ>
+__global__ void __launch_bounds__(REFL_THREADS)
+k_mie_radar(ReflConsts c, DopplerConsts dc, MieArgs<T> a, int64_t ncol, int nz)
+{
+    int lane;
+    const int64_t col = enter_column(lane);
+    if (col >= ncol) return;                                         // whole wavefronts only: the scans need every lane
+    const int64_t base = col * int64_t(nz);
+    T *const *out = a.out;
+    const MieChannel<T> ch{out, 0, a.pia_total, a.k_gas ? a.k_gas + col * a.k_gas_col_stride : nullptr, a.kc, a.rho_w};
+    const MieWants want = mie_wants<T>(out, a.pia_total);
+    const auto wants = [&](int x) __attribute__((always_inline)) { return want.all || out[MIE_DBZ_X + x] || out[MIE_MIE_X + x]; };
+
+    ChannelLevels<NJ> L;
+    load_channel_levels<NJ>(c, dc, a, base, nz, lane, L);
+
+    // what the species leave behind: ze_x' in ze_x, ext = (ext_r + ext_s) + ext_g, and the Doppler sums over the species
+    // that are present with A above 0
+    double ext[NJ], zw[NJ], zv[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) ext[j] = zw[j] = zv[j] = 0.;
+    double A[1][NJ], B[NJ], E[1][NJ], M[NJ], V[1][NJ];
+    if (wants(0)) {
+        double rr[NJ];
+        rain_mass<NJ>(a, base, lane, L, rr);
+        const double *const rows[1] = {a.rows[0]};
+        mie_sums<0, NJ, 1>(a.D[0], a.dD[0], a.nb[0], rows, 1, lane, L.lqr,
+                           [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(L.N0_r[j], L.lamr[j], D, dD); },
+                           A, B, E, M, V);
+        mie_species_finish<T, NJ>(L.lqr, rr, A[0], B, E[0], M, V[0], L.ze_r, ext, zw, zv, out[MIE_MIE_X + 0], out[MIE_DBZ_X + 0], base, nz, lane);
+    }
+    if (wants(1)) {
+        const double *const rows[1] = {a.rows[1]};
+        mie_sums<1, NJ, 1>(a.D[1], a.dD[1], a.nb[1], rows, 1, lane, L.lqs,
+                           [&](int j, double D, double dD, double Dmu) __attribute__((always_inline)) { return lvl::snow_bin(L.ss[j], D, Dmu, dD); },
+                           A, B, E, M, V);
+        mie_species_finish<T, NJ>(L.lqs, L.rs, A[0], B, E[0], M, V[0], L.ze_s, ext, zw, zv, out[MIE_MIE_X + 1], out[MIE_DBZ_X + 1], base, nz, lane);
+    }
+    if (wants(2)) {
+        const double *const rows[1] = {a.rows[2]};
+        mie_sums<2, NJ, 1>(a.D[2], a.dD[2], a.nb[2], rows, 1, lane, L.lqg,
+                           [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(L.N0_g[j], L.lamg[j], D, dD); },
+                           A, B, E, M, V);
+        mie_species_finish<T, NJ>(L.lqg, L.rg, A[0], B, E[0], M, V[0], L.ze_g, ext, zw, zv, out[MIE_MIE_X + 2], out[MIE_DBZ_X + 2], base, nz, lane);
+    }
+    if (!want.all) return;                                           // wave-uniform: one species' own profiles alone
+    mie_tail<T, NJ>(a, ch, want, col, base, nz, lane, L, L.ze_r, L.ze_s, L.ze_g, ext, zw, zv);
+}
+
+namespace {
+template <class T>
+hipError_t launch_mie_radar(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const MieArgs<T> &a, hipStream_t s)
+{
+    if (ncol <= 0) return hipSuccess;                                // an empty batch is not looked at
+    for (int x = 0; x < MIE_NSPEC; ++x)
+        if (a.nb[x] < 1 || a.nb[x] > MIE_MAX_BINS) return hipErrorInvalidValue;
+    return launch_level_groups(ncol, nz, [&](auto nj) {
+        constexpr int NJ = decltype(nj)::value;
+        hipLaunchKernelGGL((k_mie_radar<T, NJ>), column_grid(ncol), dim3(REFL_THREADS), 0, s, c, dc, a, ncol, nz);
+    });
+}
+}  // namespace
+
+}  // namespace kidmp
 
 using namespace kidmp;
 

@@ -12,6 +12,7 @@
 #include "../../include/kidmp_mie.h"
 
 namespace kidmp {
+constexpr int MIE_NSPEC = 3, MIE_MAX_BINS = 256;           // rain, snow, graupel; the bins a species' table may have
 
 struct MieTableData {
     kidmp_ctx *ctx;

@@ -1,6 +1,6 @@
 // kidmp_polarimetric.hip -- the entries of include/kidmp_polarimetric.h: the spheroid and the per-bin rows on the host
 // (kidmp_spheroid.h), the table object that carries them and the uniform species' scalars to the device, and the
-// polarimetric radar of device arrays in one launch of k_polarimetric (thompson_reflectivity.hip) or of host arrays in
+// polarimetric radar of device arrays in one launch of k_polarimetric (below) or of host arrays in
 // chunks through the context's staging memory.
 #include <cmath>
 #include <cstddef>
@@ -8,6 +8,181 @@
 #include "kidmp_mie_table.h"
 #include "kidmp_spheroid.h"
 #include "../../include/kidmp_polarimetric.h"
+
+#include "kidmp_column.h"
+
+namespace kidmp {
+
+// The polarimetric radar (include/kidmp_polarimetric.h): Z_DR, K_DP and rho_hv of oblate spheroids from k_mie_radar's load
+// and a table of seven rows per diameter bin (s_h, s_v, c_re, c_im, s_0, k, mass).  Null means: qs, qg -- zero; an output
+// -- not wanted.  out in the order of kidmp_pol_out.  uniform[x] != 0: the species walks no bins and takes scal[x] (s_h/s_0,
+// s_v/s_0, c_re/s_0, c_im/s_0, k/mass) in place of the ratios of its sums; its D, dD, rows and nb are not read.
+// kfac: 90e3 pi/lambda.  One launch; lanes over levels, a loop over the bins.
+constexpr int POL_NOUT = 13, POL_NROWS = 7, POL_NSCAL = 5;
+constexpr int POL_DBZ_H = 0, POL_ZDR = 1, POL_KDP = 2, POL_RHOHV = 3, POL_DBZ_H_X = 4, POL_ZDR_X = 7, POL_KDP_X = 10;
+template <class T> struct PolArgs {
+    const T *t, *p, *qv, *qr, *nr, *qs, *qg;
+    T *out[POL_NOUT];
+    const double *D[MIE_NSPEC], *dD[MIE_NSPEC], *rows[MIE_NSPEC];
+    int32_t nb[MIE_NSPEC];
+    int32_t uniform[MIE_NSPEC];
+    double scal[MIE_NSPEC][POL_NSCAL];
+    double kfac;
+};
+
+// ---- the polarimetric radar (include/kidmp_polarimetric.h) ----
+// One wavefront per column.  The load and the scan are k_mie_radar's (radar_level, graupel_running_min), lanes over
+// levels.  Then species by species -- rain, snow, graupel -- the seven sums over the table's bins (bin_loop), which leave
+// behind only the species' share of Zh, Zv, C and kdp.  A uniform species (a.uniform[x], wave-uniform) walks no bins and
+// forms no density: the table's scalars stand in for the ratios of its sums.  A request for one species' own profiles alone
+// walks that species only.  No atomics, no scratch, no scan but the graupel minimum, nothing but the fastmath tables in LDS.
+template <class T, int NJ>
+__global__ void __launch_bounds__(REFL_THREADS)
+k_polarimetric(ReflConsts c, DopplerConsts dc, PolArgs<T> a, int64_t ncol, int nz)
+{
+    int lane;
+    const int64_t col = enter_column(lane);
+    if (col >= ncol) return;                                         // whole wavefronts only: the scans need every lane
+    const int64_t base = col * int64_t(nz);
+    T *const *out = a.out;
+    const bool all = out[POL_DBZ_H] || out[POL_ZDR] || out[POL_KDP] || out[POL_RHOHV];   // what takes every species
+    const auto wants = [&](int x) __attribute__((always_inline)) { return all || out[POL_DBZ_H_X + x] || out[POL_ZDR_X + x] || out[POL_KDP_X + x]; };
+
+    double ze_r[NJ], ze_s[NJ], ze_g[NJ], rho[NJ], rs[NJ], rg[NJ], n0[NJ], N0_r[NJ], lamr[NJ];
+    lvl::SnowSpectrum ss[NJ];
+    bool lqr[NJ], lqs[NJ], lqg[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int k = 64 * j + lane;
+        ze_r[j] = ze_s[j] = ze_g[j] = 1.E-22;
+        rho[j] = 1.;
+        rs[j] = rg[j] = R1;
+        N0_r[j] = lamr[j] = 0.;
+        ss[j] = lvl::SnowSpectrum{0., 0., 0., 0.};
+        lqr[j] = lqs[j] = lqg[j] = false;
+        n0[j] = double(__builtin_inf());                             // levels past kte do not enter the minimum
+        if (k >= nz) continue;
+        const RadarLevel r = radar_level(c, a, base + k);            // ---- load, M:4991-5028 ----
+        ze_r[j] = r.ze_rain;
+        ze_s[j] = r.ze_snow;
+        rho[j] = r.rho;
+        rs[j] = r.rs;
+        rg[j] = r.rg;
+        N0_r[j] = r.N0_r;
+        lamr[j] = r.lamr;
+        lqr[j] = r.L_qr; lqs[j] = r.L_qs; lqg[j] = r.L_qg;
+        if (r.L_qs && !a.uniform[1]) ss[j] = lvl::snow_spectrum(r.sl, lvl::snow_moment(c.sa, c.sb, dc.cse1, r.sl));
+        n0[j] = r.n0_exp;
+    }
+    graupel_running_min<NJ>(n0, lane);
+    double N0_g[NJ], lamg[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        N0_g[j] = lamg[j] = 0.;
+        if (!lqg[j]) continue;
+        double ilamg;
+        ze_g[j] = lvl::graupel_ze(c, n0[j], rg[j], ilamg, lamg[j], N0_g[j]);
+    }
+
+    // what the species leave behind: Zh = (zh_r + zh_s) + zh_g, Zv, C and kdp likewise
+    double Zh[NJ], Zv[NJ], Cr[NJ], Ci[NJ], Kd[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) Zh[j] = Zv[j] = Cr[j] = Ci[j] = Kd[j] = 0.;
+    double H[NJ], V[NJ], Xr[NJ], Xi[NJ], S[NJ], K[NJ], M[NJ];
+    const auto zero = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) H[j] = V[j] = Xr[j] = Xi[j] = S[j] = K[j] = M[j] = 0.;
+    };
+    const auto add = [&](int j, double n, const double (&r)[POL_NROWS]) __attribute__((always_inline)) {
+        H[j] += n * r[0];
+        V[j] += n * r[1];
+        Xr[j] += n * r[2];
+        Xi[j] += n * r[3];
+        S[j] += n * r[4];
+        K[j] += n * r[5];
+        M[j] += n * r[6];
+    };
+    const auto finish = [&](int x, const bool (&has)[NJ], const double (&ze)[NJ], const double (&rq)[NJ]) __attribute__((always_inline)) {
+        const bool uni = a.uniform[x] != 0;                          // wave-uniform
+        double o_dbz[NJ], o_zdr[NJ], o_kdp[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            double rh = 1., rv = 1., rcr = 1., rci = 0., rk = 0.;
+            if (uni) {
+                if (has[j]) { rh = a.scal[x][0]; rv = a.scal[x][1]; rcr = a.scal[x][2]; rci = a.scal[x][3]; rk = a.scal[x][4]; }
+            } else {
+                if (has[j] && S[j] > 0.) { rh = H[j] / S[j]; rv = V[j] / S[j]; rcr = Xr[j] / S[j]; rci = Xi[j] / S[j]; }
+                if (has[j] && M[j] > 0.) rk = K[j] / M[j];
+            }
+            const double zh = ze[j] * rh, zv = ze[j] * rv;
+            const double kd = has[j] ? (a.kfac * rq[j]) * rk : 0.;
+            Zh[j] = Zh[j] + zh;
+            Zv[j] = Zv[j] + zv;
+            Cr[j] = Cr[j] + ze[j] * rcr;
+            Ci[j] = Ci[j] + ze[j] * rci;
+            Kd[j] = Kd[j] + kd;
+            o_dbz[j] = lvl::dbz_of(zh);
+            o_zdr[j] = 10. * fm::log10(zh / zv);
+            o_kdp[j] = kd;
+        }
+        store_profile<T, NJ>(out[POL_DBZ_H_X + x], base, nz, lane, o_dbz);
+        store_profile<T, NJ>(out[POL_ZDR_X + x], base, nz, lane, o_zdr);
+        store_profile<T, NJ>(out[POL_KDP_X + x], base, nz, lane, o_kdp);
+    };
+    if (wants(0)) {
+        double rr[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) rr[j] = lqr[j] ? double(a.qr[base + 64 * j + lane]) * rho[j] : 0.;
+        if (!a.uniform[0]) {
+            zero();
+            bin_loop<0, NJ, POL_NROWS>(a, lane, lqr, [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(N0_r[j], lamr[j], D, dD); }, add);
+        }
+        finish(0, lqr, ze_r, rr);
+    }
+    if (wants(1)) {
+        if (!a.uniform[1]) {
+            zero();
+            bin_loop<1, NJ, POL_NROWS>(a, lane, lqs, [&](int j, double D, double dD, double Dmu) __attribute__((always_inline)) { return lvl::snow_bin(ss[j], D, Dmu, dD); }, add);
+        }
+        finish(1, lqs, ze_s, rs);
+    }
+    if (wants(2)) {
+        if (!a.uniform[2]) {
+            zero();
+            bin_loop<2, NJ, POL_NROWS>(a, lane, lqg, [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(N0_g[j], lamg[j], D, dD); }, add);
+        }
+        finish(2, lqg, ze_g, rg);
+    }
+    if (!all) return;                                                // wave-uniform: one species' own profiles alone
+
+    double dbz[NJ], zdr[NJ], rhohv[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        dbz[j] = lvl::dbz_of(Zh[j]);                                 // M:5196
+        zdr[j] = 10. * fm::log10(Zh[j] / Zv[j]);
+        rhohv[j] = fmin(1., fm::sqrt_pos(Cr[j] * Cr[j] + Ci[j] * Ci[j]) / fm::sqrt_pos(Zh[j] * Zv[j]));
+    }
+    store_profile<T, NJ>(out[POL_DBZ_H], base, nz, lane, dbz);
+    store_profile<T, NJ>(out[POL_ZDR], base, nz, lane, zdr);
+    store_profile<T, NJ>(out[POL_KDP], base, nz, lane, Kd);
+    store_profile<T, NJ>(out[POL_RHOHV], base, nz, lane, rhohv);
+}
+
+namespace {
+template <class T>
+hipError_t launch_polarimetric(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const PolArgs<T> &a, hipStream_t s)
+{
+    if (ncol <= 0) return hipSuccess;                                // an empty batch is not looked at
+    for (int x = 0; x < MIE_NSPEC; ++x)
+        if (!a.uniform[x] && (a.nb[x] < 1 || a.nb[x] > MIE_MAX_BINS)) return hipErrorInvalidValue;
+    return launch_level_groups(ncol, nz, [&](auto nj) {
+        constexpr int NJ = decltype(nj)::value;
+        hipLaunchKernelGGL((k_polarimetric<T, NJ>), column_grid(ncol), dim3(REFL_THREADS), 0, s, c, dc, a, ncol, nz);
+    });
+}
+}  // namespace
+
+}  // namespace kidmp
 
 using namespace kidmp;
 

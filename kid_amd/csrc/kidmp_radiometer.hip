@@ -1,11 +1,82 @@
 // kidmp_radiometer.hip -- the entries of include/kidmp_radiometer.h: the sphere's four efficiencies and the per-bin rows on
 // the host (kidmp_mie_sphere.h), the table object that carries them to the device (kidmp_mie_table.h), and the radiometer
-// of device arrays in one launch of k_radiometer (thompson_reflectivity.hip) or of host arrays in chunks through the
+// of device arrays in one launch of k_radiometer (below) or of host arrays in chunks through the
 // context's staging memory.  No kernel of its own.
 #include <cmath>
 #include <cstddef>
 
-#include "kidmp_channel_call.h"
+#include "kidmp_radiometer_channel.h"
+
+namespace kidmp {
+
+// The microwave radiometer (include/kidmp_radiometer.h): absorption and back-hemisphere scattering coefficients from
+// k_mie_radar's load and a table of three rows per diameter bin (s_abs, s_bsc, mass), the two-stream layer of every level
+// and the adding of the layers by two wave scans.  Null means: qc, qs, qg, k_gas -- zero; t_sfc -- the column's t at level
+// 0; an output -- not wanted; dz -- not read when only k_abs and k_bsc are wanted.  out: k_abs, k_bsc, refl, trans, tb_up,
+// tb_down [ncol][nz]; tb_toa, tb_ground, tau_abs [ncol].  One launch; lanes over levels, a loop over the bins.
+template <class T> struct RadiometerArgs {
+    const T *t, *p, *qv, *qc, *qr, *nr, *qs, *qg, *dz, *k_gas, *t_sfc;
+    int64_t dz_col_stride, k_gas_col_stride;
+    T *out[RAD_NOUT];
+    T *tb_toa, *tb_ground, *tau_abs;
+    const double *D[MIE_NSPEC], *dD[MIE_NSPEC], *rows[MIE_NSPEC];
+    int32_t nb[MIE_NSPEC];
+    double kc, rho_w, mu, emissivity, t_cosmic;
+};
+
+// One wavefront per column: the radiometer of include/kidmp_radiometer.h.  The load is k_mie_radar's (load_channel_levels),
+// lanes over levels.  Then species by species the three sums over the table's bins (radiometer_sums), which leave behind
+// only k_abs and k_bsc; the rest is radiometer_tail.  No atomics, no scratch, nothing but the fastmath tables in LDS.
+template <class T, int NJ>
+__global__ void __launch_bounds__(REFL_THREADS)
+k_radiometer(ReflConsts c, DopplerConsts dc, RadiometerArgs<T> a, int64_t ncol, int nz)
+{
+    int lane;
+    const int64_t col = enter_column(lane);
+    if (col >= ncol) return;                                         // whole wavefronts only: the scans need every lane
+    const int64_t base = col * int64_t(nz);
+    const RadChannel<T> ch{a.out, 0, a.tb_toa, a.tb_ground, a.tau_abs, a.k_gas ? a.k_gas + col * a.k_gas_col_stride : nullptr,
+                           a.kc, a.rho_w, a.mu, a.emissivity, a.t_cosmic};
+
+    ChannelLevels<NJ> L;
+    load_channel_levels<NJ>(c, dc, a, base, nz, lane, L);
+
+    // ---- k_abs = (((abs_r + abs_s) + abs_g) + abs_c) + k_gas, k_bsc = (bsc_r + bsc_s) + bsc_g; levels past nz keep +0.0 ----
+    double kabs[NJ], kbsc[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) kabs[j] = kbsc[j] = 0.;
+    {
+        double A[1][NJ], S[1][NJ], M[NJ], rr[NJ];
+        rain_mass<NJ>(a, base, lane, L, rr);
+        const double *const rows_r[1] = {a.rows[0]}, *const rows_s[1] = {a.rows[1]}, *const rows_g[1] = {a.rows[2]};
+        radiometer_sums<0, NJ, 1>(a.D[0], a.dD[0], a.nb[0], rows_r, 1, lane, L.lqr,
+                                  [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(L.N0_r[j], L.lamr[j], D, dD); }, A, S, M);
+        radiometer_species_finish<NJ>(L.lqr, rr, A[0], S[0], M, kabs, kbsc);
+        radiometer_sums<1, NJ, 1>(a.D[1], a.dD[1], a.nb[1], rows_s, 1, lane, L.lqs,
+                                  [&](int j, double D, double dD, double Dmu) __attribute__((always_inline)) { return lvl::snow_bin(L.ss[j], D, Dmu, dD); }, A, S, M);
+        radiometer_species_finish<NJ>(L.lqs, L.rs, A[0], S[0], M, kabs, kbsc);
+        radiometer_sums<2, NJ, 1>(a.D[2], a.dD[2], a.nb[2], rows_g, 1, lane, L.lqg,
+                                  [&](int j, double D, double dD, double) __attribute__((always_inline)) { return lvl::exp_bin(L.N0_g[j], L.lamg[j], D, dD); }, A, S, M);
+        radiometer_species_finish<NJ>(L.lqg, L.rg, A[0], S[0], M, kabs, kbsc);
+    }
+    radiometer_tail<T, NJ>(a, ch, col, base, nz, lane, L, kabs, kbsc);
+}
+
+namespace {
+template <class T>
+hipError_t launch_radiometer(const ReflConsts &c, const DopplerConsts &dc, int64_t ncol, int nz, const RadiometerArgs<T> &a, hipStream_t s)
+{
+    if (ncol <= 0) return hipSuccess;                                // an empty batch is not looked at
+    for (int x = 0; x < MIE_NSPEC; ++x)
+        if (a.nb[x] < 1 || a.nb[x] > MIE_MAX_BINS) return hipErrorInvalidValue;
+    return launch_level_groups(ncol, nz, [&](auto nj) {
+        constexpr int NJ = decltype(nj)::value;
+        hipLaunchKernelGGL((k_radiometer<T, NJ>), column_grid(ncol), dim3(REFL_THREADS), 0, s, c, dc, a, ncol, nz);
+    });
+}
+}  // namespace
+
+}  // namespace kidmp
 
 using namespace kidmp;
 

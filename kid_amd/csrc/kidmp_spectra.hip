@@ -1,10 +1,137 @@
 // kidmp_spectra.hip -- the entries of include/kidmp_spectra.h: each species' distribution parameters and its numbers per
-// diameter bin, of device arrays in one launch of k_size_spectra (thompson_reflectivity.hip), and of host arrays in chunks
+// diameter bin, of device arrays in one launch of k_size_spectra (below), and of host arrays in chunks
 // through the context's staging memory.
 #include <cstddef>
 
 #include "kidmp_ctx.h"
 #include "../../include/kidmp_spectra.h"
+
+#include "kidmp_column.h"
+
+namespace kidmp {
+
+// The size spectra (include/kidmp_spectra.h): each species' distribution parameters [ncol][nz] and its numbers per bin
+// [ncol][nb][nz].  Species in the order c, i, r, s, g; par in the order of kidmp_spectra_out.  Null means: nc -- Nt_c (the
+// context is not aerosol-aware); qi and ni, qs, qg -- the species is absent everywhere (iiwarm); an output -- not wanted;
+// set_nc_col -- the context's Nt_c.  D, dD: device arrays of nb[x] doubles, read only where spec[x] is wanted.
+constexpr int SPECTRA_NPAR = 11;                    // SPECTRA_NSPEC: kidmp_column.h
+constexpr int SPECTRA_LAM_C = 0, SPECTRA_LAM_I = 3, SPECTRA_LAM_R = 5, SPECTRA_SMOB = 7, SPECTRA_LAM_G = 9;   // each followed by its n0 / smoc (and nu_c)
+constexpr int SPECTRA_MAX_SHARES = 16, SPECTRA_MIN_BLOCKS = 1024;
+template <class T> struct SpectraArgs {
+    const T *t, *p, *qv, *qc, *nc, *qi, *ni, *qr, *nr, *qs, *qg;
+    T *par[SPECTRA_NPAR];
+    T *spec[SPECTRA_NSPEC];
+    const double *D[SPECTRA_NSPEC], *dD[SPECTRA_NSPEC];
+    int32_t nb[SPECTRA_NSPEC];
+    const double *set_nc_col;                        // null, or the batch's share of a bound per-column droplet number (cm**-3)
+    int aero;                                        // the context's is_aerosol_aware: nc is read and size-limited (M:1398-1409)
+};
+
+// One wavefront per column and share of the bins: the size distributions of the state as mp_thompson loads it, on diameter
+// bins (include/kidmp_spectra.h).  Species by species -- rain first, whose median volume diameter the graupel intercept
+// reads -- the level's slope and intercept are formed once in registers, stored by the column's first share if asked for,
+// and the species' bins follow at once, so that only one species' parameters are live at a time.  The load is
+// k_fall_speeds' own, through the same lvl:: functions, stated once in load_air .. load_cloud above, which
+// k_lidar_profiles calls as well.  Nothing but the fastmath tables is in LDS.
+template <class T, int NJ>
+__global__ void __launch_bounds__(REFL_THREADS)
+k_size_spectra(const Consts *__restrict__ hc, SpectraArgs<T> a, int64_t ncol, int nz)
+{
+    int lane;
+    const int64_t col = enter_column(lane);
+    if (col >= ncol) return;                                         // whole wavefronts only: the scans need every lane
+    const int64_t base = col * int64_t(nz);
+    const bool first = blockIdx.y == 0;                              // the share that stores the parameters
+    T *const *par = a.par;
+    const auto params = [&](int v, const double (&x)[NJ]) __attribute__((always_inline)) { if (first) store_profile<T, NJ>(par[v], base, nz, lane, x); };
+    const auto wants = [&](int sp, int p0, int p1, int p2) __attribute__((always_inline)) { return a.spec[sp] || par[p0] || par[p1] || (p2 >= 0 && par[p2]); };
+
+    double temp[NJ], pres[NJ], rho[NJ], mvd[NJ], n0[NJ], lam[NJ];
+
+    // (each species picks its own few constants from the context's copy in HBM just before it needs them: all fifty of
+    //  fall_consts at once, beside the forty pointers of the arguments, do not fit the scalar registers)
+    FallConsts c{};
+    load_air<NJ>(a, base, nz, lane, temp, pres, rho);
+    load_rain<NJ>(hc, c, a, base, nz, lane, rho, mvd, lam, n0);
+    params(SPECTRA_LAM_R, lam);
+    params(SPECTRA_LAM_R + 1, n0);
+    store_bins<T, NJ, false>(a.spec[2], a.D[2], a.dD[2], a.nb[2], col, nz, lane, n0,
+                             [&](int j, double D, double dD, double) __attribute__((always_inline)) { return n0[j] > 0. ? lvl::exp_bin(n0[j], lam[j], D, dD) : 0.; });
+
+    if (wants(1, SPECTRA_LAM_I, SPECTRA_LAM_I + 1, -1)) {
+        load_ice<NJ>(hc, c, a, base, nz, lane, rho, lam, n0);
+        params(SPECTRA_LAM_I, lam);
+        params(SPECTRA_LAM_I + 1, n0);
+        store_bins<T, NJ, false>(a.spec[1], a.D[1], a.dD[1], a.nb[1], col, nz, lane, n0,
+                                 [&](int j, double D, double dD, double) __attribute__((always_inline)) { return n0[j] > 0. ? lvl::exp_bin(n0[j], lam[j], D, dD) : 0.; });
+    }
+
+    if (wants(3, SPECTRA_SMOB, SPECTRA_SMOB + 1, -1)) {
+        lvl::SnowSpectrum sp[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { lam[j] = 0.; sp[j] = lvl::SnowSpectrum{0., 0., 0., 0.}; }
+        c.cse1 = hc->cse[0];
+#pragma unroll
+        for (int i = 0; i < 10; ++i) { c.sa[i] = hc->sa[i]; c.sb[i] = hc->sb[i]; }
+        load_snow<NJ>(hc, c, a, base, nz, lane, temp, rho, n0, [&](int j, const lvl::SnowLevel &sl) __attribute__((always_inline)) {
+            lam[j] = lvl::snow_moment(c.sa, c.sb, c.cse1, sl);      // smoc, M:1590-1600
+            sp[j] = lvl::snow_spectrum(sl, lam[j]);
+        });
+        params(SPECTRA_SMOB, n0);
+        params(SPECTRA_SMOB + 1, lam);
+        store_bins<T, NJ, true>(a.spec[3], a.D[3], a.dD[3], a.nb[3], col, nz, lane, n0,
+                                [&](int j, double D, double dD, double Dmu) __attribute__((always_inline)) { return n0[j] > 0. ? lvl::snow_bin(sp[j], D, Dmu, dD) : 0.; });
+    }
+
+    if (wants(4, SPECTRA_LAM_G, SPECTRA_LAM_G + 1, -1)) {
+        load_graupel<NJ>(hc, c, a, base, nz, lane, temp, rho, mvd, lam, n0);
+        params(SPECTRA_LAM_G, lam);
+        params(SPECTRA_LAM_G + 1, n0);
+        store_bins<T, NJ, false>(a.spec[4], a.D[4], a.dD[4], a.nb[4], col, nz, lane, n0,
+                                 [&](int j, double D, double dD, double) __attribute__((always_inline)) { return n0[j] > 0. ? lvl::exp_bin(n0[j], lam[j], D, dD) : 0.; });
+    }
+
+    if (wants(0, SPECTRA_LAM_C, SPECTRA_LAM_C + 1, SPECTRA_LAM_C + 2)) {
+        int nu[NJ];
+        double ncl[NJ], fnu[NJ];
+        load_cloud<NJ>(hc, a, col, base, nz, lane, rho, lam, n0, ncl, nu);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) fnu[j] = double(nu[j]);
+        params(SPECTRA_LAM_C, lam);
+        params(SPECTRA_LAM_C + 1, n0);
+        params(SPECTRA_LAM_C + 2, fnu);
+        store_bins<T, NJ, false>(a.spec[0], a.D[0], a.dD[0], a.nb[0], col, nz, lane, n0,
+                                 [&](int j, double D, double dD, double) __attribute__((always_inline)) {
+                                     const double D2 = D * D, D4 = D2 * D2;
+                                     return n0[j] > 0. ? lvl::cloud_bin(n0[j], lam[j], nu[j], D, D2, D4, D4 * D4, dD) : 0.;
+                                 });
+    }
+}
+
+namespace {
+// d_consts: the context's Consts in device memory (kidmp_ctx::d_consts)
+template <class T>
+hipError_t launch_size_spectra(const Consts *c, int64_t ncol, int nz, const SpectraArgs<T> &a, hipStream_t s)
+{
+    if (ncol <= 0) return hipSuccess;                                // no column group: nothing to share out
+    const int64_t nblk = column_grid(ncol).x;
+    // few columns and many bins: a column's bins go to several blocks, up to SPECTRA_MAX_SHARES, until the grid holds
+    // SPECTRA_MIN_BLOCKS workgroups (four to a compute unit)
+    int maxnb = 1;
+    for (int x = 0; x < SPECTRA_NSPEC; ++x)
+        if (a.spec[x] && a.nb[x] > maxnb) maxnb = a.nb[x];
+    int64_t shares = (SPECTRA_MIN_BLOCKS + nblk - 1) / nblk;
+    shares = shares > SPECTRA_MAX_SHARES ? SPECTRA_MAX_SHARES : shares;
+    shares = shares > maxnb ? maxnb : shares;
+    return launch_level_groups(ncol, nz, [&](auto nj) {
+        constexpr int NJ = decltype(nj)::value;
+        hipLaunchKernelGGL((k_size_spectra<T, NJ>), column_grid(ncol, (unsigned)shares), dim3(REFL_THREADS), 0, s,
+                           c, a, ncol, nz);
+    });
+}
+}  // namespace
+
+}  // namespace kidmp
 
 using namespace kidmp;
 

@@ -1,7 +1,7 @@
-// kidmp_wave.h -- internal to kidmp_kinematic.hip, kidmp_slab.hip, thompson_reflectivity.hip and kidmp_scan.hip (not
-// installed): a column (or a ray) held by one wavefront, level (gate) k = 64 j + lane, the moves between neighbouring levels
-// that both advection kernels are built from, and the sum scan that the path integrals of the column diagnostics and of
-// the scan share.
+// kidmp_wave.h -- internal to kidmp_kinematic.hip, kidmp_slab.hip, kidmp_scan.hip and the wave-per-column diagnostics
+// (kidmp_column.h; not installed): a column (or a ray) held by one wavefront, level (gate) k = 64 j + lane, the moves between
+// neighbouring levels that both advection kernels are built from, and the sum scan that the path integrals of the column
+// diagnostics and of the scan share.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,8 +1,8 @@
 // thompson_levels.h -- the per-level arithmetic of the column diagnostics, calc_effectRad (M:4834-4935), calc_refl10cm
 // (M:4946-5244), the fall speeds of block O (M:3206-3354) and the Doppler moments of a vertically pointing radar
 // (include/kidmp_doppler.h), as __device__ functions: the pointwise radii kernel
-// (kidmp_diag.hip) and the wave-per-column kernels (thompson_reflectivity.hip) are built from these, so no statement
-// exists twice.
+// (kidmp_diag.hip) and the wave-per-column kernels (kidmp_column.h and the units that include it) are built from these,
+// so no statement exists twice.
 //
 // What the two diagnostics share at a level -- rho, the snow content rs = qs*rho, tc0, the snow moment smob = rs*oams and
 // its logarithm -- is held in SnowLevel and formed once when both are wanted.

@@ -37,7 +37,7 @@ EINVAL, ESTATE = -1, -5
 ULP = 2.220446049250313e-16
 # the largest differences from the reference measured on the MI355X over every shape and configuration of this file
 MEASURED = {"enh_s": 8.9e-16, "enh_g": 6.7e-16, "dbz": 6.6e-15}
-NZS = (2, 33, 64, 65, 120, 200, 256)
+NZS = (2, 33, 64, 65, 120, 129, 200, 256)
 SHAPES = [(nz, ncol) for nz in NZS for ncol in (1, 5)] + [(120, 257), (200, 18)]
 NUMBERS = ref.PROFILES
 
@@ -264,12 +264,13 @@ def test_a_column_alone_at_any_position_and_again(gpu_mixed, main_set):
 
 
 def test_binary32_entries_round_once(gpu_mixed, main_set):
-    st = {k: v.astype(np.float32) for k, v in main_set[0].items()}
-    got = _bb(gpu_mixed, st)
-    ref64 = _bb(gpu_mixed, {k: v.astype(np.float64) for k, v in st.items()})
-    for n in NUMBERS:
-        assert got[n].dtype == np.float32 and _same(got[n], ref64[n].astype(np.float32)), n
-    assert got["k0"].dtype == np.int32 and np.array_equal(got["k0"], ref64["k0"]) and (got["k0"] >= 0).any()
+    for st0 in [main_set[0]] + [bc.batch(nz, 5, 100 * nz + 5)[0] for nz in (33, 129, 256)]:   # two, then one, three and four level groups
+        st = {k: v.astype(np.float32) for k, v in st0.items()}
+        got = _bb(gpu_mixed, st)
+        ref64 = _bb(gpu_mixed, {k: v.astype(np.float64) for k, v in st.items()})
+        for n in NUMBERS:
+            assert got[n].dtype == np.float32 and _same(got[n], ref64[n].astype(np.float32)), (st["t"].shape[1], n)
+        assert got["k0"].dtype == np.int32 and np.array_equal(got["k0"], ref64["k0"]) and (got["k0"] >= 0).any()
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])

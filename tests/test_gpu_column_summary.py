@@ -154,6 +154,8 @@ def test_nz_sweep(gpu_mixed, nz):
     dbz, re, formed = _own_profiles(gpu_mixed, st)
     want, mag, _ = ref.summary(st, st["dz"], dbz, re, formed)
     print("summary nz=%d: worst error %.3f of its bound" % (nz, ref.check(_summary(gpu_mixed, st), want, mag, nz)))
+    st32 = {k: v[:5].astype(np.float32) for k, v in st.items()}                    # binary32 storage at every level-group count
+    assert _same(_summary(gpu_mixed, st32), _summary(gpu_mixed, {k: v.astype(np.float64) for k, v in st32.items()}))
 
 
 @pytest.mark.parametrize("ncol", NCOL_SWEEP)

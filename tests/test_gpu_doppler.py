@@ -222,9 +222,12 @@ def test_subsets_and_sentinels(gpu_mixed, sets):
 
 # ---- 4. binary32 entries ----
 def test_binary32_entries_round_once(gpu_mixed, gpu_warm, sets):
-    for name, m in (("config3", gpu_mixed), ("random65_366", gpu_mixed), ("config2", gpu_warm)):
-        st = {k: v.astype(np.float32) for k, v in sets[name][0].items()}
-        w = sets[name][1].astype(np.float32)
+    scans = {"scan%d" % nz: (_take(_scan_state(nz), np.arange(5)), np.linspace(-3.0, 3.0, 5 * nz).reshape(5, nz))
+             for nz in (2, 129, 256)}                                                # one, three and four level groups
+    for name, m in (("config3", gpu_mixed), ("random65_366", gpu_mixed), ("config2", gpu_warm)) + tuple((n, gpu_mixed) for n in scans):
+        st0, w0 = scans[name] if name in scans else sets[name][:2]
+        st = {k: v.astype(np.float32) for k, v in st0.items()}
+        w = np.ascontiguousarray(w0.astype(np.float32))
         wide = {k: v.astype(np.float64) for k, v in st.items()}
         got = _doppler(m, st, w)
         ref64 = _doppler(m, wide, w.astype(np.float64))

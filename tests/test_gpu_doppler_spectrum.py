@@ -275,9 +275,12 @@ def test_every_subset_and_sentinels(gpu_mixed, sets):
 
 # ---- 4. binary32 entries ----
 def test_binary32_entries_round_once(gpu_mixed, gpu_warm, sets):
-    for name, m in (("config3", gpu_mixed), ("random65_366", gpu_mixed), ("config2", gpu_warm)):
-        st = {k: v[:16].astype(np.float32) for k, v in sets[name][0].items()}
-        w = sets[name][1][:16].astype(np.float32)
+    scans = {"scan%d" % nz: (only(fc.scan_state(nz, 5, 1200 + nz)), np.linspace(-6.0, 6.0, 5 * nz).reshape(5, nz))
+             for nz in (2, 129, 256)}                                                # one, three and four level groups
+    for name, m in (("config3", gpu_mixed), ("random65_366", gpu_mixed), ("config2", gpu_warm)) + tuple((n, gpu_mixed) for n in scans):
+        st0, w0 = scans[name] if name in scans else sets[name][:2]
+        st = {k: v[:16].astype(np.float32) for k, v in st0.items()}
+        w = np.ascontiguousarray(w0[:16].astype(np.float32))
         wide = {k: v.astype(np.float64) for k, v in st.items()}
         got = _spectrum(m, st, w=w)
         ref64 = _spectrum(m, wide, w=w.astype(np.float64))

@@ -216,10 +216,11 @@ def test_boost_and_subsets(gpu_mixed, sets, refs, consts):
 
 # ---- 4. binary32 entries ----
 def test_binary32_entries_round_once(gpu_mixed, gpu_warm, sets):
-    for name, m in (("config3", gpu_mixed), ("random65_266", gpu_mixed), ("config2", gpu_warm)):
-        st = {k: v.astype(np.float32) for k, v in sets[name][0].items()}
+    scans = {"scan%d" % nz: fc.only(fc.scan_state(nz, 5, 700 + nz)) for nz in (2, 129, 256)}     # one, three and four level groups
+    for name, m in (("config3", gpu_mixed), ("random65_266", gpu_mixed), ("config2", gpu_warm)) + tuple((n, gpu_mixed) for n in scans):
+        st = {k: v.astype(np.float32) for k, v in (scans[name] if name in scans else sets[name][0]).items()}
         wide = {k: v.astype(np.float64) for k, v in st.items()}
-        dz32 = cases.config5(2)["dz"][0, :st["t"].shape[1]].astype(np.float32)
+        dz32 = np.resize(cases.config5(2)["dz"][0], st["t"].shape[1]).astype(np.float32)             # its 120 levels, repeated
         got = _fall(m, st, dz=dz32, dt=10.0)
         ref64 = _fall(m, wide, dz=dz32.astype(np.float64), dt=10.0)
         for n in ref.NAMES:

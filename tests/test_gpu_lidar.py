@@ -295,8 +295,10 @@ def test_each_output_alone_subsets_and_sentinels(gpu_mixed, sets):
 
 
 def test_binary32_entries_round_once(gpu_mixed, gpu_warm, sets):
-    for name, m in (("config3", gpu_mixed), ("fall_hand_built", gpu_mixed), ("config2", gpu_warm)):
-        st0, _, dz0 = sets[name]
+    randoms = {"random%d" % nz: (_only(ec.random_state(nz, 5, 700 + nz)), None, lc.uneven_dz(nz, nz, 5.0, 80.0))
+               for nz in (2, 129, 256)}                                              # one, three and four level groups
+    for name, m in (("config3", gpu_mixed), ("fall_hand_built", gpu_mixed), ("config2", gpu_warm)) + tuple((n, gpu_mixed) for n in randoms):
+        st0, _, dz0 = randoms[name] if name in randoms else sets[name]
         st = {k: v.astype(np.float32) for k, v in st0.items()}
         dz = dz0.astype(np.float32)
         got = _lidar(m, st, dz)

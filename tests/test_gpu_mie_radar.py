@@ -275,14 +275,14 @@ def test_the_middle_of_a_nan_filled_tensor(gpu_mixed, tables, main_set):
 # ---- 3. the other entries ----
 def test_binary32_entries_round_once(gpu_mixed, tables, main_set):
     table = tables["w"][0]
-    st, dz, w, k_gas, _ = main_set
     f = lambda a: a.astype(np.float32)   # noqa: E731
-    st32 = {k: f(v) for k, v in st.items()}
-    got = _run(gpu_mixed, table, st32, f(dz), f(w), f(k_gas))
-    ref64 = _run(gpu_mixed, table, {k: v.astype(np.float64) for k, v in st32.items()}, f(dz).astype(np.float64), f(w).astype(np.float64),
-                 f(k_gas).astype(np.float64))
-    for n in ref.NAMES:
-        assert got[n].dtype == np.float32 and _same(got[n], ref64[n].astype(np.float32)), n
+    for st, dz, w, k_gas in [main_set[:4]] + [state(nz) for nz in (2, 129, 256)]:     # two, then one, three and four level groups
+        st32 = {k: f(v) for k, v in st.items()}
+        got = _run(gpu_mixed, table, st32, f(dz), f(w), f(k_gas))
+        ref64 = _run(gpu_mixed, table, {k: v.astype(np.float64) for k, v in st32.items()}, f(dz).astype(np.float64), f(w).astype(np.float64),
+                     f(k_gas).astype(np.float64))
+        for n in ref.NAMES:
+            assert got[n].dtype == np.float32 and _same(got[n], ref64[n].astype(np.float32)), (st["t"].shape[1], n)
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])

@@ -292,18 +292,18 @@ def test_an_iiwarm_context_absent_species_and_a_dry_column(gpu_warm, gpu_mixed, 
 # ---- 5. binary32 ----
 def test_binary32_entries(gpu_mixed, tables):
     from kid_amd import multichannel_tile
-    m, nz = gpu_mixed, 129
-    f = np.float32
-    (st, dz, kgs, t_sfc), ref = rad_reference(m, tables, "scheme", nz, dtype=f)
-    nch = multichannel_tile("radiometer", nz) + 1
-    got = rad_multi(m, tables["rad", "scheme"][:nch], st, dz, kgs[:nch], t_sfc, _rcfgs(nch), dtype=f)
-    assert all(v.dtype == f for v in got.values())
-    assert_slabs(got, ref)
-    (st, dz, w, kgs), ref = mie_reference(m, tables, "scheme", nz, dtype=f)
-    nch = multichannel_tile("radar", nz) + 1
-    got = mie_multi(m, tables["mie", "scheme"][:nch], st, dz, w, kgs[:nch], dtype=f)
-    assert all(v.dtype == f for v in got.values())
-    assert_slabs(got, ref)
+    m, f = gpu_mixed, np.float32
+    for nz in mcc.NZS:                                                            # every level-group count
+        (st, dz, kgs, t_sfc), ref = rad_reference(m, tables, "scheme", nz, dtype=f)
+        nch = multichannel_tile("radiometer", nz) + 1
+        got = rad_multi(m, tables["rad", "scheme"][:nch], st, dz, kgs[:nch], t_sfc, _rcfgs(nch), dtype=f)
+        assert all(v.dtype == f for v in got.values())
+        assert_slabs(got, ref)
+        (st, dz, w, kgs), ref = mie_reference(m, tables, "scheme", nz, dtype=f)
+        nch = multichannel_tile("radar", nz) + 1
+        got = mie_multi(m, tables["mie", "scheme"][:nch], st, dz, w, kgs[:nch], dtype=f)
+        assert all(v.dtype == f for v in got.values())
+        assert_slabs(got, ref)
 
 
 # ---- 6. the host entries ----

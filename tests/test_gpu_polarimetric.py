@@ -46,7 +46,7 @@ pytestmark = pytest.mark.gpu
 MEASURED = {"dbz_h": 6.6e-15, "zdr": 2.1e-15, "kdp": 3.0e-15, "rhohv": 1.7e-15}
 # the restatement's uniform route against its quadrature, graupel
 QUADRATURE = {"dbz_h": 3.3e-15, "zdr": 1.3e-15, "kdp": 2.2e-15, "rhohv": 1.3e-15}
-NZS = (2, 33, 64, 65, 120, 200, 256)
+NZS = (2, 33, 64, 65, 120, 129, 200, 256)
 SHAPES = [(nz, ncol) for nz in NZS for ncol in (1, 5)] + [(120, 257), (200, 18)]
 WORST = {k: 0.0 for k in MEASURED}
 SPHERES = dict(axis_r=(1.0, 0.0, 0.0, 0.0, 0.0), axis_s=1.0, axis_g=1.0)
@@ -354,12 +354,12 @@ def test_bits_do_not_depend_on_batch_position_request_or_repeat(gpu_mixed, table
 
 def test_binary32_entries_round_once(gpu_mixed, tables, main_set):
     table = tables["default"][0]
-    st, _ = main_set
-    st32 = {k: v.astype(np.float32) for k, v in st.items()}
-    got = _run(gpu_mixed, table, st32)
-    ref64 = _run(gpu_mixed, table, {k: v.astype(np.float64) for k, v in st32.items()})
-    for n in ref.NAMES:
-        assert got[n].dtype == np.float32 and _same(got[n], ref64[n].astype(np.float32)), n
+    for st in [main_set[0]] + [_state(nz, 5) for nz in (2, 129, 256)]:             # two, then one, three and four level groups
+        st32 = {k: v.astype(np.float32) for k, v in st.items()}
+        got = _run(gpu_mixed, table, st32)
+        ref64 = _run(gpu_mixed, table, {k: v.astype(np.float64) for k, v in st32.items()})
+        for n in ref.NAMES:
+            assert got[n].dtype == np.float32 and _same(got[n], ref64[n].astype(np.float32)), (st["t"].shape[1], n)
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])

@@ -328,14 +328,14 @@ def test_the_middle_of_a_nan_filled_tensor(gpu_mixed, tables, main_set):
 # ---- 4. the other entries ----
 def test_binary32_entries_round_once(gpu_mixed, tables, main_set):
     table = tables["absorbing"][0]
-    st, dz, k_gas, t_sfc, _ = main_set
     f = lambda a: a.astype(np.float32)   # noqa: E731
-    st32 = {k: f(v) for k, v in st.items()}
-    got = _run(gpu_mixed, table, st32, f(dz), f(k_gas), f(t_sfc))
     d = lambda a: f(a).astype(np.float64)   # noqa: E731
-    ref64 = _run(gpu_mixed, table, {k: d(v) for k, v in st.items()}, d(dz), d(k_gas), d(t_sfc))
-    for n in ref.NAMES:
-        assert got[n].dtype == np.float32 and _same(got[n], ref64[n].astype(np.float32)), n
+    for st, dz, k_gas, t_sfc in [main_set[:4]] + [rc.state(nz) for nz in (2, 65, 256)]:   # three, then one, two and four level groups
+        st32 = {k: f(v) for k, v in st.items()}
+        got = _run(gpu_mixed, table, st32, f(dz), f(k_gas), f(t_sfc))
+        ref64 = _run(gpu_mixed, table, {k: d(v) for k, v in st.items()}, d(dz), d(k_gas), d(t_sfc))
+        for n in ref.NAMES:
+            assert got[n].dtype == np.float32 and _same(got[n], ref64[n].astype(np.float32)), (st["t"].shape[1], n)
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])

@@ -280,8 +280,9 @@ def test_subsets_sentinels_and_the_default_grid_given_by_the_caller(gpu_mixed, s
 
 def test_binary32_entries_round_once(gpu_mixed, gpu_warm, sets):
     grids = _sweep_grids(dict(r=7))
-    for name, m in (("config3", gpu_mixed), ("random65_272", gpu_mixed), ("config2", gpu_warm)):
-        st = {k: v.astype(np.float32) for k, v in sets[name][0].items()}
+    randoms = {"random%d" % nz: _only(ec.random_state(nz, 5, 900 + nz)) for nz in (2, 129, 256)}  # one, three and four level groups
+    for name, m in (("config3", gpu_mixed), ("random65_272", gpu_mixed), ("config2", gpu_warm)) + tuple((n, gpu_mixed) for n in randoms):
+        st = {k: v.astype(np.float32) for k, v in (randoms[name] if name in randoms else sets[name][0]).items()}
         wide = {k: v.astype(np.float64) for k, v in st.items()}
         got = _spectra(m, st, grids=grids)
         ref64 = _spectra(m, wide, grids=grids)
